@@ -6,14 +6,19 @@ camera stream of this rank's stream group receives one new stereo pair
 (pushBack: detect on 2 images) and is quad-matched against its previous pair
 (matchFeatures(2)).  Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times exactly K steps and prints the line.  --full adds
+everything else the bench measures: per-kernel durations and the roofline, the
+as-shipped loop, the mono flow workload, the other BASELINE configs, the CPU
+baselines and the oracle parity check.
 
 N>1 is launched by the driver through torch.distributed.run, one rank per GPU;
 ranks run independent streams (no data-path collective: the path partitions by
 camera sequence) and only the timing is reduced (MAX over ranks).
 
 Rank 0 prints ONE JSON line; see README/DESIGN.md for the `roofline` and
-`cpu_baseline` objects.
+`cpu_baseline` objects (--full).
 """
 from __future__ import annotations
 
@@ -352,6 +357,50 @@ def context_workload(pkg, torch, dev, local_rank, name, noise, ob=None, steps=40
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE_STREAMS = 16
+
+
+def dump_outputs(path, pkg, grp, rank: int, world: int):
+    """--dump-outputs: what the timed path hands its caller after the last timed step, as DIR/<name>.npy, so that two
+    builds can be compared output for output (the inputs depend on the arguments alone).  Every stream's feature and
+    match counts; for a fixed sample of streams (seed 0, at most DUMP_SAMPLE_STREAMS, within DUMP_BUDGET_BYTES over all
+    ranks) their match lists and the two feature sets the last step detected, concatenated in stream order:
+      feature_counts [S, 4] f64, match_counts [S] f64    (getCounts: sets 1p, 2p, 1c, 2c; matches)
+      sample_streams [K] f64                            the sampled streams
+      matches [M, 12] f32                               p_match fields in record order: float32 holds the coordinates
+                                                        and the feature indices (< 2^24) exactly
+      features_left, features_right [F, 12] f64         current left / right feature records (int32 fields)
+    With N > 1 ranks every rank writes its own streams' files, prefixed rank<r>_."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BUDGET_BYTES // world
+    nf, nm = grp.getCounts()
+    out = {"feature_counts": nf.astype(np.float64), "match_counts": nm.astype(np.float64)}
+    used = sum(a.nbytes for a in out.values())
+    rng = np.random.default_rng(0)
+    pick = np.sort(rng.choice(grp.S, min(grp.S, DUMP_SAMPLE_STREAMS), replace=False))
+    kept, matches, left, right = [], [], [], []
+    for s in pick:
+        m = grp.getMatches(int(s))
+        for f in m.dtype.names:
+            assert m.dtype[f].kind == "f" or np.all(np.abs(m[f]) < 2**24), f  # float32 must hold every field exactly
+        rec = np.stack([m[f].astype(np.float32) for f in m.dtype.names], axis=1).reshape(-1, 12)
+        fl = grp.getFeatures(int(s), pkg.SET_1C).astype(np.float64)
+        fr = grp.getFeatures(int(s), pkg.SET_2C).astype(np.float64)
+        need = rec.nbytes + fl.nbytes + fr.nbytes + 8
+        if used + need > budget:
+            break
+        used += need
+        kept.append(s); matches.append(rec); left.append(fl); right.append(fr)
+    out["sample_streams"] = np.array(kept, np.float64)
+    out["matches"] = np.concatenate(matches) if matches else np.zeros((0, 12), np.float32)
+    out["features_left"] = np.concatenate(left) if left else np.zeros((0, 12), np.float64)
+    out["features_right"] = np.concatenate(right) if right else np.zeros((0, 12), np.float64)
+    pre = f"rank{rank}_" if world > 1 else ""
+    for name, a in out.items():
+        np.save(os.path.join(path, pre + name + ".npy"), a)
+
+
 def self_launch(n: int) -> int:
     """`python bench.py --gpus N` outside a launcher: this process -- which has imported neither torch nor the HIP
     library and never will -- starts `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` as
@@ -392,7 +441,7 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--noise", type=int, default=0, help="context runs: +-N grey levels of uniform noise on every frame "
                     "(many more, mostly unmatched features; the driver's line is noise 0, the BASELINE workload)")
-    ap.add_argument("--blocks", type=int, default=0, help="timed blocks of --steps steps each (0: as many as make the timed region >= 0.5 s, "
+    ap.add_argument("--blocks", type=int, default=1, help="timed blocks of --steps steps each (0: as many as make the timed region >= 0.5 s, "
                     "at least 3); every block is bracketed by the barrier + synchronize fence, the median block is reported")
     ap.add_argument("--noise-frac", type=float, default=1.0, help="context runs: share of the pixels that receive --noise")
     ap.add_argument("--no-cpu", action="store_true")
@@ -407,6 +456,11 @@ def main():
     ap.add_argument("--dist-selftest", action="store_true",
                     help="CPU-only rehearsal of the multi-rank plumbing (gloo): sharding, barrier, MAX-reduced timing")
     ap.add_argument("--no-other", action="store_true", help="skip the short context runs of the other BASELINE configs (other_workloads)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel durations and roofline, exclusive durations, the "
+                    "as-shipped loop, the mono flow workload, the other BASELINE configs, the CPU baselines and the parity check "
+                    "(the --no-* switches above act within --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed "
+                    "as DIR/<name>.npy (float32/float64, <= 64 MB; see dump_outputs)")
     args = ap.parse_args()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         return self_launch(args.gpus)
@@ -488,11 +542,13 @@ def main():
         nonlocal k
         step(k); k += 1
 
-    # One block of K steps is ~0.1 s at the default K: a single scheduler hiccup would be 5 % of it.  So the
-    # block is repeated (every one under the same protocol: EXACTLY --steps steps between two fences, MAX over
-    # ranks) until >= 0.5 s have been timed, and the MEDIAN block is the one reported; all block times are in the line.
+    # The timed region is ONE block of EXACTLY --steps steps between two fences (MAX over ranks), so that --steps is the
+    # number of timed steps and the last step -- what --dump-outputs writes -- depends on the arguments alone.  --blocks B
+    # repeats the block B times (0: until >= 0.5 s have been timed) and reports the MEDIAN block; all block times are in the line.
     block_s = proto.timed_blocks(one_step, fence, args.steps, args.blocks)
     dt = float(np.median(block_s))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pkg, grp, rank, world)
 
     # per-kernel device time: the same loop once more with HIP events recorded around every
     # launch on the stream it is launched on (two internal streams: detect of frame t+1 overlaps
@@ -512,11 +568,13 @@ def main():
             if n_:
                 out_[name] = {"ms_total": ms, "launches": n_, "us_per_launch": 1e3 * ms / n_}
         return out_
-    prof = profiled(grp, args.steps, k)
-    k += args.steps
+    prof = {}
+    if args.full:
+        prof = profiled(grp, args.steps, k)
+        k += args.steps
     # ... and exclusive durations: a second group whose kernels all run on ONE stream (VH_SERIAL=1)
     prof_excl = {}
-    if not args.no_exclusive and rank == 0:
+    if args.full and not args.no_exclusive and rank == 0:
         os.environ["VH_SERIAL"] = "1"
         g2 = pkg.StreamGroup(S, pkg.Params.default(**wl["params"]), device=local_rank, max_features=wl["cap"], max_matches=wl["cap"])
         os.environ.pop("VH_SERIAL")
@@ -532,7 +590,7 @@ def main():
     # Delaunay vote as one lane per match list, several steps in flight); `e2e_matchfeatures_host_vote`: round 3's form,
     # vote + bucketing of step t on the host threads while the GPU computes step t+1.
     e2e = e2e_host = None
-    if not args.no_e2e and args.workload == "kitti" and world == 1:  # (like cpu_baseline: a context measurement of the N = 1 run)
+    if args.full and not args.no_e2e and args.workload == "kitti" and world == 1:  # (like cpu_baseline: a context measurement of the N = 1 run)
         nthr = max(1, min(len(os.sched_getaffinity(0)), 16))
         ego = pkg.EgoParams.default(f=645.24, cu=635.96, cv=194.13, base=0.5707)
         r3 = np.random.default_rng(7).integers(0, 2 ** 31 - 1, (S, ego.ransac_iters, 3)).astype(np.int32)
@@ -635,7 +693,7 @@ def main():
     # (src/matcher.cpp:308-336).  Same S streams, same frames (left camera); after the timing stream 0's first frame pair,
     # which is SURVEY Appendix B's pair, is matched once more on its own and compared with the reference's known answers.
     flow = None
-    if not args.no_flow and args.workload == "kitti" and world == 1:
+    if args.full and not args.no_flow and args.workload == "kitti" and world == 1:
         gf = pkg.StreamGroup(S, pkg.Params.default(**wl["params"]), device=local_rank, max_features=wl["cap"], max_matches=wl["cap"])
         gf.setStream(stream.cuda_stream)
         kf = 0
@@ -692,7 +750,7 @@ def main():
 
     # ---- the other BASELINE.json configs and one noisy run, a few steps each (context keys of the N = 1 line, never `value`)
     other = None
-    if rank == 0 and world == 1 and args.workload == "kitti" and not args.no_other and not NOISE:
+    if args.full and rank == 0 and world == 1 and args.workload == "kitti" and not args.no_other and not NOISE:
         other = {}
         ob_ = None if args.no_cpu else entry.load_oracle()
         for key, (name_, noise_) in (("1080p", ("1080p", 0)), ("4k", ("4k", 0)), ("kitti_noise1", ("kitti", 1))):
@@ -780,22 +838,25 @@ def main():
                        "streams_per_gpu": S, "frames_in_hbm": T, "features_per_image": float(nfm.mean()),
                        "matches_per_pair": float(nm.mean()), "parallelism": f"{world}x independent stream groups",
                        "device_mib_per_stream": round(grp.deviceBytes() / S / 2**20, 2)},
-            "roofline": roofline,
             "search_loop": {"form": "speculative" if search_spec else "tested", "queries_searched_again": search_redo,
                             "note": "chosen per launch from the share of queries whose best candidate over the walked region "
                                     "lies outside their own window (DESIGN.md 4.1); results are identical either way"},
-            "kernels_us_per_launch": {n_: round(v["us_per_launch"], 2) for n_, v in prof.items()},
-            # detection runs in sub-batches of streams (engine.hip): several launches per step
-            "kernels_launches_per_step": {n_: round(v["launches"] / args.steps, 2) for n_, v in prof.items()},
-            "kernels_us_per_launch_exclusive": {n_: round(v["us_per_launch"], 2) for n_, v in prof_excl.items()},
-            "flow_pinned": flow,
-            "other_workloads": other,
-            "e2e_matchfeatures": e2e,
-            "e2e_matchfeatures_host_vote": e2e_host,
-            "parity_scope": "primitives (computeFeatures, createIndexVector, findMatch, flow matching) pinned to the reference; "
-                            "stereo/quad composition per SURVEY A.7 (absent from the reference: unpinned)",
         }
-        if not args.no_cpu:
+        if args.full:
+            out.update({
+                "roofline": roofline,
+                "kernels_us_per_launch": {n_: round(v["us_per_launch"], 2) for n_, v in prof.items()},
+                # detection runs in sub-batches of streams (engine.hip): several launches per step
+                "kernels_launches_per_step": {n_: round(v["launches"] / args.steps, 2) for n_, v in prof.items()},
+                "kernels_us_per_launch_exclusive": {n_: round(v["us_per_launch"], 2) for n_, v in prof_excl.items()},
+                "flow_pinned": flow,
+                "other_workloads": other,
+                "e2e_matchfeatures": e2e,
+                "e2e_matchfeatures_host_vote": e2e_host,
+                "parity_scope": "primitives (computeFeatures, createIndexVector, findMatch, flow matching) pinned to the reference; "
+                                "stereo/quad composition per SURVEY A.7 (absent from the reference: unpinned)",
+            })
+        if args.full and not args.no_cpu:
             ob = entry.load_oracle()
             rate, n_pairs, secs, results = cpu_baseline(ob, frames_np, dims, args.cpu_seconds, wl["params"])
             calib = None

@@ -17,6 +17,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(HERE, "libviso_oracle.so")
 REF_SO = os.path.join(HERE, "_ref", "libviso_ref.so")
+#: the reference's answers to the calls the CPU tests put to it, in shards <prefix>_<i>.npz of < 1 MiB each
+#: (RecordedReference; oracle/gen_golden_reference.py)
+REFERENCE_ANSWERS = os.path.join(os.path.dirname(HERE), "tests", "golden", "reference_answers")
 REFERENCE_ROOT = "/root/reference"
 
 
@@ -408,3 +411,122 @@ class Reference:
         U = np.zeros((m, m)); W = np.zeros(min(m, n)); V = np.zeros((n, n))
         self.lib.ref_svd(_ptr(a), C.c_int32(m), C.c_int32(n), _ptr(U), _ptr(W), _ptr(V))
         return U, W, V
+
+
+def _call_key(method: str, args, kwargs) -> str:
+    """sha256 over a Reference call: the method and the exact bytes of its arguments."""
+    import hashlib
+    h = hashlib.sha256(method.encode() + b"\0")
+
+    def feed(x):
+        if isinstance(x, np.ndarray):
+            h.update(b"a" + str(x.dtype.descr).encode() + str(x.shape).encode())
+            h.update(np.ascontiguousarray(x).tobytes())
+        elif isinstance(x, C.Structure):
+            h.update(b"s" + type(x).__name__.encode() + bytes(x))
+        elif isinstance(x, (list, tuple)):
+            h.update(b"l%d" % len(x))
+            for v in x:
+                feed(v)
+        elif isinstance(x, (bool, np.bool_)) or x is None:
+            h.update(b"v" + repr(None if x is None else bool(x)).encode())
+        elif isinstance(x, (int, np.integer)):
+            h.update(b"i%d" % int(x))
+        elif isinstance(x, (float, np.floating)):
+            h.update(b"f" + float(x).hex().encode())
+        else:
+            raise TypeError(f"Reference.{method}: cannot key an argument of type {type(x).__name__}")
+    feed(list(args))
+    for k in sorted(kwargs):
+        h.update(k.encode())
+        feed(kwargs[k])
+    return h.hexdigest()
+
+
+class ReferenceRecorder:
+    """Wraps a live Reference: every call is answered by it and its answer kept under the call's key;
+    save() writes them all for RecordedReference (oracle/gen_golden_reference.py)."""
+
+    def __init__(self, ref: "Reference"):
+        self.ref = ref
+        self.answers = {}
+
+    def __getattr__(self, method):
+        fn = getattr(self.ref, method)
+
+        def call(*args, **kwargs):
+            out = fn(*args, **kwargs)
+            self.answers[_call_key(method, args, kwargs)] = out
+            return out
+        return call
+
+    def save(self, prefix: str = REFERENCE_ANSWERS, shard_bytes: int = 800 << 10):
+        """Shards <prefix>_<i>.npz, a new one whenever the deflated size of the current one would pass shard_bytes."""
+        import glob
+        import zlib
+        for f in glob.glob(prefix + "_*.npz"):
+            os.remove(f)
+        shards, z, size = [], {}, 0
+        for key, out in self.answers.items():
+            one = self._entries(key, out)
+            n = sum(len(zlib.compress(a.tobytes(), 6)) for a in one.values())
+            if z and size + n > shard_bytes:
+                shards.append(z); z, size = {}, 0
+            z.update(one); size += n
+        shards.append(z)
+        for i, z in enumerate(shards):
+            np.savez_compressed(f"{prefix}_{i}.npz", **z)
+        return len(shards)
+
+    @staticmethod
+    def _entries(key, out):
+        z = {}
+        items = list(out) if isinstance(out, tuple) else [out]
+        tags = []
+        for i, v in enumerate(items):
+            if v is None:
+                tags.append("none")
+            elif isinstance(v, bool):
+                tags.append("bool"); z[f"{key}:{i}"] = np.array(v)
+            elif isinstance(v, list):
+                tags.append("list"); z[f"{key}:{i}"] = np.array(v)
+            else:
+                tags.append("array"); z[f"{key}:{i}"] = np.ascontiguousarray(v)
+        z[key + ":tags"] = np.array([("tuple" if isinstance(out, tuple) else "single")] + tags)
+        return z
+
+
+class RecordedReference:
+    """The reference's answers replayed from REFERENCE_ANSWERS: the same methods as Reference, each call looked up
+    by its key.  A call that was never recorded is an error (regenerate with oracle/gen_golden_reference.py)."""
+
+    def __init__(self, prefix: str = REFERENCE_ANSWERS):
+        import glob
+        self.path = os.path.basename(prefix) + "_*.npz"
+        self.z = {}
+        for f in sorted(glob.glob(prefix + "_*.npz")):
+            with np.load(f) as shard:
+                self.z.update({k: shard[k] for k in shard.files})
+
+    def __getattr__(self, method):
+        if method.startswith("_") or not hasattr(Reference, method):
+            raise AttributeError(method)
+
+        def call(*args, **kwargs):
+            key = _call_key(method, args, kwargs)
+            if key + ":tags" not in self.z:
+                raise KeyError(f"no recorded answer of Reference.{method} for these inputs in {self.path}: "
+                               "regenerate it with oracle/gen_golden_reference.py")
+            tags = [str(t) for t in self.z[key + ":tags"]]
+            items = []
+            for i, t in enumerate(tags[1:]):
+                if t == "none":
+                    items.append(None)
+                elif t == "bool":
+                    items.append(bool(self.z[f"{key}:{i}"]))
+                elif t == "list":
+                    items.append([int(v) for v in self.z[f"{key}:{i}"]])
+                else:
+                    items.append(self.z[f"{key}:{i}"].copy())
+            return tuple(items) if tags[0] == "tuple" else items[0]
+        return call

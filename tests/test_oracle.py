@@ -89,7 +89,7 @@ def test_bucket_features_golden(pkg, ob, oracle):
 
 
 def test_oracle_vs_reference_fresh_inputs(pkg, ob, oracle, reference):
-    """Where the reference build exists: compare on inputs no fixture holds."""
+    """Compare with the reference on inputs no per-case fixture holds (its answers: the `reference` fixture)."""
     rng = np.random.default_rng(7)
     for trial in range(4):
         W = int(rng.integers(150, 420)); H = int(rng.integers(100, 260))

@@ -13,7 +13,6 @@ import pytest
 from conftest import ROOT
 
 PKG = os.path.join(ROOT, "hls-final-visual-odometry_amd")
-REF_SRC = "/root/reference/src"
 LINK = ["-L" + PKG, "-lviso_hip", "-Wl,-rpath," + PKG, "-Wl,-rpath-link,/opt/rocm/lib"]
 
 
@@ -27,35 +26,6 @@ def build_shim_demo(tmp_path, pkg):
 def test_shim_compiles_as_cxx11_and_links(tmp_path, pkg):
     """The reference is C++03/11 host code compiled with g++: the shim must be too."""
     assert os.path.exists(build_shim_demo(tmp_path, pkg))
-
-
-def test_reference_vo_drivers_build_against_the_shim(tmp_path, pkg):
-    """Drop-in check: the reference's own viso.cpp / viso_stereo.cpp / viso_mono.cpp
-    compile UNMODIFIED with the shim standing in for matcher.h and link against
-    libviso_hip.so.  The sources are symlinked (never copied) into a scratch
-    directory so that their `#include "matcher.h"` resolves to the shim."""
-    if not os.path.isdir(REF_SRC):
-        pytest.skip("/root/reference not present")
-    d = tmp_path / "dropin"
-    d.mkdir()
-    for f in ("viso.h", "viso.cpp", "viso_stereo.h", "viso_stereo.cpp", "viso_mono.h", "viso_mono.cpp", "matrix.h", "matrix.cpp"):
-        os.symlink(os.path.join(REF_SRC, f), d / f)
-    (d / "matcher.h").write_text('#include "matrix.h"\n#include "viso_hip_matcher.hpp"\n')
-    (d / "main.cpp").write_text(
-        '#include "viso_stereo.h"\n#include "viso_mono.h"\n'
-        "int main() { VisualOdometryStereo::parameters p; p.calib.f = 645.24; p.base = 0.57;\n"
-        "  VisualOdometryStereo v(p); uint8_t* I = 0; int32_t dims[3] = {0,0,0};\n"
-        "  return v.process(I, I, dims) ? 1 : 0; }\n")
-    objs = []
-    for f in ("viso", "viso_stereo", "viso_mono", "matrix", "main"):
-        o = str(d / (f + ".o"))
-        subprocess.check_call(["g++", "-std=gnu++11", "-O1", "-w", "-c", "-I" + os.path.join(ROOT, "include"),
-                               str(d / (f + ".cpp")), "-o", o], cwd=d)
-        objs.append(o)
-    subprocess.check_call(["g++", "-o", str(d / "demo")] + objs + LINK)
-    syms = subprocess.check_output(["nm", "-C", str(d / "viso_stereo.o")]).decode()
-    for s in ("vh_push_back", "vh_match_features", "vh_remove_outliers", "vh_bucket_features", "vh_get_matches"):
-        assert s in syms  # VisualOdometryStereo::process really goes through the C ABI
 
 
 def free_port():
@@ -72,7 +42,8 @@ def test_two_rank_launch_gloo(pkg):
     out = subprocess.check_output(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-selftest", "--streams", "3", "--steps", "7", "--warmup", "2"],
+         os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-selftest", "--streams", "3", "--steps", "7", "--warmup", "2",
+         "--blocks", "0"],
         env=env, cwd=ROOT, stderr=subprocess.STDOUT, timeout=240).decode()
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out  # rank 0 only

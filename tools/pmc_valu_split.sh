@@ -7,7 +7,7 @@ export VH_SERIAL=1
 for v in "" _nostereo _noflow; do
   OUT=gpurun_out/pmc_split$v
   rm -rf $OUT
-  VISO_HIP_LIB=$PWD/hls-final-visual-odometry_amd/libviso_hip$v.so rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d $OUT -- python bench.py --no-cpu --no-other --no-exclusive --no-e2e --no-flow --streams 128 --steps 4 --warmup 2 --blocks 1 > $OUT.log 2>&1 || { tail -3 $OUT.log; continue; }
+  VISO_HIP_LIB=$PWD/hls-final-visual-odometry_amd/libviso_hip$v.so rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d $OUT -- python bench.py --full --no-cpu --no-other --no-exclusive --no-e2e --no-flow --streams 128 --steps 4 --warmup 2 --blocks 1 > $OUT.log 2>&1 || { tail -3 $OUT.log; continue; }
   python - "$OUT" "${v:-shipped}" <<'PY'
 import csv, glob, sys, os
 f = max(glob.glob(os.path.join(sys.argv[1], "*", "*counter_collection.csv")), key=os.path.getmtime)

@@ -3,12 +3,12 @@
 #   tools/vote_trace.sh B NB LANES [STEPS]
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-rm -rf $R/gpurun_out/vtrace
-rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/vtrace -- python3 $R/bench.py --no-cpu --no-other --no-exclusive --no-e2e-host --steps 5 --warmup 2 --blocks 1 --e2e-steps-per-batch $1 --e2e-batches $2 --e2e-lanes $3 --e2e-steps ${4:-48} > $R/gpurun_out/vtrace.json 2> $R/gpurun_out/vtrace.err
-python3 - <<'PY'
-import csv, glob, os
-R = os.environ["GRAFT_REPO_ROOT"]
-f = glob.glob(R + "/gpurun_out/vtrace/**/*kernel_trace.csv", recursive=True)[0]
+T=${VTRACE_DIR:-$R/results/vtrace}
+rm -rf "$T" && mkdir -p "$(dirname "$T")"
+rocprofv3 --kernel-trace --output-format csv -d "$T" -- python3 $R/bench.py --full --no-cpu --no-other --no-exclusive --no-e2e-host --steps 5 --warmup 2 --blocks 1 --e2e-steps-per-batch $1 --e2e-batches $2 --e2e-lanes $3 --e2e-steps ${4:-48} > "$T.json" 2> "$T.err"
+python3 - "$T" <<'PY'
+import csv, glob, sys
+f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = [r for r in csv.DictReader(open(f))]
 sw = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id"), r.get("Stream_Id", "")) for r in rows if "vote_sweep" in r["Kernel_Name"]]
 mk = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if "match_kernel" in r["Kernel_Name"]]
