@@ -204,7 +204,7 @@ detect_nms_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_t *__
 // ---------------------------------------------------------- detect_nms (fast)
 // Same algorithm with nms_n as a compile-time constant (the values that occur in
 // practice: 1..4) so that every LDS offset is an immediate and every loop is
-// unrolled, and with the image tile staged by aligned 4-byte loads.  Requires
+// unrolled, and with the image tile staged by 16-byte loads (4-byte aligned).  Requires
 // 4-byte aligned rows (base, bpl and stream stride multiples of 4); anything
 // else takes the generic kernel above.
 #ifdef VH_EMIT_TIMING
@@ -238,14 +238,30 @@ extern "C" int32_t vh_debug_emit_timing(unsigned long long *out, int32_t reset) 
 #define VH_ETICK_INIT do { } while (0)
 #endif
 
+#ifdef VH_EXP_DET_STOP  // timing-only builds (EXTRA=-DVH_EXP_DET_STOP=k): stop after phase k (1 image tile, 2 filters,
+// 3 block extrema, 4 window checks) and leave empty records, so that the SQ_INSTS_VALU differences between the builds
+// split the kernel's instructions by phase.  No features are found.  (The runtime condition keeps the phases before
+// the stop from being optimised away.)
+#define VH_DET_STOP(k)                                                                                   \
+  if (VH_EXP_DET_STOP == (k) && g.nbx > 0) {                                                              \
+    const int32_t sbx = bx0 + tid % T::TBX, sby = by0 + tid / T::TBX;                                     \
+    if (sbx < g.nbx && sby < g.nby) rec[(int64_t)id * g.nblocks + sby * g.nbx + sbx] = ~0ull;              \
+    return;                                                                                               \
+  }
+#else
+#define VH_DET_STOP(k) do { } while (0)
+#endif
+
 template <int N> struct DetTile {
   static constexpr int N1 = N + 1, TBX = 32, TBY = 8;
   static constexpr int FW = TBX * N1 + 2 * N, FH = TBY * N1 + 2 * N;
   static constexpr int IW = FW + 4, IH = FH + 4;
   // Tile origins are 32*N1 columns apart, so response column 0 always sits at byte OFF of an aligned dword
   static constexpr int OFF = (VH_MARGIN - 2) & 3;
-  static constexpr int DW = (IW + 3 + 3) / 4;  // dwords per staged row (room for the alignment offset)
+  // dwords per staged row (room for the alignment offset), a whole number of 16-byte chunks
+  static constexpr int DW = ((IW + 3 + 3) / 4 + 3) / 4 * 4;
   static constexpr int IP = DW * 4;
+  static constexpr int NC = DW / 4;  // 16-byte chunks per staged row
   // The filter pass works on groups of PX = 2 or 4 adjacent response columns, two per register: column
   // cx is column OFF + cx of the staged row and of the response rows (pitch FP, int16).  A lane
   // filters one group over ROWS consecutive rows after 4 rows of run-in, SEG = number of row
@@ -305,32 +321,37 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
   const int32_t ax0 = ix0 - T::OFF;  // a multiple of 4 (DetTile::OFF)
   VH_DTICK_INIT;
 
-  // 1. stage the image tile with aligned dword loads (zero outside the image).  All loads of a lane
-  //    are issued before the first is stored: as a rolled load-store loop this stage was 4 dependent
-  //    HBM round trips and 40 % of a workgroup's life.  Out-of-image dwords are loaded from a clamped
-  //    (valid) address and zeroed afterwards, so that no load sits behind a branch.
+  // 1. stage the image tile, one 16-byte load per lane and chunk (224 chunks at nms_n = 2: one load per
+  //    lane).  All loads of a lane are issued before the first is stored: as a rolled load-store loop
+  //    this stage was 4 dependent HBM round trips and 40 % of a workgroup's life.  Nothing is zeroed:
+  //    staged bytes outside the image (past the end of a row: the next row's first bytes; past the
+  //    last row: the clamped end of the image) only feed responses beyond the clipping limits
+  //    W-1-margin / H-1-margin, which neither the block extrema nor the window checks read.  A chunk
+  //    that holds a byte the responses inside the limits need (image column <= W-6, row <= H-6) ends
+  //    rows before the image does, so the clamp never moves it; every other chunk is clamped into it.
   {
-    constexpr int NLD = (T::IH * T::DW + 255) / 256;
-    uint32_t stg[NLD];
-    bool inside[NLD];
+    constexpr int NLD = (T::IH * T::NC + 255) / 256;
+    typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    const uint32_t last = (uint32_t)g.Hm * (uint32_t)g.bplm - 16u;  // (images are <= 2^28 bytes: the launcher rejects larger ones)
+    u32x4 stg[NLD];
 #pragma unroll
     for (int32_t i = 0; i < NLD; i++) {
-      const int32_t k = min(tid + 256 * i, T::IH * T::DW - 1);
-      const int32_t r = k / T::DW, c = k - r * T::DW;
-      const int32_t gy = iy0 + r, gx = ax0 + 4 * c;
-      stg[i] = *(const uint32_t *)(I + (int64_t)min(gy, g.Hm - 1) * g.bplm + min(gx, g.bplm - 4));
-      inside[i] = gy < g.Hm && gx < g.bplm;
+      const int32_t k = min(tid + 256 * i, T::IH * T::NC - 1);
+      const int32_t r = k / T::NC, c = k - r * T::NC;
+      stg[i] = *(const u32x4a4 *)(I + min((uint32_t)(iy0 + r) * (uint32_t)g.bplm + (uint32_t)(ax0 + 16 * c), last));
     }
     __builtin_amdgcn_sched_barrier(0);  // (left alone the scheduler pairs each load with its store again)
 #pragma unroll
     for (int32_t i = 0; i < NLD; i++) {
       const int32_t k = tid + 256 * i;
-      if (k < T::IH * T::DW) ((uint32_t *)sI)[k] = inside[i] ? stg[i] : 0u;
+      if (k < T::IH * T::NC) ((u32x4 *)sI)[k] = stg[i];
     }
   }
   __syncthreads();
 
   VH_DTICK(0);
+  VH_DET_STOP(1);
   // 2. blob / checkerboard responses, PX columns per lane and two columns per register: the row
   //    sums live in the 16-bit halves of a dword and are added with plain 32-bit adds (full-rate
   //    instructions; every field stays in [0, 65535] through every intermediate, so no carry or
@@ -410,6 +431,7 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
   }
   __syncthreads();  // responses complete; the image tile is dead from here on
   VH_DTICK(1);
+  VH_DET_STOP(2);
 
   // 3. NMS (Neubeck/Van Gool alg. 4, matcher.cpp:381-466).  The dominance test
   //    "no strictly smaller value in the (2n+1)^2 window outside the block"
@@ -417,10 +439,11 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
   //    its own block, the same as "the candidate equals the minimum of the whole
   //    window".  The window is clipped at W-1-margin / H-1-margin on the high
   //    side only, which row/column replication reproduces.  (a) One lane per
-  //    block finds the four block extrema (first in scan order,
-  //    matcher.cpp:393-417) and applies the threshold (matcher.cpp:427,439,451,
-  //    463); only ~13 % of them pass it on typical images, and those are queued
-  //    in LDS.  (b) The queued candidates are checked one per lane by reading
+  //    block finds the values of the four block extrema and applies the
+  //    threshold (matcher.cpp:427,439,451,463); only ~13 % of them pass it on
+  //    typical images, and those are queued in LDS.  (b) The queued candidates
+  //    are located in their block (first in scan order, matcher.cpp:393-417)
+  //    and checked one per lane by reading
   //    their whole window: far fewer instructions than window extrema for every
   //    pixel, and the queue keeps all lanes of the checking waves busy.
   const int32_t xlim = min(max((g.Wm - 1 - VH_MARGIN) - fx0, 0), T::FW - 1);
@@ -429,25 +452,27 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
   const int32_t bx = bx0 + lbx, by = by0 + lby;
   const bool have_block = bx < g.nbx && by < g.nby;
   const int32_t fx = N + lbx * N1, fy = N + lby * N1;
-  // queues: [0] minima, [1] maxima; entry = owner | type << 8 | (PACKED ? extremum : row << 3 | column of it in the block) << 16
-  // With odd N a block row is N1/2 aligned dwords of the response rows, so (a) takes the block
-  // extrema with packed 16-bit min/max over whole dwords -- the VALUE only; where in the block it
-  // first occurs is looked up in (b), for the ~13 % that are candidates at all.
-  constexpr bool PACKED = (N & 1) != 0;
+  // queues: [0] minima, [1] maxima; entry = owner | type << 8 | extremum << 16.  (a) takes the block
+  // extrema -- the VALUE only: where in the block it first occurs is looked up in (b), for the ~13 %
+  // that are candidates at all.  With odd N a block row is N1/2 aligned dwords of the response rows,
+  // min/max over whole dwords with packed 16-bit ops; with even N over the single responses (v_min3 /
+  // v_max3 chains: 8 instructions per plane at N = 2, where value-and-position keys took 35).
   uint32_t *sQueue = (uint32_t *)sX;             // [2][512]
   uint16_t *sCode = (uint16_t *)(sQueue + 1024); // [256][4]: position code of each (block, type) that survives
-  __shared__ int32_t sQueueN[2];
-  if (tid < 2) sQueueN[tid] = 0;
+  __shared__ uint32_t sQueueN;                   // queue lengths: minima | maxima << 16 (each <= 512)
+  if (tid == 0) sQueueN = 0;
   ((uint2 *)sCode)[tid] = make_uint2(VH_NO_CODE * 0x00010001u, VH_NO_CODE * 0x00010001u);
   __syncthreads();
   {
     typedef int16_t i16x2 __attribute__((ext_vector_type(2)));
     const int32_t lane = tid & 63;
+    bool cand[4];      // type = 2 * plane + (0: block minimum, 1: block maximum)
+    uint32_t ext[4];
 #pragma unroll
     for (int32_t plane = 0; plane < 2; plane++) {
       const int16_t *b = (plane ? sF2 : sF1) + fy * T::FP + fx + T::OFF;
-      int32_t vn, vx, pn = 0, px = 0;
-      if (PACKED) {
+      int32_t vn, vx;
+      if (N & 1) {
         const i16x2 *bw = (const i16x2 *)b;  // fx + OFF and FP are even
         i16x2 mn = bw[0], mx = mn;
 #pragma unroll
@@ -463,99 +488,108 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
         vn = min((int32_t)mn.x, (int32_t)mn.y);
         vx = max((int32_t)mx.x, (int32_t)mx.y);
       } else {
-        // value and scan position in one key: min over (value << 6 | kk) is the smallest value at its FIRST
-        // position in scan order, max over (value << 6 | 63 - kk) the largest value at its first position --
-        // the reference's strict `<` / `else if >` updates (matcher.cpp:397-405; the `else` never matters:
-        // a value below the running minimum cannot exceed the running maximum).  Stored responses are
-        // f + 8192 in [0, 16383], kk = row << 3 | column <= 36.  One v_lshl_add per key and one
-        // v_min3 / v_max3 per two pixels instead of two compares and four selects per pixel.
-        uint32_t kmin = 0xFFFFFFFFu, kmax = 0u;
+        vn = vx = b[0];
 #pragma unroll
-        for (int32_t j = 0; j < N1; j++) {
-#pragma unroll
-          for (int32_t i = 0; i < N1; i++) {
-            const uint32_t cur = (uint32_t)(uint16_t)b[j * T::FP + i], kk = (uint32_t)((j << 3) | i);
-            kmin = min(kmin, (cur << 6) + kk);
-            kmax = max(kmax, (cur << 6) + (63u - kk));
-          }
+        for (int32_t k = 1; k < N1 * N1; k++) {
+          const int32_t cur = b[(k / N1) * T::FP + k % N1];
+          vn = min(vn, cur);
+          vx = max(vx, cur);
         }
-        vn = (int32_t)(kmin >> 6); pn = (int32_t)(kmin & 63u);
-        vx = (int32_t)(kmax >> 6); px = 63 - (int32_t)(kmax & 63u);
       }
+      cand[2 * plane] = have_block && vn <= T::BIAS - g.tau;
+      cand[2 * plane + 1] = have_block && vx >= T::BIAS + g.tau;
+      ext[2 * plane] = (uint32_t)vn;
+      ext[2 * plane + 1] = (uint32_t)vx;
+    }
+    // one LDS atomic per wave reserves the wave's entries of both queues (queue mm: the plane 0
+    // candidates of type mm, then the plane 1 ones)
+    uint64_t bal[4];
 #pragma unroll
-      for (int32_t mm = 0; mm < 2; mm++) {  // 0: the block minimum, 1: the block maximum
-        const bool cand = have_block && (mm ? vx >= T::BIAS + g.tau : vn <= T::BIAS - g.tau);
-        const uint32_t payload = PACKED ? (uint32_t)(mm ? vx : vn) : (uint32_t)(mm ? px : pn);
-        const uint64_t bal = __ballot(cand);
-        if (bal) {  // wave-uniform
-          int32_t base = 0;
-          if (lane == 0) base = atomicAdd(&sQueueN[mm], (int32_t)__popcll(bal));
-          base = __builtin_amdgcn_readfirstlane(base);
-          const int32_t rank = (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-          if (cand) sQueue[mm * 512 + base + rank] = (uint32_t)tid | ((uint32_t)(2 * plane + mm) << 8) | (payload << 16);
-        }
+    for (int32_t t = 0; t < 4; t++) bal[t] = __ballot(cand[t]);
+    const uint32_t n0 = (uint32_t)__popcll(bal[0]), n1 = (uint32_t)__popcll(bal[1]);
+    const uint32_t add = (n0 + (uint32_t)__popcll(bal[2])) | ((n1 + (uint32_t)__popcll(bal[3])) << 16);
+    if (add) {  // wave-uniform
+      uint32_t base = 0;
+      if (lane == 0) base = atomicAdd(&sQueueN, add);
+      base = __builtin_amdgcn_readfirstlane(base);
+#pragma unroll
+      for (int32_t t = 0; t < 4; t++) {
+        const int32_t mm = t & 1;
+        const uint32_t first = ((base >> (16 * mm)) & 0xFFFFu) + (t >= 2 ? (mm ? n1 : n0) : 0u);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[t], 0u));
+        if (cand[t]) sQueue[mm * 512 + first + rank] = (uint32_t)tid | ((uint32_t)t << 8) | (ext[t] << 16);
       }
     }
   }
   __syncthreads();
   VH_DTICK(2);
+  VH_DET_STOP(3);
   {
-    // waves 0-1 check the minima, waves 2-3 the maxima.  Tiles that do not touch
-    // the high-side clipping limits (almost all) address the window relative to
-    // its top-left corner, so that every read offset is an immediate.
-    const int32_t mm = __builtin_amdgcn_readfirstlane(tid >> 7);
-    const int32_t nq = sQueueN[mm];
+    // Both queues are checked as one list (the minima, then the maxima) by all four waves: ~130
+    // candidates fill two waves and a few lanes of a third, where one queue per wave pair left two
+    // waves nearly empty.  A wave whose candidates are all minima (all maxima) takes the window
+    // minimum (maximum) only; the one wave that holds both kinds takes both and selects per lane.
+    // Tiles that do not touch the high-side clipping limits (almost all) address the window relative
+    // to its top-left corner, so that every read offset is an immediate.
+    const int32_t n0 = (int32_t)(sQueueN & 0xFFFFu), ntot = n0 + (int32_t)(sQueueN >> 16);
     const bool unclipped = xlim == T::FW - 1 && ylim == T::FH - 1;
-    auto check = [&](auto is_max, auto no_clip) {
-      for (int32_t e = tid & 127; e < nq; e += 128) {
-        const uint32_t q = sQueue[mm * 512 + e];
-        const int32_t owner = q & 255, type = (q >> 8) & 3;
-        const int32_t ofy = N + (owner / T::TBX) * N1, ofx = N + (owner % T::TBX) * N1;  // the owner's block
-        const int16_t *F = ((type & 2) ? sF2 : sF1) + T::OFF;
-        int32_t bj = 0, bi = 0;  // the extremum's row and column in the block
-        if (PACKED) {
-          // first occurrence of the extremum in scan order (matcher.cpp:393-417: strict comparisons, the first one stays)
-          const int32_t val = (int32_t)(q >> 16);
-          const int16_t *bb = F + ofy * T::FP + ofx;
+    // kind: 0 minima only, 1 maxima only, 2 both
+    auto check = [&](auto kind, auto no_clip, int32_t e) {
+      const uint32_t q = sQueue[e < n0 ? e : 512 + e - n0];
+      const int32_t owner = q & 255, type = (q >> 8) & 3;
+      const int32_t ofy = N + (owner / T::TBX) * N1, ofx = N + (owner % T::TBX) * N1;  // the owner's block
+      const int16_t *F = ((type & 2) ? sF2 : sF1) + T::OFF;
+      // first occurrence of the extremum in scan order (matcher.cpp:393-417: strict comparisons, the first one
+      // stays); the value is in the block, so where no earlier position holds it the last one does
+      const int32_t val = (int32_t)(q >> 16);
+      const int16_t *bb = F + ofy * T::FP + ofx;
+      int32_t pos = (N << 6) | N;  // row << 6 | column in the block
 #pragma unroll
-          for (int32_t idx = N1 * N1 - 1; idx >= 0; idx--) {
-            const bool eq = bb[(idx / N1) * T::FP + idx % N1] == val;
-            bj = eq ? idx / N1 : bj; bi = eq ? idx % N1 : bi;
-          }
-        } else {
-          bj = (q >> 19) & 7; bi = (q >> 16) & 7;
+      for (int32_t idx = N1 * N1 - 2; idx >= 0; idx--)
+        pos = bb[(idx / N1) * T::FP + idx % N1] == val ? (((idx / N1) << 6) | (idx % N1)) : pos;
+      const int32_t bj = pos >> 6, bi = pos & 63;
+      const int32_t cy = ofy + bj, cx = ofx + bi;
+      int32_t v[WN * WN];
+      if (decltype(no_clip)::value) {
+        const int16_t *w = F + (cy - N) * T::FP + (cx - N);
+#pragma unroll
+        for (int32_t j = 0; j < WN; j++)
+#pragma unroll
+          for (int32_t k = 0; k < WN; k++) v[j * WN + k] = w[j * T::FP + k];
+      } else {
+        int32_t col[WN];
+#pragma unroll
+        for (int32_t k = 0; k < WN; k++) col[k] = min(cx - N + k, xlim);
+#pragma unroll
+        for (int32_t j = 0; j < WN; j++) {
+          const int16_t *row = F + min(cy - N + j, ylim) * T::FP;
+#pragma unroll
+          for (int32_t k = 0; k < WN; k++) v[j * WN + k] = row[col[k]];
         }
-        const int32_t cy = ofy + bj, cx = ofx + bi;
-        int32_t v[WN * WN];
-        if (decltype(no_clip)::value) {
-          const int16_t *w = F + (cy - N) * T::FP + (cx - N);
-#pragma unroll
-          for (int32_t j = 0; j < WN; j++)
-#pragma unroll
-            for (int32_t k = 0; k < WN; k++) v[j * WN + k] = w[j * T::FP + k];
-        } else {
-          int32_t col[WN];
-#pragma unroll
-          for (int32_t k = 0; k < WN; k++) col[k] = min(cx - N + k, xlim);
-#pragma unroll
-          for (int32_t j = 0; j < WN; j++) {
-            const int16_t *row = F + min(cy - N + j, ylim) * T::FP;
-#pragma unroll
-            for (int32_t k = 0; k < WN; k++) v[j * WN + k] = row[col[k]];
-          }
-        }
-        const int32_t centre = v[N * WN + N];
-        int32_t ext = centre;
-#pragma unroll
-        for (int32_t k = 0; k < WN * WN; k++) ext = decltype(is_max)::value ? max(ext, v[k]) : min(ext, v[k]);
-        if (ext == centre) sCode[owner * 4 + type] = (uint16_t)((bj << 6) | bi);
       }
+      const int32_t centre = v[N * WN + N];
+      int32_t emin = centre, emax = centre;
+#pragma unroll
+      for (int32_t k = 0; k < WN * WN; k++) {
+        if (decltype(kind)::value != 1) emin = min(emin, v[k]);
+        if (decltype(kind)::value != 0) emax = max(emax, v[k]);
+      }
+      const int32_t ext = decltype(kind)::value == 0 ? emin : decltype(kind)::value == 1 ? emax : ((type & 1) ? emax : emin);
+      if (ext == centre) sCode[owner * 4 + type] = (uint16_t)((bj << 6) | bi);
     };
-    if (mm) { if (unclipped) check(std::true_type{}, std::true_type{}); else check(std::true_type{}, std::false_type{}); }
-    else { if (unclipped) check(std::false_type{}, std::true_type{}); else check(std::false_type{}, std::false_type{}); }
+    typedef std::integral_constant<int, 0> KMin;
+    typedef std::integral_constant<int, 1> KMax;
+    typedef std::integral_constant<int, 2> KBoth;
+    for (int32_t e = tid; e < ntot; e += 256) {
+      const int32_t e0 = __builtin_amdgcn_readfirstlane(e & ~63);  // the wave's first list index (wave-uniform)
+      if (e0 + 63 < n0) { if (unclipped) check(KMin{}, std::true_type{}, e); else check(KMin{}, std::false_type{}, e); }
+      else if (e0 >= n0) { if (unclipped) check(KMax{}, std::true_type{}, e); else check(KMax{}, std::false_type{}, e); }
+      else { if (unclipped) check(KBoth{}, std::true_type{}, e); else check(KBoth{}, std::false_type{}, e); }
+    }
   }
   __syncthreads();
   VH_DTICK(3);
+  VH_DET_STOP(4);
   uint32_t codes[4];
   {
     const uint2 cw = ((const uint2 *)sCode)[tid];

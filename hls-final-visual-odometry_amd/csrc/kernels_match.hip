@@ -1136,7 +1136,7 @@ void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32
   //    workgroups) 104.2-105.2, 22 units (five workgroups) 104.8-105.1 -- the window is one allocation unit wide, because
   //    it is the arithmetic of what fits beside what (detect_nms 14 units, emit_features 21), and it moves with those.
   //    Same rule: 1080p 18.5 -> 19.2, KITTI + noise (tested loops) 73.2 -> 74.9, mono flow 140.7 -> 144.7, S = 32 / 64 /
-  //    128 streams 93.0 -> 97.8 / 102.7 -> 104.9 / 105.7 -> 105.8.  4K (detect_nms<3>: 22 units, 69 registers) wants FIVE
+  //    128 streams 93.0 -> 97.8 / 102.7 -> 104.9 / 105.7 -> 105.8.  4K (detect_nms<3>: 22 units, 69 registers; 79 now) wants FIVE
   //    workgroups instead: 21 / 22 / 23 / 24 / 25 / 26 units = 3.67 / 3.94 / 4.08 / 4.08 / 4.08 / 3.96 against 3.68 -- the
   //    caller picks the units per detector (engine.hip: match_queued).
   // VH_FLOW_WGS / VH_FLOW_LDS_PAD override both (experiments).
