@@ -19,7 +19,7 @@ def parity(pkg, ob, oracle, img, dims, n, tau, min_feats):
     got = pkg.compute_features(p, img, dims)
     want = oracle.compute_features(po, img, dims)
     assert len(want[1]) > min_feats, (n, dims, tau, len(want[1]))
-    # [0]: the sparse pass (nms_n_sparse = 3n: detect_nms_fast<3> at n = 1), [1]: the dense one
+    # [0]: the sparse pass (nms_n_sparse = 4n, max(n, 10) once 4n > 10: detect_nms_fast<4> at n = 1), [1]: the dense one
     assert np.array_equal(got[0], want[0]), (n, dims, tau, "sparse")
     assert np.array_equal(got[1], want[1]), (n, dims, tau, "dense")
 
