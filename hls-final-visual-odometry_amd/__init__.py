@@ -65,6 +65,7 @@ ABI_SYMBOLS = (
     "vh_default_mono_params", "vh_estimate_motion_mono", "vh_group_estimate_motion_mono",
     "vh_group_post_begin", "vh_group_post_finish", "vh_group_post_finish_mono",
     "vh_group_post_device_config", "vh_group_post_begin_device", "vh_group_post_finish_device",
+    "vh_sequence_create", "vh_sequence_push_back_device", "vh_sequence_push_back", "vh_sequence_position",
 )
 
 
@@ -197,6 +198,10 @@ def _lib():
             "vh_group_post_begin_device": [vp, i32, i32, f32, f32, vp, vp, vp, vp, i32],
             "vh_group_post_finish_device": [vp, i32, vp, vp, vp, vp, i32, vp],
             "vh_group_search_stats": [vp, vp, vp],
+            "vh_sequence_create": [vp, i32, i32, i32, i32, vp],
+            "vh_sequence_push_back_device": [vp, vp, vp, i64, vp, i32],
+            "vh_sequence_push_back": [vp, vp, vp, i64, vp, i32],
+            "vh_sequence_position": [vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -574,6 +579,54 @@ class StreamGroup:
         n = C.c_int64(0)
         _check(_lib().vh_group_profile_read(self._h, name.encode(), C.byref(ms), C.byref(n)), "vh_group_profile_read")
         return ms.value, n.value
+
+
+# ------------------------------------------------------------------ one camera's consecutive frames in lock step
+class SequenceGroup(StreamGroup):
+    """Consecutive frames of ONE camera in the rows of a group (vh_sequence_*): each push brings a chunk of
+    n <= max_frames frames, and after matching row r holds the pair frame F+r-1 -> frame F+r (F = position()[0]), row 0
+    linking to the last frame of the previous chunk.  Row 0 of a sequence's first chunk and the rows >= n of a short
+    chunk are empty.  Every StreamGroup getter and post step reads "stream s" as "row s"; self.S is max_frames."""
+
+    def __init__(self, max_frames: int, param: Params | None = None, device: int = 0,
+                 max_features: int = 0, max_matches: int = 0):
+        self.param = param if param is not None else Params.default()
+        self.S = int(max_frames)
+        h = C.c_void_p()
+        _check(_lib().vh_sequence_create(C.byref(self.param), device, self.S, max_features, max_matches, C.byref(h)),
+               "vh_sequence_create")
+        self._h = h
+
+    def pushBack(self, I1, I2=None, dims=None):
+        """I1/I2: (n, H, bpl) uint8 numpy arrays, frames F .. F+n-1 of the sequence (I2 None: mono)."""
+        I1 = np.ascontiguousarray(I1, dtype=np.uint8)
+        assert I1.ndim == 3 and 1 <= I1.shape[0] <= self.S
+        if I2 is not None:
+            I2 = np.ascontiguousarray(I2, dtype=np.uint8)
+            assert I2.shape == I1.shape
+        if dims is None:
+            dims = [I1.shape[2], I1.shape[1], I1.shape[2]]
+        _check(_lib().vh_sequence_push_back(self._h, _ptr(I1), _ptr(I2), I1.shape[1] * I1.shape[2], _dims(dims),
+                                            I1.shape[0]), "vh_sequence_push_back")
+
+    def pushBackDevice(self, ptr1: int, ptr2: int | None, stride_bytes: int, dims, n_frames: int):
+        """Frame F+r at ptr1 + r * stride_bytes (and ptr2 + ...; None: mono), device memory."""
+        _check(_lib().vh_sequence_push_back_device(self._h, C.c_void_p(ptr1), C.c_void_p(ptr2) if ptr2 else None,
+                                                   int(stride_bytes), _dims(dims), int(n_frames)),
+               "vh_sequence_push_back_device")
+
+    def position(self):
+        """-> (index within the sequence of row 0's current frame, rows valid in the last push)."""
+        first = C.c_int64(0); n = C.c_int32(0)
+        _check(_lib().vh_sequence_position(self._h, C.byref(first), C.byref(n)), "vh_sequence_position")
+        return first.value, n.value
+
+    def matchFeaturesPrior(self, method: int, Tr_delta):
+        """matchFeatures with a motion prior per row of the last chunk: Tr_delta [n, 4, 4]."""
+        n = self.position()[1]
+        tr = np.ascontiguousarray(Tr_delta, dtype=np.float64).reshape(-1, 16)
+        assert tr.shape[0] == n, (tr.shape, n)
+        _check(_lib().vh_group_match_features_prior(self._h, int(method), _ptr(tr)), "vh_group_match_features_prior")
 
 
 # ------------------------------------------------------------------ stateless primitives

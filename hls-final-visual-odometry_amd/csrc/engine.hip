@@ -108,6 +108,11 @@ struct Group {
   int32_t *h_overflow = nullptr; // page-locked mirror for the asynchronous download
   int32_t pair_prev = 1;
   bool serial = false, own_post = false;
+  // Sequence handle (vh_sequence_*): the S rows of a slot are consecutive frames of one camera, a push brings a chunk of
+  // seq_n <= S of them and every match links row r to row r - 1 (row 0 to the last row of the previous chunk: vh_row_set).
+  bool seq = false;
+  int32_t seq_n = 0, seq_n_prev = 0;      // frames of the last chunk / of the one before
+  int64_t seq_first = 0, seq_total = 0;   // index in the sequence of the last chunk's first frame / frames pushed so far
 
   bool allocated = false;
   int32_t dims[3] = {0, 0, 0};
@@ -171,6 +176,20 @@ struct Group {
     if (own_stream) (void)hipStreamDestroy(own_stream);
   }
   int32_t pairs() const { return pair_cur | (pair_prev << 8); }
+  // feature sets: ring slots x (left, right) per row, and a sequence handle's empty pair after them (VhMatchArgs::seq_void)
+  size_t n_sets() const { return 2 * VH_RING * (size_t)S + (seq ? 2 : 0); }
+  // the role -> set mapping of the current step (vh_row_set), without the passes of a method
+  VhMatchArgs role_args() const {
+    VhMatchArgs a{};
+    a.S = S; a.pair_cur = pairs(); a.rows = S;
+    if (seq) {
+      a.rows = seq_n;
+      a.seq_prev_last = std::max(seq_n_prev - 1, 0);
+      a.seq_lo = seq_first == 0 ? 1 : 0;
+      a.seq_void = 2 * VH_RING * S;
+    }
+    return a;
+  }
   int32_t sync_all() {
     VH_HIP(hipStreamSynchronize(stream));
     VH_HIP(hipStreamSynchronize(match_stream));
@@ -318,7 +337,7 @@ struct Group {
       const int64_t per_axis = (p.match_binsize + blk - 1) / blk + 1;
       sets.stage_cap = (int32_t)std::min<int64_t>(per_axis * per_axis, cap);
     }
-    const size_t ns = 2 * VH_RING * (size_t)S;  // ring slots x (left, right) per stream
+    const size_t ns = n_sets();
     if ((rc = dmalloc(&sets.feat, ns * cap * 12, false))) return rc;
     if ((rc = dmalloc(&sets.f_uv, ns * cap, false))) return rc;
     if ((rc = dmalloc(&sets.s_uv, ns * cap, false))) return rc;
@@ -365,6 +384,7 @@ struct Group {
       if ((rc = dmalloc(&d_half, 2 * (size_t)S * g.bplm * g.Hm, false))) return rc;
     allocated = true;
     pair_cur = 0; pair_prev = 1; frames = 0; epoch = 0; last_method = -1; failed = false;
+    seq_n = seq_n_prev = 0; seq_first = seq_total = 0;
     host_matches.assign((size_t)S, {}); host_filtered.assign((size_t)S, 0);
     for (int k = 0; k < VH_RING; k++) ev_read_valid[k] = false;
     ev_post_valid[0] = ev_post_valid[1] = false; match_seq = 0;
@@ -418,19 +438,25 @@ struct Group {
   // pushBack: a failure after the ring has rotated leaves the new slot half written;
   // the roles are put back and the handle refuses to match (VH_ERR_STATE) until a
   // later push has succeeded.
-  int32_t push_device(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace) {
+  // rows: streams whose images are pushed (a sequence chunk: its frames; the counters of the other rows of the slot
+  // read 0); < 0: all S
+  int32_t push_device(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows = -1) {
     if (!dI1 || !d) return VH_ERR_INVALID_ARG;
+    if (rows < 0) rows = S;
     int32_t rc = ensure(d);
     if (rc != VH_OK) return rc;
     const int32_t old_cur = pair_cur, old_prev = pair_prev;
     const int64_t old_frames = frames;
-    rc = push_device_queued(dI1, dI2, stride, d, replace);
+    rc = push_device_queued(dI1, dI2, stride, d, replace, rows);
     if (rc != VH_OK) { pair_cur = old_cur; pair_prev = old_prev; frames = old_frames; failed = true; }
-    else failed = false;
+    else {
+      failed = false;
+      if (seq) { seq_n_prev = seq_n; seq_n = rows; seq_first = seq_total; seq_total += rows; }
+    }
     return rc;
   }
 
-  int32_t push_device_queued(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace) {
+  int32_t push_device_queued(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows) {
     int32_t rc = VH_OK;
     if (!replace && frames > 0) {  // ring buffer shift (matcher.cpp:64-79): prev <- cur, cur <- the slot used longest ago
       const int32_t fresh = (pair_cur + 1) % VH_RING;
@@ -458,14 +484,14 @@ struct Group {
     // two alternating streams lose 8 %.  VH_SUBBATCH=n overrides.
     const int32_t ncam = dI2 ? 2 : 1;
     static const int subbatch_env = [] { const char *ev = getenv("VH_SUBBATCH"); return ev ? atoi(ev) : 0; }();
-    const int64_t det_wgs = (int64_t)S * ncam * ((g.nblocks + 255) / 256);
+    const int64_t det_wgs = (int64_t)rows * ncam * ((g.nblocks + 255) / 256);
     // (a mono push is half the detection work of a stereo one: 4 sub-batches of 64 KITTI images leave emit_features with two
     //  rounds of workgroups per launch -- mono flow, S = 256: 1 / 2 / 4 / 8 sub-batches = 118 / 115 / 109 / 101 k frames/s)
     const int32_t subbatch = subbatch_env > 0 ? subbatch_env : (serial ? 1 : (int32_t)std::min<int64_t>(4, det_wgs / (ncam == 2 ? 12000 : 40000)));
-    const int32_t nsub = std::max(1, std::min(subbatch, S));
-    const int32_t ssub = (S + nsub - 1) / nsub;
-    for (int32_t s0 = 0; s0 < S; s0 += ssub) {
-      const int32_t sn = std::min(ssub, S - s0);
+    const int32_t nsub = std::max(1, std::min(subbatch, rows));
+    const int32_t ssub = (rows + nsub - 1) / nsub;
+    for (int32_t s0 = 0; s0 < rows; s0 += ssub) {
+      const int32_t sn = std::min(ssub, rows - s0);
       VhImages im{};
       im.base[0] = (const uint8_t *)dI1 + (int64_t)s0 * stride;
       im.base[1] = dI2 ? (const uint8_t *)dI2 + (int64_t)s0 * stride : nullptr;
@@ -488,8 +514,9 @@ struct Group {
     return VH_OK;
   }
 
-  int32_t push_host(const uint8_t *I1, const uint8_t *I2, int64_t stride, const int32_t d[3], int32_t replace) {
+  int32_t push_host(const uint8_t *I1, const uint8_t *I2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows = -1) {
     if (!I1 || !d) return VH_ERR_INVALID_ARG;
+    if (rows < 0) rows = S;
     int32_t rc = ensure(d);
     if (rc != VH_OK) return rc;
     const size_t isz = (size_t)d[2] * d[1];
@@ -509,10 +536,10 @@ struct Group {
       const uint8_t *src = k ? I2 : I1;
       d_stage[k] = d_stage_buf[sl][k];
       if (!src) continue;
-      if (stride == (int64_t)isz) {  // one transfer for all S images
-        VH_HIP(hipMemcpyAsync(d_stage[k], src, isz * S, hipMemcpyHostToDevice, cs));
+      if (stride == (int64_t)isz) {  // one transfer for all the images
+        VH_HIP(hipMemcpyAsync(d_stage[k], src, isz * rows, hipMemcpyHostToDevice, cs));
       } else {
-        for (int32_t s = 0; s < S; s++)
+        for (int32_t s = 0; s < rows; s++)
           VH_HIP(hipMemcpyAsync(d_stage[k] + isz * s, src + stride * s, isz, hipMemcpyHostToDevice, cs));
       }
     }
@@ -522,7 +549,7 @@ struct Group {
     if (!ev_h2d) VH_HIP(hipEventCreateWithFlags(&ev_h2d, hipEventDisableTiming));
     VH_HIP(hipEventRecord(ev_h2d, cs));
     if (!serial) VH_HIP(hipStreamWaitEvent(stream, ev_h2d, 0));
-    rc = push_device(d_stage[0], I2 ? d_stage[1] : nullptr, (int64_t)isz, d, replace);
+    rc = push_device(d_stage[0], I2 ? d_stage[1] : nullptr, (int64_t)isz, d, replace, rows);
     VH_HIP(hipEventSynchronize(ev_h2d));
     if (rc == VH_OK) {
       VH_HIP(hipEventRecord(ev_stage[sl], stream));
@@ -533,8 +560,8 @@ struct Group {
 
   // ---- match ---------------------------------------------------------------
   VhMatchArgs match_args(int32_t method) const {
-    VhMatchArgs a{};
-    a.S = S; a.pair_cur = pairs(); a.radius = p.match_radius; a.disp_tol = p.match_disp_tolerance;
+    VhMatchArgs a = role_args();
+    a.radius = p.match_radius; a.disp_tol = p.match_disp_tolerance;
     if (method == VH_METHOD_FLOW) {  // matcher.cpp:320-321
       a.npass = 2; a.pass[0] = {VH_SET_1C, VH_SET_1P, 1, 0}; a.pass[1] = {VH_SET_1P, VH_SET_1C, 1, 1};
     } else if (method == VH_METHOD_STEREO) {
@@ -636,8 +663,8 @@ struct Group {
     if (tr16) {  // hop 2 of the circle, per driving feature, behind the 1p -> 2p table of the launch above
       double *ht = h_prior_tr + (size_t)buf * 16 * S;
       VH_HIP(hipEventSynchronize(ev_tables[buf]));  // (recorded behind the copy that last read this slot, two matches ago; at once if never recorded)
-      memcpy(ht, tr16, sizeof(double) * 16 * (size_t)S);
-      VH_HIP(hipMemcpyAsync(d_prior_tr, ht, sizeof(double) * 16 * (size_t)S, hipMemcpyHostToDevice, ms));
+      memcpy(ht, tr16, sizeof(double) * 16 * (size_t)a.rows);  // (a sequence chunk: one per frame pair)
+      VH_HIP(hipMemcpyAsync(d_prior_tr, ht, sizeof(double) * 16 * (size_t)a.rows, hipMemcpyHostToDevice, ms));
       { Scope sc(this, "quad_prior", ms); vh_launch_quad_prior(sets, a, d_prior_tr, p.f, p.cu, p.cv, p.base, d_best2[buf], ms); }
       VH_HIP(hipGetLastError());
     }
@@ -726,7 +753,7 @@ struct Group {
     if (!n || s < 0 || s >= S || which < 0 || which > 3 || capo < 0 || (capo > 0 && !out12)) return VH_ERR_INVALID_ARG;
     *n = 0;
     if (!allocated) return VH_OK;
-    const int32_t set = vh_role_set(S, pairs(), s, which);
+    const int32_t set = vh_row_set(role_args(), s, which);
     int32_t cnt = 0;
     VH_HIP(hipMemcpyAsync(&cnt, sets.count + set, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
     VH_HIP(hipStreamSynchronize(stream));
@@ -743,11 +770,12 @@ struct Group {
   int32_t get_counts(int32_t *nf, int32_t *nm) {
     if (!allocated) return VH_ERR_STATE;
     if (nf) {
-      std::vector<int32_t> all(2 * VH_RING * (size_t)S);
+      std::vector<int32_t> all(n_sets());
       VH_HIP(hipMemcpyAsync(all.data(), sets.count, sizeof(int32_t) * all.size(), hipMemcpyDeviceToHost, stream));
       VH_HIP(hipStreamSynchronize(stream));
+      const VhMatchArgs a = role_args();
       for (int32_t s = 0; s < S; s++)
-        for (int32_t r = 0; r < 4; r++) nf[4 * s + r] = all[vh_role_set(S, pairs(), s, r)];
+        for (int32_t r = 0; r < 4; r++) nf[4 * s + r] = all[vh_row_set(a, s, r)];
     }
     if (nm) {
       VH_HIP(hipMemcpyAsync(nm, d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
@@ -1338,7 +1366,7 @@ struct Group {
       const int32_t *f = m + 12 * (size_t)i;
       if (f[0] < 0 || f[0] >= dims[0] || f[1] < 0 || f[1] >= dims[1] || f[3] < 0 || f[3] > 3) return VH_ERR_INVALID_ARG;
     }
-    const int32_t set = vh_role_set(S, pairs(), 0, role);
+    const int32_t set = vh_row_set(role_args(), 0, role);
     const int32_t slot = (role >= 2) ? pair_cur : pair_prev;
     if (ev_read_valid[slot]) VH_HIP(hipStreamWaitEvent(stream, ev_read[slot], 0));
     { int32_t rz = zero_bin_counters(set, 1); if (rz) return rz; }  // also clears the count, set right below
@@ -1551,12 +1579,49 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
 int32_t vh_group_push_back_device(vh_group *g, const void *dI1, const void *dI2, int64_t stride_bytes,
                                   const int32_t dims[3], int32_t replace) {
   Group *gq = (Group *)g; ENTER(gq);
+  if (gq->seq) return VH_ERR_STATE;  // a sequence handle takes chunks (vh_sequence_push_back_device)
   return gq->push_device(dI1, dI2, stride_bytes, dims, replace);
 }
 int32_t vh_group_push_back(vh_group *g, const uint8_t *I1, const uint8_t *I2, int64_t stride_bytes,
                            const int32_t dims[3], int32_t replace) {
   Group *gq = (Group *)g; ENTER(gq);
+  if (gq->seq) return VH_ERR_STATE;
   return gq->push_host(I1, I2, stride_bytes, dims, replace);
+}
+
+// ---- sequence --------------------------------------------------------------
+int32_t vh_sequence_create(const vh_params *p, int32_t device, int32_t max_frames, int32_t max_features, int32_t max_matches,
+                           vh_group **out) {
+  if (!out) return VH_ERR_INVALID_ARG;
+  *out = nullptr;
+  Group *gq = nullptr;
+  const int32_t rc = group_new(p, device, max_frames, max_features, max_matches, &gq);
+  if (rc) return rc;
+  gq->seq = true;  // (before the first push: the feature sets are allocated there, with the empty pair of a sequence)
+  *out = (vh_group *)gq;
+  return VH_OK;
+}
+int32_t vh_sequence_push_back_device(vh_group *g, const void *dI1, const void *dI2, int64_t stride_bytes, const int32_t dims[3],
+                                     int32_t n_frames) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (!gq->seq) return VH_ERR_STATE;
+  if (n_frames < 1 || n_frames > gq->S) return VH_ERR_INVALID_ARG;
+  return gq->push_device(dI1, dI2, stride_bytes, dims, 0, n_frames);
+}
+int32_t vh_sequence_push_back(vh_group *g, const uint8_t *I1, const uint8_t *I2, int64_t stride_bytes, const int32_t dims[3],
+                              int32_t n_frames) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (!gq->seq) return VH_ERR_STATE;
+  if (n_frames < 1 || n_frames > gq->S) return VH_ERR_INVALID_ARG;
+  return gq->push_host(I1, I2, stride_bytes, dims, 0, n_frames);
+}
+int32_t vh_sequence_position(const vh_group *g, int64_t *first_frame, int32_t *n_frames) {
+  if (!g || !first_frame || !n_frames) return VH_ERR_INVALID_ARG;
+  const Group *gq = (const Group *)g;
+  if (!gq->seq) return VH_ERR_STATE;
+  *first_frame = gq->seq_first;
+  *n_frames = gq->seq_n;
+  return VH_OK;
 }
 int32_t vh_group_match_features(vh_group *g, int32_t method) {
   Group *gq = (Group *)g; ENTER(gq);

@@ -866,8 +866,8 @@ match_kernel(VhSets s, VhMatchArgs a, int32_t *__restrict__ best, int32_t *__res
 #ifdef VH_EXP_SKIP  // timing-only builds (tools/ab_bench.sh): 1 = no stereo passes, 2 = no flow passes; results are wrong
   if (VH_EXP_SKIP & (a.pass[pass].flow ? 2 : 1)) return;
 #endif
-  const int32_t qset = vh_role_set(a.S, a.pair_cur, stream, a.pass[pass].qset);
-  const int32_t cset = vh_role_set(a.S, a.pair_cur, stream, a.pass[pass].cset);
+  const int32_t qset = vh_row_set(a, stream, a.pass[pass].qset);
+  const int32_t cset = vh_row_set(a, stream, a.pass[pass].cset);
   uint4 *wD = sDesc + (threadIdx.x >> 6) * 256;
   uint32_t *wU = sAux + (threadIdx.x >> 6) * 128;
   uint32_t *wV = sAux2 + (SPEC ? 0 : (threadIdx.x >> 6) * 64);
@@ -885,8 +885,8 @@ match_kernel(VhSets s, VhMatchArgs a, int32_t *__restrict__ best, int32_t *__res
 // keeps the first strict minimum, all in double exactly as the reference
 // (sqrt is the correctly rounded IEEE one; du*du+dv*dv is exact in double).
 __global__ void match_prior_kernel(VhSets s, VhMatchArgs a, double u_, double v_, int32_t *__restrict__ best) {
-  const int32_t qset = vh_role_set(a.S, a.pair_cur, 0, a.pass[0].qset);
-  const int32_t cset = vh_role_set(a.S, a.pair_cur, 0, a.pass[0].cset);
+  const int32_t qset = vh_row_set(a, 0, a.pass[0].qset);
+  const int32_t cset = vh_row_set(a, 0, a.pass[0].cset);
   const int32_t nq = indexed_count(s, qset);
   const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nq) return;
@@ -947,8 +947,8 @@ __global__ void chain_kernel(VhSets s, VhMatchArgs a, int32_t method, const int3
                              int4 *__restrict__ chain, uint32_t *__restrict__ mask, uint32_t epoch,
                              int32_t *__restrict__ mchunk, int32_t nchm) {
   const int32_t stream = blockIdx.y;
-  const int32_t set1p = vh_role_set(a.S, a.pair_cur, stream, 0), set2p = vh_role_set(a.S, a.pair_cur, stream, 1);
-  const int32_t set1c = vh_role_set(a.S, a.pair_cur, stream, 2), set2c = vh_role_set(a.S, a.pair_cur, stream, 3);
+  const int32_t set1p = vh_row_set(a, stream, 0), set2p = vh_row_set(a, stream, 1);
+  const int32_t set1c = vh_row_set(a, stream, 2), set2c = vh_row_set(a, stream, 3);
   const int32_t n1p = indexed_count(s, set1p), n2p = indexed_count(s, set2p);
   const int32_t n1c = indexed_count(s, set1c), n2c = indexed_count(s, set2c);
   const int32_t *__restrict__ T = best + (int64_t)stream * 4 * s.cap;
@@ -1002,7 +1002,7 @@ __global__ void flow_keep_kernel(VhSets s, VhMatchArgs a, int4 *__restrict__ cha
                                  const uint32_t *__restrict__ mask, uint32_t epoch,
                                  int32_t *__restrict__ mchunk, int32_t nchm) {
   const int32_t stream = blockIdx.y;
-  const int32_t set1c = vh_role_set(a.S, a.pair_cur, stream, 2);
+  const int32_t set1c = vh_row_set(a, stream, 2);
   const int32_t n1c = indexed_count(s, set1c);
   int4 *__restrict__ ch = chain + 2 * (int64_t)stream * s.cap;
   for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n1c; i += gridDim.x * blockDim.x) {
@@ -1034,7 +1034,7 @@ emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restr
   if (tid == 0) mchunk_next[stream * nchm + chunk] = 0;
   int32_t sets[4];
 #pragma unroll
-  for (int32_t r = 0; r < 4; r++) sets[r] = vh_role_set(a.S, a.pair_cur, stream, r);
+  for (int32_t r = 0; r < 4; r++) sets[r] = vh_row_set(a, stream, r);
   const int32_t drive = (method == 2) ? sets[0] : sets[2];
   const int32_t n = indexed_count(s, drive);
   if (chunk * 256 >= n && chunk != nchm - 1) return;
@@ -1103,7 +1103,7 @@ emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restr
     // statistics of this launch for the host's loop policy: queries searched again / queries searched
     int32_t nq = 0;
 #pragma unroll
-    for (int32_t k = 0; k < 4; k++) if (k < a.npass) nq += indexed_count(s, vh_role_set(a.S, a.pair_cur, stream, a.pass[k].qset));
+    for (int32_t k = 0; k < 4; k++) if (k < a.npass) nq += indexed_count(s, vh_row_set(a, stream, a.pass[k].qset));
     // count, overflow flag and the launch's statistics also go straight to host-mapped memory: the host reads
     // them after the launch's event instead of through small device->host copies (each a blit kernel + a round trip)
     host_out[stream] = make_int4(base + tot, ov, redo[stream], nq);
@@ -1143,7 +1143,7 @@ void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32
   static const int wgs = [] { const char *e = getenv("VH_FLOW_WGS"); return e ? atoi(e) : 0; }();
   static const int pad_env = [] { const char *e = getenv("VH_FLOW_LDS_PAD"); return e ? atoi(e) : -1; }();
   const int32_t gx = wgs > 0 ? wgs : (grid_x > 0 ? (grid_x | 1) : (((s.max_tiles + 3) / 4) | 1));
-  dim3 grid(gx, m.npass, a.S);
+  dim3 grid(gx, m.npass, a.rows);
   static const size_t static_lds[2] = {
       [] { hipFuncAttributes at{}; return hipFuncGetAttributes(&at, (const void *)match_kernel<false>) == hipSuccess ? at.sharedSizeBytes : (size_t)0; }(),
       [] { hipFuncAttributes at{}; return hipFuncGetAttributes(&at, (const void *)match_kernel<true>) == hipSuccess ? at.sharedSizeBytes : (size_t)0; }()};
@@ -1155,7 +1155,7 @@ void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32
 void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *best,
                      int4 *chain, uint32_t *mask, uint32_t epoch, int32_t *mchunk, hipStream_t st) {
   const int32_t nchm = (s.cap + 255) / 256;
-  dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.S);
+  dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.rows);
   hipLaunchKernelGGL(chain_kernel, grid, dim3(256), 0, st, s, a, method, best, chain, mask, epoch, mchunk, nchm);
   if (method == 0)
     hipLaunchKernelGGL(flow_keep_kernel, grid, dim3(256), 0, st, s, a, chain, (const uint32_t *)mask, epoch, mchunk, nchm);
@@ -1165,6 +1165,8 @@ void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t metho
                             const int32_t *mchunk, int32_t *redo, int32_t *mchunk_next, void *host_out, void *host_matches,
                             hipStream_t st) {
   const int32_t nchm = (s.cap + 255) / 256;
+  // every row of the handle, a.rows or not: the rows a sequence chunk leaves empty read the empty set here and report 0
+  // matches (their chain tables were not written, their chunk counters are zero), and their counters are reset
   hipLaunchKernelGGL(emit_matches_kernel, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
                      (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches);
 }

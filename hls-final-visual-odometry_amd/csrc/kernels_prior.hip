@@ -18,8 +18,8 @@ namespace {
 __global__ void __launch_bounds__(128) quad_prior_kernel(VhSets s, VhMatchArgs a, const double *__restrict__ tr, double f, double cu, double cv,
                                                          double base, int32_t *__restrict__ best) {
   const int32_t stream = blockIdx.y;
-  const int32_t set1p = vh_role_set(a.S, a.pair_cur, stream, 0), set2p = vh_role_set(a.S, a.pair_cur, stream, 1);
-  const int32_t set2c = vh_role_set(a.S, a.pair_cur, stream, 3);
+  const int32_t set1p = vh_row_set(a, stream, 0), set2p = vh_row_set(a, stream, 1);
+  const int32_t set2c = vh_row_set(a, stream, 3);
   const int64_t cap = s.cap;
   const int32_t n1p = s.bin_start[(int64_t)set1p * (s.nbins + 1) + s.nbins], n2p = s.bin_start[(int64_t)set2p * (s.nbins + 1) + s.nbins];
   const int32_t n2c = s.bin_start[(int64_t)set2c * (s.nbins + 1) + s.nbins];
@@ -78,6 +78,6 @@ __global__ void __launch_bounds__(128) quad_prior_kernel(VhSets s, VhMatchArgs a
 
 void vh_launch_quad_prior(const VhSets &s, const VhMatchArgs &a, const double *tr, double f, double cu, double cv, double base, int32_t *best,
                           hipStream_t st) {
-  dim3 grid((uint32_t)((s.cap + 127) / 128 < 256 ? (s.cap + 127) / 128 : 256), a.S);
+  dim3 grid((uint32_t)((s.cap + 127) / 128 < 256 ? (s.cap + 127) / 128 : 256), a.rows);
   hipLaunchKernelGGL(quad_prior_kernel, grid, dim3(128), 0, st, s, a, tr, f, cu, cv, base, best);
 }

@@ -8,7 +8,9 @@
 //   set id    = pair*(2*S) + stream*2 + cam         (pair = ring slot 0..2; the
 //               current/previous roles move from slot to slot, never by copy:
 //               reference ring buffer src/matcher.cpp:64-79.  Three slots, so
-//               that detection of frame t+1 can run while frame t is matched)
+//               that detection of frame t+1 can run while frame t is matched.
+//               A sequence handle holds consecutive frames of one camera in the
+//               rows of a slot and two more, always empty, sets: vh_row_set)
 //
 //   feat      [set][cap][12] int32   the reference's packed record
 //                                    {u,v,0,c,d1..d8} (src/matcher.cpp:663-671)
@@ -144,6 +146,12 @@ struct VhMatchArgs {
   int32_t wide_keys;  // test hook (VH_FLOW_WIDE_KEYS): 1 = never the 16-bit position keys, 2 = always the 64-bit keys
   int32_t prior;      // quad with a motion prior (kernels_prior.hip): pass 1 is not searched by match_kernel, and its table is
                       // indexed by the driving feature i1p instead of by the query i2p
+  int32_t rows;       // rows (streams) the searches, chains and prior cover: S in group mode, the chunk's frames in sequence mode
+  // Sequence mode (vh_sequence_*, vh_row_set): the rows of a slot are consecutive frames of ONE camera.  -1: group mode;
+  // otherwise the row of the previous slot that holds the predecessor of row 0 (the last frame of the previous chunk).
+  int32_t seq_prev_last = -1;
+  int32_t seq_lo;     // sequence mode: rows [seq_lo, rows) are frame pairs (seq_lo = 1 on the first chunk: row 0 has no predecessor)
+  int32_t seq_void;   // sequence mode: set id of the (left) empty set that the other rows read -- zeroed once, never written
 };
 
 __host__ __device__ inline int32_t vh_set_id(int32_t S, int32_t pair, int32_t stream, int32_t cam) {
@@ -153,6 +161,17 @@ __host__ __device__ inline int32_t vh_set_id(int32_t S, int32_t pair, int32_t st
 __host__ __device__ inline int32_t vh_role_set(int32_t S, int32_t pairs, int32_t stream, int32_t role) {
   const int32_t pair = (role >= 2) ? (pairs & 0xFF) : (pairs >> 8);
   return vh_set_id(S, pair, stream, role & 1);
+}
+// The set of `role` for row `row` of a match launch, both modes (every kernel and host getter goes through this).
+//   group:    the stream's own slots, vh_role_set (row = stream).
+//   sequence: current roles (pair_cur, row, cam); previous roles (pair_cur, row - 1, cam) for row >= 1 and
+//             (pair_prev, seq_prev_last, cam) for row 0.  Rows outside [seq_lo, rows) read the empty set seq_void.
+__host__ __device__ inline int32_t vh_row_set(const VhMatchArgs &a, int32_t row, int32_t role) {
+  if (a.seq_prev_last < 0) return vh_role_set(a.S, a.pair_cur, row, role);
+  const int32_t cam = role & 1;
+  if (row < a.seq_lo || row >= a.rows) return a.seq_void + cam;
+  if (role >= 2) return vh_set_id(a.S, a.pair_cur & 0xFF, row, cam);
+  return row > 0 ? vh_set_id(a.S, a.pair_cur & 0xFF, row - 1, cam) : vh_set_id(a.S, a.pair_cur >> 8, a.seq_prev_last, cam);
 }
 
 struct VhImages {

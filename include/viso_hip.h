@@ -301,6 +301,39 @@ int32_t vh_group_set_stream(vh_group *g, void *hip_stream);
 int32_t vh_group_clear_stream(vh_group *g);
 int32_t vh_group_stream_wait_images(vh_group *g, void *hip_stream);
 
+/* ---- consecutive frames of ONE camera in one launch ---------------------- */
+/* A sequence handle is a vh_group whose rows ("streams") hold consecutive frames of one camera (stereo or mono), so
+ * that one sequence -- an offline replay, one sequence per GPU -- fills the GPU as a group of max_frames cameras does.
+ * Each push brings a chunk of n frames (1 <= n <= max_frames); with F frames pushed before it in the current sequence:
+ *   - row r < n holds the pair frame F+r-1 -> frame F+r: after vh_group_match_features(_prior) its match list is exactly
+ *     what a lone vh_matcher returns after pushing those two frames and matching with the same method, and its four
+ *     feature sets (vh_group_get_features: 1p/2p = frame F+r-1, 1c/2c = frame F+r) are that matcher's;
+ *   - row 0 links to the last frame of the previous chunk, so chunk boundaries lose no pair;
+ *   - on the first chunk of a sequence (F = 0) row 0 has no predecessor: it is an empty row -- 0 matches and 0 features
+ *     in every role -- and matching returns VH_OK;
+ *   - rows r >= n of a short chunk are empty rows too;
+ *   - a chunk whose dims differ from the previous chunk's starts a new sequence (F = 0), as vh_push_back does.
+ * Every frame is detected once.  The ring rotates one slot per chunk: detection of chunk k+1 overlaps matching of
+ * chunk k exactly as for a group.  Every vh_group_* call below works on a sequence handle with "stream s" read as
+ * "row s": vh_group_match_features, vh_group_match_features_prior (Tr_delta16[n][16], one motion per row of the last
+ * chunk), vh_group_get_matches(_all), vh_group_download_matches_async, vh_group_get_features, vh_group_get_counts,
+ * vh_group_streams (= max_frames), the post chains (vh_group_post_begin/_finish(_mono), vh_group_post_begin_device /
+ * vh_group_post_finish_device: empty rows come out as ok = 0 with no error) and vh_group_estimate_motion(_mono).
+ * vh_group_push_back(_device) on a sequence handle, and vh_sequence_push_back(_device) on a plain group, return
+ * VH_ERR_STATE; n_frames outside [1, max_frames] returns VH_ERR_INVALID_ARG.  Destroy with vh_group_destroy. */
+int32_t vh_sequence_create(const vh_params *p, int32_t device, int32_t max_frames, int32_t max_features,
+                           int32_t max_matches, vh_group **out);
+/* Frame F+r of the chunk at dI1 + r*stride_bytes (and dI2 + ..., NULL for mono), device memory, asynchronous as
+ * vh_group_push_back_device. */
+int32_t vh_sequence_push_back_device(vh_group *g, const void *dI1, const void *dI2, int64_t stride_bytes,
+                                     const int32_t dims[3], int32_t n_frames);
+/* Host images, same addressing (only the n_frames images are read). */
+int32_t vh_sequence_push_back(vh_group *g, const uint8_t *I1, const uint8_t *I2, int64_t stride_bytes,
+                              const int32_t dims[3], int32_t n_frames);
+/* *first_frame = F, the index within the sequence of row 0's current frame, and *n_frames = n, the rows valid in the
+ * last push (both 0 before the first push); both pointers are required. */
+int32_t vh_sequence_position(const vh_group *g, int64_t *first_frame, int32_t *n_frames);
+
 /* ---- stereo egomotion ------------------------------------- */
 
 /* VisualOdometryStereo::parameters and the calibration it reads
