@@ -66,6 +66,7 @@ ABI_SYMBOLS = (
     "vh_group_post_begin", "vh_group_post_finish", "vh_group_post_finish_mono",
     "vh_group_post_device_config", "vh_group_post_begin_device", "vh_group_post_finish_device",
     "vh_sequence_create", "vh_sequence_push_back_device", "vh_sequence_push_back", "vh_sequence_position",
+    "vh_refine_matches",
 )
 
 
@@ -202,6 +203,7 @@ def _lib():
             "vh_sequence_push_back_device": [vp, vp, vp, i64, vp, i32],
             "vh_sequence_push_back": [vp, vp, vp, i64, vp, i32],
             "vh_sequence_position": [vp, vp, vp],
+            "vh_refine_matches": [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -775,3 +777,14 @@ def match(param: Params, dims, method: int, m1p=None, m2p=None, m1c=None, m2c=No
                            _ptr(sets[2][0]), sets[2][1], _ptr(sets[3][0]), sets[3][1],
                            _ptr(out), cap, C.byref(n)), "vh_match")
     return out[:n.value].copy()
+
+
+def refine_matches(param: Params, dims, method: int, pm, I1p=None, I2p=None, I1c=None, I2c=None, device: int = 0):
+    """Stock libviso2's match refinement (param.refinement: 1 pixel, 2 sub-pixel) on the
+    records pm with the full-resolution images of the pair -> the refined records that are kept, in order."""
+    pm = np.ascontiguousarray(pm, dtype=P_MATCH_DTYPE).copy()
+    imgs = [None if I is None else np.ascontiguousarray(I, dtype=np.uint8) for I in (I1p, I2p, I1c, I2c)]
+    n = C.c_int32(0)
+    _check(_lib().vh_refine_matches(C.byref(param), device, int(method), _dims(dims), *[_ptr(I) for I in imgs],
+                                    _ptr(pm) if len(pm) else None, len(pm), C.byref(n)), "vh_refine_matches")
+    return pm[:n.value].copy()

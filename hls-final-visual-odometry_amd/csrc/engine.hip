@@ -138,6 +138,10 @@ struct Group {
   bool ev_down_valid = false;
   int32_t last_buf = 0;
   uint8_t *d_half = nullptr;                 // half-resolution images [S*2]
+  // refinement > 0 (kernels_refine.hip): full-resolution du/dv per feature set of the ring, written with the detection
+  // of a push, and the refined coordinates of each match-table buffer ([S][cap][2] float4)
+  VhRefine rf{};
+  float4 *d_ref2[2] = {nullptr, nullptr};
   uint64_t *d_rec = nullptr;
   int32_t *d_chunk_count = nullptr;
   int32_t *d_best = nullptr, *d_best2[2] = {nullptr, nullptr};
@@ -224,7 +228,7 @@ struct Group {
     device_bytes = 0;
     d_stage[0] = d_stage[1] = nullptr; stage_bytes = 0; ev_down_valid = false;
     for (int k = 0; k < 2; k++) d_stage_buf[k][0] = d_stage_buf[k][1] = nullptr, ev_stage_valid[k] = false;
-    d_half = nullptr; d_rec = nullptr; d_chunk_count = nullptr; d_best = nullptr; d_chain = nullptr; d_prior_tr = nullptr;
+    d_half = nullptr; rf.du = rf.dv = nullptr; d_ref2[0] = d_ref2[1] = nullptr; d_rec = nullptr; d_chunk_count = nullptr; d_best = nullptr; d_chain = nullptr; d_prior_tr = nullptr;
     d_best2[0] = d_best2[1] = nullptr; d_chain2[0] = d_chain2[1] = nullptr; d_mchunk2[0] = d_mchunk2[1] = nullptr; d_redo = nullptr;
     for (int k = 0; k < 2; k++) if (h_out[k]) { (void)hipHostFree(h_out[k]); h_out[k] = nullptr; d_out_mapped[k] = nullptr; }
     if (h_matches) { (void)hipHostFree(h_matches); h_matches = nullptr; d_matches_mapped = nullptr; }
@@ -382,6 +386,17 @@ struct Group {
     memset(h_overflow, 0, sizeof(int32_t) * (size_t)S);
     if (p.half_resolution)
       if ((rc = dmalloc(&d_half, 2 * (size_t)S * g.bplm * g.Hm, false))) return rc;
+    if (p.refinement > 0) {  // (a sequence handle's empty sets hold no features: they need no planes)
+      rf.W = dims[0]; rf.H = dims[1]; rf.bpl = dims[2];
+      rf.pitch = round_up(dims[0], 16);
+      rf.plane = (int64_t)rf.pitch * dims[1];
+      rf.mode = p.refinement == 2 ? 2 : 1;
+      const size_t nplanes = 2 * VH_RING * (size_t)S;
+      if ((rc = dmalloc(&rf.du, nplanes * rf.plane, false))) return rc;
+      if ((rc = dmalloc(&rf.dv, nplanes * rf.plane, false))) return rc;
+      for (int k = 0; k < 2; k++)
+        if ((rc = dmalloc(&d_ref2[k], 2 * (size_t)S * cap, false))) return rc;
+    }
     allocated = true;
     pair_cur = 0; pair_prev = 1; frames = 0; epoch = 0; last_method = -1; failed = false;
     seq_n = seq_n_prev = 0; seq_first = seq_total = 0;
@@ -497,6 +512,8 @@ struct Group {
       im.base[1] = dI2 ? (const uint8_t *)dI2 + (int64_t)s0 * stride : nullptr;
       im.stride = stride; im.ncam = ncam; im.S = sn; im.S_total = S; im.s0 = s0; im.pair_cur = pair_cur;
       uint64_t *rec = d_rec + (size_t)s0 * ncam * std::max(g.nblocks, 1);
+      // the refinement's planes come from the pushed full-resolution images, inside the window they are borrowed for
+      if (p.refinement > 0) { Scope sc(this, "refine_planes", stream); vh_launch_refine_planes(im, rf, stream); }
       int32_t *chunks = d_chunk_count + (size_t)s0 * ncam * g.nchunks;
       if (p.half_resolution) {
         const int64_t isz = (int64_t)g.bplm * g.Hm;
@@ -682,9 +699,11 @@ struct Group {
       }
     }
     { Scope sc(this, "chain", ps); vh_launch_chain(sets, a, method, d_best2[buf], d_chain2[buf], d_mask, epoch, d_mchunk, ps); }
+    float4 *ref = p.refinement > 0 ? d_ref2[buf] : nullptr;  // (before the emission: every reader of the list sees the refined one)
+    if (ref) { Scope sc(this, "refine", ps); vh_launch_refine(sets, a, method, rf, d_chain2[buf], ref, d_mchunk, ps); }
     // a download of the previous step's lists may still be reading d_matches
     if (ev_down_valid) VH_HIP(hipStreamWaitEvent(ps, ev_down, 0));
-    { Scope sc(this, "emit_matches", ps); vh_launch_emit_matches(sets, a, method, d_chain2[buf], d_matches, mcap, d_match_count, d_overflow, d_mchunk, d_redo + (size_t)buf * S, d_mchunk2[buf ^ 1], d_out_mapped[buf], d_matches_mapped, ps); }
+    { Scope sc(this, "emit_matches", ps); vh_launch_emit_matches(sets, a, method, d_chain2[buf], d_matches, mcap, d_match_count, d_overflow, d_mchunk, d_redo + (size_t)buf * S, d_mchunk2[buf ^ 1], d_out_mapped[buf], d_matches_mapped, ref, ps); }
     VH_HIP(hipGetLastError());
     // (re-searched, searched) of this launch are read from h_out[buf] by a later choose_loop()
     stats_pending[buf] = true; stats_was_spec[buf] = spec; stats_npass[buf] = a.npass;
@@ -1461,6 +1480,7 @@ int32_t group_new(const vh_params *p, int32_t device, int32_t S, int32_t mf, int
   if ((rc = select_device(device))) return rc;
   Group *gq = new Group();
   gq->p = *p; gq->device = device; gq->S = S; gq->req_features = mf; gq->req_matches = mm;
+  if (p->refinement > 0) vh_refine_setup(gq->rf);
   // Both streams at the default priority: raising the detect stream's priority
   // (so that detection finishes inside the shadow of the flow search) was
   // measured and lost ~3 % -- the single-workgroup-per-set kernels then wait for
@@ -1518,6 +1538,15 @@ struct Temp {  // transient one-stream group for the stateless entry points
   Group *gq = nullptr;
   ~Temp() { if (gq) { (void)gq->sync_all(); delete gq; } }
 };
+// A transient group never refines: none of the stateless entry points that use one has the images of a pair (vh_match
+// matches caller-supplied features and must return the unrefined list, whatever p->refinement says), so refinement is
+// cleared and no planes or refined-coordinate buffers are allocated or written.
+int32_t temp_new(const vh_params *p, int32_t device, int32_t mf, int32_t mm, Temp &t) {
+  if (!p) return VH_ERR_INVALID_ARG;
+  vh_params q = *p;
+  q.refinement = 0;
+  return group_new(&q, device, 1, mf, mm, &t.gq);
+}
 
 }  // namespace
 
@@ -2010,7 +2039,7 @@ int32_t vh_compute_features(const vh_params *p, int32_t device, const uint8_t *I
   int32_t rc, overflow = VH_OK;
   {  // dense set (matcher.cpp:634-635)
     Temp t;
-    if ((rc = group_new(p, device, 1, 0, 0, &t.gq))) return rc;
+    if ((rc = temp_new(p, device, 0, 0, t))) return rc;
     if ((rc = t.gq->push_host(I, nullptr, 0, dims, 0))) return rc;
     int32_t n = 0;
     rc = t.gq->get_features(0, VH_SET_1C, max2, max2 ? cap2 : 0, &n);
@@ -2036,7 +2065,7 @@ int32_t vh_compute_features(const vh_params *p, int32_t device, const uint8_t *I
     if (ns > 10) ns = std::max(p->nms_n, 10);
     ps.nms_n = ns;
     Temp t;
-    if ((rc = group_new(&ps, device, 1, 0, 0, &t.gq))) return rc;
+    if ((rc = temp_new(&ps, device, 0, 0, t))) return rc;
     if ((rc = t.gq->push_host(I, nullptr, 0, dims, 0))) return rc;
     int32_t n = 0;
     rc = t.gq->get_features(0, VH_SET_1C, max1, max1 ? cap1 : 0, &n);
@@ -2051,7 +2080,7 @@ int32_t vh_create_index(const vh_params *p, int32_t device, const int32_t dims[3
   if (!p || !dims || !bin_start || (n > 0 && !list)) return VH_ERR_INVALID_ARG;
   Temp t;
   int32_t rc;
-  if ((rc = group_new(p, device, 1, std::max(n, 64), 1, &t.gq))) return rc;
+  if ((rc = temp_new(p, device, std::max(n, 64), 1, t))) return rc;
   const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
   if ((rc = t.gq->ensure(d))) return rc;
   if ((rc = t.gq->load_features(VH_SET_1C, m, n))) return rc;
@@ -2071,7 +2100,7 @@ int32_t vh_match_all(const vh_params *p, int32_t device, const int32_t dims[3], 
   if (!p || !dims || (n1 > 0 && !best)) return VH_ERR_INVALID_ARG;
   Temp t;
   int32_t rc;
-  if ((rc = group_new(p, device, 1, std::max(std::max(n1, n2), 64), 1, &t.gq))) return rc;
+  if ((rc = temp_new(p, device, std::max(std::max(n1, n2), 64), 1, t))) return rc;
   const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
   Group *gq = t.gq;
   if ((rc = gq->ensure(d))) return rc;
@@ -2091,7 +2120,7 @@ int32_t vh_match_all_prior(const vh_params *p, int32_t device, const int32_t dim
   if (!p || !dims || (n1 > 0 && !best)) return VH_ERR_INVALID_ARG;
   Temp t;
   int32_t rc;
-  if ((rc = group_new(p, device, 1, std::max(std::max(n1, n2), 64), 1, &t.gq))) return rc;
+  if ((rc = temp_new(p, device, std::max(std::max(n1, n2), 64), 1, t))) return rc;
   const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
   Group *gq = t.gq;
   if ((rc = gq->ensure(d))) return rc;
@@ -2114,7 +2143,7 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
   Temp t;
   int32_t rc;
   const int32_t nmax = std::max(std::max(n1p, n2p), std::max(n1c, n2c));
-  if ((rc = group_new(p, device, 1, std::max(nmax, 64), std::max(nmax, 64), &t.gq))) return rc;
+  if ((rc = temp_new(p, device, std::max(nmax, 64), std::max(nmax, 64), t))) return rc;
   const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
   Group *gq = t.gq;
   if ((rc = gq->ensure(d))) return rc;
@@ -2124,6 +2153,58 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
   if ((rc = gq->load_features(VH_SET_2C, m2c, n2c))) return rc;
   if ((rc = gq->match(method))) return rc;
   return gq->get_matches(0, out, cap, n);
+}
+
+// Matcher::refinement on caller-owned records (kernels_refine.hip: the hops of the stateful path, same device code)
+int32_t vh_refine_matches(const vh_params *p, int32_t device, int32_t method, const int32_t dims[3], const uint8_t *I1p,
+                          const uint8_t *I2p, const uint8_t *I1c, const uint8_t *I2c, vh_p_match *pm, int32_t n, int32_t *n_out) {
+  if (!p || !dims || !n_out || n < 0 || (n > 0 && !pm) || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
+  int32_t rc = check_params(p);
+  if (rc) return rc;
+  if (dims[0] <= 0 || dims[1] <= 0 || dims[2] < dims[0]) return VH_ERR_INVALID_ARG;
+  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  const uint8_t *img[4] = {I1p, I2p, I1c, I2c};
+  const bool need[4] = {method != VH_METHOD_STEREO, method == VH_METHOD_QUAD, true, method != VH_METHOD_FLOW};
+  for (int k = 0; k < 4; k++) if (need[k] && !img[k]) return VH_ERR_INVALID_ARG;
+  *n_out = n;
+  if (p->refinement <= 0 || n == 0) return VH_OK;  // nothing to do: nothing is launched
+  if ((rc = select_device(device))) return rc;
+  VhRefine rf{};
+  vh_refine_setup(rf);
+  rf.W = dims[0]; rf.H = dims[1]; rf.bpl = dims[2];
+  rf.pitch = round_up(dims[0], 16);
+  rf.plane = (int64_t)rf.pitch * dims[1];
+  rf.mode = p->refinement == 2 ? 2 : 1;
+  const size_t isz = (size_t)dims[2] * dims[1], ialloc = (isz + 255) / 256 * 256;
+  const size_t bytes = 4 * ialloc + 8 * (size_t)rf.plane + sizeof(vh_p_match) * (size_t)n + sizeof(int32_t) * (size_t)n;
+  uint8_t *d = nullptr;
+  VH_HIP(hipMalloc((void **)&d, bytes));
+  rf.du = d + 4 * ialloc; rf.dv = rf.du + 4 * rf.plane;
+  vh_p_match *dpm = (vh_p_match *)(rf.dv + 4 * rf.plane);
+  int32_t *dkeep = (int32_t *)(dpm + n);
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 4 && e == hipSuccess; k++) {
+    if (!need[k]) continue;
+    e = hipMemcpy(d + k * ialloc, img[k], isz, hipMemcpyHostToDevice);
+    VhImages im{};
+    im.base[0] = d + k * ialloc; im.stride = (int64_t)isz; im.ncam = 1; im.S = 1; im.S_total = 1;
+    VhRefine rk = rf;  // planes of role k: set 0 of this launch
+    rk.du += k * rf.plane; rk.dv += k * rf.plane;
+    if (e == hipSuccess) { vh_launch_refine_planes(im, rk, nullptr); e = hipGetLastError(); }
+  }
+  if (e == hipSuccess) e = hipMemcpy(dpm, pm, sizeof(vh_p_match) * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) { vh_launch_refine_records(rf, method, dpm, n, dkeep, nullptr); e = hipGetLastError(); }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  std::vector<vh_p_match> out((size_t)n);
+  std::vector<int32_t> keep((size_t)n);
+  if (e == hipSuccess) e = hipMemcpy(out.data(), dpm, sizeof(vh_p_match) * (size_t)n, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(keep.data(), dkeep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (e != hipSuccess) { t_last_error = hipGetErrorString(e); return VH_ERR_HIP; }
+  int32_t k = 0;
+  for (int32_t i = 0; i < n; i++) if (keep[i]) pm[k++] = out[i];
+  *n_out = k;
+  return VH_OK;
 }
 
 // ---- removeOutliers (+ bucketFeatures) on the device, stateless form ------------

@@ -1020,12 +1020,14 @@ __global__ void flow_keep_kernel(VhSets s, VhMatchArgs a, int4 *__restrict__ cha
 // circles into p_match records (48 B, src/matcher.h:89-104), in ascending order
 // of the driving feature index as the reference's loops emit them.  The offset of
 // a chunk is the sum of the survivor counts of the chunks before it.
+// REFINED (refinement > 0): the coordinates of a kept entry come from ref (kernels_refine.hip) instead of the chain.
+template <bool REFINED>
 __global__ void __launch_bounds__(256)
 emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restrict__ chain,
                     float *__restrict__ matches, int32_t mcap, int32_t *__restrict__ match_count,
                     int32_t *__restrict__ overflow, const int32_t *__restrict__ mchunk, int32_t nchm,
                     int32_t *__restrict__ redo, int32_t *__restrict__ mchunk_next, int4 *__restrict__ host_out,
-                    float *__restrict__ host_matches) {
+                    float *__restrict__ host_matches, const float4 *__restrict__ ref) {
   __shared__ int32_t sWave[4];
   __shared__ int32_t sBase;
   const int32_t chunk = blockIdx.x, stream = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -1062,11 +1064,16 @@ emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restr
   if (keep) {
     const int32_t idx[4] = {r.x, r.y, r.z, r.w};
     const uint32_t uv[4] = {(uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w};
+    float q[8];
+    if (REFINED) {
+      const float4 q0 = ref[2 * ((int64_t)stream * s.cap + i)], q1 = ref[2 * ((int64_t)stream * s.cap + i) + 1];
+      q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
+    }
 #pragma unroll
     for (int32_t k = 0; k < 4; k++) {
       if (idx[k] >= 0) {
-        rec[3 * k + 0] = __float_as_uint((float)(uv[k] & 0xFFFFu));
-        rec[3 * k + 1] = __float_as_uint((float)(uv[k] >> 16));
+        rec[3 * k + 0] = __float_as_uint(REFINED ? q[2 * k] : (float)(uv[k] & 0xFFFFu));
+        rec[3 * k + 1] = __float_as_uint(REFINED ? q[2 * k + 1] : (float)(uv[k] >> 16));
       }
       rec[3 * k + 2] = (uint32_t)idx[k];
     }
@@ -1163,10 +1170,14 @@ void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, cons
 void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
                             void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,
                             const int32_t *mchunk, int32_t *redo, int32_t *mchunk_next, void *host_out, void *host_matches,
-                            hipStream_t st) {
+                            const float4 *ref, hipStream_t st) {
   const int32_t nchm = (s.cap + 255) / 256;
   // every row of the handle, a.rows or not: the rows a sequence chunk leaves empty read the empty set here and report 0
   // matches (their chain tables were not written, their chunk counters are zero), and their counters are reset
-  hipLaunchKernelGGL(emit_matches_kernel, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
-                     (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches);
+  if (ref)
+    hipLaunchKernelGGL(emit_matches_kernel<true>, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
+                       (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches, ref);
+  else
+    hipLaunchKernelGGL(emit_matches_kernel<false>, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
+                       (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches, ref);
 }

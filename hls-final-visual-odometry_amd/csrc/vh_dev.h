@@ -191,6 +191,19 @@ __host__ __device__ inline int32_t vh_image_set(const VhImages &im, int32_t id) 
   return vh_set_id(im.S_total, im.pair_cur, im.s0 + id / im.ncam, id % im.ncam);
 }
 
+// Refinement (kernels_refine.hip): full-resolution du/dv planes, one pair per feature set
+// (indexed like the sets; vh_refine_matches: one per role 1p, 2p, 1c, 2c), and the recorded Gauss-Jordan steps of the
+// sub-pixel fit's constant normal matrix.
+struct VhRefine {
+  uint8_t *du, *dv;   // [set][H][pitch]
+  int64_t plane;      // bytes per plane: pitch * H
+  int32_t pitch;      // W rounded up to 16
+  int32_t W, H, bpl;  // full-resolution dims of the pushed images
+  int32_t mode;       // 1: pixel (relocateMinimum), 2: sub-pixel (parabolicFitting)
+  int32_t gj_row[6], gj_col[6];
+  double gj_pivinv[6], gj_dum[6][6];
+};
+
 // ---- launchers (defined in the kernels_*.hip files) ------------------------
 void vh_launch_half_res(const VhImages &src, uint8_t *dst, const VhGeom &g, hipStream_t st);
 void vh_launch_detect_nms(const VhImages &im, const VhGeom &g, uint64_t *rec, int32_t *chunk_count,
@@ -219,10 +232,19 @@ void vh_launch_quad_prior(const VhSets &s, const VhMatchArgs &a, const double *t
 // chain: [stream][cap][2] int4 = {i1p,i2p,i1c,i2c} (z = -2: no match), {uv1p,uv2p,uv1c,uv2c}
 void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *best,
                      int4 *chain, uint32_t *mask, uint32_t epoch, int32_t *mchunk, hipStream_t st);
+// ref: refined coordinates of the step (vh_launch_refine), or null: the chain's own
 void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
                             void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,
                             const int32_t *mchunk, int32_t *redo, int32_t *mchunk_next, void *host_out, void *host_matches,
-                            hipStream_t st);
+                            const float4 *ref, hipStream_t st);
+
+void vh_refine_setup(VhRefine &rf);  // fills gj_* (host, once per handle)
+void vh_launch_refine_planes(const VhImages &im, const VhRefine &rf, hipStream_t st);
+// ref: [row][cap][2] float4 {u1p, v1p, u2p, v2p}, {u1c, v1c, u2c, v2c}, written for the kept entries
+void vh_launch_refine(const VhSets &s, const VhMatchArgs &a, int32_t method, const VhRefine &rf, int4 *chain, float4 *ref,
+                      int32_t *mchunk, hipStream_t st);
+// planes of role r (0 = 1p .. 3 = 2c) at rf.du/dv + r * rf.plane; keep[i] = 0 for a dropped record
+void vh_launch_refine_records(const VhRefine &rf, int32_t method, struct vh_p_match *pm, int32_t n, int32_t *keep, hipStream_t st);
 
 struct vh_ego_params;
 struct vh_p_match;

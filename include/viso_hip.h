@@ -50,7 +50,8 @@ typedef struct vh_params {
   int32_t outlier_flow_tolerance; /* accepted, unused by this path */
   int32_t multi_stage;            /* 1 = also extract the sparse feature set (max1) */
   int32_t half_resolution;        /* 1 = detect at half resolution, coordinates x2 */
-  int32_t refinement;             /* accepted, unused (absent from the reference) */
+  int32_t refinement;             /* 0 = none, 1 = pixel, 2 = sub-pixel relocation of the matches (stock libviso2;
+                                     absent from the reference): see vh_refine_matches */
   double f, cu, cv, base;         /* calibration (only for match prediction; unused) */
 } vh_params;
 
@@ -240,11 +241,30 @@ int32_t vh_match_all_prior(const vh_params *p, int32_t device, const int32_t dim
                            const int32_t *m1, int32_t n1, const int32_t *m2, int32_t n2,
                            int32_t flow, double u_, double v_, int32_t *best);
 /* Matcher::matching (src/matcher.h:218, src/matcher.cpp:274-344) on
- * caller-supplied feature arrays. Unused sets: NULL/0. */
+ * caller-supplied feature arrays. Unused sets: NULL/0.  There are no images
+ * here: the list is never refined, whatever p->refinement says. */
 int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method,
                  const int32_t *m1p, int32_t n1p, const int32_t *m2p, int32_t n2p,
                  const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
                  vh_p_match *out, int32_t cap, int32_t *n);
+
+/* Stock libviso2's match refinement [upstream-recollection; absent from the reference tree, built on its
+ * computeSmallDescriptor, src/matcher.cpp:516-543, and Matrix::solve, src/matrix.cpp:417-504; DESIGN.md section 6
+ * (f-3) is the specification] on caller-owned records, in place, order preserved; *n_out = records kept.
+ * p->refinement <= 0: nothing changes (*n_out = n, nothing is launched); 2: sub-pixel (a 7x7 window of 16-byte SADs,
+ * a quadratic fit around the minimum; matches whose fit fails are dropped); any other positive value: pixel (the
+ * minimum of a 5x5 window).  Each record is refined hop by hop from the anchor (u1c, v1c) on image I1c, which never
+ * moves: flow 1c -> 1p, stereo 1c -> 2c, quad 1c -> 1p, 1c -> 2c, 1c -> 2p; indices are kept.  The images are host
+ * images at full resolution (dims = W, H, bytes per line, as pushed; also with half_resolution, whose coordinates are
+ * full-resolution already); NULL where the method does not read one (flow: I1p, I1c; stereo: I1c, I2c; quad: all
+ * four).  Hops outside the bounds (anchor 4 <= u <= W-5, 4 <= v <= H-5; target the same, narrowed by the window
+ * radius) are left as they are in pixel mode and dropped in sub-pixel mode.
+ * The stateful calls refine with the handle's p.refinement after every match step, before anything reads the list:
+ * vh_get_matches, every vh_group_* getter and download, vh_remove_outliers, the post chains (host and device) and
+ * vh_group_estimate_motion(_mono) all see the refined list and its count. */
+int32_t vh_refine_matches(const vh_params *p, int32_t device, int32_t method, const int32_t dims[3], const uint8_t *I1p,
+                          const uint8_t *I2p, const uint8_t *I1c, const uint8_t *I2c, vh_p_match *pm, int32_t n,
+                          int32_t *n_out);
 
 /* ---- S independent camera streams stepped together ---------------------- */
 /* The multi-stream configuration (one sequence per stream, no exchange
@@ -493,7 +513,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  * kernel launch while enabled).  vh_group_profile_read returns the
  * accumulated milliseconds and launch count of kernel `name`
  * ("detect_nms", "emit_features", "bin_hist", "bin_scan", "bin_fill",
- *  "bin_sort", "match", "chain", "emit_matches") since the last reset. */
+ *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine")
+ *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches);
 int32_t vh_group_profile_reset(vh_group *g);

@@ -60,7 +60,7 @@ class Matcher {
     int32_t outlier_flow_tolerance;
     int32_t multi_stage;
     int32_t half_resolution;
-    int32_t refinement;
+    int32_t refinement;  // forwarded: 1 = pixel, 2 = sub-pixel refinement on the GPU before removeOutliers (vh_refine_matches)
     double f, cu, cv, base;
     parameters() {
       nms_n = 2;
