@@ -67,6 +67,8 @@ ABI_SYMBOLS = (
     "vh_group_post_device_config", "vh_group_post_begin_device", "vh_group_post_finish_device",
     "vh_sequence_create", "vh_sequence_push_back_device", "vh_sequence_push_back", "vh_sequence_position",
     "vh_refine_matches",
+    "vh_set_multi_stage_matching", "vh_group_set_multi_stage_matching", "vh_get_sparse_matches", "vh_group_get_sparse_matches",
+    "vh_prior_statistics", "vh_match_ranged",
 )
 
 
@@ -204,6 +206,10 @@ def _lib():
             "vh_sequence_push_back": [vp, vp, vp, i64, vp, i32],
             "vh_sequence_position": [vp, vp, vp],
             "vh_refine_matches": [vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp],
+            "vh_set_multi_stage_matching": [vp, i32], "vh_group_set_multi_stage_matching": [vp, i32],
+            "vh_get_sparse_matches": [vp, vp, i32, vp], "vh_group_get_sparse_matches": [vp, i32, vp, i32, vp],
+            "vh_prior_statistics": [vp, vp, i32, vp, i32, vp],
+            "vh_match_ranged": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -331,6 +337,20 @@ class Matcher:
             raise VisoHipError(rc, "vh_get_matches")
         return out
 
+    def setMultiStageMatching(self, on: bool = True):
+        """Two-pass matching of stock libviso2 (vh_set_multi_stage_matching): before the first pushBack, with
+        param.multi_stage = 1."""
+        _check(_lib().vh_set_multi_stage_matching(self._h, 1 if on else 0), "vh_set_multi_stage_matching")
+
+    def getSparseMatches(self) -> np.ndarray:
+        """The sparse list of pass 1 after the vote (multi-stage matching on)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_get_sparse_matches(self._h, None, 0, C.byref(n)), "vh_get_sparse_matches", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, P_MATCH_DTYPE)
+        if n.value:
+            _check(_lib().vh_get_sparse_matches(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_sparse_matches")
+        return out
+
     def getFeatures(self, which: int) -> np.ndarray:
         n = C.c_int32(0)
         _check(_lib().vh_get_features(self._h, which, None, 0, C.byref(n)), "vh_get_features", allow=(VH_ERR_CAPACITY,))
@@ -418,6 +438,21 @@ class StreamGroup:
             _check(_lib().vh_group_get_matches(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_matches")
         elif rc != VH_OK:
             raise VisoHipError(rc, "vh_group_get_matches")
+        return out
+
+    def setMultiStageMatching(self, on: bool = True):
+        """Two-pass matching of stock libviso2 for every stream (vh_group_set_multi_stage_matching): before the first
+        pushBack, with param.multi_stage = 1; not on a SequenceGroup."""
+        _check(_lib().vh_group_set_multi_stage_matching(self._h, 1 if on else 0), "vh_group_set_multi_stage_matching")
+
+    def getSparseMatches(self, stream: int) -> np.ndarray:
+        """The sparse list of pass 1 after the vote (multi-stage matching on)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_group_get_sparse_matches(self._h, stream, None, 0, C.byref(n)), "vh_group_get_sparse_matches",
+               allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, P_MATCH_DTYPE)
+        if n.value:
+            _check(_lib().vh_group_get_sparse_matches(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_sparse_matches")
         return out
 
     def getFeatures(self, stream: int, which: int) -> np.ndarray:
@@ -776,6 +811,37 @@ def match(param: Params, dims, method: int, m1p=None, m2p=None, m1c=None, m2c=No
                            _ptr(sets[0][0]), sets[0][1], _ptr(sets[1][0]), sets[1][1],
                            _ptr(sets[2][0]), sets[2][1], _ptr(sets[3][0]), sets[3][1],
                            _ptr(out), cap, C.byref(n)), "vh_match")
+    return out[:n.value].copy()
+
+
+def prior_statistics(param: Params, dims, method: int, pm) -> np.ndarray:
+    """computePriorStatistics of multi-stage matching (vh_prior_statistics; host only) -> ranges [nb, 4, 4] float32:
+    per statistics bin (v_bin * ubn + u_bin) and stage u_min, u_max, v_min, v_max."""
+    pm = np.ascontiguousarray(pm, dtype=P_MATCH_DTYPE)
+    ubn = -(-int(dims[0]) // param.match_binsize)
+    vbn = -(-int(dims[1]) // param.match_binsize)
+    out = np.zeros((ubn * vbn, 4, 4), np.float32)
+    _check(_lib().vh_prior_statistics(C.byref(param), _dims(dims), int(method), _ptr(pm) if len(pm) else None, len(pm), _ptr(out)),
+           "vh_prior_statistics")
+    return out
+
+
+def match_ranged(param: Params, dims, method: int, ranges, m1p=None, m2p=None, m1c=None, m2c=None, device: int = 0, cap=None):
+    """Matcher::matching with use_prior = true (vh_match_ranged): every stage searches inside ranges [nb, 4, 4] of the
+    driving feature's statistics bin."""
+    sets = [_feat(m) for m in (m1p, m2p, m1c, m2c)]
+    if cap is None:
+        cap = max(s[1] for s in sets) + 1
+    ubn = -(-int(dims[0]) // param.match_binsize)
+    vbn = -(-int(dims[1]) // param.match_binsize)
+    ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+    assert ranges.shape == (ubn * vbn, 4, 4), ranges.shape
+    out = np.zeros(cap, P_MATCH_DTYPE)
+    n = C.c_int32(0)
+    _check(_lib().vh_match_ranged(C.byref(param), device, _dims(dims), int(method),
+                                  _ptr(sets[0][0]), sets[0][1], _ptr(sets[1][0]), sets[1][1],
+                                  _ptr(sets[2][0]), sets[2][1], _ptr(sets[3][0]), sets[3][1],
+                                  _ptr(ranges), _ptr(out), cap, C.byref(n)), "vh_match_ranged")
     return out[:n.value].copy()
 
 

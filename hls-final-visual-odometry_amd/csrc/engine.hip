@@ -59,6 +59,14 @@ uint32_t lfsr_next(uint32_t x);
 int32_t bucket_records(const vh_p_match *pm, int32_t n, int32_t max_features, float bw, float bh, vh_p_match *out, int32_t out_cap,
                        std::vector<int32_t> &work);
 
+// computePriorStatistics of multi-stage matching (include/viso_hip.h: vh_prior_statistics), host side
+int32_t prior_statistics(const vh_params &p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges);
+// the integer accept window of a float range: ceil(min) .. floor(max), clamped so that coordinate + bound cannot overflow
+inline int32_t range_bound(float x, bool is_min) {
+  const float r = is_min ? ceilf(x) : floorf(x);
+  return (int32_t)std::min(std::max(r, -1048576.0f), 1048576.0f);
+}
+
 struct Group {
   vh_params p{};
   int32_t device = 0, S = 1;
@@ -111,6 +119,12 @@ struct Group {
   // Sequence handle (vh_sequence_*): the S rows of a slot are consecutive frames of one camera, a push brings a chunk of
   // seq_n <= S of them and every match links row r to row r - 1 (row 0 to the last row of the previous chunk: vh_row_set).
   bool seq = false;
+  // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
+  // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
+  // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
+  // and searches this group's sets inside d_ranges (kernels_ranged.hip).
+  Group *sparse = nullptr;
+  int32_t *d_ranges = nullptr, *h_ranges = nullptr;  // [S][ubn * vbn][4 stages][4] integer windows; page-locked staging
   int32_t seq_n = 0, seq_n_prev = 0;      // frames of the last chunk / of the one before
   int64_t seq_first = 0, seq_total = 0;   // index in the sequence of the last chunk's first frame / frames pushed so far
 
@@ -164,6 +178,7 @@ struct Group {
   std::map<std::string, ProfEntry> prof_entries;
 
   ~Group() {
+    delete sparse;  // (first: its detect stream is this group's)
     release();
     for (int k = 0; k < VH_RING; k++) { if (ev_det[k]) (void)hipEventDestroy(ev_det[k]); if (ev_read[k]) (void)hipEventDestroy(ev_read[k]); }
     if (ev_user) (void)hipEventDestroy(ev_user);
@@ -200,6 +215,7 @@ struct Group {
     VH_HIP(hipStreamSynchronize(post_stream));
     VH_HIP(hipStreamSynchronize(down_stream));
     for (int k = 0; k < kVoteStreams; k++) if (vote_stream[k]) VH_HIP(hipStreamSynchronize(vote_stream[k]));
+    if (sparse) { const int32_t rs = sparse->sync_all(); if (rs) return rs; }
     return check_violation();
   }
   // -DVH_CHECK builds: the kernels verify the index invariants they otherwise trust (vh_dev.h,
@@ -246,6 +262,8 @@ struct Group {
     }
     if (h_overflow) { (void)hipHostFree(h_overflow); h_overflow = nullptr; }
     if (h_prior_tr) { (void)hipHostFree(h_prior_tr); h_prior_tr = nullptr; }
+    d_ranges = nullptr;
+    if (h_ranges) { (void)hipHostFree(h_ranges); h_ranges = nullptr; }
     allocated = false;
   }
 
@@ -463,6 +481,11 @@ struct Group {
     const int32_t old_cur = pair_cur, old_prev = pair_prev;
     const int64_t old_frames = frames;
     rc = push_device_queued(dI1, dI2, stride, d, replace, rows);
+    if (rc == VH_OK && sparse) {
+      // the sparse sets of the same images, behind the dense ones on the same stream; the images stay in use until then
+      rc = sparse->push_device(dI1, dI2, stride, d, replace, rows);
+      if (rc == VH_OK && hipEventRecord(ev_det[pair_cur], stream) != hipSuccess) rc = VH_ERR_HIP;
+    }
     if (rc != VH_OK) { pair_cur = old_cur; pair_prev = old_prev; frames = old_frames; failed = true; }
     else {
       failed = false;
@@ -632,9 +655,60 @@ struct Group {
   // tr16: null, or [S][16] row-major motion estimates for the quad method's prior (kernels_prior.hip); the intrinsics must be set
   double *d_prior_tr = nullptr;
   double *h_prior_tr = nullptr;  // page-locked staging, two slots (one per table buffer): the caller's array is only borrowed
-  int32_t match(int32_t method, const double *tr16 = nullptr) {
+  size_t n_ranges() const { return (size_t)S * sets.ubn * sets.vbn * 16; }
+  int32_t ensure_ranges() {
+    if (!d_ranges) { const int32_t rc = dmalloc(&d_ranges, n_ranges(), false); if (rc) { d_ranges = nullptr; return rc; } }
+    if (!h_ranges) VH_HIP(hipHostMalloc((void **)&h_ranges, sizeof(int32_t) * n_ranges(), hipHostMallocDefault));
+    return VH_OK;
+  }
+  void prof_host(const char *name, std::chrono::steady_clock::time_point t0) {
+    if (!prof) return;
+    ProfEntry &e = prof_entries[name];
+    e.ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); e.launches++;
+  }
+  // Pass 1 of multi-stage matching and the statistics: the method's matching on the sparse sets, the vote on the host
+  // (flow and quad lists), one range table per stream into h_ranges, queued for the match stream.
+  int32_t multi_stage_ranges(int32_t method) {
+    int32_t rc = sparse->match(method);
+    if (rc) return rc;
+    auto t0 = std::chrono::steady_clock::now();
+    for (int32_t s = 0; s < S; s++) if ((rc = sparse->fetch_matches(s))) return rc;
+    const int32_t threads = (int32_t)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
+    if ((rc = sparse->remove_outliers(0, S, threads))) return rc;
+    prof_host("sparse_vote_host", t0);
+    // (the table the previous match's pass 2 read has gone up: the copy below is the next thing on the match stream)
+    VH_HIP(hipStreamSynchronize(match_stream));
+    t0 = std::chrono::steady_clock::now();
+    const size_t per = (size_t)sets.ubn * sets.vbn * 16;
+    std::vector<float> fr(per);
+    for (int32_t s = 0; s < S; s++) {
+      const std::vector<vh_p_match> &pm = sparse->host_matches[s];
+      if ((rc = prior_statistics(p, dims, method, pm.data(), (int32_t)pm.size(), fr.data()))) return rc;
+      for (size_t k = 0; k < per; k++) h_ranges[s * per + k] = range_bound(fr[k], (k & 1) == 0);
+    }
+    prof_host("statistics_host", t0);
+    VH_HIP(hipMemcpyAsync(d_ranges, h_ranges, sizeof(int32_t) * n_ranges(), hipMemcpyHostToDevice, match_stream));
+    return VH_OK;
+  }
+  // Caller-supplied ranges (vh_match_ranged): [ubn * vbn][4][4] float for every stream of the group
+  int32_t load_ranges(const float *ranges) {
+    int32_t rc = ensure_ranges();
+    if (rc) return rc;
+    const size_t per = (size_t)sets.ubn * sets.vbn * 16;
+    for (size_t k = 0; k < per; k++) if (!std::isfinite(ranges[k])) return VH_ERR_INVALID_ARG;
+    VH_HIP(hipStreamSynchronize(match_stream));
+    for (int32_t s = 0; s < S; s++)
+      for (size_t k = 0; k < per; k++) h_ranges[s * per + k] = range_bound(ranges[k], (k & 1) == 0);
+    VH_HIP(hipMemcpyAsync(d_ranges, h_ranges, sizeof(int32_t) * n_ranges(), hipMemcpyHostToDevice, match_stream));
+    return VH_OK;
+  }
+
+  // ranged: search inside the ranges load_ranges() queued (vh_match_ranged); a handle with multi-stage matching on
+  // produces its own (multi_stage_ranges)
+  int32_t match(int32_t method, const double *tr16 = nullptr, bool ranged = false) {
     if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
     if (!allocated || failed) return VH_ERR_STATE;
+    if (sparse && tr16) return VH_ERR_UNSUPPORTED;  // the motion prior does not combine with multi-stage matching
     if (tr16 && method != VH_METHOD_QUAD) tr16 = nullptr;  // (stock libviso2 uses the prediction in the quad circle only)
     if (tr16 && !(p.f > 0 && p.base > 0)) return VH_ERR_STATE;  // setIntrinsics first
     if (match_dirty) { const int32_t rr = match_recover(); if (rr) return rr; }
@@ -646,12 +720,17 @@ struct Group {
       int32_t rc = dmalloc(&d_mask, (size_t)S * dims[0] * dims[1], false); if (rc) { d_mask = nullptr; return rc; }
       fresh_mask = true;
     }
-    const int32_t rc = match_queued(method, fresh_mask, tr16);
+    if (sparse) {
+      int32_t rr = ensure_ranges();
+      if (rr) return rr;
+      if ((rr = multi_stage_ranges(method))) return rr;
+    }
+    const int32_t rc = match_queued(method, fresh_mask, tr16, (sparse || ranged) ? d_ranges : nullptr);
     if (rc) match_dirty = true;
     return rc;
   }
 
-  int32_t match_queued(int32_t method, bool fresh_mask, const double *tr16) {
+  int32_t match_queued(int32_t method, bool fresh_mask, const double *tr16, const int32_t *ranges) {
     VhMatchArgs a = match_args(method);
     a.prior = tr16 ? 1 : 0;
     hipStream_t ms = match_stream, ps = post_stream;
@@ -662,6 +741,7 @@ struct Group {
     VH_HIP(hipStreamWaitEvent(ms, ev_det[pair_cur], 0));
     VH_HIP(hipStreamWaitEvent(ms, ev_det[pair_prev], 0));
     if (ev_post_valid[buf]) VH_HIP(hipStreamWaitEvent(ms, ev_post[buf], 0));
+    if (ranges) return match_queued_ranged(method, fresh_mask, a, buf, ranges);
     const bool spec = choose_loop();
     // A stepped group shares the chip with its own detection chain: a grid as tight as the tiles the sets really hold, and
     // the searches' workgroups padded to an LDS footprint that leaves the chain room on every CU (vh_launch_match has the
@@ -709,6 +789,43 @@ struct Group {
     stats_pending[buf] = true; stats_was_spec[buf] = spec; stats_npass[buf] = a.npass;
     VH_HIP(hipEventRecord(ev_post[buf], ps)); ev_post_valid[buf] = true;
     // both slots stay in use until this point of the post stream
+    VH_HIP(hipEventRecord(ev_read[pair_cur], ps)); ev_read_valid[pair_cur] = true;
+    VH_HIP(hipEventRecord(ev_read[pair_prev], ps)); ev_read_valid[pair_prev] = true;
+    last_method = method; drop_host_matches(); last_buf = buf;
+    return VH_OK;
+  }
+
+  // Pass 2 of multi-stage matching: no tables -- kernels_ranged.hip walks every driver's circle inside the ranges of its
+  // statistics bin and writes the chain entries itself, on the match stream (it is the step's search); the flow method's
+  // keep step, the refinement and the emission follow on the post stream as in match_queued.  The kernel adds to the
+  // chunk counters the previous emission zeroed and bids into the pixel mask the previous keep step read, so the match
+  // stream also waits for the previous step's post-processing.
+  int32_t match_queued_ranged(int32_t method, bool fresh_mask, const VhMatchArgs &a, int32_t buf, const int32_t *ranges) {
+    hipStream_t ms = match_stream, ps = post_stream;
+    if (ev_post_valid[buf ^ 1]) VH_HIP(hipStreamWaitEvent(ms, ev_post[buf ^ 1], 0));
+    int32_t *d_mchunk = d_mchunk2[buf];
+    if (method == VH_METHOD_FLOW) {
+      if (fresh_mask) {
+        VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ms));
+        epoch = 0;
+      }
+      if (++epoch >= (1u << (32 - VH_MASK_IDX_BITS)) - 1) {
+        VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ms));
+        epoch = 1;
+      }
+    }
+    { Scope sc(this, "ranged", ms); vh_launch_ranged_circle(sets, a, method, ranges, d_chain2[buf], d_mask, epoch, d_mchunk, ms); }
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipEventRecord(ev_tables[buf], ms));
+    VH_HIP(hipStreamWaitEvent(ps, ev_tables[buf], 0));
+    if (method == VH_METHOD_FLOW) { Scope sc(this, "chain", ps); vh_launch_flow_keep(sets, a, d_chain2[buf], d_mask, epoch, d_mchunk, ps); }
+    float4 *ref = p.refinement > 0 ? d_ref2[buf] : nullptr;
+    if (ref) { Scope sc(this, "refine", ps); vh_launch_refine(sets, a, method, rf, d_chain2[buf], ref, d_mchunk, ps); }
+    if (ev_down_valid) VH_HIP(hipStreamWaitEvent(ps, ev_down, 0));
+    { Scope sc(this, "emit_matches", ps); vh_launch_emit_matches(sets, a, method, d_chain2[buf], d_matches, mcap, d_match_count, d_overflow, d_mchunk, d_redo + (size_t)buf * S, d_mchunk2[buf ^ 1], d_out_mapped[buf], d_matches_mapped, ref, ps); }
+    VH_HIP(hipGetLastError());
+    stats_pending[buf] = true; stats_was_spec[buf] = false; stats_npass[buf] = a.npass;
+    VH_HIP(hipEventRecord(ev_post[buf], ps)); ev_post_valid[buf] = true;
     VH_HIP(hipEventRecord(ev_read[pair_cur], ps)); ev_read_valid[pair_cur] = true;
     VH_HIP(hipEventRecord(ev_read[pair_prev], ps)); ev_read_valid[pair_prev] = true;
     last_method = method; drop_host_matches(); last_buf = buf;
@@ -1463,6 +1580,59 @@ int32_t check_params(const vh_params *p) {
   return VH_OK;
 }
 
+int32_t prior_statistics(const vh_params &p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges) {
+  const float bs = (float)p.match_binsize, R = (float)p.match_radius;
+  const int32_t ubn = (int32_t)ceilf((float)dims[0] / bs), vbn = (int32_t)ceilf((float)dims[1] / bs);  // matcher.cpp:282-283
+  const int32_t nst = method == VH_METHOD_QUAD ? 4 : 2;
+  const size_t nb = (size_t)ubn * vbn;
+  std::vector<uint8_t> seen(nb, 0);
+  for (size_t k = 0; k < nb * 16; k++) ranges[k] = (k & 1) ? R : -R;
+  for (int32_t i = 0; i < n; i++) {
+    const vh_p_match &m = pm[i];
+    float d[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u, v;
+    if (method == VH_METHOD_FLOW) {
+      d[0] = m.u1p - m.u1c; d[1] = m.v1p - m.v1c; d[2] = m.u1c - m.u1p; d[3] = m.v1c - m.v1p;
+      u = m.u1c; v = m.v1c;
+    } else if (method == VH_METHOD_STEREO) {
+      d[0] = m.u2c - m.u1c; d[2] = m.u1c - m.u2c;
+      u = m.u1c; v = m.v1c;
+    } else {
+      d[0] = m.u2p - m.u1p; d[2] = m.u2c - m.u2p; d[3] = m.v2c - m.v2p; d[4] = m.u1c - m.u2c; d[6] = m.u1p - m.u1c; d[7] = m.v1p - m.v1c;
+      u = m.u1p; v = m.v1p;
+    }
+    bool finite = std::isfinite(u) && std::isfinite(v);
+    for (int32_t k = 0; k < 2 * nst; k++) finite = finite && std::isfinite(d[k]);
+    if (!finite) return VH_ERR_INVALID_ARG;
+    // the bin of the reference point, kept in float until it is inside [-1, bin count] (any finite coordinate)
+    const int32_t ub = (int32_t)std::min(std::max(floorf(u / bs), -1.0f), (float)ubn);
+    const int32_t vb = (int32_t)std::min(std::max(floorf(v / bs), -1.0f), (float)vbn);
+    const auto clampi = [](int32_t x, int32_t nbin) { return std::min(std::max(x, 0), nbin - 1); };
+    for (int32_t y = clampi(vb - 1, vbn); y <= clampi(vb + 1, vbn); y++)
+      for (int32_t x = clampi(ub - 1, ubn); x <= clampi(ub + 1, ubn); x++) {
+        const size_t b = (size_t)y * ubn + x;
+        float *r = ranges + b * 16;
+        for (int32_t st = 0; st < nst; st++)
+          for (int32_t ax = 0; ax < 2; ax++) {
+            float &lo = r[4 * st + 2 * ax], &hi = r[4 * st + 2 * ax + 1];
+            const float x_ = d[2 * st + ax];
+            if (!seen[b]) { lo = x_; hi = x_; }
+            else { lo = std::min(lo, x_); hi = std::max(hi, x_); }
+          }
+        seen[b] = 1;
+      }
+  }
+  for (size_t b = 0; b < nb; b++) {
+    if (!seen[b]) continue;  // no observation: +-radius, not widened
+    for (int32_t st = 0; st < nst; st++)
+      for (int32_t ax = 0; ax < 2; ax++) {
+        float &lo = ranges[b * 16 + 4 * st + 2 * ax], &hi = ranges[b * 16 + 4 * st + 2 * ax + 1];
+        const float dd = hi - lo;
+        if (dd < 20.0f) { const float h = ceilf((20.0f - dd) / 2.0f); lo -= h; hi += h; }
+      }
+  }
+  return VH_OK;
+}
+
 int32_t select_device(int32_t device) {
   int cnt = 0;
   if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) { t_last_error = "no HIP device visible"; return VH_ERR_NO_DEVICE; }
@@ -1602,6 +1772,7 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
   if (!g) return (int64_t)VH_ERR_INVALID_ARG;
   const Group *gq = (const Group *)g;
   int64_t b = (int64_t)gq->device_bytes;
+  if (gq->sparse) b += vh_group_device_bytes((const vh_group *)gq->sparse);  // the sparse sets of multi-stage matching
   for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes;
   return b;
 }
@@ -1651,6 +1822,42 @@ int32_t vh_sequence_position(const vh_group *g, int64_t *first_frame, int32_t *n
   *first_frame = gq->seq_first;
   *n_frames = gq->seq_n;
   return VH_OK;
+}
+int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: the sparse sets belong to every frame of the ring
+  if (on && !gq->p.multi_stage) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;
+  if (!on) { delete gq->sparse; gq->sparse = nullptr; return VH_OK; }
+  if (gq->sparse) return VH_OK;
+  vh_params q = gq->p;
+  q.nms_n = gq->p.nms_n * 4;  // matcher.cpp:621-623
+  if (q.nms_n > 10) q.nms_n = std::max(gq->p.nms_n, 10);
+  q.multi_stage = 0; q.refinement = 0;
+  Group *sp = nullptr;
+  const int32_t rc = group_new(&q, gq->device, gq->S, 0, 0, &sp);
+  if (rc) return rc;
+  sp->stream = gq->stream;  // (its own detect stream stays idle, or carries its searches in a small group)
+  gq->sparse = sp;
+  return VH_OK;
+}
+int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on) { return vh_group_set_multi_stage_matching((vh_group *)m, on); }
+int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (!gq->sparse) return VH_ERR_STATE;
+  return gq->sparse->get_matches(stream, out, cap, n);
+}
+int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n) {
+  return vh_group_get_sparse_matches((vh_group *)m, 0, out, cap, n);
+}
+int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges) {
+  if (!p || !dims || !ranges || n < 0 || (n > 0 && !pm) || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
+  const int32_t rc = check_params(p);
+  if (rc) return rc;
+  if (dims[0] <= 0 || dims[1] <= 0) return VH_ERR_INVALID_ARG;
+  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  return prior_statistics(*p, dims, method, pm, n, ranges);
 }
 int32_t vh_group_match_features(vh_group *g, int32_t method) {
   Group *gq = (Group *)g; ENTER(gq);
@@ -1724,11 +1931,15 @@ int32_t vh_group_debug_fail_next_alloc(vh_group *g) {
 int32_t vh_group_profile_enable(vh_group *g, int32_t on) {
   Group *gq = (Group *)g; ENTER(gq);
   gq->prof = on != 0;
+  if (gq->sparse) gq->sparse->prof = gq->prof;
   return VH_OK;
 }
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches) {
   Group *gq = (Group *)g; ENTER(gq);
   if (!name) return VH_ERR_INVALID_ARG;
+  if (gq->sparse && !strncmp(name, "sparse_", 7) && strcmp(name, "sparse_vote_host")) {  // the sparse group's kernels
+    gq = gq->sparse; name += 7;
+  }
   gq->prof_collect();
   auto it = gq->prof_entries.find(name);
   if (ms) *ms = it == gq->prof_entries.end() ? 0.0 : it->second.ms;
@@ -1739,6 +1950,7 @@ int32_t vh_group_profile_reset(vh_group *g) {
   Group *gq = (Group *)g; ENTER(gq);
   gq->prof_collect();
   gq->prof_entries.clear();
+  if (gq->sparse) { gq->sparse->prof_collect(); gq->sparse->prof_entries.clear(); }
   return VH_OK;
 }
 
@@ -2152,6 +2364,28 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
   if ((rc = gq->load_features(VH_SET_1C, m1c, n1c))) return rc;
   if ((rc = gq->load_features(VH_SET_2C, m2c, n2c))) return rc;
   if ((rc = gq->match(method))) return rc;
+  return gq->get_matches(0, out, cap, n);
+}
+
+// Matcher::matching with use_prior = true on caller-supplied features and ranges (kernels_ranged.hip)
+int32_t vh_match_ranged(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, const int32_t *m1p,
+                        int32_t n1p, const int32_t *m2p, int32_t n2p, const int32_t *m1c, int32_t n1c,
+                        const int32_t *m2c, int32_t n2c, const float *ranges, vh_p_match *out, int32_t cap, int32_t *n) {
+  if (!p || !dims || !n || !ranges) return VH_ERR_INVALID_ARG;
+  if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
+  Temp t;
+  int32_t rc;
+  const int32_t nmax = std::max(std::max(n1p, n2p), std::max(n1c, n2c));
+  if ((rc = temp_new(p, device, std::max(nmax, 64), std::max(nmax, 64), t))) return rc;
+  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
+  Group *gq = t.gq;
+  if ((rc = gq->ensure(d))) return rc;
+  if ((rc = gq->load_features(VH_SET_1P, m1p, n1p))) return rc;
+  if ((rc = gq->load_features(VH_SET_2P, m2p, n2p))) return rc;
+  if ((rc = gq->load_features(VH_SET_1C, m1c, n1c))) return rc;
+  if ((rc = gq->load_features(VH_SET_2C, m2c, n2c))) return rc;
+  if ((rc = gq->load_ranges(ranges))) return rc;
+  if ((rc = gq->match(method, nullptr, true))) return rc;
   return gq->get_matches(0, out, cap, n);
 }
 

@@ -1164,8 +1164,13 @@ void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, cons
   const int32_t nchm = (s.cap + 255) / 256;
   dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.rows);
   hipLaunchKernelGGL(chain_kernel, grid, dim3(256), 0, st, s, a, method, best, chain, mask, epoch, mchunk, nchm);
-  if (method == 0)
-    hipLaunchKernelGGL(flow_keep_kernel, grid, dim3(256), 0, st, s, a, chain, (const uint32_t *)mask, epoch, mchunk, nchm);
+  if (method == 0) vh_launch_flow_keep(s, a, chain, mask, epoch, mchunk, st);
+}
+void vh_launch_flow_keep(const VhSets &s, const VhMatchArgs &a, int4 *chain, const uint32_t *mask, uint32_t epoch, int32_t *mchunk,
+                         hipStream_t st) {
+  const int32_t nchm = (s.cap + 255) / 256;
+  dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.rows);
+  hipLaunchKernelGGL(flow_keep_kernel, grid, dim3(256), 0, st, s, a, chain, mask, epoch, mchunk, nchm);
 }
 void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
                             void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,

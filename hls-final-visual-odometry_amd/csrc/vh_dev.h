@@ -232,6 +232,14 @@ void vh_launch_quad_prior(const VhSets &s, const VhMatchArgs &a, const double *t
 // chain: [stream][cap][2] int4 = {i1p,i2p,i1c,i2c} (z = -2: no match), {uv1p,uv2p,uv1c,uv2c}
 void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *best,
                      int4 *chain, uint32_t *mask, uint32_t epoch, int32_t *mchunk, hipStream_t st);
+// the flow method's second half of the chain step (first-writer pixel mask): what vh_launch_chain ends with
+void vh_launch_flow_keep(const VhSets &s, const VhMatchArgs &a, int4 *chain, const uint32_t *mask, uint32_t epoch, int32_t *mchunk,
+                         hipStream_t st);
+// pass 2 of multi-stage matching (kernels_ranged.hip): the whole circle per driving feature inside the ranges of the
+// driver's statistics bin, ranges [row][ubn * vbn][4 stages]{u_min, u_max, v_min, v_max}; writes what vh_launch_chain's
+// first kernel writes (flow: vh_launch_flow_keep follows)
+void vh_launch_ranged_circle(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *ranges, int4 *chain, uint32_t *mask,
+                             uint32_t epoch, int32_t *mchunk, hipStream_t st);
 // ref: refined coordinates of the step (vh_launch_refine), or null: the chain's own
 void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
                             void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,

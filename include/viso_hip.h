@@ -248,6 +248,45 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
                  const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
                  vh_p_match *out, int32_t cap, int32_t *n);
 
+/* ---- multi-stage matching (stock libviso2's multi_stage = 1) [upstream-recollection; DESIGN.md section 6 (f-3) is the
+ * specification; the reference tree keeps struct range / struct delta, src/matcher.h:163-178, and the stat_bin, stage
+ * and use_prior arguments of findMatch and matching, src/matcher.cpp:216-218, 274-276, with nothing behind them] ----
+ * With the switch on, every push also detects the sparse set of each image (src/matcher.cpp:621-628) and every
+ * vh_match_features / vh_group_match_features runs two passes: (1) the method's matching on the sparse sets, unranged,
+ * followed by removeOutliers (flow and quad lists); (2) the statistics of the surviving sparse matches give every
+ * statistics bin a search range per stage of the circle (vh_prior_statistics), and the dense sets are matched inside
+ * the range of the DRIVING feature's bin (vh_match_ranged; csrc/kernels_ranged.hip).  The dense list of pass 2 is the
+ * handle's match list: refinement, every getter and download, vh_remove_outliers, the post chains and the estimators
+ * see it.  Off (the default), nothing is allocated or launched and p.multi_stage keeps its only other meaning
+ * (vh_compute_features hands out the sparse set).
+ * Before the first push only (VH_ERR_STATE afterwards); on = 1 needs p.multi_stage = 1 (VH_ERR_INVALID_ARG);
+ * a sequence handle (vh_sequence_create) does not support the mode: VH_ERR_UNSUPPORTED.  The motion prior does not
+ * combine with it: vh_match_features / vh_group_match_features_prior with Tr_delta16 != NULL return VH_ERR_UNSUPPORTED.
+ * The vote between the passes runs on the host: a match call waits for pass 1 (DESIGN.md section 6 has the cost). */
+int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on);
+int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on);
+/* The sparse list of pass 1 after the vote, of the last match step (*n = 0 before it); VH_ERR_STATE with the switch off. */
+int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n);
+/* computePriorStatistics on caller-owned records (host function, needs no device): ranges[nb][4][4] float, nb = ubn * vbn
+ * statistics bins of matching's grid for dims (src/matcher.cpp:282-283), bin = v_bin * ubn + u_bin, then stage 0..3, then
+ * u_min, u_max, v_min, v_max relative to the query of the stage.  Each match contributes its displacement per stage
+ * (flow: 1c->1p, 1p->1c; stereo: 1c->2c, 2c->1c, v = 0; quad: 1p->2p, 2p->2c, 2c->1c, 1c->1p, v = 0 in the stereo
+ * stages) to the 3 x 3 bins, clamped to the grid, around the bin of its reference point ((u1c, v1c); quad: (u1p, v1p)).
+ * A bin without observations gets +-match_radius; otherwise min / max of the observations, an axis narrower than 20 is
+ * widened by ceil((20 - d) / 2) on both sides.  Stages the method does not have (2, 3 of flow and stereo) read
+ * +-match_radius.  Coordinates must be finite (VH_ERR_INVALID_ARG). */
+int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n,
+                            float *ranges);
+/* vh_match with use_prior = true: every stage of a circle searches query + ranges[stat_bin][stage], stat_bin the bin of
+ * the circle's driving feature (1c; quad: 1p; src/matcher.cpp:314-317); 1-d stages (stereo, quad stages 0 and 2) take
+ * v = query +- match_disp_tolerance whatever the range says.  Everything else is vh_match: unrefined.  Range values must
+ * be finite (VH_ERR_INVALID_ARG); they are used as the integer window ceil(min) .. floor(max), clamped to +-2^20. */
+int32_t vh_match_ranged(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method,
+                        const int32_t *m1p, int32_t n1p, const int32_t *m2p, int32_t n2p,
+                        const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
+                        const float *ranges, vh_p_match *out, int32_t cap, int32_t *n);
+
 /* Stock libviso2's match refinement [upstream-recollection; absent from the reference tree, built on its
  * computeSmallDescriptor, src/matcher.cpp:516-543, and Matrix::solve, src/matrix.cpp:417-504; DESIGN.md section 6
  * (f-3) is the specification] on caller-owned records, in place, order preserved; *n_out = records kept.
@@ -513,7 +552,9 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  * kernel launch while enabled).  vh_group_profile_read returns the
  * accumulated milliseconds and launch count of kernel `name`
  * ("detect_nms", "emit_features", "bin_hist", "bin_scan", "bin_fill",
- *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine")
+ *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine";
+ *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
+ *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds)
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches);

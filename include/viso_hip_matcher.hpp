@@ -110,6 +110,16 @@ class Matcher {
     if (handle) vh_set_intrinsics(handle, f, cu, cv, base);
   }
 
+  // Two-pass matching of stock libviso2 (vh_set_multi_stage_matching): off by default -- the reference ignores
+  // param.multi_stage in matching, and the shim follows the reference.  Before the first pushBack, with
+  // param.multi_stage = 1; returns false (and says why) otherwise.
+  bool setMultiStageMatching(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_multi_stage_matching(handle, on ? 1 : 0);
+    if (rc != VH_OK) report("setMultiStageMatching", rc);
+    return rc == VH_OK;
+  }
+
   // src/matcher.h:116, src/matcher.cpp:51-91
   void pushBack(uint8_t *I1, uint8_t *I2, int32_t *dims, const bool replace) {
     if (!handle) return;
