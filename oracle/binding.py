@@ -213,6 +213,30 @@ class Oracle:
             raise ValueError("vo_matching: invalid method")
         return out[:min(n.value, cap)].copy()
 
+    def ranged_matching(self, params, dims, method, m1p=None, m2p=None, m1c=None, m2c=None, ranges=None, cap=None, detail=False):
+        """tests/multistage_oracle.py's ranged_matching in C (oracle/viso_ranged.c), for large sets.  detail=True also
+        returns dict(stage_idx [ndrive, 4], stage_hit [ndrive, 4], state [ndrive]; see vo_ranged_matching)."""
+        z = np.zeros((0, 12), np.int32)
+        sets = [_feat(z if m is None else m) for m in (m1p, m2p, m1c, m2c)]
+        ubn, vbn = bin_counts(dims, params.match_binsize)
+        ranges = np.ascontiguousarray(ranges, dtype=np.float32)
+        assert ranges.shape == (ubn * vbn, 4, 4), ranges.shape
+        if cap is None:
+            cap = max(s[1] for s in sets) + 1
+        nd = max(sets[0 if method == 2 else 2][1], 1)
+        out = np.zeros(cap, P_MATCH_DTYPE); n = C.c_int32(0)
+        sidx = np.full((nd, 4), -1, np.int32); shit = np.zeros((nd, 4), np.uint8); state = np.zeros(nd, np.uint8)
+        rc = self.lib.vo_ranged_matching(C.byref(params), _dims(dims), C.c_int32(method),
+                                         _ptr(sets[0][0]), C.c_int32(sets[0][1]), _ptr(sets[1][0]), C.c_int32(sets[1][1]),
+                                         _ptr(sets[2][0]), C.c_int32(sets[2][1]), _ptr(sets[3][0]), C.c_int32(sets[3][1]),
+                                         _ptr(ranges), _ptr(out), C.c_int32(cap), C.byref(n), _ptr(sidx), _ptr(shit), _ptr(state))
+        if rc != 0:
+            raise ValueError("vo_ranged_matching: invalid argument (%d)" % rc)
+        res = out[:min(n.value, cap)].copy()
+        if detail:
+            return res, {"n": n.value, "stage_idx": sidx, "stage_hit": shit, "state": state}
+        return res
+
     def matching_quad_prior(self, params, dims, tr16, m1p, m2p, m1c, m2c):
         """Quad matching with the motion prior Tr_delta (row-major 4x4) on hop 2 [upstream-recollection]."""
         sets = [_feat(m) for m in (m1p, m2p, m1c, m2c)]

@@ -122,6 +122,12 @@ int32_t vo_matching_quad_prior(const vo_params *p, const int32_t dims[3], const 
                                const int32_t *m1p, int32_t n1p, const int32_t *m2p, int32_t n2p,
                                const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
                                vo_p_match *out, int32_t cap, int32_t *n_out);
+/* Matcher::matching with use_prior = true (viso_ranged.c: the C form of tests/multistage_oracle.py's ranged_matching).
+ * ranges[ubn * vbn][4][4] float; stage_idx / stage_hit [n drivers][4] and state [n drivers] may be NULL. */
+int32_t vo_ranged_matching(const vo_params *p, const int32_t dims[3], int32_t method, const int32_t *m1p, int32_t n1p,
+                           const int32_t *m2p, int32_t n2p, const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
+                           const float *ranges, vo_p_match *out, int32_t cap, int32_t *n_out, int32_t *stage_idx,
+                           uint8_t *stage_hit, uint8_t *state);
 
 /* For all i1 in set 1: best match index in set 2 (vo_find_match for every
  * query).  Used to check the GPU's whole-set match tables. */

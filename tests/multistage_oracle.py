@@ -16,6 +16,9 @@ P_MATCH_DTYPE = np.dtype([
     ("u1p", "<f4"), ("v1p", "<f4"), ("i1p", "<i4"), ("u2p", "<f4"), ("v2p", "<f4"), ("i2p", "<i4"),
     ("u1c", "<f4"), ("v1c", "<f4"), ("i1c", "<i4"), ("u2c", "<f4"), ("v2c", "<f4"), ("i2c", "<i4")])
 
+#: roles a method reads (0 = 1p, 1 = 2p, 2 = 1c, 3 = 2c)
+NEED = {0: (0, 2), 1: (2, 3), 2: (0, 1, 2, 3)}
+
 #: stages of a method's circle: (query role, candidate role, flow?) with roles 0 = 1p, 1 = 2p, 2 = 1c, 3 = 2c
 STAGES = {
     0: ((2, 0, True), (0, 2, True)),
@@ -138,7 +141,7 @@ def ranged_matching(params, dims, method, m1p, m2p, m1c, m2c, ranges, trace=None
     ubn, vbn = bin_grid(params, dims)
     bs = F32(params.match_binsize)
     ranges = np.asarray(ranges, F32).reshape(ubn * vbn, 4, 4)
-    need = {0: (0, 2), 1: (2, 3), 2: (0, 1, 2, 3)}[method]
+    need = NEED[method]
     out = []
     if any(n[r] <= 0 for r in need):
         return np.zeros(0, P_MATCH_DTYPE)
@@ -173,6 +176,44 @@ def ranged_matching(params, dims, method, m1p, m2p, m1c, m2c, ranges, trace=None
     return np.array(out, P_MATCH_DTYPE) if out else np.zeros(0, P_MATCH_DTYPE)
 
 
+def candidates_in_order(params, q, i1, c, rng, flow):
+    """The candidates findMatch accepts for query i1, in its visiting order (u-bin outer, v-bin inner, list order)
+    -> (indices, costs).  find_match's answer is the first strict minimum of this sequence."""
+    bs = F32(params.match_binsize)
+    u1, v1, cls = int(q.m[i1, 0]), int(q.m[i1, 1]), int(q.m[i1, 3])
+    u_min, u_max = F32(F32(u1) + rng[0]), F32(F32(u1) + rng[1])
+    v_min, v_max = F32(F32(v1) + rng[2]), F32(F32(v1) + rng[3])
+    if not flow:
+        v_min, v_max = F32(v1 - params.match_disp_tolerance), F32(v1 + params.match_disp_tolerance)
+    cl = lambda x, n: min(max(int(math.floor(x / bs)), 0), n - 1)
+    ind, cost = [], []
+    for ub in range(cl(u_min, c.ubn), cl(u_max, c.ubn) + 1):
+        for vb in range(cl(v_min, c.vbn), cl(v_max, c.vbn) + 1):
+            for j in c.bins.get((cls * c.vbn + vb) * c.ubn + ub, ()):
+                u2, v2 = F32(c.m[j, 0]), F32(c.m[j, 1])
+                if u_min <= u2 <= u_max and v_min <= v2 <= v_max:
+                    ind.append(int(j))
+                    cost.append(int(np.abs(c.desc[j] - q.desc[i1]).sum()))
+    return np.array(ind, np.int64), np.array(cost, np.int64)
+
+
+def misrounded(ranges, how):
+    """ranges with the bounds turned into integers the WRONG way (the right way is ceil(min), floor(max)): what a kernel
+    with that rounding would search.  how: "nearest" (halves away from zero), "trunc" (toward zero), "outward"
+    (floor(min), ceil(max))."""
+    r = np.asarray(ranges, np.float64).copy()
+    if how == "nearest":
+        r = np.sign(r) * np.floor(np.abs(r) + 0.5)
+    elif how == "trunc":
+        r = np.trunc(r)
+    elif how == "outward":
+        r[..., 0::2] = np.floor(r[..., 0::2])
+        r[..., 1::2] = np.ceil(r[..., 1::2])
+    else:
+        raise ValueError(how)
+    return r.astype(F32)
+
+
 # ------------------------------------------------------------------ the composition
 def sparse_params(ob, po):
     q = ob.Params.default(**{n: getattr(po, n) for n, _ in ob.Params._fields_})
@@ -180,16 +221,35 @@ def sparse_params(ob, po):
     return q
 
 
-def multistage(ob, oracle, po, dims, method, images):
+def multistage(ob, oracle, po, dims, method, images, fast=False):
     """Both passes for one pair.  images = (I1p, I2p, I1c, I2c), None where the method reads none.
-    -> dict(sparse_sets, dense_sets, sparse_raw, sparse, ranges, dense)."""
+    -> dict(sparse_sets, dense_sets, sparse_raw, sparse, ranges, dense).  fast: pass 2 by the C form of ranged_matching
+    (oracle.ranged_matching, tied to the numpy form by tests/test_multistage_scale.py) -- full-size frames."""
     q = sparse_params(ob, po)
     feats = [None if I is None else oracle.compute_features(q, I, dims) for I in images]
-    need = {0: (0, 2), 1: (2, 3), 2: (0, 1, 2, 3)}[method]
+    need = NEED[method]
     sp = [feats[r][0] if r in need and feats[r] is not None else None for r in range(4)]
     de = [feats[r][1] if r in need and feats[r] is not None else None for r in range(4)]
     raw = oracle.matching(po, dims, method, *sp)
     voted = raw if method == 1 else oracle.remove_outliers(raw)[0]  # (stereo lists carry no flow: left alone)
     ranges = statistics(po, dims, method, voted)
-    dense = ranged_matching(po, dims, method, *de, ranges)
+    dense = oracle.ranged_matching(po, dims, method, *de, ranges) if fast else ranged_matching(po, dims, method, *de, ranges)
     return {"sparse_sets": sp, "dense_sets": de, "sparse_raw": raw, "sparse": voted, "ranges": ranges, "dense": dense}
+
+
+# ------------------------------------------------------------------ recorded answers
+def recorded_answers(ob, oracle, cases):
+    """What tests/golden/multistage_answers.npz records.  cases: (name, dims, parameter overrides, fast, previous pair,
+    current pair), see answer_cases() of tests/test_multistage_scale.py -> name_m<method> -> ([n sparse, n range values,
+    n dense], [SHA-256 of sparse, ranges, dense])."""
+    import hashlib
+    out = {}
+    for name, dims, kw, fast, prev, cur in cases:
+        po = ob.Params.default(multi_stage=1, **kw)
+        imgs = (prev[0], prev[1], cur[0], cur[1])
+        for method in (0, 1, 2):
+            r = multistage(ob, oracle, po, dims, method, [imgs[k] if k in NEED[method] else None for k in range(4)], fast=fast)
+            parts = [np.ascontiguousarray(r[k]) for k in ("sparse", "ranges", "dense")]
+            out["%s_m%d" % (name, method)] = ([len(parts[0]), int(parts[1].size), len(parts[2])],
+                                             [hashlib.sha256(x.tobytes()).hexdigest() for x in parts])
+    return out
