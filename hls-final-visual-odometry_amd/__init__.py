@@ -69,6 +69,8 @@ ABI_SYMBOLS = (
     "vh_refine_matches",
     "vh_set_multi_stage_matching", "vh_group_set_multi_stage_matching", "vh_get_sparse_matches", "vh_group_get_sparse_matches",
     "vh_prior_statistics", "vh_match_ranged",
+    "vh_set_track_linking", "vh_group_set_track_linking", "vh_get_tracks", "vh_group_get_tracks", "vh_group_get_tracks_all",
+    "vh_group_tracks_device", "vh_link_tracks", "vh_track_carry_free", "vh_group_debug_fail_alloc_after",
 )
 
 
@@ -128,6 +130,10 @@ P_MATCH_DTYPE = np.dtype([
     ("u2p", "<f4"), ("v2p", "<f4"), ("i2p", "<i4"),
     ("u1c", "<f4"), ("v1c", "<f4"), ("i1c", "<i4"),
     ("u2c", "<f4"), ("v2c", "<f4"), ("i2c", "<i4")])
+
+
+#: vh_track (include/viso_hip.h), 24 bytes: one per match record of a tracked list
+TRACK = np.dtype([("birth_frame", "<i8"), ("birth_pos", "<i4"), ("age", "<i4"), ("prev", "<i4"), ("reserved", "<i4")])
 
 
 class VisoHipError(RuntimeError):
@@ -210,11 +216,18 @@ def _lib():
             "vh_get_sparse_matches": [vp, vp, i32, vp], "vh_group_get_sparse_matches": [vp, i32, vp, i32, vp],
             "vh_prior_statistics": [vp, vp, i32, vp, i32, vp],
             "vh_match_ranged": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp],
+            "vh_set_track_linking": [vp, i32], "vh_group_set_track_linking": [vp, i32],
+            "vh_get_tracks": [vp, vp, i32, vp], "vh_group_get_tracks": [vp, i32, vp, i32, vp],
+            "vh_group_get_tracks_all": [vp, vp, i32, vp], "vh_group_tracks_device": [vp, vp, vp],
+            "vh_link_tracks": [i32, i32, vp, i64, vp, i32, vp, vp, vp],
+            "vh_group_debug_fail_alloc_after": [vp, i32],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
             fn.argtypes = args
             fn.restype = None if name.endswith("destroy") else i32
+        lib.vh_track_carry_free.argtypes = [vp]
+        lib.vh_track_carry_free.restype = None
         lib.vh_group_device_bytes.argtypes = [vp]
         lib.vh_group_device_bytes.restype = i64
         _LIB = lib
@@ -351,6 +364,23 @@ class Matcher:
             _check(_lib().vh_get_sparse_matches(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_sparse_matches")
         return out
 
+    def setTrackLinking(self, on: bool = True):
+        """Link every match list to the list of the previous pair on the GPU (vh_set_track_linking): before the first
+        pushBack.  The tracks describe the list as matching left it: use outlier_removal=False, or link the voted lists
+        with link_tracks()."""
+        _check(_lib().vh_set_track_linking(self._h, 1 if on else 0), "vh_set_track_linking")
+
+    def getTracks(self) -> np.ndarray:
+        """One TRACK record per record of the last matchFeatures' list (vh_get_tracks)."""
+        n = C.c_int32(0)
+        rc = _check(_lib().vh_get_tracks(self._h, None, 0, C.byref(n)), "vh_get_tracks", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, TRACK)
+        if n.value:
+            _check(_lib().vh_get_tracks(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_tracks")
+        elif rc != VH_OK:
+            raise VisoHipError(rc, "vh_get_tracks")
+        return out
+
     def getFeatures(self, which: int) -> np.ndarray:
         n = C.c_int32(0)
         _check(_lib().vh_get_features(self._h, which, None, 0, C.byref(n)), "vh_get_features", allow=(VH_ERR_CAPACITY,))
@@ -454,6 +484,39 @@ class StreamGroup:
         if n.value:
             _check(_lib().vh_group_get_sparse_matches(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_sparse_matches")
         return out
+
+    def setTrackLinking(self, on: bool = True):
+        """Link every stream's (row's) match lists to their predecessors on the GPU (vh_group_set_track_linking): before
+        the first pushBack; also on a SequenceGroup."""
+        _check(_lib().vh_group_set_track_linking(self._h, 1 if on else 0), "vh_group_set_track_linking")
+
+    def getTracks(self, stream: int) -> np.ndarray:
+        """One TRACK record per record of the stream's (row's) list of the last matchFeatures (vh_group_get_tracks)."""
+        n = C.c_int32(0)
+        rc = _check(_lib().vh_group_get_tracks(self._h, stream, None, 0, C.byref(n)), "vh_group_get_tracks", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, TRACK)
+        if n.value:
+            _check(_lib().vh_group_get_tracks(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_tracks")
+        elif rc != VH_OK:
+            raise VisoHipError(rc, "vh_group_get_tracks")
+        return out
+
+    def getTracksAll(self, out: np.ndarray | None = None, cap_per_stream: int | None = None):
+        """-> (records [S, cap_per_stream] TRACK, counts [S]) as getMatchesAll (vh_group_get_tracks_all)."""
+        if out is None:
+            if cap_per_stream is None:
+                cap_per_stream = int(self.getCounts()[1].max(initial=0))
+            out = np.zeros((self.S, max(cap_per_stream, 1)), TRACK)
+        assert out.dtype == TRACK and out.ndim == 2 and out.shape[0] == self.S and out.flags.c_contiguous
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_get_tracks_all(self._h, _ptr(out), out.shape[1], _ptr(counts)), "vh_group_get_tracks_all")
+        return out, counts
+
+    def tracksDevice(self):
+        """-> (device address of stream 0's track records, stride in records): valid until the next matchFeatures."""
+        ptr = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_tracks_device(self._h, C.byref(ptr), C.byref(stride)), "vh_group_tracks_device")
+        return ptr.value, stride.value
 
     def getFeatures(self, stream: int, which: int) -> np.ndarray:
         n = C.c_int32(0)
@@ -604,6 +667,10 @@ class StreamGroup:
     def debugFailNextAlloc(self):
         """Test hook: the group's next device allocation fails once."""
         _check(_lib().vh_group_debug_fail_next_alloc(self._h), "vh_group_debug_fail_next_alloc")
+
+    def debugFailAllocAfter(self, skip: int):
+        """Test hook: the group's device allocation after `skip` more successful ones fails once."""
+        _check(_lib().vh_group_debug_fail_alloc_after(self._h, int(skip)), "vh_group_debug_fail_alloc_after")
 
     def profileEnable(self, on: bool = True):
         _check(_lib().vh_group_profile_enable(self._h, 1 if on else 0), "vh_group_profile_enable")
@@ -798,6 +865,32 @@ def remove_outliers_device(lists, lanes_per_wave: int = 1, max_features: int = 0
         _check(rc, "vh_remove_outliers_device")
         return [out[l, :oc[l]].copy() for l in range(n)], ntri, ms.value
     return [out[l, :min(int(oc[l]), out_cap)].copy() for l in range(n)], ntri, ms.value, rc
+
+
+class TrackCarry:
+    """The opaque carry of link_tracks(): the last list of a call and its tracks, for the next call to continue."""
+
+    def __init__(self, handle):
+        import weakref
+        self._h = handle
+        weakref.finalize(self, _lib().vh_track_carry_free, C.c_void_p(handle.value))
+
+
+def link_tracks(lists, n_index: int, carry: "TrackCarry | None" = None, device: int = 0):
+    """Feature tracks over caller-owned match lists (vh_link_tracks): list l continues list l - 1, list 0 the last
+    list of the call that returned `carry`.  -> ([TRACK array per list], carry for the next call)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in lists]
+    n = len(lists)
+    stride = max([len(m) for m in lists] + [1])
+    pm = np.zeros((n, stride), P_MATCH_DTYPE)
+    for l, m in enumerate(lists):
+        pm[l, :len(m)] = m
+    counts = np.array([len(m) for m in lists], np.int32)
+    out = np.zeros((n, stride), TRACK)
+    h = C.c_void_p()
+    _check(_lib().vh_link_tracks(device, n, _ptr(pm), stride, _ptr(counts), int(n_index), carry._h if carry is not None else None,
+                                 C.byref(h), _ptr(out)), "vh_link_tracks")
+    return [out[l, :counts[l]].copy() for l in range(n)], TrackCarry(h)
 
 
 def match(param: Params, dims, method: int, m1p=None, m2p=None, m1c=None, m2c=None, device: int = 0, cap=None):

@@ -262,6 +262,7 @@ struct Group {
     }
     if (h_overflow) { (void)hipHostFree(h_overflow); h_overflow = nullptr; }
     if (h_prior_tr) { (void)hipHostFree(h_prior_tr); h_prior_tr = nullptr; }
+    d_ttab = d_ttabp = nullptr; d_trk = nullptr; d_tcount = nullptr; trk_fresh = mask_fresh = false;
     d_ranges = nullptr;
     if (h_ranges) { (void)hipHostFree(h_ranges); h_ranges = nullptr; }
     allocated = false;
@@ -270,7 +271,8 @@ struct Group {
   template <class T> int32_t dmalloc(T **out, size_t count, bool zero) {
     void *q = nullptr;
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (fail_next_alloc) { fail_next_alloc = false; t_last_error = "allocation failure requested by vh_group_debug_fail_next_alloc"; return VH_ERR_HIP; }
+    if (fail_next_alloc && fail_alloc_skip > 0) fail_alloc_skip--;
+    else if (fail_next_alloc) { fail_next_alloc = false; t_last_error = "allocation failure requested by vh_group_debug_fail_next_alloc"; return VH_ERR_HIP; }
     VH_HIP(hipMalloc(&q, bytes));
     allocs.push_back(q);
     device_bytes += (int64_t)bytes;
@@ -417,7 +419,7 @@ struct Group {
     }
     allocated = true;
     pair_cur = 0; pair_prev = 1; frames = 0; epoch = 0; last_method = -1; failed = false;
-    seq_n = seq_n_prev = 0; seq_first = seq_total = 0;
+    seq_n = seq_n_prev = 0; seq_first = seq_total = 0; trk_reset();
     host_matches.assign((size_t)S, {}); host_filtered.assign((size_t)S, 0);
     for (int k = 0; k < VH_RING; k++) ev_read_valid[k] = false;
     ev_post_valid[0] = ev_post_valid[1] = false; match_seq = 0;
@@ -489,6 +491,7 @@ struct Group {
     if (rc != VH_OK) { pair_cur = old_cur; pair_prev = old_prev; frames = old_frames; failed = true; }
     else {
       failed = false;
+      trk_pushed(pair_cur != old_cur, old_frames == 0, seq_n);
       if (seq) { seq_n_prev = seq_n; seq_n = rows; seq_first = seq_total; seq_total += rows; }
     }
     return rc;
@@ -640,6 +643,11 @@ struct Group {
   // match() puts both buffers back to zero before it queues anything.
   bool match_dirty = false;
   bool fail_next_alloc = false;  // test hook (vh_group_debug_fail_next_alloc)
+  // A buffer that was allocated but not cleared yet: set at the allocation, reset only once the clearing memsets are queued,
+  // so a match call that fails between the two leaves the duty to the next one
+  bool trk_fresh = false;        // track tables (trk_queue() clears them on the post stream)
+  bool mask_fresh = false;       // the flow method's pixel mask (match_queued / match_queued_ranged)
+  int32_t fail_alloc_skip = 0;   // test hook: allocations that still succeed before the requested failure
 
   int32_t match_recover() {
     VH_HIP(hipStreamSynchronize(match_stream));
@@ -648,6 +656,9 @@ struct Group {
     VH_HIP(hipMemset(d_redo, 0, sizeof(int32_t) * 2 * (size_t)S));
     stats_pending[0] = stats_pending[1] = false; tiles_hint = 0;
     last_method = -1;
+    // tracks: the failed call's lists are void (match()); a carry copy it may have left half done is void as well, so the
+    // next lists of a sequence start new tracks instead of following a table in an unknown state
+    if (trk_on && seq) { trk_pred_valid = false; trk_carry_src = -1; }
     match_dirty = false;
     return VH_OK;
   }
@@ -715,22 +726,22 @@ struct Group {
     if (tr16 && !d_prior_tr) { const int32_t rt = dmalloc(&d_prior_tr, 16 * (size_t)S, false); if (rt) { d_prior_tr = nullptr; return rt; } }
     if (tr16 && !h_prior_tr) VH_HIP(hipHostMalloc((void **)&h_prior_tr, sizeof(double) * 2 * 16 * (size_t)S, hipHostMallocDefault));
     // everything that can fail without a kernel of the step in flight comes first
-    bool fresh_mask = false;
     if (method == VH_METHOD_FLOW && !d_mask) {
       int32_t rc = dmalloc(&d_mask, (size_t)S * dims[0] * dims[1], false); if (rc) { d_mask = nullptr; return rc; }
-      fresh_mask = true;
+      mask_fresh = true;
     }
+    if (trk_on) { const int32_t rt = trk_ensure(); if (rt) return rt; }
     if (sparse) {
       int32_t rr = ensure_ranges();
       if (rr) return rr;
       if ((rr = multi_stage_ranges(method))) return rr;
     }
-    const int32_t rc = match_queued(method, fresh_mask, tr16, (sparse || ranged) ? d_ranges : nullptr);
-    if (rc) match_dirty = true;
+    const int32_t rc = match_queued(method, tr16, (sparse || ranged) ? d_ranges : nullptr);
+    if (rc) { match_dirty = true; trk_cur_valid = false; }
     return rc;
   }
 
-  int32_t match_queued(int32_t method, bool fresh_mask, const double *tr16, const int32_t *ranges) {
+  int32_t match_queued(int32_t method, const double *tr16, const int32_t *ranges) {
     VhMatchArgs a = match_args(method);
     a.prior = tr16 ? 1 : 0;
     hipStream_t ms = match_stream, ps = post_stream;
@@ -741,7 +752,7 @@ struct Group {
     VH_HIP(hipStreamWaitEvent(ms, ev_det[pair_cur], 0));
     VH_HIP(hipStreamWaitEvent(ms, ev_det[pair_prev], 0));
     if (ev_post_valid[buf]) VH_HIP(hipStreamWaitEvent(ms, ev_post[buf], 0));
-    if (ranges) return match_queued_ranged(method, fresh_mask, a, buf, ranges);
+    if (ranges) return match_queued_ranged(method, a, buf, ranges);
     const bool spec = choose_loop();
     // A stepped group shares the chip with its own detection chain: a grid as tight as the tiles the sets really hold, and
     // the searches' workgroups padded to an LDS footprint that leaves the chain room on every CU (vh_launch_match has the
@@ -769,9 +780,9 @@ struct Group {
     VH_HIP(hipStreamWaitEvent(ps, ev_tables[buf], 0));
     int32_t *d_mchunk = d_mchunk2[buf];  // zeroed by the previous launch's emission (at allocation for the first two)
     if (method == VH_METHOD_FLOW) {
-      if (fresh_mask) {
+      if (mask_fresh) {
         VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ps));
-        epoch = 0;
+        epoch = 0; mask_fresh = false;
       }
       if (++epoch >= (1u << (32 - VH_MASK_IDX_BITS)) - 1) {
         VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ps));
@@ -785,6 +796,7 @@ struct Group {
     if (ev_down_valid) VH_HIP(hipStreamWaitEvent(ps, ev_down, 0));
     { Scope sc(this, "emit_matches", ps); vh_launch_emit_matches(sets, a, method, d_chain2[buf], d_matches, mcap, d_match_count, d_overflow, d_mchunk, d_redo + (size_t)buf * S, d_mchunk2[buf ^ 1], d_out_mapped[buf], d_matches_mapped, ref, ps); }
     VH_HIP(hipGetLastError());
+    if (trk_on) { const int32_t rt = trk_queue(a, ps); if (rt) return rt; }
     // (re-searched, searched) of this launch are read from h_out[buf] by a later choose_loop()
     stats_pending[buf] = true; stats_was_spec[buf] = spec; stats_npass[buf] = a.npass;
     VH_HIP(hipEventRecord(ev_post[buf], ps)); ev_post_valid[buf] = true;
@@ -800,14 +812,14 @@ struct Group {
   // keep step, the refinement and the emission follow on the post stream as in match_queued.  The kernel adds to the
   // chunk counters the previous emission zeroed and bids into the pixel mask the previous keep step read, so the match
   // stream also waits for the previous step's post-processing.
-  int32_t match_queued_ranged(int32_t method, bool fresh_mask, const VhMatchArgs &a, int32_t buf, const int32_t *ranges) {
+  int32_t match_queued_ranged(int32_t method, const VhMatchArgs &a, int32_t buf, const int32_t *ranges) {
     hipStream_t ms = match_stream, ps = post_stream;
     if (ev_post_valid[buf ^ 1]) VH_HIP(hipStreamWaitEvent(ms, ev_post[buf ^ 1], 0));
     int32_t *d_mchunk = d_mchunk2[buf];
     if (method == VH_METHOD_FLOW) {
-      if (fresh_mask) {
+      if (mask_fresh) {
         VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ms));
-        epoch = 0;
+        epoch = 0; mask_fresh = false;
       }
       if (++epoch >= (1u << (32 - VH_MASK_IDX_BITS)) - 1) {
         VH_HIP(hipMemsetAsync(d_mask, 0, sizeof(uint32_t) * (size_t)S * dims[0] * dims[1], ms));
@@ -824,12 +836,142 @@ struct Group {
     if (ev_down_valid) VH_HIP(hipStreamWaitEvent(ps, ev_down, 0));
     { Scope sc(this, "emit_matches", ps); vh_launch_emit_matches(sets, a, method, d_chain2[buf], d_matches, mcap, d_match_count, d_overflow, d_mchunk, d_redo + (size_t)buf * S, d_mchunk2[buf ^ 1], d_out_mapped[buf], d_matches_mapped, ref, ps); }
     VH_HIP(hipGetLastError());
+    if (trk_on) { const int32_t rt = trk_queue(a, ps); if (rt) return rt; }
     stats_pending[buf] = true; stats_was_spec[buf] = false; stats_npass[buf] = a.npass;
     VH_HIP(hipEventRecord(ev_post[buf], ps)); ev_post_valid[buf] = true;
     VH_HIP(hipEventRecord(ev_read[pair_cur], ps)); ev_read_valid[pair_cur] = true;
     VH_HIP(hipEventRecord(ev_read[pair_prev], ps)); ev_read_valid[pair_prev] = true;
     last_method = method; drop_host_matches(); last_buf = buf;
     return VH_OK;
+  }
+
+  // ---- feature tracks (vh_group_set_track_linking; kernels_track.hip) ---------------------
+  // Slots of d_ttab / d_trk: a group keeps two lists per stream, buffer b in the slots [b * S, (b + 1) * S): trk_cur is
+  // the buffer of the current pair's list, the other one holds the previous step's (the predecessors).  A sequence handle
+  // keeps its S rows in the slots [0, S) and the carry -- the last row of the last match call on the previous chunk -- in
+  // slot S; the carry is copied when the first match call of the next chunk is queued, so that matching a chunk again
+  // still finds the carry of the chunk before it.
+  bool trk_on = false;
+  uint32_t *d_ttab = nullptr, *d_ttabp = nullptr;  // [slots][cap] bids by i1c; [S][cap] bids by i1p
+  vh_track *d_trk = nullptr;                       // [slots][mcap]
+  int32_t *d_tcount = nullptr;                     // [slots]
+  uint32_t trk_epoch = 0, trk_cur_epoch = 0, trk_pred_epoch = 0;
+  int32_t trk_cur = 0;
+  bool trk_cur_valid = false;   // the current pair (sequence: chunk) has a tracked list, bid for at trk_cur_epoch
+  bool trk_pred_valid = false;  // group: the other buffer holds the predecessors; sequence: the carry slot is valid
+  int32_t trk_carry_src = -1;   // sequence: row to copy into the carry before the next bids (-1: none)
+  int64_t trk_serial = 0;       // group: serial of the current frame
+  int32_t trk_slots() const { return seq ? S + 1 : 2 * S; }
+  // no list is tracked any more (the tables were cleared, or are about to be)
+  void trk_reset_lists() { trk_epoch = trk_cur_epoch = trk_pred_epoch = 0; trk_cur_valid = trk_pred_valid = false; trk_carry_src = -1; }
+  void trk_reset() { trk_reset_lists(); trk_cur = 0; trk_serial = 0; }  // ... and the sequence starts again (new dims)
+  // a push has succeeded: which list is whose predecessor now
+  void trk_pushed(bool shifted, bool first, int32_t prev_chunk_rows) {
+    if (!trk_on) return;
+    if (seq) {
+      if (first) { trk_pred_valid = false; trk_carry_src = -1; }
+      else if (trk_cur_valid) trk_carry_src = prev_chunk_rows - 1;        // (supersedes a carry that was never needed)
+      else { trk_pred_valid = false; trk_carry_src = -1; }                  // the previous chunk was never matched
+      trk_cur_valid = false;
+      return;
+    }
+    if (first) { trk_serial = 0; trk_cur_valid = trk_pred_valid = false; return; }
+    if (!shifted) { trk_cur_valid = false; return; }  // replace: the pair's list is void, its predecessor stays
+    trk_serial++;
+    trk_pred_valid = trk_cur_valid; trk_pred_epoch = trk_cur_epoch;
+    if (trk_cur_valid) trk_cur ^= 1;
+    trk_cur_valid = false;
+  }
+  // before a match call queues anything: the buffers (the first call allocates them)
+  int32_t trk_ensure() {
+    int32_t rc;
+    if (mcap > (int32_t)VH_TRACK_POS_MASK) return VH_ERR_UNSUPPORTED;  // a table entry has VH_TRACK_POS_BITS bits for the position
+    const size_t slots = (size_t)trk_slots();
+    if (!d_ttab) { if ((rc = dmalloc(&d_ttab, slots * cap, false))) { d_ttab = nullptr; return rc; } trk_fresh = true; }
+    if (!d_ttabp) { if ((rc = dmalloc(&d_ttabp, (size_t)S * cap, false))) { d_ttabp = nullptr; return rc; } trk_fresh = true; }
+    if (!d_trk) { if ((rc = dmalloc((uint8_t **)&d_trk, slots * mcap * sizeof(vh_track), false))) { d_trk = nullptr; return rc; } trk_fresh = true; }
+    if (!d_tcount) { if ((rc = dmalloc(&d_tcount, slots, false))) { d_tcount = nullptr; return rc; } trk_fresh = true; }
+    return VH_OK;
+  }
+  VhTrackArgs trk_args(int32_t rows) const {
+    VhTrackArgs t{};
+    t.pm = (const vh_p_match *)d_matches; t.pm_stride = mcap; t.counts = d_match_count; t.count_cap = mcap;
+    t.rows = rows; t.n_index = cap;
+    t.tab_c = d_ttab; t.tab_p = d_ttabp; t.trk = d_trk; t.trk_stride = mcap; t.slot_count = d_tcount;
+    t.chain = seq ? 1 : 0;
+    t.slot0 = seq ? 0 : trk_cur * S;
+    t.pred0 = trk_pred_valid ? (seq ? S : (trk_cur ^ 1) * S) : -1;
+    t.epoch = trk_epoch; t.pred_epoch = trk_pred_epoch;
+    t.serial0 = seq ? seq_first : trk_serial;
+    t.check = sets.check;
+    return t;
+  }
+  // behind emit_matches on the post stream: the lists of this match call are linked to their predecessors
+  int32_t trk_queue(const VhMatchArgs &a, hipStream_t ps) {
+    const size_t slots = (size_t)trk_slots();
+    if (trk_fresh) {
+      VH_HIP(hipMemsetAsync(d_ttab, 0, sizeof(uint32_t) * slots * cap, ps));
+      VH_HIP(hipMemsetAsync(d_ttabp, 0, sizeof(uint32_t) * (size_t)S * cap, ps));
+      VH_HIP(hipMemsetAsync(d_tcount, 0, sizeof(int32_t) * slots, ps));
+      trk_reset_lists();
+      trk_fresh = false;
+    }
+    trk_cur_valid = false;  // (until everything below is queued)
+    if (seq && trk_carry_src >= 0) {
+      const int32_t src = trk_carry_src;
+      trk_carry_src = -1; trk_pred_valid = false;
+      { Scope sc(this, "track_carry", ps); vh_launch_track_copy(trk_args(0), src, S, ps); }
+      VH_HIP(hipGetLastError());
+      trk_pred_valid = true; trk_pred_epoch = trk_cur_epoch;
+    }
+    if (trk_epoch >= VH_TRACK_EPOCH_MAX) {  // the epochs have come round: the predecessors' bids become epoch 1, everything else empty
+      const int64_t keep0 = seq ? S : (int64_t)(trk_cur ^ 1) * S, keep1 = seq ? S + 1 : keep0 + S;
+      vh_launch_track_retag(d_ttab, cap, (int64_t)slots, keep0, keep1, trk_pred_valid ? trk_pred_epoch : 0u, ps);
+      VH_HIP(hipGetLastError());
+      VH_HIP(hipMemsetAsync(d_ttabp, 0, sizeof(uint32_t) * (size_t)S * cap, ps));
+      trk_pred_epoch = 1; trk_epoch = 1;
+    }
+    trk_epoch++;
+    const VhTrackArgs t = trk_args(a.rows);
+    { Scope sc(this, "track_scatter", ps); vh_launch_track_scatter(t, ps); }
+    { Scope sc(this, "track_link", ps); vh_launch_track_link(t, ps); }
+    { Scope sc(this, "track_rank", ps); vh_launch_track_rank(t, ps); }
+    VH_HIP(hipGetLastError());
+    trk_cur_valid = true; trk_cur_epoch = trk_epoch;
+    return VH_OK;
+  }
+  int32_t get_tracks(int32_t s, vh_track *out, int32_t capo, int32_t *n) {
+    if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+    *n = 0;
+    if (!trk_on || !allocated || last_method < 0 || !trk_cur_valid) return VH_ERR_STATE;
+    VH_HIP(hipEventSynchronize(ev_post[last_buf]));
+    { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+    const int32_t cnt = h_out[last_buf][s].x, ov = h_out[last_buf][s].y;
+    *n = cnt;
+    const int32_t k = std::min(std::min(cnt, mcap), capo);
+    if (k > 0) {
+      VH_HIP(hipMemcpyAsync(out, d_trk + ((size_t)(seq ? 0 : trk_cur * S) + s) * mcap, sizeof(vh_track) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+      VH_HIP(hipStreamSynchronize(post_stream));
+    }
+    return (cnt > capo || cnt > mcap || ov) ? VH_ERR_CAPACITY : VH_OK;
+  }
+  int32_t get_tracks_all(vh_track *out, int32_t cap_per_stream, int32_t *counts) {
+    if (!out || !counts || cap_per_stream < 0) return VH_ERR_INVALID_ARG;
+    for (int32_t s = 0; s < S; s++) counts[s] = 0;
+    if (!trk_on || !allocated || last_method < 0 || !trk_cur_valid) return VH_ERR_STATE;
+    VH_HIP(hipEventSynchronize(ev_post[last_buf]));
+    { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+    bool over = false;
+    for (int32_t s = 0; s < S; s++) {
+      counts[s] = h_out[last_buf][s].x;
+      over = over || h_out[last_buf][s].y != 0 || counts[s] > cap_per_stream || counts[s] > mcap;
+      const int32_t k = std::min(std::min(counts[s], mcap), cap_per_stream);
+      if (k > 0)
+        VH_HIP(hipMemcpyAsync(out + (size_t)s * cap_per_stream, d_trk + ((size_t)(seq ? 0 : trk_cur * S) + s) * mcap, sizeof(vh_track) * (size_t)k,
+                              hipMemcpyDeviceToHost, post_stream));
+    }
+    VH_HIP(hipStreamSynchronize(post_stream));
+    return over ? VH_ERR_CAPACITY : VH_OK;
   }
 
   // Start the device->host copy of every stream's first cap_per_stream match
@@ -1859,6 +2001,124 @@ int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t m
   if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
   return prior_statistics(*p, dims, method, pm, n, ranges);
 }
+// ---- feature tracks ----------------------------------------------------------
+int32_t vh_group_set_track_linking(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: every list since the first frame has its place in the chain
+  gq->trk_on = on != 0;
+  return VH_OK;
+}
+int32_t vh_set_track_linking(vh_matcher *m, int32_t on) { return vh_group_set_track_linking((vh_group *)m, on); }
+int32_t vh_group_get_tracks(vh_group *g, int32_t stream, vh_track *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->get_tracks(stream, out, cap, n);
+}
+int32_t vh_get_tracks(vh_matcher *m, vh_track *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)m; ENTER(gq);
+  return gq->get_tracks(0, out, cap, n);
+}
+int32_t vh_group_get_tracks_all(vh_group *g, vh_track *out, int32_t cap_per_stream, int32_t *counts) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->get_tracks_all(out, cap_per_stream, counts);
+}
+int32_t vh_group_tracks_device(vh_group *g, const vh_track **d_tracks, int64_t *stride) {
+  Group *gq = (Group *)g;
+  if (!gq || !d_tracks || !stride) return VH_ERR_INVALID_ARG;
+  *d_tracks = nullptr; *stride = 0;
+  if (!gq->trk_on || !gq->allocated || gq->last_method < 0 || !gq->trk_cur_valid) return VH_ERR_STATE;
+  *d_tracks = gq->d_trk + (size_t)(gq->seq ? 0 : gq->trk_cur * gq->S) * gq->mcap;
+  *stride = gq->mcap;
+  return VH_OK;
+}
+
+// The stateless form: the lists of one call are the rows of a chain (row l continues row l - 1), the carry of an earlier
+// call -- its last list and that list's tracks, kept on the host -- is bid for again in the slot behind them.
+struct vh_track_carry {
+  int64_t next_serial = 0;
+  std::vector<vh_p_match> pm;
+  std::vector<vh_track> trk;
+};
+void vh_track_carry_free(vh_track_carry *c) { delete c; }
+int32_t vh_link_tracks(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index,
+                       const vh_track_carry *carry_in, vh_track_carry **carry_out, vh_track *out) {
+  if (carry_out) *carry_out = nullptr;
+  if (n_lists < 1 || !counts || stride < 0 || n_index < 1) return VH_ERR_INVALID_ARG;
+  int32_t cmax = 0;
+  for (int32_t l = 0; l < n_lists; l++) {
+    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
+    cmax = std::max(cmax, counts[l]);
+  }
+  if (cmax > 0 && (!pm || !out)) return VH_ERR_INVALID_ARG;
+  if (cmax > (int32_t)VH_TRACK_POS_MASK || (int64_t)n_lists + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;  // (positions share a table entry with the epoch; rows are a grid dimension)
+  const int32_t rc = select_device(device);
+  if (rc) return rc;
+  const int32_t ccnt = carry_in ? (int32_t)carry_in->pm.size() : 0;
+  const int32_t lcap = std::max(std::max(cmax, ccnt), 1), slots = n_lists + 1, cslot = n_lists;
+  struct Guard { std::vector<void *> q; ~Guard() { for (void *x : q) (void)hipFree(x); } } gd;
+  const auto alloc = [&](void **ptr, size_t bytes) { const hipError_t e = hipMalloc(ptr, std::max<size_t>(bytes, 1)); if (e == hipSuccess) gd.q.push_back(*ptr); return e; };
+  vh_p_match *d_pm = nullptr; vh_track *d_trk = nullptr; uint32_t *d_tc = nullptr, *d_tp = nullptr, *d_check = nullptr; int32_t *d_cnt = nullptr, *d_scnt = nullptr;
+  VH_HIP(alloc((void **)&d_pm, sizeof(vh_p_match) * (size_t)slots * lcap));
+  VH_HIP(alloc((void **)&d_trk, sizeof(vh_track) * (size_t)slots * lcap));
+  VH_HIP(alloc((void **)&d_tc, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(alloc((void **)&d_tp, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(alloc((void **)&d_cnt, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(alloc((void **)&d_scnt, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(alloc((void **)&d_check, sizeof(uint32_t) * 4));
+  VH_HIP(hipMemset(d_tc, 0, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(hipMemset(d_tp, 0, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(hipMemset(d_scnt, 0, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(hipMemset(d_check, 0, sizeof(uint32_t) * 4));
+  std::vector<int32_t> hc(counts, counts + n_lists);
+  hc.push_back(ccnt);
+  VH_HIP(hipMemcpy(d_cnt, hc.data(), sizeof(int32_t) * (size_t)slots, hipMemcpyHostToDevice));
+  for (int32_t l = 0; l < n_lists; l++)
+    if (counts[l]) VH_HIP(hipMemcpy(d_pm + (size_t)l * lcap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  VhTrackArgs t{};
+  t.pm = d_pm; t.pm_stride = lcap; t.counts = d_cnt; t.count_cap = lcap; t.n_index = n_index;
+  t.tab_c = d_tc; t.tab_p = d_tp; t.trk = d_trk; t.trk_stride = lcap; t.slot_count = d_scnt; t.check = d_check;
+  t.chain = 1; t.epoch = 1; t.pred_epoch = 1; t.pred0 = -1;
+  if (carry_in) {  // the carry's list bids for its table in the slot behind the lists; its tracks are final
+    if (ccnt) {
+      VH_HIP(hipMemcpy(d_pm + (size_t)cslot * lcap, carry_in->pm.data(), sizeof(vh_p_match) * (size_t)ccnt, hipMemcpyHostToDevice));
+    }
+    VhTrackArgs c = t;
+    c.pm = d_pm + (size_t)cslot * lcap; c.counts = d_cnt + cslot; c.rows = 1; c.slot0 = cslot; c.tab_p = d_tp + (size_t)cslot * n_index;
+    vh_launch_track_scatter(c, nullptr);
+    if (ccnt) VH_HIP(hipMemcpyAsync(d_trk + (size_t)cslot * lcap, carry_in->trk.data(), sizeof(vh_track) * (size_t)ccnt, hipMemcpyHostToDevice, nullptr));
+    t.pred0 = cslot;
+  }
+  t.rows = n_lists; t.slot0 = 0; t.serial0 = carry_in ? carry_in->next_serial : 0;
+  vh_launch_track_scatter(t, nullptr);
+  vh_launch_track_link(t, nullptr);
+  vh_launch_track_rank(t, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+#ifdef VH_CHECK
+  {
+    uint32_t c[4] = {0, 0, 0, 0};
+    VH_HIP(hipMemcpy(c, d_check, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[0]) {
+      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
+      fflush(stderr);
+      abort();
+    }
+  }
+#endif
+  for (int32_t l = 0; l < n_lists; l++)
+    if (counts[l]) VH_HIP(hipMemcpy(out + (size_t)l * stride, d_trk + (size_t)l * lcap, sizeof(vh_track) * (size_t)counts[l], hipMemcpyDeviceToHost));
+  if (carry_out) {
+    vh_track_carry *c = new vh_track_carry();
+    const int32_t last = n_lists - 1;
+    c->next_serial = t.serial0 + n_lists;
+    if (counts[last]) {
+      c->pm.assign(pm + (size_t)last * stride, pm + (size_t)last * stride + counts[last]);
+      c->trk.assign(out + (size_t)last * stride, out + (size_t)last * stride + counts[last]);
+    }
+    *carry_out = c;
+  }
+  return VH_OK;
+}
 int32_t vh_group_match_features(vh_group *g, int32_t method) {
   Group *gq = (Group *)g; ENTER(gq);
   return gq->match(method);
@@ -1925,7 +2185,13 @@ int32_t vh_group_search_stats(vh_group *g, int32_t *speculative, double *researc
 }
 int32_t vh_group_debug_fail_next_alloc(vh_group *g) {
   Group *gq = (Group *)g; ENTER(gq);
-  gq->fail_next_alloc = true;
+  gq->fail_next_alloc = true; gq->fail_alloc_skip = 0;
+  return VH_OK;
+}
+int32_t vh_group_debug_fail_alloc_after(vh_group *g, int32_t skip) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (skip < 0) return VH_ERR_INVALID_ARG;
+  gq->fail_next_alloc = true; gq->fail_alloc_skip = skip;
   return VH_OK;
 }
 int32_t vh_group_profile_enable(vh_group *g, int32_t on) {

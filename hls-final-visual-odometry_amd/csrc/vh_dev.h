@@ -115,7 +115,7 @@ struct VhSets {
 // (engine.hip: check_violation) -- loud, but without a wild access on a shared GPU.
 //   codes: 1 rows_tile query position, 2 rows_tile candidate position, 3 row re-search candidate
 //          position, 4 bin_sort row slot, 5 emit_features stage slot, 6 bin_sort staged bin length,
-//          7 winner position of a search
+//          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position
 #ifdef VH_CHECK
 #define VH_CHECK_RANGE(s_, code_, x_, lo_, hi_)                                          \
   do {                                                                                   \
@@ -254,8 +254,48 @@ void vh_launch_refine(const VhSets &s, const VhMatchArgs &a, int32_t method, con
 // planes of role r (0 = 1p .. 3 = 2c) at rf.du/dv + r * rf.plane; keep[i] = 0 for a dropped record
 void vh_launch_refine_records(const VhRefine &rf, int32_t method, struct vh_p_match *pm, int32_t n, int32_t *keep, hipStream_t st);
 
-struct vh_ego_params;
+// Feature tracks (kernels_track.hip).  Lists live in the rows of a launch; tables and track
+// records live in SLOTS, so that a list which is final already (the previous step of a group, the carry of a sequence)
+// can be looked up beside the rows being linked.
+#define VH_TRACK_POS_BITS 24  // table entry: epoch << 24 | (2^24 - 1 - position); a list holds at most 2^24 - 1 records
+#define VH_TRACK_POS_MASK ((1u << VH_TRACK_POS_BITS) - 1u)
+#define VH_TRACK_EPOCH_MAX ((1u << (32 - VH_TRACK_POS_BITS)) - 1u)
+struct vh_track;
 struct vh_p_match;
+struct VhTrackArgs {
+  const vh_p_match *pm;   // list of row r: pm + r * pm_stride, min(counts[r], count_cap) records
+  int64_t pm_stride;
+  const int32_t *counts;
+  int32_t count_cap;
+  int32_t rows, n_index;  // rows of the launch; feature indices outside [0, n_index) never link
+  uint32_t *tab_c;        // [slots][n_index] lowest position holding the feature as i1c (what the next list looks up)
+  uint32_t *tab_p;        // [rows][n_index]  lowest position holding the feature as i1p (this launch only)
+  vh_track *trk;          // [slots][trk_stride]
+  int64_t trk_stride;
+  int32_t *slot_count;    // [slots] records of the list in each slot
+  int32_t slot0;          // slot of row 0; row r lives in slot0 + r
+  int32_t pred0;          // slot of the predecessor outside the launch, -1: none (see vh_track_pred)
+  int32_t chain;          // 1: the rows are consecutive pairs of one camera, row r continues row r - 1; 0: independent streams
+  uint32_t epoch, pred_epoch;  // of this launch's bids / of the bids in the predecessor outside the launch
+  int64_t serial0;        // serial of row 0's frame B (chain: row r's is serial0 + r)
+  uint32_t *check;        // VH_CHECK builds: VhSets::check
+};
+// The slot that holds the predecessor list of row `row`, -1 if it has none; *in_launch: that list is row - 1 of this launch
+// (not final yet: track_rank walks into it).  The counterpart of vh_row_set for lists.
+//   chain (sequence handle, vh_link_tracks): row r >= 1 -> row r - 1; row 0 -> the carry slot pred0.
+//   group / lone matcher: row r -> slot pred0 + r, the same stream's list of the previous step.
+__host__ __device__ inline int32_t vh_track_pred(const VhTrackArgs &t, int32_t row, bool *in_launch) {
+  *in_launch = t.chain && row > 0;
+  if (*in_launch) return t.slot0 + row - 1;
+  return t.pred0 < 0 ? -1 : t.pred0 + (t.chain ? 0 : row);
+}
+void vh_launch_track_scatter(const VhTrackArgs &t, hipStream_t st);
+void vh_launch_track_link(const VhTrackArgs &t, hipStream_t st);
+void vh_launch_track_rank(const VhTrackArgs &t, hipStream_t st);
+void vh_launch_track_copy(const VhTrackArgs &t, int32_t src, int32_t dst, hipStream_t st);
+void vh_launch_track_retag(uint32_t *tab, int64_t n_index, int64_t n_slots, int64_t keep0, int64_t keep1, uint32_t live, hipStream_t st);
+
+struct vh_ego_params;
 void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
                    const int32_t *counts, int32_t count_cap, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr,
                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st);

@@ -393,6 +393,60 @@ int32_t vh_sequence_push_back(vh_group *g, const uint8_t *I1, const uint8_t *I2,
  * last push (both 0 before the first push); both pointers are required. */
 int32_t vh_sequence_position(const vh_group *g, int64_t *first_frame, int32_t *n_frames);
 
+/* ---- feature tracks: the match lists of consecutive frame pairs linked on the GPU -------------------------------------
+ * Every p_match carries the feature indices i1p / i1c "for tracking" (src/matcher.h:92-98): a record of pair (Z -> A)
+ * with i1c = k and a record of pair (A -> B) with i1p = k are the same left-image feature of frame A.  With the switch on,
+ * every match call also links its lists to their predecessors (csrc/kernels_track.hip) and keeps
+ * one vh_track per match record, same order and count as the list.
+ *   Tracked list: the match list of a handle row as the getters return it right after the match call (after refinement
+ *   if set; host-side post-processing -- vh_remove_outliers, vh_bucket_features -- is not reflected: the tracks describe
+ *   the device list) for a pair of pushed frames (A -> B).  Every push gives its frame a serial number: 0 for the first
+ *   frame of a sequence, + 1 per push; a replace push keeps the serial of the frame it replaces; a change of dims starts
+ *   a new sequence at 0.  On a sequence handle the serial is the frame's index (vh_sequence_position).
+ *   Predecessor of the list of (A -> B): the most recent tracked list of the same camera for a pair (Z -> A) with the
+ *   same frame A -- sequence handle: row r - 1 of the same match call, for row 0 the last row of the last match call
+ *   on the previous chunk; group / lone matcher: the same stream's list of the previous step.  None if no match call
+ *   was made for (Z -> A), if dims changed in between, or if A was replaced after (Z -> A) was matched.  Matching the same
+ *   pair again replaces its tracked list and keeps the predecessor.  Empty rows of a sequence handle hold empty lists.
+ *   Link: record j continues record q of the predecessor iff i1p(j) >= 0 and i1c(q) == i1p(j); of several q the lowest;
+ *   a predecessor record is continued by the lowest such j only.  Every other record starts a new track (age 1), as do
+ *   records whose index lies outside the table (the feature capacity; n_index of vh_link_tracks). */
+typedef struct vh_track {
+  int64_t birth_frame; /* serial of frame B of the pair whose list holds the track's first record */
+  int32_t birth_pos;   /* that record's position in its list: (birth_frame, birth_pos) names the track */
+  int32_t age;         /* records in the track up to and including this one, >= 1 */
+  int32_t prev;        /* position of the continued record in the predecessor list, -1 if none */
+  int32_t reserved;    /* 0 */
+} vh_track;
+/* Before the first push only (VH_ERR_STATE afterwards).  Works on sequence handles and together with refinement, the
+ * motion prior and multi-stage matching.  Off (the default): nothing is allocated or launched.  On: two tables of
+ * 4 * max_features bytes and 24 * max_matches bytes of records per list kept -- S rows and one carry list for a sequence
+ * handle, two lists per stream for a group -- allocated by the first match call and counted by vh_group_device_bytes.
+ * A table entry keeps a list position in 24 bits: with max_matches above 16 777 215 the match calls return
+ * VH_ERR_UNSUPPORTED while the switch is on. */
+int32_t vh_set_track_linking(vh_matcher *m, int32_t on);
+int32_t vh_group_set_track_linking(vh_group *g, int32_t on);
+/* The tracks of the last match call's list(s): capacity and error rules of vh_get_matches / vh_group_get_matches(_all);
+ * VH_ERR_STATE with the switch off or before a match call. */
+int32_t vh_get_tracks(vh_matcher *m, vh_track *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_tracks(vh_group *g, int32_t stream, vh_track *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_tracks_all(vh_group *g, vh_track *out, int32_t cap_per_stream, int32_t *counts);
+/* The device array those getters copy from: stream s's records at *d_tracks + s * *stride (in records), complete once
+ * the work queued by the match call has run (vh_group_synchronize), valid until the next match call. */
+int32_t vh_group_tracks_device(vh_group *g, const vh_track **d_tracks, int64_t *stride);
+/* The same linking for caller-owned lists (host pointers, as vh_remove_outliers_device): list l = pm[l * stride ..
+ * + counts[l]), its predecessor is list l - 1, list 0's the last list of the call that produced carry_in (NULL: none).
+ * This is how lists the handle never sees again -- voted, bucketed -- are linked.  out[l * stride ..] receives list l's
+ * tracks.  n_index >= 1 bounds the feature indices (the table size); birth frames count on from the carry (from 0
+ * without one).  *carry_out (nullable pointer) receives a new carry, to be released with vh_track_carry_free; carry_in
+ * is not consumed.  Lists of more than 16 777 215 records: VH_ERR_UNSUPPORTED.
+ * A convenience entry, not a throughput path: every call allocates and clears two tables of (n_lists + 1) * n_index
+ * words and moves every list with a transfer of its own, so its cost grows with n_lists * n_index. */
+typedef struct vh_track_carry vh_track_carry;
+int32_t vh_link_tracks(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index,
+                       const vh_track_carry *carry_in, vh_track_carry **carry_out, vh_track *out);
+void vh_track_carry_free(vh_track_carry *c);
+
 /* ---- stereo egomotion ------------------------------------- */
 
 /* VisualOdometryStereo::parameters and the calibration it reads
@@ -544,6 +598,9 @@ int32_t vh_group_search_stats(vh_group *g, int32_t *speculative, double *researc
 /* Test hook: the next device allocation the group makes fails (VH_ERR_HIP), once.  Lets the suite drive the error
  * paths of lazily allocated buffers (the flow method's pixel mask). */
 int32_t vh_group_debug_fail_next_alloc(vh_group *g);
+/* The same after `skip` (>= 0) more allocations have succeeded: a failure in the middle of a call that allocates several
+ * buffers (the track tables, then the range tables of multi-stage matching). */
+int32_t vh_group_debug_fail_alloc_after(vh_group *g, int32_t skip);
 /* Test hook: flip-stack entries the device vote's sweep may hold per list (1..31; 0 restores the default, 31), process-wide.
  * With a small value ordinary match lists take the refusal path (VH_ERR_UNSUPPORTED for that list, see
  * vh_remove_outliers_device). */
@@ -553,6 +610,7 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  * accumulated milliseconds and launch count of kernel `name`
  * ("detect_nms", "emit_features", "bin_hist", "bin_scan", "bin_fill",
  *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine";
+ *  with track linking "track_scatter", "track_link", "track_rank" and, once per chunk of a sequence handle, "track_carry";
  *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds)
  *  since the last reset. */

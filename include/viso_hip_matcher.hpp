@@ -120,6 +120,37 @@ class Matcher {
     return rc == VH_OK;
   }
 
+  // Feature tracks (vh_set_track_linking): every matchFeatures also links its list to the list of the previous pair on
+  // the GPU.  Off by default; before the first pushBack, returns false (and says why) otherwise.  The tracks describe
+  // the list as matching left it, before removeOutliers: read them with outlier_removal = false, or link the voted
+  // lists with vh_link_tracks.
+  struct track {
+    int64_t birth_frame;  // serial of the frame whose list holds the track's first record
+    int32_t birth_pos;    // that record's position in its list: (birth_frame, birth_pos) names the track
+    int32_t age;          // records in the track up to and including this one, >= 1
+    int32_t prev;         // position of the continued record in the previous pair's list, -1 if none
+    int32_t reserved;
+  };
+  bool setTrackLinking(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_track_linking(handle, on ? 1 : 0);
+    if (rc != VH_OK) report("setTrackLinking", rc);
+    return rc == VH_OK;
+  }
+  // one record per match of the last matchFeatures, same order as the list matching produced (empty with the switch off)
+  std::vector<Matcher::track> getTracks() {
+    static_assert(sizeof(track) == sizeof(vh_track) && sizeof(track) == 24, "track must mirror vh_track");
+    std::vector<Matcher::track> out;
+    if (!handle) return out;
+    int32_t n = 0;
+    int32_t rc = vh_get_tracks(handle, 0, 0, &n);
+    if ((rc != VH_OK && rc != VH_ERR_CAPACITY) || n <= 0) return out;
+    out.resize((size_t)n);
+    rc = vh_get_tracks(handle, reinterpret_cast<vh_track *>(out.data()), n, &n);
+    if (rc != VH_OK) { report("getTracks", rc); out.clear(); }
+    return out;
+  }
+
   // src/matcher.h:116, src/matcher.cpp:51-91
   void pushBack(uint8_t *I1, uint8_t *I2, int32_t *dims, const bool replace) {
     if (!handle) return;
