@@ -69,6 +69,7 @@ ABI_SYMBOLS = (
     "vh_refine_matches",
     "vh_set_multi_stage_matching", "vh_group_set_multi_stage_matching", "vh_get_sparse_matches", "vh_group_get_sparse_matches",
     "vh_prior_statistics", "vh_match_ranged",
+    "vh_set_multi_stage_device", "vh_group_set_multi_stage_device", "vh_prior_statistics_device",
     "vh_set_track_linking", "vh_group_set_track_linking", "vh_get_tracks", "vh_group_get_tracks", "vh_group_get_tracks_all",
     "vh_group_tracks_device", "vh_link_tracks", "vh_track_carry_free", "vh_group_debug_fail_alloc_after",
 )
@@ -215,6 +216,8 @@ def _lib():
             "vh_set_multi_stage_matching": [vp, i32], "vh_group_set_multi_stage_matching": [vp, i32],
             "vh_get_sparse_matches": [vp, vp, i32, vp], "vh_group_get_sparse_matches": [vp, i32, vp, i32, vp],
             "vh_prior_statistics": [vp, vp, i32, vp, i32, vp],
+            "vh_set_multi_stage_device": [vp, i32], "vh_group_set_multi_stage_device": [vp, i32],
+            "vh_prior_statistics_device": [vp, i32, vp, i32, i32, vp, i64, vp, vp],
             "vh_match_ranged": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp],
             "vh_set_track_linking": [vp, i32], "vh_group_set_track_linking": [vp, i32],
             "vh_get_tracks": [vp, vp, i32, vp], "vh_group_get_tracks": [vp, i32, vp, i32, vp],
@@ -355,6 +358,11 @@ class Matcher:
         param.multi_stage = 1."""
         _check(_lib().vh_set_multi_stage_matching(self._h, 1 if on else 0), "vh_set_multi_stage_matching")
 
+    def setMultiStageDevice(self, on: bool = True):
+        """The vote and the statistics between the two passes on the GPU (vh_set_multi_stage_device): matchFeatures only
+        queues work.  After setMultiStageMatching(True), before the first pushBack."""
+        _check(_lib().vh_set_multi_stage_device(self._h, 1 if on else 0), "vh_set_multi_stage_device")
+
     def getSparseMatches(self) -> np.ndarray:
         """The sparse list of pass 1 after the vote (multi-stage matching on)."""
         n = C.c_int32(0)
@@ -474,6 +482,11 @@ class StreamGroup:
         """Two-pass matching of stock libviso2 for every stream (vh_group_set_multi_stage_matching): before the first
         pushBack, with param.multi_stage = 1; not on a SequenceGroup."""
         _check(_lib().vh_group_set_multi_stage_matching(self._h, 1 if on else 0), "vh_group_set_multi_stage_matching")
+
+    def setMultiStageDevice(self, on: bool = True):
+        """The vote and the statistics between the two passes on the GPU for every stream
+        (vh_group_set_multi_stage_device): after setMultiStageMatching(True), before the first pushBack."""
+        _check(_lib().vh_group_set_multi_stage_device(self._h, 1 if on else 0), "vh_group_set_multi_stage_device")
 
     def getSparseMatches(self, stream: int) -> np.ndarray:
         """The sparse list of pass 1 after the vote (multi-stage matching on)."""
@@ -916,6 +929,24 @@ def prior_statistics(param: Params, dims, method: int, pm) -> np.ndarray:
     out = np.zeros((ubn * vbn, 4, 4), np.float32)
     _check(_lib().vh_prior_statistics(C.byref(param), _dims(dims), int(method), _ptr(pm) if len(pm) else None, len(pm), _ptr(out)),
            "vh_prior_statistics")
+    return out
+
+
+def prior_statistics_device(param: Params, dims, method: int, lists, device: int = 0, stride: int = 0) -> np.ndarray:
+    """prior_statistics of several lists in one launch on the GPU (vh_prior_statistics_device) -> ranges
+    [n_lists, nb, 4, 4] float32.  stride: record slots per list in the array handed over (default: the longest list)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in lists]
+    n = len(lists)
+    stride = max([len(m) for m in lists] + [1, int(stride)])
+    pm = np.zeros((n, stride), P_MATCH_DTYPE)
+    for l, m in enumerate(lists):
+        pm[l, :len(m)] = m
+    counts = np.array([len(m) for m in lists], np.int32)
+    ubn = -(-int(dims[0]) // param.match_binsize)
+    vbn = -(-int(dims[1]) // param.match_binsize)
+    out = np.zeros((n, ubn * vbn, 4, 4), np.float32)
+    _check(_lib().vh_prior_statistics_device(C.byref(param), device, _dims(dims), int(method), n, _ptr(pm), stride, _ptr(counts), _ptr(out)),
+           "vh_prior_statistics_device")
     return out
 
 

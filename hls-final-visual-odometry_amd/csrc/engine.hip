@@ -125,6 +125,12 @@ struct Group {
   // and searches this group's sets inside d_ranges (kernels_ranged.hip).
   Group *sparse = nullptr;
   int32_t *d_ranges = nullptr, *h_ranges = nullptr;  // [S][ubn * vbn][4 stages][4] integer windows; page-locked staging
+  // vh_group_set_multi_stage_device: the vote and the statistics between the passes run on the device, behind pass 1 on the
+  // sparse group's post stream (multi_stage_ranges_device); ms_vb holds the S voted sparse lists, ev_stats orders pass 2
+  // behind the statistics
+  bool ms_device = false;
+  VhVoteBuffers ms_vb;
+  hipEvent_t ev_stats = nullptr;
   int32_t seq_n = 0, seq_n_prev = 0;      // frames of the last chunk / of the one before
   int64_t seq_first = 0, seq_total = 0;   // index in the sequence of the last chunk's first frame / frames pushed so far
 
@@ -182,6 +188,7 @@ struct Group {
     release();
     for (int k = 0; k < VH_RING; k++) { if (ev_det[k]) (void)hipEventDestroy(ev_det[k]); if (ev_read[k]) (void)hipEventDestroy(ev_read[k]); }
     if (ev_user) (void)hipEventDestroy(ev_user);
+    if (ev_stats) (void)hipEventDestroy(ev_stats);
     for (int k = 0; k < 2; k++) if (ev_stage[k]) (void)hipEventDestroy(ev_stage[k]);
     if (copy_stream) (void)hipStreamDestroy(copy_stream);
     if (ev_h2d) (void)hipEventDestroy(ev_h2d);
@@ -265,14 +272,22 @@ struct Group {
     d_ttab = d_ttabp = nullptr; d_trk = nullptr; d_tcount = nullptr; trk_fresh = mask_fresh = false;
     d_ranges = nullptr;
     if (h_ranges) { (void)hipHostFree(h_ranges); h_ranges = nullptr; }
+    ms_vb.release();
     allocated = false;
   }
 
+  // test hook (vh_group_debug_fail_next_alloc / _fail_alloc_after): true when the allocation about to be made is the one to fail
+  bool alloc_refused() {
+    if (!fail_next_alloc) return false;
+    if (fail_alloc_skip > 0) { fail_alloc_skip--; return false; }
+    fail_next_alloc = false;
+    t_last_error = "allocation failure requested by vh_group_debug_fail_next_alloc";
+    return true;
+  }
   template <class T> int32_t dmalloc(T **out, size_t count, bool zero) {
     void *q = nullptr;
     const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-    if (fail_next_alloc && fail_alloc_skip > 0) fail_alloc_skip--;
-    else if (fail_next_alloc) { fail_next_alloc = false; t_last_error = "allocation failure requested by vh_group_debug_fail_next_alloc"; return VH_ERR_HIP; }
+    if (alloc_refused()) return VH_ERR_HIP;
     VH_HIP(hipMalloc(&q, bytes));
     allocs.push_back(q);
     device_bytes += (int64_t)bytes;
@@ -667,9 +682,9 @@ struct Group {
   double *d_prior_tr = nullptr;
   double *h_prior_tr = nullptr;  // page-locked staging, two slots (one per table buffer): the caller's array is only borrowed
   size_t n_ranges() const { return (size_t)S * sets.ubn * sets.vbn * 16; }
-  int32_t ensure_ranges() {
+  int32_t ensure_ranges(bool staging = true) {
     if (!d_ranges) { const int32_t rc = dmalloc(&d_ranges, n_ranges(), false); if (rc) { d_ranges = nullptr; return rc; } }
-    if (!h_ranges) VH_HIP(hipHostMalloc((void **)&h_ranges, sizeof(int32_t) * n_ranges(), hipHostMallocDefault));
+    if (staging && !h_ranges) VH_HIP(hipHostMalloc((void **)&h_ranges, sizeof(int32_t) * n_ranges(), hipHostMallocDefault));
     return VH_OK;
   }
   void prof_host(const char *name, std::chrono::steady_clock::time_point t0) {
@@ -701,6 +716,61 @@ struct Group {
     VH_HIP(hipMemcpyAsync(d_ranges, h_ranges, sizeof(int32_t) * n_ranges(), hipMemcpyHostToDevice, match_stream));
     return VH_OK;
   }
+  // The same on the device (vh_group_set_multi_stage_device): nothing here waits for the GPU or moves a list.  Pass 1, the
+  // vote (kernels_vote.hip, the vote only: the lists are compacted in place in ms_vb) and the statistics (kernels_stats.hip,
+  // straight into d_ranges) follow each other on the sparse group's post stream; the match stream waits for the statistics.
+  // The statistics of this step overwrite the table the previous step's pass 2 read: they wait for that launch
+  // (ev_tables of the previous buffer is recorded right behind it), the vote before them does not.
+  static constexpr int32_t kMsVoteLanes = 16;  // lists per wave of the sweep
+  int32_t ensure_ms_vote() {
+    if (!ev_stats) VH_HIP(hipEventCreateWithFlags(&ev_stats, hipEventDisableTiming));
+    if (ms_vb.block) return VH_OK;
+    if (alloc_refused()) return VH_ERR_HIP;
+    // (a sparse list beyond the vote's list length is refused by vote_prep: VH_VOTE_TRUNCATED)
+    VH_HIP(ms_vb.alloc(S, std::min(sparse->mcap, VH_VOTE_LIST_MAX), 1, 1));
+    return VH_OK;
+  }
+  int32_t multi_stage_ranges_device(int32_t method) {
+    int32_t rc = sparse->match(method);
+    if (rc) return rc;
+    hipStream_t vs = sparse->post_stream;
+    {
+      Scope sc(this, "sparse_vote", vs);
+      vh_launch_vote_prep(ms_vb.v, 0, S, (const vh_p_match *)sparse->d_matches, sparse->mcap, sparse->d_match_count, sparse->mcap, sparse->d_overflow,
+                          method != VH_METHOD_STEREO ? 1 : 0, vs);
+      vh_launch_vote(ms_vb.v, kMsVoteLanes, 0, 0.0f, 0.0f, ms_vb.lfsr, ms_vb.lfsr_n, ms_vb.out, ms_vb.out_cap, ms_vb.out_count, nullptr, vs);
+    }
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipStreamWaitEvent(vs, ev_tables[(match_seq + 1) & 1], 0));  // (never recorded: no wait)
+    VhStatsArgs sa{};
+    sa.pm = ms_vb.v.pm; sa.pm_stride = ms_vb.v.cap;
+    sa.counts = &ms_vb.v.meta->kept; sa.status = &ms_vb.v.meta->status;
+    sa.count_stride = (int32_t)(sizeof(VhVoteMeta) / sizeof(int32_t)); sa.count_cap = ms_vb.v.cap;
+    sa.n_lists = S; sa.method = method; sa.ubn = sets.ubn; sa.vbn = sets.vbn;
+    sa.bs = (float)p.match_binsize; sa.R = (float)p.match_radius;
+    sa.out = d_ranges; sa.err = nullptr;
+    { Scope sc(this, "prior_stats", vs); vh_launch_prior_stats(sa, 1, vs); }
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipEventRecord(ev_stats, vs));
+    VH_HIP(hipStreamWaitEvent(match_stream, ev_stats, 0));
+    return VH_OK;
+  }
+  // The voted sparse list of stream s in device mode: from the vote buffer (waits for the vote)
+  int32_t get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n) {
+    if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+    *n = 0;
+    if (!allocated || !ms_vb.block || sparse->last_method < 0) return VH_OK;
+    VH_HIP(hipStreamSynchronize(sparse->post_stream));
+    { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+    VhVoteMeta m{};
+    VH_HIP(hipMemcpy(&m, ms_vb.v.meta + s, sizeof(m), hipMemcpyDeviceToHost));
+    if (m.status == VH_VOTE_TRUNCATED) return VH_ERR_CAPACITY;
+    if (m.status != VH_VOTE_OK && m.status != VH_VOTE_SKIP) return VH_ERR_UNSUPPORTED;
+    *n = m.kept;
+    const int32_t k = std::min(m.kept, capo);
+    if (k > 0) VH_HIP(hipMemcpy(out, ms_vb.v.pm + (size_t)s * ms_vb.v.cap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost));
+    return m.kept > capo ? VH_ERR_CAPACITY : VH_OK;
+  }
   // Caller-supplied ranges (vh_match_ranged): [ubn * vbn][4][4] float for every stream of the group
   int32_t load_ranges(const float *ranges) {
     int32_t rc = ensure_ranges();
@@ -731,7 +801,12 @@ struct Group {
       mask_fresh = true;
     }
     if (trk_on) { const int32_t rt = trk_ensure(); if (rt) return rt; }
-    if (sparse) {
+    if (sparse && ms_device) {
+      int32_t rr = ensure_ranges(false);
+      if (rr) return rr;
+      if ((rr = ensure_ms_vote())) return rr;
+      if ((rr = multi_stage_ranges_device(method))) { match_dirty = true; return rr; }
+    } else if (sparse) {
       int32_t rr = ensure_ranges();
       if (rr) return rr;
       if ((rr = multi_stage_ranges(method))) return rr;
@@ -1915,6 +1990,7 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
   const Group *gq = (const Group *)g;
   int64_t b = (int64_t)gq->device_bytes;
   if (gq->sparse) b += vh_group_device_bytes((const vh_group *)gq->sparse);  // the sparse sets of multi-stage matching
+  b += (int64_t)gq->ms_vb.bytes;                                             // and the voted sparse lists of its device mode
   for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes;
   return b;
 }
@@ -1971,7 +2047,7 @@ int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on) {
   if (gq->allocated) return VH_ERR_STATE;  // before the first push only: the sparse sets belong to every frame of the ring
   if (on && !gq->p.multi_stage) return VH_ERR_INVALID_ARG;
   if (gq->seq) return VH_ERR_UNSUPPORTED;
-  if (!on) { delete gq->sparse; gq->sparse = nullptr; return VH_OK; }
+  if (!on) { delete gq->sparse; gq->sparse = nullptr; gq->ms_device = false; return VH_OK; }
   if (gq->sparse) return VH_OK;
   vh_params q = gq->p;
   q.nms_n = gq->p.nms_n * 4;  // matcher.cpp:621-623
@@ -1988,8 +2064,19 @@ int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on) { return vh_group
 int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n) {
   Group *gq = (Group *)g; ENTER(gq);
   if (!gq->sparse) return VH_ERR_STATE;
+  if (gq->ms_device) return gq->get_sparse_device(stream, out, cap, n);
   return gq->sparse->get_matches(stream, out, cap, n);
 }
+int32_t vh_group_set_multi_stage_device(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;
+  if (gq->allocated) return VH_ERR_STATE;   // before the first push only, like the mode it belongs to
+  if (on && !gq->sparse) return VH_ERR_STATE;  // multi-stage matching first
+  gq->ms_device = on != 0;
+  return VH_OK;
+}
+int32_t vh_set_multi_stage_device(vh_matcher *m, int32_t on) { return vh_group_set_multi_stage_device((vh_group *)m, on); }
 int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n) {
   return vh_group_get_sparse_matches((vh_group *)m, 0, out, cap, n);
 }
@@ -2000,6 +2087,49 @@ int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t m
   if (dims[0] <= 0 || dims[1] <= 0) return VH_ERR_INVALID_ARG;
   if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
   return prior_statistics(*p, dims, method, pm, n, ranges);
+}
+// The statistics of n_lists lists at once on the device (kernels_stats.hip), list l = pm[l * stride .. + counts[l]):
+// value for value what vh_prior_statistics gives for each list.  The handle's device mode is the throughput path; this
+// entry exists for tests and timing.
+int32_t vh_prior_statistics_device(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, int32_t n_lists, const vh_p_match *pm,
+                                   int64_t stride, const int32_t *counts, float *ranges) {
+  if (!p || !dims || !ranges || !counts || n_lists < 1 || stride < 0 || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
+  int32_t rc = check_params(p);
+  if (rc) return rc;
+  if (dims[0] <= 0 || dims[1] <= 0) return VH_ERR_INVALID_ARG;
+  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  int32_t cap = 1;
+  for (int32_t l = 0; l < n_lists; l++) {
+    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
+    if (counts[l] > 0 && !pm) return VH_ERR_INVALID_ARG;
+    cap = std::max(cap, counts[l]);
+  }
+  if ((rc = select_device(device))) return rc;
+  const float bs = (float)p->match_binsize;
+  VhStatsArgs sa{};
+  sa.ubn = (int32_t)ceilf((float)dims[0] / bs); sa.vbn = (int32_t)ceilf((float)dims[1] / bs);  // matcher.cpp:282-283
+  if ((int64_t)sa.ubn * sa.vbn > INT32_MAX / 16) return VH_ERR_UNSUPPORTED;  // (the kernel indexes a list's table with 32 bits)
+  const size_t per = (size_t)sa.ubn * sa.vbn * 16;
+  struct Guard { vh_p_match *src = nullptr; int32_t *cnt = nullptr; float *out = nullptr;
+                 ~Guard() { if (src) (void)hipFree(src); if (cnt) (void)hipFree(cnt); if (out) (void)hipFree(out); } } gd;
+  VH_HIP(hipMalloc((void **)&gd.src, sizeof(vh_p_match) * (size_t)n_lists * cap));
+  VH_HIP(hipMalloc((void **)&gd.cnt, sizeof(int32_t) * 2 * (size_t)n_lists));  // counts, then the error flags
+  VH_HIP(hipMalloc((void **)&gd.out, sizeof(float) * per * (size_t)n_lists));
+  for (int32_t l = 0; l < n_lists; l++)
+    if (counts[l]) VH_HIP(hipMemcpy(gd.src + (size_t)l * cap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(gd.cnt, counts, sizeof(int32_t) * (size_t)n_lists, hipMemcpyHostToDevice));
+  VH_HIP(hipMemset(gd.cnt + n_lists, 0, sizeof(int32_t) * (size_t)n_lists));
+  sa.pm = gd.src; sa.pm_stride = cap; sa.counts = gd.cnt; sa.status = nullptr; sa.count_stride = 1; sa.count_cap = cap;
+  sa.n_lists = n_lists; sa.method = method; sa.bs = bs; sa.R = (float)p->match_radius;
+  sa.out = gd.out; sa.err = gd.cnt + n_lists;
+  vh_launch_prior_stats(sa, 0, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+  std::vector<int32_t> err((size_t)n_lists);
+  VH_HIP(hipMemcpy(err.data(), gd.cnt + n_lists, sizeof(int32_t) * (size_t)n_lists, hipMemcpyDeviceToHost));
+  for (int32_t l = 0; l < n_lists; l++) if (err[(size_t)l]) return VH_ERR_INVALID_ARG;
+  VH_HIP(hipMemcpy(ranges, gd.out, sizeof(float) * per * (size_t)n_lists, hipMemcpyDeviceToHost));
+  return VH_OK;
 }
 // ---- feature tracks ----------------------------------------------------------
 int32_t vh_group_set_track_linking(vh_group *g, int32_t on) {
@@ -2203,7 +2333,7 @@ int32_t vh_group_profile_enable(vh_group *g, int32_t on) {
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches) {
   Group *gq = (Group *)g; ENTER(gq);
   if (!name) return VH_ERR_INVALID_ARG;
-  if (gq->sparse && !strncmp(name, "sparse_", 7) && strcmp(name, "sparse_vote_host")) {  // the sparse group's kernels
+  if (gq->sparse && !strncmp(name, "sparse_", 7) && strcmp(name, "sparse_vote_host") && strcmp(name, "sparse_vote")) {  // the sparse group's kernels
     gq = gq->sparse; name += 7;
   }
   gq->prof_collect();

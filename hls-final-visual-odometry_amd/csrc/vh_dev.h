@@ -246,6 +246,23 @@ void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t metho
                             const int32_t *mchunk, int32_t *redo, int32_t *mchunk_next, void *host_out, void *host_matches,
                             const float4 *ref, hipStream_t st);
 
+// computePriorStatistics of multi-stage matching on the device (kernels_stats.hip): one workgroup per list.
+#define VH_STATS_LDS_MAX 65536  // bytes of LDS the key table [bins][16] may take; larger grids keep their keys in `out`
+struct vh_p_match;
+struct VhStatsArgs {
+  const vh_p_match *pm;   // list l: pm + l * pm_stride, min(counts[l * count_stride], count_cap) records
+  int64_t pm_stride;
+  const int32_t *counts;  // (a plain array with count_stride = 1, or a field of an array of structures)
+  const int32_t *status;  // null, or VH_VOTE_* of list l at status[l * count_stride]: a refused list reads as empty
+  int32_t count_stride, count_cap;
+  int32_t n_lists, method;
+  int32_t ubn, vbn;       // the bin grid of `matching` (matcher.cpp:282-283)
+  float bs, R;            // match_binsize, match_radius
+  void *out;              // [n_lists][ubn * vbn][4 stages]{u_min, u_max, v_min, v_max}: float, or the int32 windows of vh_launch_ranged_circle
+  int32_t *err;           // null, or [n_lists]: set to 1 for a list with a non-finite reference point or delta (zeroed by the caller)
+};
+void vh_launch_prior_stats(const VhStatsArgs &a, int32_t windows, hipStream_t st);
+
 void vh_refine_setup(VhRefine &rf);  // fills gj_* (host, once per handle)
 void vh_launch_refine_planes(const VhImages &im, const VhRefine &rf, hipStream_t st);
 // ref: [row][cap][2] float4 {u1p, v1p, u2p, v2p}, {u1c, v1c, u2c, v2c}, written for the kept entries

@@ -262,10 +262,25 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
  * Before the first push only (VH_ERR_STATE afterwards); on = 1 needs p.multi_stage = 1 (VH_ERR_INVALID_ARG);
  * a sequence handle (vh_sequence_create) does not support the mode: VH_ERR_UNSUPPORTED.  The motion prior does not
  * combine with it: vh_match_features / vh_group_match_features_prior with Tr_delta16 != NULL return VH_ERR_UNSUPPORTED.
- * The vote between the passes runs on the host: a match call waits for pass 1 (DESIGN.md section 6 has the cost). */
+ * The vote between the passes runs on the host: a match call waits for pass 1 (DESIGN.md section 6 has the cost),
+ * unless vh_set_multi_stage_device moves it to the device. */
 int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on);
 int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on);
-/* The sparse list of pass 1 after the vote, of the last match step (*n = 0 before it); VH_ERR_STATE with the switch off. */
+/* Both steps between the passes on the device: the vote (csrc/kernels_vote.hip, as vh_remove_outliers_device with
+ * max_features = 0) and the statistics (csrc/kernels_stats.hip, as vh_prior_statistics_device) are queued behind pass 1,
+ * pass 2 behind them.  A match call then only queues work, like every other match call of the library: no wait, no
+ * transfer of lists, no host threads.  Lists and ranges equal the host form's (off, the default: that form, unchanged).
+ * Before the first push only (VH_ERR_STATE afterwards); on = 1 needs multi-stage matching switched on already
+ * (VH_ERR_STATE); a sequence handle: VH_ERR_UNSUPPORTED.  Switching multi-stage matching off clears it.
+ * A sparse list the device vote refuses (truncated, above 65 535 records, more pending flips than its stack holds) gets
+ * +-match_radius in every bin, for which pass 2 is single-stage matching: the match call returns VH_OK, and
+ * vh_(group_)get_sparse_matches returns the refusal's code for that stream (VH_ERR_CAPACITY / VH_ERR_UNSUPPORTED) with
+ * *n = 0.  The first match call allocates the vote buffer (176 bytes per record slot of the sparse lists; counted by
+ * vh_group_device_bytes); when that fails the call returns VH_ERR_HIP and the handle keeps working. */
+int32_t vh_set_multi_stage_device(vh_matcher *m, int32_t on);
+int32_t vh_group_set_multi_stage_device(vh_group *g, int32_t on);
+/* The sparse list of pass 1 after the vote, of the last match step (*n = 0 before it); VH_ERR_STATE with the switch off.
+ * In device mode the list comes from the vote buffer, and the call waits for the vote. */
 int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n);
 int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n);
 /* computePriorStatistics on caller-owned records (host function, needs no device): ranges[nb][4][4] float, nb = ubn * vbn
@@ -278,6 +293,13 @@ int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out
  * +-match_radius.  Coordinates must be finite (VH_ERR_INVALID_ARG). */
 int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n,
                             float *ranges);
+/* The same for n_lists lists in one launch on the device (csrc/kernels_stats.hip; host pointers): list l is
+ * pm[l * stride .. + counts[l]), its table ranges[l][nb][4][4].  Every value equals vh_prior_statistics' (a zero may
+ * carry the other sign).  counts[l] = 0 gives the +-match_radius table.  VH_ERR_INVALID_ARG for n_lists < 1, null
+ * pointers, a bad method, counts[l] outside [0, stride], or a list that holds a non-finite value (ranges is then
+ * left unwritten); VH_ERR_UNSUPPORTED for a grid of more than 2^27 - 1 bins. */
+int32_t vh_prior_statistics_device(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, int32_t n_lists,
+                                   const vh_p_match *pm, int64_t stride, const int32_t *counts, float *ranges);
 /* vh_match with use_prior = true: every stage of a circle searches query + ranges[stat_bin][stage], stat_bin the bin of
  * the circle's driving feature (1c; quad: 1p; src/matcher.cpp:314-317); 1-d stages (stereo, quad stages 0 and 2) take
  * v = query +- match_disp_tolerance whatever the range says.  Everything else is vh_match: unrefined.  Range values must
@@ -612,7 +634,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine";
  *  with track linking "track_scatter", "track_link", "track_rank" and, once per chunk of a sequence handle, "track_carry";
  *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
- *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds)
+ *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
+ *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place)
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches);

@@ -120,6 +120,15 @@ class Matcher {
     return rc == VH_OK;
   }
 
+  // The vote and the statistics between the two passes on the GPU (vh_set_multi_stage_device): matchFeatures then only
+  // queues work.  After setMultiStageMatching(true), before the first pushBack; returns false (and says why) otherwise.
+  bool setMultiStageDevice(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_multi_stage_device(handle, on ? 1 : 0);
+    if (rc != VH_OK) report("setMultiStageDevice", rc);
+    return rc == VH_OK;
+  }
+
   // Feature tracks (vh_set_track_linking): every matchFeatures also links its list to the list of the previous pair on
   // the GPU.  Off by default; before the first pushBack, returns false (and says why) otherwise.  The tracks describe
   // the list as matching left it, before removeOutliers: read them with outlier_removal = false, or link the voted
