@@ -18,7 +18,7 @@
 //    (walk_region_lds), and the four phases take candidates j, j+1, j+2, j+3 of a buffer in the
 //    same step: one candidate stream shared by all phases, every record read from LDS serves two
 //    queries per lane, 8 v_sad_u8 / v_sad_hi_u8 per pair, the partial minima joined by two
-//    shuffles per tile.
+//    row swaps per tile (join_phases).
 //    Positions in bin order ARE the reference's visiting order, so its first-minimum tie-break
 //    (strict `<`, src/matcher.cpp:264) is the minimum of the key (SAD << 19 | position) -- or
 //    (SAD << 16 | position - class base), which the v_sad_hi_u8 chain produces by itself --
@@ -101,6 +101,21 @@ __device__ __forceinline__ int32_t row16_allreduce(int32_t v) {
   return v;
 }
 
+// Gathers of the tiles.  Every array base below is wave-uniform and every index is below 2^24, so a lane's address is
+// a uniform base plus a 32-bit BYTE offset: the scalar-base form of the global loads and stores (base in two scalar
+// registers, offset in one vector register) instead of a sign extension and a 64-bit shift-and-add per access.
+template <class T>
+__device__ __forceinline__ T ld_off(const T *base, uint32_t byte_off) { return *(const T *)((const char *)base + byte_off); }
+template <class T>
+__device__ __forceinline__ void st_off(T *base, uint32_t byte_off, T x) { *(T *)((char *)base + byte_off) = x; }
+// A wave-uniform word of the index arrays (tile records, bin and row starts).  match_kernel only reads them -- earlier
+// kernels of the stream wrote them -- but it also stores (the tables), so through a plain pointer the compiler has to
+// assume they may change and emits a vector load plus v_readfirstlane.  Read through the constant address space the
+// same access is one scalar load.
+template <class T>
+__device__ __forceinline__ T ld_uniform(const T *p) { return *(const __attribute__((address_space(4))) T *)(uintptr_t)p; }
+__device__ __forceinline__ int32_t ld_uniform_i32(const int32_t *p) { return __builtin_amdgcn_readfirstlane(ld_uniform(p)); }
+
 // The candidate stream of a tile of the flow search: every candidate of class c in
 // the bins [UB0, UB1] x [VB0, VB1] (u-bin major, as Matcher::findMatch visits them,
 // matcher.cpp:243-246), handed to `consume` in chunks of <= 64 consecutive positions,
@@ -132,7 +147,8 @@ __device__ __forceinline__ void walk_region(const VhSets &s, const int32_t *__re
     int32_t t_p0 = 0, t_p1 = 0, t_a0 = 0, t_a1 = 0;
     if (lane < ncb) {
       const int32_t row = (c * s.ubn + cb + lane) * s.vbn;
-      t_p0 = cbs[row + VB0]; t_p1 = merged ? cbs[(c * s.ubn + UB1 + 1) * s.vbn] : cbs[row + VB1 + 1];
+      t_p0 = ld_off(cbs, (uint32_t)(row + VB0) * 4u);
+      t_p1 = ld_off(cbs, (uint32_t)(merged ? (c * s.ubn + UB1 + 1) * s.vbn : row + VB1 + 1) * 4u);
       if (TESTED) {
         const int32_t ubx = cb + lane;
         const bool in_ = ubx * s.binsize >= ULO_MAX && ubx * s.binsize + s.binsize - 1 <= UHI_MIN;
@@ -178,11 +194,12 @@ __device__ __forceinline__ void walk_region(const VhSets &s, const int32_t *__re
 // addresses straight to LDS at M0 + lane * size -- no VGPR destination, no ds_write.  hipcc does not count an asm
 // memory operation, so completion is waited for by hand (vmcnt) before the chunk is read; the builtin form makes
 // hipcc drain every DMA (vmcnt(0)) before ANY ds_read, which would serialise the prefetch of the next chunk.
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(gsrc), "s"(lds_dst) : "memory");
+// The source is a wave-uniform base (scalar registers) plus a per-lane 32-bit byte offset.
+__device__ __forceinline__ void glds16(const void *gbase, uint32_t byte_off, uint32_t lds_dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(byte_off), "s"(gbase), "s"(lds_dst) : "memory");
 }
-__device__ __forceinline__ void glds4(const void *gsrc, uint32_t lds_dst) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(gsrc), "s"(lds_dst) : "memory");
+__device__ __forceinline__ void glds4(const void *gbase, uint32_t byte_off, uint32_t lds_dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(byte_off), "s"(gbase), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ uint32_t lds_addr(const void *p) {
   return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p);
@@ -200,6 +217,7 @@ __device__ __forceinline__ void walk_region_lds(const VhSets &s, const int32_t *
                                                 uint4 *wD, uint32_t *wU, Consume consume) {
   const int32_t lane = threadIdx.x & 63;
   const uint32_t ldsD = lds_addr(wD), ldsU = lds_addr(wU);
+  const uint32_t lane32 = (uint32_t)lane * 32u;
   const bool merged = !TESTED && VB0 == 0 && VB1 == s.vbn - 1;
   const int32_t UB1w = merged ? UB0 : UB1;
   for (int32_t cb = UB0; cb <= UB1w; cb += 64) {
@@ -207,7 +225,8 @@ __device__ __forceinline__ void walk_region_lds(const VhSets &s, const int32_t *
     int32_t t_p0 = 0, t_p1 = 0, t_a0 = 0, t_a1 = 0;
     if (lane < ncb) {
       const int32_t row = (c * s.ubn + cb + lane) * s.vbn;
-      t_p0 = cbs[row + VB0]; t_p1 = merged ? cbs[(c * s.ubn + UB1 + 1) * s.vbn] : cbs[row + VB1 + 1];
+      t_p0 = ld_off(cbs, (uint32_t)(row + VB0) * 4u);
+      t_p1 = ld_off(cbs, (uint32_t)(merged ? (c * s.ubn + UB1 + 1) * s.vbn : row + VB1 + 1) * 4u);
       if (TESTED) {
         const int32_t ubx = cb + lane;
         const bool in_ = ubx * s.binsize >= ULO_MAX && ubx * s.binsize + s.binsize - 1 <= UHI_MIN;
@@ -225,10 +244,10 @@ __device__ __forceinline__ void walk_region_lds(const VhSets &s, const int32_t *
       return true;
     };
     const auto issue = [&](int32_t b) {  // chunk [pc, p1) -> buffer b
-      const int32_t pl = min(pc + lane, p1 - 1);
-      const uint4 *g = cdesc + 2 * (int64_t)pl;
-      glds16(g, ldsD + (uint32_t)b * 2048u); glds16(g + 1, ldsD + (uint32_t)b * 2048u + 1024u);
-      if (TESTED) glds4(cuv + pl, ldsU + (uint32_t)b * 256u);
+      // 32 * min(pc + lane, p1 - 1) with the scalar terms shifted on the scalar unit: one add and one min per chunk
+      const uint32_t off = min((uint32_t)pc * 32u + lane32, (uint32_t)(p1 - 1) * 32u);
+      glds16(cdesc, off, ldsD + (uint32_t)b * 2048u); glds16(cdesc, off + 16u, ldsD + (uint32_t)b * 2048u + 1024u);
+      if (TESTED) glds4(cuv, off >> 3, ldsU + (uint32_t)b * 256u);
     };
     if (!advance()) continue;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the buffers by an earlier walk has returned
@@ -302,18 +321,41 @@ __device__ __forceinline__ typename KeyT<KM>::type sad_key(const uint4 &a0, cons
   if (KM == KEY_W19) return (typename KeyT<KM>::type)((sad << 19) | seed);
   return (typename KeyT<KM>::type)(((uint64_t)sad << 32) | seed);
 }
-// any encoding -> SAD << 32 | position (or ~0 for "none")
-template <int KM>
-__device__ __forceinline__ uint64_t key_to_64(typename KeyT<KM>::type k) {
-  if (KM == KEY_64) return (uint64_t)k;
-  if ((uint32_t)k == 0xFFFFFFFFu) return ~0ull;
-  const uint32_t kk = (uint32_t)k;
-  return KM == KEY_HI16 ? (((uint64_t)(kk >> 16) << 32) | (kk & 0xFFFFu)) : (((uint64_t)(kk >> 19) << 32) | (kk & 0x7FFFFu));
-}
 __device__ __forceinline__ int32_t key_mode_of(int32_t class_count, int32_t wide_keys) {
   // (+64: the copies past the end of a run carry positions up to 63 past it)
   if (class_count + 64 <= 0x10000 && !wide_keys) return KEY_HI16;
   return class_count <= VH_CLASS_POS_MAX && wide_keys < 2 ? KEY_W19 : KEY_64;
+}
+
+// Joins the partial minima of the four phases (lanes l, l + 16, l + 32, l + 48 hold those of the same two queries)
+// and returns ONE winner per lane: the class-relative position of the winner of query slot 0 in lanes 0-31, of slot 1
+// in lanes 32-63 (-1: none), each on both 16-lane rows of its half.
+//   32-bit keys: their order is the order of (SAD, position), so the join stays in key space.  v_permlane32_swap with
+//   slot 0's keys as the first and slot 1's as the second operand leaves {k0[l], k0[l + 32]} in lanes l < 32 and
+//   {k1[l - 32], k1[l]} in lanes l >= 32: one swap and one v_min_u32 join the halves of BOTH slots.  v_permlane16_swap
+//   of the result with itself pairs every row with its neighbour: a second swap and min complete the join.  Two swaps
+//   and two minima per tile, no LDS; the round-5 form widened each key to 64 bits first and paid two ds_bpermute, a
+//   64-bit compare and two selects per step and slot (31 VALU instructions per tile against 7).
+//   64-bit keys: shuffles and 64-bit minima as before; each half then keeps its slot.
+template <int Q, int P, int KM>
+__device__ __forceinline__ int32_t join_phases(const typename KeyT<KM>::type (&best_key)[Q]) {
+  static_assert(Q == 2 && P == 4, "the join splits the wave into two slots of two 16-lane rows");
+  if (KM == KEY_64) {
+    uint64_t k[Q];
+#pragma unroll
+    for (int32_t qi = 0; qi < Q; qi++) {
+      k[qi] = (uint64_t)best_key[qi];
+#pragma unroll
+      for (int32_t d = 16; d < 64; d <<= 1) k[qi] = min(k[qi], shfl_xor_u64(k[qi], d));
+    }
+    const uint64_t kk = (threadIdx.x & 32) ? k[1] : k[0];
+    return kk == ~0ull ? -1 : (int32_t)(uint32_t)kk;
+  }
+  const auto h = __builtin_amdgcn_permlane32_swap((uint32_t)best_key[0], (uint32_t)best_key[1], false, false);
+  const uint32_t kh = min(h[0], h[1]);
+  const auto r = __builtin_amdgcn_permlane16_swap(kh, kh, false, false);
+  const uint32_t k = min(r[0], r[1]);
+  return k == 0xFFFFFFFFu ? -1 : (int32_t)(k & (KM == KEY_HI16 ? 0xFFFFu : 0x7FFFFu));
 }
 
 // Second half of the speculative searches.  A query whose winner over the walked region lies
@@ -332,21 +374,20 @@ __device__ __forceinline__ int32_t key_mode_of(int32_t class_count, int32_t wide
 struct RedoGroup {
   uint32_t qd[VH_REDO_G][8];  // descriptors (wave-uniform)
   us2 lo2[VH_REDO_G];         // window origins
-  int32_t lane[VH_REDO_G], qi[VH_REDO_G], n;
+  int32_t lane[VH_REDO_G], n;  // lane: the lane of finish_tile that owns the query
   int32_t umin, umax, vmin, vmax;
 };
-// Takes up to VH_REDO_G (lane, query slot) pairs off the ballots `todo[Q]`; false when none is left.
+// Takes up to VH_REDO_G lanes off the ballot `todo`; false when none is left.  A lane of the ballot stands for its own
+// query slot (finish_tile: lane >> 5), lowest lane first: slot 0's queries before slot 1's, each in tile order.
 template <int Q>
-__device__ __forceinline__ bool redo_take(uint64_t (&todo)[Q], const uint4 (&a0)[Q], const uint4 (&a1)[Q], const uint32_t (&uv1)[Q],
+__device__ __forceinline__ bool redo_take(uint64_t &todo, const uint4 (&a0)[Q], const uint4 (&a1)[Q], const uint32_t (&uv1)[Q],
                                           int32_t radius, int32_t rv, RedoGroup &g) {
   g.n = 0; g.umin = g.vmin = 0x7FFFFFFF; g.umax = g.vmax = -1;
 #pragma unroll
   for (int32_t k = 0; k < VH_REDO_G; k++) {
-    int32_t fl = -1, fq = 0;
-#pragma unroll
-    for (int32_t qi = 0; qi < Q; qi++)
-      if (fl < 0 && todo[qi]) { fl = (int32_t)__builtin_ctzll(todo[qi]); fq = qi; todo[qi] &= todo[qi] - 1; }
-    if (fl < 0) break;  // wave-uniform
+    if (!todo) break;  // wave-uniform
+    const int32_t fl = (int32_t)__builtin_ctzll(todo), fq = fl >> 5;
+    todo &= todo - 1;
     uint4 x0 = a0[0], x1 = a1[0];
     uint32_t xu = uv1[0];
 #pragma unroll
@@ -358,16 +399,16 @@ __device__ __forceinline__ bool redo_take(uint64_t (&todo)[Q], const uint4 (&a0)
     const uint32_t quv1 = __builtin_amdgcn_readlane(xu, fl);
     const int32_t u1 = (int32_t)(quv1 & 0xFFFF), v1 = (int32_t)(quv1 >> 16);
     g.lo2[k] = us2{(unsigned short)(u1 - radius), (unsigned short)(v1 - rv)};
-    g.lane[k] = fl; g.qi[k] = fq; g.n = k + 1;
+    g.lane[k] = fl; g.n = k + 1;
     g.umin = min(g.umin, u1); g.umax = max(g.umax, u1); g.vmin = min(g.vmin, v1); g.vmax = max(g.vmax, v1);
   }
   return g.n > 0;
 }
 
-// What a tile hands to finish_tile: per query slot the minimum key over the walked region, joined over
-// the phases (SAD << 32 | class-relative position, ~0: none), and the query itself.
+// What a tile hands to finish_tile: the winner over the walked region of ONE query per lane, joined over the phases
+// (join_phases: lanes 0-31 hold query slot 0, lanes 32-63 slot 1), and the lane's queries themselves.
 template <int Q> struct TileOut {
-  uint64_t k[Q];
+  int32_t wp;  // class-relative position of the winner of query slot (lane >> 5), -1: none
   uint4 a0[Q], a1[Q];
   uint32_t uv1[Q];
   int32_t qpos[Q];  // the query's bin-order position
@@ -388,8 +429,8 @@ template <int Q, int P, bool SPEC, bool FLOW>
 __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &a, int32_t pass, int32_t stream, int32_t qset, int32_t cset,
                                             int32_t c, int32_t pbase, int32_t pcnt, const TileOut<Q> &o,
                                             int32_t *__restrict__ best, int32_t *__restrict__ redo_count) {
-  constexpr int L = 64 / P;
-  const int32_t lane = threadIdx.x & 63, ph = lane / L;
+  static_assert(Q == 2 && P == 4, "one query per lane: slot lane >> 5, on the first 16-lane row of each half (join_phases)");
+  const int32_t lane = threadIdx.x & 63;
   const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
   const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
   const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
@@ -398,33 +439,31 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
   const int32_t *__restrict__ cidx = s.s_idx + (int64_t)cset * s.cap;
   const int32_t *__restrict__ qidx = s.s_idx + (int64_t)qset * s.cap;
   int32_t *__restrict__ tbl = best + ((int64_t)stream * 4 + a.pass[pass].slot) * s.cap;
-  int32_t res[Q];
-  uint64_t todo[Q];
-#pragma unroll
-  for (int32_t qi = 0; qi < Q; qi++) {
-    res[qi] = -1;  // no candidate accepted
-    bool fail = false;
-    if (o.valid[qi] && ph == 0 && o.k[qi] != ~0ull) {
-      // (a winner is never one of the copies past the end of a run -- the original has the same SAD at a lower
-      //  position -- so its position lies inside the class)
-      int32_t wp = (int32_t)(uint32_t)o.k[qi];
-      VH_CHECK_RANGE(s, 7, wp, 0, pcnt);
-      res[qi] = pbase + wp;
-      if (SPEC) {  // the winner over the walked region: inside this query's own window?
-        const int32_t u1 = o.uv1[qi] & 0xFFFF, v1 = o.uv1[qi] >> 16;
-        const us2 lo2 = {(unsigned short)(u1 - a.radius), (unsigned short)(v1 - rv)};
-        const us2 t = as_us2(cuv[res[qi]]) - lo2;
-        const us2 m = __builtin_elementwise_min(t, span2);
-        fail = as_u32(t) != as_u32(m);
-      }
+  // After the join every lane holds a winner, so the test, the gathers and the store run ONCE for the tile's 32
+  // queries, on 32 lanes (rows 0 and 2), instead of once per slot on the 16 lanes of phase 0.
+  const bool hi = lane & 32;
+  const bool mine = !(lane & 16) && (hi ? o.valid[1] : o.valid[0]);
+  const uint32_t uv1 = hi ? o.uv1[1] : o.uv1[0];
+  const int32_t qpos = hi ? o.qpos[1] : o.qpos[0];
+  int32_t res = -1;  // no candidate accepted
+  bool fail = false;
+  if (mine && o.wp >= 0) {
+    // (a winner is never one of the copies past the end of a run -- the original has the same SAD at a lower
+    //  position -- so its position lies inside the class)
+    int32_t wp = o.wp;
+    VH_CHECK_RANGE(s, 7, wp, 0, pcnt);
+    res = pbase + wp;
+    if (SPEC) {  // the winner over the walked region: inside this query's own window?
+      const us2 lo2 = as_us2(uv1) - us2{(unsigned short)a.radius, (unsigned short)rv};
+      const us2 t = as_us2(ld_off(cuv, (uint32_t)res * 4u)) - lo2;
+      const us2 m = __builtin_elementwise_min(t, span2);
+      fail = as_u32(t) != as_u32(m);
     }
-    todo[qi] = SPEC ? __ballot(fail) : 0ull;
   }
   if (SPEC) {
-    int32_t nfail = 0;
-#pragma unroll
-    for (int32_t qi = 0; qi < Q; qi++) nfail += (int32_t)__popcll(todo[qi]);
-    if (nfail) {  // wave-uniform
+    uint64_t todo = __ballot(fail);
+    if (todo) {  // wave-uniform
+      const int32_t nfail = (int32_t)__popcll(todo);
       VH_STAT(FLOW ? 7 : 10, nfail);
       if (lane == 0) atomicAdd(redo_count, nfail);
       RedoGroup g;
@@ -449,8 +488,8 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
           // the union of the group's own rows [v - tol, v + tol]
           const int32_t *__restrict__ crs = s.row_start + (int64_t)cset * (4 * s.H + 1);
           const int32_t *__restrict__ cpos = s.r_pos + (int64_t)cset * s.cap;
-          const int32_t x0 = __builtin_amdgcn_readfirstlane(crs[c * s.H + max(g.vmin - rv, 0)]);
-          const int32_t x1 = __builtin_amdgcn_readfirstlane(crs[c * s.H + min(g.vmax + rv, s.H - 1) + 1]);
+          const int32_t x0 = ld_uniform_i32(crs + c * s.H + max(g.vmin - rv, 0));
+          const int32_t x1 = ld_uniform_i32(crs + c * s.H + min(g.vmax + rv, s.H - 1) + 1);
           for (int32_t x = x0 + lane; x < x1; x += 64) {
             int32_t cp = cpos[x];
             VH_CHECK_RANGE(s, 3, cp, pbase, pbase + pcnt);
@@ -467,17 +506,13 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
             const uint64_t kf = wave_min_u64(kk[k]);
             int32_t wp = (int32_t)(uint32_t)kf;
             if (kf != ~0ull) VH_CHECK_RANGE(s, 7, wp, 0, pcnt);
-            const int32_t r = kf == ~0ull ? -1 : pbase + wp;
-#pragma unroll
-            for (int32_t qi = 0; qi < Q; qi++) if (lane == g.lane[k] && g.qi[k] == qi) res[qi] = r;
+            if (lane == g.lane[k]) res = kf == ~0ull ? -1 : pbase + wp;
           }
       }
     }
   }
-#pragma unroll
-  for (int32_t qi = 0; qi < Q; qi++)
-    if (o.valid[qi] && ph == 0)  // min_ind defaults to 0 when no candidate was accepted (matcher.cpp:221)
-      tbl[qidx[o.qpos[qi]]] = res[qi] < 0 ? 0 : cidx[res[qi]];
+  // min_ind defaults to 0 when no candidate was accepted (matcher.cpp:221)
+  if (mine) st_off(tbl, (uint32_t)ld_off(qidx, (uint32_t)qpos * 4u) * 4u, res < 0 ? 0 : ld_off(cidx, (uint32_t)res * 4u));
 }
 
 // One tile of the flow search.
@@ -497,7 +532,7 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
 //    sharing one LDS array) otherwise saturate the LDS beside 8 v_sad_u8 per
 //    step: profiles/r02_ubench_valu.txt, last block.
 // The minimum over a query's candidates is split over the P phases and joined
-// with log2(P) shuffles per tile.
+// once per tile (join_phases).
 //
 // SPEC (the default): *speculative* search.  The per-pair accept test of
 // matcher.cpp:249 is not applied in the loop at all: every lane takes the minimum
@@ -556,7 +591,7 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   {
     const int32_t *__restrict__ qbs = s.bin_start + (int64_t)qset * (s.nbins + 1);
     int32_t colb = col0, j = 0;
-    int32_t csv = qbs[(c * s.ubn + min(colb + lane, s.ubn)) * s.vbn];
+    int32_t csv = ld_off(qbs, (uint32_t)((c * s.ubn + min(colb + lane, s.ubn)) * s.vbn) * 4u);
     int32_t A = __builtin_amdgcn_readlane(csv, 0);
     int32_t k[Q];
 #pragma unroll
@@ -569,14 +604,14 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
       }
       if (B >= q1 || colb + j + 1 >= s.ubn) break;  // (wave-uniform)
       A = B;
-      if (++j == 63) { colb += 63; j = 0; csv = qbs[(c * s.ubn + min(colb + lane, s.ubn)) * s.vbn]; }
+      if (++j == 63) { colb += 63; j = 0; csv = ld_off(qbs, (uint32_t)((c * s.ubn + min(colb + lane, s.ubn)) * s.vbn) * 4u); }
     }
   }
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
     const int32_t ql = qp[qi];
-    uv1[qi] = quv[ql];
-    a0[qi] = qdesc[2 * (int64_t)ql]; a1[qi] = qdesc[2 * (int64_t)ql + 1];
+    uv1[qi] = ld_off(quv, (uint32_t)ql * 4u);
+    a0[qi] = ld_off(qdesc, (uint32_t)ql * 32u); a1[qi] = ld_off(qdesc, (uint32_t)ql * 32u + 16u);
     const int32_t u1 = uv1[qi] & 0xFFFF, v1 = uv1[qi] >> 16;
     // search window (matcher.cpp:231-234; stereo: v narrowed to +-disp_tolerance).
     // Accept test of matcher.cpp:249 in packed 16-bit arithmetic: with
@@ -676,12 +711,10 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
       }
     });
   // join the phases: lanes l, l+L, l+2L, .. hold partial minima of the same query
+  out.wp = join_phases<Q, P, KM>(best_key);
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
-    uint64_t k = key_to_64<KM>(best_key[qi]);
-#pragma unroll
-    for (int32_t d = L; d < 64; d <<= 1) k = min(k, shfl_xor_u64(k, d));
-    out.k[qi] = k; out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
+    out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
     out.qpos[qi] = qp[qi];
   }
 }
@@ -689,16 +722,17 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
 template <bool SPEC>
 __device__ __forceinline__ void flow_pass(const VhSets &s, const VhMatchArgs &a, int32_t pass, int32_t stream, int32_t qset,
                                           int32_t cset, uint4 *wD, uint32_t *wU, int32_t *__restrict__ best, int32_t *__restrict__ redo_count) {
-  const int32_t ntile = s.tile_cnt[qset];
+  const int32_t ntile = ld_uniform_i32(s.tile_cnt + qset);
   for (int32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); tile < ntile;
        tile += gridDim.x * 4) {
-    const int4 t = s.tiles[(int64_t)qset * s.max_tiles + tile];
+    typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+    const i32x4 t = ld_uniform((const i32x4 *)(s.tiles + (int64_t)qset * s.max_tiles + tile));
     const int32_t q0 = __builtin_amdgcn_readfirstlane(t.x), q1 = __builtin_amdgcn_readfirstlane(t.y);
     const int32_t c = __builtin_amdgcn_readfirstlane(t.z), col0 = __builtin_amdgcn_readfirstlane(t.w);
     // candidates of class c occupy the contiguous positions [pbase, pend) of the bin order
     const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-    const int32_t pbase = __builtin_amdgcn_readfirstlane(cbs[c * s.ubn * s.vbn]);
-    const int32_t pend = __builtin_amdgcn_readfirstlane(cbs[(c + 1) * s.ubn * s.vbn]);
+    const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
+    const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
     const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
     TileOut<VH_FLOW_Q> out;
     if (km == KEY_HI16) flow_tile<VH_FLOW_Q, VH_FLOW_P, KEY_HI16, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pend - pbase, wD, wU, out);
@@ -756,10 +790,10 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
   for (int32_t qi = 0; qi < Q; qi++) {
     const int32_t q = q0 + L * qi + l;
     valid[qi] = q < q1;
-    qp[qi] = qpos[valid[qi] ? q : q0];  // row order holds bin positions; the records are gathered from the bin-ordered arrays
+    qp[qi] = ld_off(qpos, (uint32_t)(valid[qi] ? q : q0) * 4u);  // row order holds bin positions; the records are gathered from the bin-ordered arrays
     VH_CHECK_RANGE(s, 1, qp[qi], 0, s.cap);
-    uv1[qi] = quv[qp[qi]];
-    a0[qi] = qdesc[2 * (int64_t)qp[qi]]; a1[qi] = qdesc[2 * (int64_t)qp[qi] + 1];
+    uv1[qi] = ld_off(quv, (uint32_t)qp[qi] * 4u);
+    a0[qi] = ld_off(qdesc, (uint32_t)qp[qi] * 32u); a1[qi] = ld_off(qdesc, (uint32_t)qp[qi] * 32u + 16u);
     const int32_t u1 = uv1[qi] & 0xFFFF, v1 = uv1[qi] >> 16;
     lo2[qi] = us2{(unsigned short)(u1 - a.radius), (unsigned short)(v1 - a.disp_tol)};  // accept test as in flow_tile
     best_key[qi] = (key_t)~(key_t)0;
@@ -769,17 +803,17 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
   vmax = __builtin_amdgcn_readfirstlane(row16_allreduce<true>(vmax));
   VH_STAT(8, 1); VH_STAT(11, q1 - q0);
   const int32_t VLO = max(vmin - a.disp_tol, 0), VHI = min(vmax + a.disp_tol, s.H - 1);
-  const int32_t r0 = __builtin_amdgcn_readfirstlane(crs[c * s.H + VLO]);
-  const int32_t r1 = __builtin_amdgcn_readfirstlane(crs[c * s.H + VHI + 1]);
+  const int32_t r0 = ld_uniform_i32(crs + c * s.H + VLO);
+  const int32_t r1 = ld_uniform_i32(crs + c * s.H + VHI + 1);
   for (int32_t rc = r0; rc < r1; rc += 64) {
     const int32_t mcnt = min(64, r1 - rc);
     // slots past the end repeat the last candidate: same key, harmless.  Every slot of the row index in
     // [row_start[0], row_start[4H]) holds a position of the row's own class (bin_sort writes each exactly once).
-    int32_t cp = cpos[min(rc + lane, r1 - 1)];
+    int32_t cp = ld_off(cpos, (uint32_t)min(rc + lane, r1 - 1) * 4u);
     VH_CHECK_RANGE(s, 2, cp, pbase, pbase + pcnt);
-    const uint4 g0 = cdesc[2 * (int64_t)cp], g1 = cdesc[2 * (int64_t)cp + 1];
+    const uint4 g0 = ld_off(cdesc, (uint32_t)cp * 32u), g1 = ld_off(cdesc, (uint32_t)cp * 32u + 16u);
     uint32_t gu = 0;
-    if (!SPEC) gu = cuv[cp];
+    if (!SPEC) gu = ld_off(cuv, (uint32_t)cp * 4u);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // previous chunk fully consumed
     wD[lane] = g0; wD[64 + lane] = g1; wU[lane] = (uint32_t)(cp - pbase);
     if (!SPEC) wV[lane] = gu;
@@ -807,12 +841,10 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
     }
   }
   // join the phases
+  out.wp = join_phases<Q, P, KM>(best_key);
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
-    uint64_t k = key_to_64<KM>(best_key[qi]);
-#pragma unroll
-    for (int32_t d = L; d < 64; d <<= 1) k = min(k, shfl_xor_u64(k, d));
-    out.k[qi] = k; out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
+    out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
     out.qpos[qi] = qp[qi];
   }
 }
@@ -825,7 +857,7 @@ __device__ __forceinline__ void rows_pass(const VhSets &s, const VhMatchArgs &a,
   // tile -> (class, query range): classes are contiguous in row order
   int32_t cls_q0[5];
 #pragma unroll
-  for (int32_t c = 0; c <= 4; c++) cls_q0[c] = __builtin_amdgcn_readfirstlane(qrs[c * s.H]);
+  for (int32_t c = 0; c <= 4; c++) cls_q0[c] = ld_uniform_i32(qrs + c * s.H);
   constexpr int T = VH_TILE_Q;
   for (int32_t tile = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));; tile += gridDim.x * 4) {
     int32_t c = -1, q0 = 0, q1 = 0, t = tile;
@@ -837,8 +869,8 @@ __device__ __forceinline__ void rows_pass(const VhSets &s, const VhMatchArgs &a,
     }
     if (c < 0) break;  // past the last tile (uniform)
     const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-    const int32_t pbase = __builtin_amdgcn_readfirstlane(cbs[c * s.ubn * s.vbn]);
-    const int32_t pend = __builtin_amdgcn_readfirstlane(cbs[(c + 1) * s.ubn * s.vbn]);
+    const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
+    const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
     const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
     TileOut<VH_FLOW_Q> out;
     if (km == KEY_HI16) rows_tile<VH_FLOW_Q, VH_FLOW_P, KEY_HI16, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pend - pbase, wD, wU, wV, out);
