@@ -1,0 +1,475 @@
+// engine.h -- the Group behind a vh_group / vh_matcher handle, shared by the engine*.hip units:
+//   engine.hip        allocation, geometry, the ring and both push paths, profiling, creation
+//   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
+//   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
+//   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
+#ifndef VH_ENGINE_H
+#define VH_ENGINE_H
+#include "vh_dev.h"
+#include "../../include/viso_hip.h"
+#include "vh_vote.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace vh_engine {
+
+// Ring slots per stream.  Three are the minimum for detecting frame t+1 while frame t is matched
+// against t-1 -- but then the detection of t+2 overwrites the slot of t-1 and has to wait for the
+// emission of match t, and the search of t+2 for that detection: both chains idle ~6 % of a step
+// (rocprofv3 timeline, KITTI, S = 256).  With four, detection runs a whole frame ahead and neither
+// stream waits for the other.  VH_RING=3 rebuilds the old ring.
+#ifndef VH_RING
+#define VH_RING 4
+#endif
+static_assert(VH_RING >= 3 && VH_RING <= 8, "ring slots");
+
+extern thread_local std::string t_last_error;  // (defined in engine.hip)
+
+#define VH_HIP(call)                                                                          \
+  do {                                                                                        \
+    hipError_t e_ = (call);                                                                   \
+    if (e_ != hipSuccess) {                                                                   \
+      t_last_error = std::string(#call) + ": " + hipGetErrorString(e_);                       \
+      return VH_ERR_HIP;                                                                      \
+    }                                                                                         \
+  } while (0)
+
+inline int32_t round_up(int32_t x, int32_t m) { return (x + m - 1) / m * m; }
+
+// ---- owners: move-only, each releases what it holds in its destructor and on reset() / assignment of {} ------------
+// page-locked host memory; `dev` is its device address when it was allocated hipHostMallocMapped
+template <class T> struct HostBlock {
+  T *p = nullptr;
+  void *dev = nullptr;
+  HostBlock() = default;
+  HostBlock(HostBlock &&o) noexcept : p(o.p), dev(o.dev) { o.p = nullptr; o.dev = nullptr; }
+  HostBlock &operator=(HostBlock &&o) noexcept { std::swap(p, o.p); std::swap(dev, o.dev); return *this; }
+  ~HostBlock() { reset(); }
+  void reset() { if (p) (void)hipHostFree(p); p = nullptr; dev = nullptr; }
+  hipError_t alloc(size_t count, unsigned flags) {
+    reset();
+    hipError_t e = hipHostMalloc((void **)&p, sizeof(T) * count, flags);
+    if (e != hipSuccess) p = nullptr;
+    else if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer(&dev, p, 0);
+    return e;
+  }
+  operator T *() const { return p; }
+};
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+  Event &operator=(Event &&o) noexcept { std::swap(e, o.e); return *this; }
+  ~Event() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create(unsigned flags = hipEventDisableTiming) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }  // (lazy sites call it every time)
+  operator hipEvent_t() const { return e; }
+};
+// `owned` is false for a handle that aliases another stream (match / post stream of a small group)
+struct Stream {
+  hipStream_t s = nullptr;
+  bool owned = false;
+  Stream() = default;
+  Stream(Stream &&o) noexcept : s(o.s), owned(o.owned) { o.s = nullptr; }
+  Stream &operator=(Stream &&o) noexcept { std::swap(s, o.s); std::swap(owned, o.owned); return *this; }
+  ~Stream() { if (s && owned) (void)hipStreamDestroy(s); }
+  hipError_t create() { owned = true; return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  hipError_t create(int priority) { owned = true; return hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority); }
+  void alias(hipStream_t o) { s = o; owned = false; }
+  operator hipStream_t() const { return s; }
+};
+// one hipMalloc'ed block: an entry of a group's arena (Group::allocs), or a block outside it
+struct DeviceBlock {
+  void *p = nullptr;
+  DeviceBlock() = default;
+  explicit DeviceBlock(void *q) : p(q) {}
+  DeviceBlock(DeviceBlock &&o) noexcept : p(o.p) { o.p = nullptr; }
+  DeviceBlock &operator=(DeviceBlock &&o) noexcept { std::swap(p, o.p); return *this; }
+  ~DeviceBlock() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) {
+    *this = DeviceBlock();
+    const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
+    if (e != hipSuccess) p = nullptr;
+    return e;
+  }
+  template <class T> T *as() const { return (T *)p; }
+};
+// VhVoteBuffers (vh_vote.h) is released by hand; this one releases itself
+struct VoteBuffers : VhVoteBuffers {
+  VoteBuffers() = default;
+  VoteBuffers(VoteBuffers &&o) noexcept : VhVoteBuffers(o) { static_cast<VhVoteBuffers &>(o) = VhVoteBuffers{}; }
+  VoteBuffers &operator=(VoteBuffers &&o) noexcept { std::swap<VhVoteBuffers>(*this, o); return *this; }
+  ~VoteBuffers() { release(); }
+};
+
+struct ProfEntry {
+  std::vector<std::pair<Event, Event>> pending;
+  double ms = 0;
+  int64_t launches = 0;
+};
+
+// ---- the arena-owned pointers of a group, with the sizes and flags that go with them, one struct per feature: ------
+// Group::release() resets each by assignment
+struct DetectScratch {
+  uint64_t *d_rec = nullptr;
+  int32_t *d_chunk_count = nullptr;
+  uint8_t *d_half = nullptr;  // half-resolution images [S*2]
+};
+struct MatchTables {
+  int32_t *d_best = nullptr, *d_best2[2] = {nullptr, nullptr};
+  int4 *d_chain = nullptr, *d_chain2[2] = {nullptr, nullptr};
+  int32_t *d_mchunk2[2] = {nullptr, nullptr};  // [S][cap/256] survivors per emission chunk, one buffer per match-table buffer (each launch's emission zeroes the other one)
+  int32_t *d_redo = nullptr;     // [2][S] queries the speculative searches had to search again, per table buffer (reset by emit_matches)
+  float4 *d_ref2[2] = {nullptr, nullptr};  // refinement > 0: the refined coordinates of each match-table buffer ([S][cap][2] float4)
+  uint32_t *d_mask = nullptr;
+  uint32_t epoch = 0;
+  // A buffer that was allocated but not cleared yet: set at the allocation, reset only once the clearing memsets are queued,
+  // so a match call that fails between the two leaves the duty to the next one
+  bool mask_fresh = false;       // the flow method's pixel mask (mask_epoch())
+  void *d_matches = nullptr;
+  int32_t *d_match_count = nullptr;
+  int32_t *d_overflow = nullptr; // [S] 1: a feature set of the stream's last match held more records than cap
+  HostBlock<int32_t> h_overflow; // page-locked mirror for the asynchronous download
+  // per stream {match count, overflow flag, queries searched again, queries searched} of the last launch on each
+  // buffer, written by emit_matches into host-mapped page-locked memory: valid after ev_post[buf]
+  HostBlock<int4> h_out[2];
+  // small groups (serial): the match records are written to host-mapped memory as well, so getMatches is an
+  // event wait and a host copy instead of a device->host transfer of its own
+  HostBlock<vh_p_match> h_matches;
+  bool ev_down_valid = false;    // a download of the lists is (or was) in flight: the next emission waits for ev_down
+  bool stats_pending[2] = {false, false}, stats_was_spec[2] = {false, false};
+  int32_t stats_npass[2] = {0, 0};
+  int32_t tiles_hint = 0;  // query tiles per (pass, stream) row seen by an earlier launch (0: none yet)
+};
+// host-image staging, S images per camera, two slots: the upload of frame t+1
+// does not wait for the detection of frame t, only for that of frame t-1
+struct Staging {
+  uint8_t *d_stage_buf[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+  uint8_t *d_stage[2] = {nullptr, nullptr};  // the slot of the last push_host
+  bool ev_stage_valid[2] = {false, false};
+  size_t stage_bytes = 0;
+};
+// tr16 of match(): [S][16] row-major motion estimates for the quad method's prior (kernels_prior.hip)
+struct Prior {
+  double *d_prior_tr = nullptr;
+  HostBlock<double> h_prior_tr;  // page-locked staging, two slots (one per table buffer): the caller's array is only borrowed
+};
+struct TrackTables {
+  uint32_t *d_ttab = nullptr, *d_ttabp = nullptr;  // [slots][cap] bids by i1c; [S][cap] bids by i1p
+  vh_track *d_trk = nullptr;                       // [slots][mcap]
+  int32_t *d_tcount = nullptr;                     // [slots]
+  bool trk_fresh = false;  // allocated, not cleared yet (as MatchTables::mask_fresh; trk_queue() clears them on the post stream)
+};
+// The group estimators' scratch (random values, 3-d points, results) belongs to the group and only grows: a
+// hipFree per call would drain the detect/match/post pipeline (it synchronises the device).
+struct EgoScratch {
+  int32_t *d_ego_rand = nullptr, *d_ego_ok = nullptr;
+  double *d_ego_xyz = nullptr, *d_ego_tr = nullptr;
+  size_t ego_rand_n = 0;
+  uint8_t *d_mono_scratch = nullptr;
+  int32_t *d_mono_rand = nullptr;
+  size_t mono_rand_n = 0;
+  int32_t mono_scratch_iters = 0;
+};
+struct PostSlot {
+  HostBlock<vh_p_match> h_pm;   // page-locked [S][cap_ps]
+  HostBlock<int32_t> h_cnt;     // page-locked [S] (+ [S] overflow flags)
+  int32_t cap_ps = 0, width = 0, method = -1;  // allocated / downloaded records per stream
+  Event ev;
+  bool pending = false;
+};
+struct HostPost {
+  PostSlot slot[2];
+  HostBlock<vh_p_match> h_bucket;  // [S][bcap]
+  vh_p_match *d_bucket = nullptr;
+  HostBlock<int32_t> h_bcnt;
+  int32_t *d_bcnt = nullptr, bcap = 0;
+  int32_t *d_post_rand = nullptr; size_t post_rand_n = 0;
+  uint8_t *d_post_mono = nullptr; int32_t post_mono_iters = 0;
+  double *d_post_xyz = nullptr, *d_post_tr = nullptr; int32_t *d_post_ok = nullptr;
+};
+struct Ranges {
+  int32_t *d_ranges = nullptr;   // [S][ubn * vbn][4 stages][4] integer windows
+  HostBlock<int32_t> h_ranges;   // page-locked staging
+};
+
+// a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
+struct VoteBatch {
+  VoteBuffers vb;
+  int32_t steps = 0;      // steps moved in so far
+  bool launched = false;  // the kernel sequence has been queued
+  bool busy = false;      // holds steps whose results have not all been handed out
+  int32_t handed = 0;
+  Event ev_prep, ev_done;
+  int32_t method = -1, max_features = 0; float bw = 0, bh = 0;
+  bool has_ego = false, has_mono = false;
+  vh_ego_params ego{}; vh_mono_params mono{};
+  int32_t *d_rand = nullptr; size_t rand_per_step = 0;
+  HostBlock<int32_t> h_rand; size_t h_rand_ints = 0;  // page-locked staging of the steps' random draws (the caller's array is only borrowed)
+  double *d_xyz = nullptr, *d_tr = nullptr; int32_t *d_ok = nullptr; uint8_t *d_mono = nullptr;
+  DeviceBlock block;  // d_rand | d_xyz | d_tr | d_ok | d_mono
+  size_t block_bytes = 0;
+  // page-locked results
+  HostBlock<double> h_tr; HostBlock<int32_t> h_ok, h_cnt; HostBlock<VhVoteMeta> h_meta; HostBlock<vh_p_match> h_out;
+  int32_t h_lists = 0, h_out_cap = 0;
+  bool want_lists = false;
+  VoteBatch() = default;
+  VoteBatch(VoteBatch &&) = default;
+  ~VoteBatch() { if (launched && ev_done) (void)hipEventSynchronize(ev_done); }  // (before the members free what the kernels use)
+};
+struct VoteStep { int32_t batch = -1, pos = 0; bool open = false; };
+
+// A vh_group owns S independent camera streams that are stepped together; a vh_matcher is a group of one.
+//
+// Nothing is released by hand: the members' destructors do it, in the reverse of the order they are declared in.
+// That order is part of the design -- streams, then events, then the device blocks (`allocs`), then the vote batches,
+// then the sparse group: so the sparse group (which runs on this group's detect stream) goes first, the vote batches
+// are synchronised and freed next, and every device block is freed before the streams are destroyed.
+struct Group {
+  vh_params p{};
+  int32_t device = 0, S = 1;
+  int32_t req_features = 0, req_matches = 0;
+  // Internal streams: detection+indexing of frame t+1 overlaps the matching
+  // of frame t (the ring has VH_RING slots for that).  `stream` is the detect
+  // stream (also used by the stateless paths; a sparse group's is its parent's); a caller-owned stream, if set,
+  // only orders our work after the caller's (image producers).
+  // A third stream (default; VH_POST_STREAM=0: the match stream) takes the short,
+  // latency-bound post-processing (chain + emission) of frame t, so that the flow
+  // search of frame t+1 follows that of frame t back to back; the match tables are
+  // double-buffered for that.
+  Stream own_stream, match_stream, post_stream, copy_stream, down_stream;
+  static constexpr int32_t kVoteStreams = 4;
+  Stream vote_stream[kVoteStreams];
+  hipStream_t stream = nullptr, user_stream = nullptr;
+  Event ev_tables[2];       // match tables of buffer b complete
+  Event ev_post[2];         // post-processing finished reading buffer b
+  Event ev_det[VH_RING];    // slot fully detected + indexed
+  Event ev_read[VH_RING];   // last match that read the slot
+  Event ev_user, ev_stage[2], ev_h2d;
+  Event ev_down;            // asynchronous download of the match lists (vh_group_download_matches_async)
+  Event ev_stats;           // multi-stage device mode: orders pass 2 behind the statistics
+  bool ev_post_valid[2] = {false, false};
+  bool ev_read_valid[VH_RING] = {};
+  int64_t match_seq = 0;
+  // Loop policy of the searches (match()): speculative (no accept test in the loop, the winner
+  // verified, failures searched again) or tested.  The speculative loop is ~12 % faster when
+  // almost every query's best candidate lies inside its window (0.5 % re-searched on the
+  // benchmark frames) and slower once more than ~6 % fail (noisy images full of features
+  // without a partner; measured round 3 with grouped second searches: +10 % at 3.3 % re-searched,
+  // +3 % at 4.8 %, -1 % at 6.6 %, -6 % at 8.9 %).  Every launch reports (re-searched, searched)
+  // with a lag of one or two steps; above 6.5 % the tested loop takes over and the speculative
+  // one is probed every 16th launch, below 5.5 % it comes back.  Results never depend on the choice.
+  int32_t probe_countdown = 0, force_mode = -1;
+  bool spec_mode = true;
+  double last_redo_rate = -1;
+  bool user_stream_set = false;  // handle 0 is a real stream (the legacy default stream): "unset" is a flag, not a value
+  bool failed = false;           // the last push did not complete: no matching until the next successful one
+  int32_t pair_prev = 1;
+  bool serial = false;
+  // Sequence handle (vh_sequence_*): the S rows of a slot are consecutive frames of one camera, a push brings a chunk of
+  // seq_n <= S of them and every match links row r to row r - 1 (row 0 to the last row of the previous chunk: vh_row_set).
+  bool seq = false;
+  int32_t seq_n = 0, seq_n_prev = 0;      // frames of the last chunk / of the one before
+  int64_t seq_first = 0, seq_total = 0;   // index in the sequence of the last chunk's first frame / frames pushed so far
+  // vh_group_set_multi_stage_device: the vote and the statistics between the passes run on the device, behind pass 1 on the
+  // sparse group's post stream (multi_stage_ranges_device); ms_vb holds the S voted sparse lists
+  bool ms_device = false;
+  static constexpr int32_t kMsVoteLanes = 16;  // lists per wave of the sweep
+
+  bool allocated = false;
+  int32_t dims[3] = {0, 0, 0};
+  VhGeom g{};
+  VhSets sets{};
+  // refinement > 0 (kernels_refine.hip): full-resolution du/dv per feature set of the ring, written with the detection of a push
+  VhRefine rf{};
+  int32_t cap = 0, mcap = 0;
+  int32_t pair_cur = 0;
+  int64_t frames = 0;
+  int32_t stage_slot = 0;
+  int32_t last_buf = 0;
+  int32_t last_method = -1;
+  // A match launch that failed half way leaves the emission's chunk counters and the re-search counters of its table
+  // buffer in an unknown state (each emission zeroes the OTHER buffer's counters for the next launch): the next
+  // match() puts both buffers back to zero before it queues anything.
+  bool match_dirty = false;
+  bool fail_next_alloc = false;  // test hook (vh_group_debug_fail_next_alloc)
+  int32_t fail_alloc_skip = 0;   // test hook: allocations that still succeed before the requested failure
+
+  // ---- feature tracks (vh_group_set_track_linking; kernels_track.hip) ---------------------
+  // Slots of d_ttab / d_trk: a group keeps two lists per stream, buffer b in the slots [b * S, (b + 1) * S): trk_cur is
+  // the buffer of the current pair's list, the other one holds the previous step's (the predecessors).  A sequence handle
+  // keeps its S rows in the slots [0, S) and the carry -- the last row of the last match call on the previous chunk -- in
+  // slot S; the carry is copied when the first match call of the next chunk is queued, so that matching a chunk again
+  // still finds the carry of the chunk before it.
+  bool trk_on = false;
+  uint32_t trk_epoch = 0, trk_cur_epoch = 0, trk_pred_epoch = 0;
+  int32_t trk_cur = 0;
+  bool trk_cur_valid = false;   // the current pair (sequence: chunk) has a tracked list, bid for at trk_cur_epoch
+  bool trk_pred_valid = false;  // group: the other buffer holds the predecessors; sequence: the carry slot is valid
+  int32_t trk_carry_src = -1;   // sequence: row to copy into the carry before the next bids (-1: none)
+  int64_t trk_serial = 0;       // group: serial of the current frame
+
+  // streams whose current matches were post-processed on the host
+  // (vh_remove_outliers / vh_bucket_features): served from here until the next step
+  std::vector<std::vector<vh_p_match>> host_matches;
+  std::vector<uint8_t> host_filtered;
+
+  bool prof = false;
+  std::map<std::string, ProfEntry> prof_entries;
+
+  int64_t post_seq = 0;
+  // The device post pipeline.  Measured on MI355X, KITTI, S = 256 (bench.py e2e_matchfeatures, k pairs/s; steps per batch x batches, 64 lists per wave):
+  // 4x5 10.4, 8x5 11.7, 16x5 19.9, 32x3 25.3, 32x4 30.4, 48x3 30.2, 64x3 33.9; 1 list per wave, 4x5: 17.9.  A batch takes
+  // 0.4-0.5 s from launch to results whatever its size (profiles/r04_vote_trace.txt): the rate is the number of steps in
+  // flight over that latency, and a wave of 64 lists costs the chip 1/14 of what 64 single-list waves cost.
+  int32_t vote_steps = 64, vote_batches = 3, vote_lanes = 16;
+  int64_t post_dev_seq = 0;   // steps begun
+  int32_t vote_cur = 0;       // batch receiving steps
+  std::vector<VoteStep> vstep;  // ring over the steps begun, indexed by sequence number
+
+  std::vector<DeviceBlock> allocs;  // the arena: every dmalloc'ed block, counted in device_bytes
+  int64_t device_bytes = 0;
+  DetectScratch det;
+  MatchTables mt;
+  Staging stg;
+  Prior pri;
+  TrackTables tk;
+  EgoScratch ego;
+  HostPost post;
+  Ranges rg;
+  VoteBuffers ms_vb;
+  std::vector<VoteBatch> vbatch;
+  // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
+  // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
+  // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
+  // and searches this group's sets inside rg.d_ranges (kernels_ranged.hip).
+  std::unique_ptr<Group> sparse;
+
+  // ---- engine.hip ----
+  void drop_host_matches() { std::fill(host_filtered.begin(), host_filtered.end(), 0); }
+  int32_t pairs() const { return pair_cur | (pair_prev << 8); }
+  // feature sets: ring slots x (left, right) per row, and a sequence handle's empty pair after them (VhMatchArgs::seq_void)
+  size_t n_sets() const { return 2 * VH_RING * (size_t)S + (seq ? 2 : 0); }
+  VhMatchArgs role_args() const;
+  int32_t sync_all();
+  int32_t check_violation();
+  void release();
+  bool alloc_refused();
+  template <class T> int32_t dmalloc(T **out, size_t count, bool zero) {
+    void *q = nullptr;
+    const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    if (alloc_refused()) return VH_ERR_HIP;
+    VH_HIP(hipMalloc(&q, bytes));
+    allocs.emplace_back(q);
+    device_bytes += (int64_t)bytes;
+    if (zero) VH_HIP(hipMemsetAsync(q, 0, bytes, stream));
+    else {
+      // VH_POISON=1 (test aid): fill every buffer that is not zero-initialised with 0xA5, so that a
+      // kernel consuming memory nobody wrote misbehaves the same way on every box
+      static const bool poison = [] { const char *e = getenv("VH_POISON"); return e && e[0] == '1'; }();
+      if (poison) { VH_HIP(hipMemset(q, 0xA5, bytes)); VH_HIP(hipDeviceSynchronize()); }  // (blocking: the buffer's first user may be any stream)
+    }
+    *out = (T *)q;
+    return VH_OK;
+  }
+  void dfree(void *q);
+  static int32_t block_count(int32_t extent, int32_t n);
+  int32_t setup_geometry(const int32_t d[3]);
+  int32_t ensure(const int32_t d[3]);
+  int32_t allocate(const int32_t d[3]);
+  int32_t ensure_staging(size_t isz);
+  void prof_collect();
+  void prof_host(const char *name, std::chrono::steady_clock::time_point t0);
+  int32_t zero_bin_counters(int32_t set0, int32_t nsets, int32_t *extra = nullptr, int64_t n_extra = 0);
+  int32_t bin_sets(int32_t set0, int32_t nsets, bool staged);
+  int32_t push_device(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows = -1);
+  int32_t push_device_queued(const void *dI1, const void *dI2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows);
+  int32_t push_host(const uint8_t *I1, const uint8_t *I2, int64_t stride, const int32_t d[3], int32_t replace, int32_t rows = -1);
+
+  // ---- engine_match.hip ----
+  VhMatchArgs match_args(int32_t method) const;
+  bool choose_loop();
+  int32_t match_recover();
+  size_t n_ranges() const { return (size_t)S * sets.ubn * sets.vbn * 16; }
+  int32_t ensure_ranges(bool staging = true);
+  int32_t multi_stage_ranges(int32_t method);
+  int32_t ensure_ms_vote();
+  int32_t multi_stage_ranges_device(int32_t method);
+  int32_t load_ranges(const float *ranges);
+  int32_t match(int32_t method, const double *tr16 = nullptr, bool ranged = false);
+  int32_t match_queued(int32_t method, const double *tr16, const int32_t *ranges);
+  int32_t mask_epoch(hipStream_t st);
+  int32_t match_post(int32_t method, const VhMatchArgs &a, int32_t buf, bool ranged, bool spec);
+  int32_t trk_slots() const { return seq ? S + 1 : 2 * S; }
+  // no list is tracked any more (the tables were cleared, or are about to be)
+  void trk_reset_lists() { trk_epoch = trk_cur_epoch = trk_pred_epoch = 0; trk_cur_valid = trk_pred_valid = false; trk_carry_src = -1; }
+  void trk_reset() { trk_reset_lists(); trk_cur = 0; trk_serial = 0; }  // ... and the sequence starts again (new dims)
+  void trk_pushed(bool shifted, bool first, int32_t prev_chunk_rows);
+  int32_t trk_ensure();
+  VhTrackArgs trk_args(int32_t rows) const;
+  int32_t trk_queue(const VhMatchArgs &a, hipStream_t ps);
+  int32_t get_tracks(int32_t s, vh_track *out, int32_t capo, int32_t *n);
+  int32_t get_tracks_all(vh_track *out, int32_t cap_per_stream, int32_t *counts);
+  int32_t load_features(int32_t role, const int32_t *m, int32_t n);
+
+  // ---- engine_post.hip ----
+  int32_t get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n);
+  int32_t download_async(vh_p_match *out, int32_t cap_per_stream, int32_t *counts);
+  int32_t wait_download();
+  int32_t get_matches(int32_t s, vh_p_match *out, int32_t capo, int32_t *n);
+  int32_t get_features(int32_t s, int32_t which, int32_t *out12, int32_t capo, int32_t *n);
+  int32_t get_counts(int32_t *nf, int32_t *nm);
+  int32_t get_matches_all(vh_p_match *out, int32_t cap_per_stream, int32_t *counts);
+  int32_t fetch_matches(int32_t s);
+  int32_t remove_outliers(int32_t s_lo, int32_t s_hi, int32_t threads);
+  int32_t estimate_motion(const vh_ego_params *e, const int32_t *rand3, double *tr, int32_t *ok, int32_t *ninl);
+  int32_t estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl);
+  int32_t estimate_results(double *tr, int32_t *ok, int32_t *ninl);
+  int32_t post_begin(int32_t cap_ps);
+  int32_t post_finish(int32_t age, int32_t max_features, float bw, float bh, int32_t threads, const vh_ego_params *e, const int32_t *rand3,
+                      const vh_mono_params *mono, const int32_t *rand8,
+                      double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts, double *host_ms);
+  void vote_release() { vbatch.clear(); vstep.clear(); post_dev_seq = 0; vote_cur = 0; }
+  int32_t post_device_config(int32_t steps_per_batch, int32_t batches, int32_t lanes);
+  int32_t bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid = nullptr) const;
+  int32_t vote_launch(VoteBatch &b, int32_t index);
+  int32_t post_begin_device(int32_t cap_ps, int32_t max_features, float bw, float bh, const vh_ego_params *e, const int32_t *rand3,
+                            const vh_mono_params *mono, const int32_t *rand8, int32_t want_lists);
+  int32_t post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts);
+};
+
+// times the HIP work queued on `st` during its lifetime under `name` (only while the group profiles)
+struct Scope {
+  Group *gq; const char *name; hipStream_t st; Event e0, e1;
+  Scope(Group *gq_, const char *n, hipStream_t st_) : gq(gq_), name(n), st(st_) {
+    if (gq->prof) { (void)e0.create(hipEventDefault); (void)e1.create(hipEventDefault); (void)hipEventRecord(e0, st); }
+  }
+  ~Scope() {
+    if (gq->prof) { (void)hipEventRecord(e1, st); gq->prof_entries[name].pending.emplace_back(std::move(e0), std::move(e1)); }
+  }
+};
+
+// engine.hip
+int32_t check_params(const vh_params *p);
+int32_t select_device(int32_t device);
+int32_t group_new(const vh_params *p, int32_t device, int32_t S, int32_t mf, int32_t mm, Group **out);
+// engine_post.hip
+// Matcher::bucketFeatures (matcher.cpp:140-187) on the records pm[0, n): the selected records are written to
+// out (at most out_cap of them) in the reference's order; returns how many the reference would keep.
+int32_t bucket_records(const vh_p_match *pm, int32_t n, int32_t max_features, float bw, float bh, vh_p_match *out, int32_t out_cap,
+                       std::vector<int32_t> &work);
+void bucket_host(std::vector<vh_p_match> &pm, int32_t max_features, float bw, float bh);
+// computePriorStatistics of multi-stage matching (include/viso_hip.h: vh_prior_statistics), host side
+int32_t prior_statistics(const vh_params &p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges);
+
+}  // namespace vh_engine
+#endif

@@ -1,0 +1,709 @@
+// engine_post.hip -- what follows a match call: downloads and getters, outlier removal, the group estimators, the
+// post pipelines on the host and on the device, bucketing and the host form of the prior statistics (engine.h).
+#include "engine.h"
+
+#include <atomic>
+#include <thread>
+
+namespace vh_engine {
+
+// fn(s) for every stream s of [lo, hi), on up to `threads` host threads (the caller's is one of them), one stream per task
+template <class Fn> static void for_each_stream(int32_t lo, int32_t hi, int32_t threads, Fn fn) {
+  std::atomic<int32_t> next(lo);
+  const auto work = [&]() { for (int32_t s = next++; s < hi; s = next++) fn(s); };
+  std::vector<std::thread> pool;
+  for (int32_t w = 1; w < std::min(threads, hi - lo); w++) pool.emplace_back(work);
+  work();
+  for (auto &t : pool) t.join();
+}
+
+// The voted sparse list of stream s in device mode: from the vote buffer (waits for the vote)
+int32_t Group::get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n) {
+  if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!allocated || !ms_vb.block || sparse->last_method < 0) return VH_OK;
+  VH_HIP(hipStreamSynchronize(sparse->post_stream));
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  VhVoteMeta m{};
+  VH_HIP(hipMemcpy(&m, ms_vb.v.meta + s, sizeof(m), hipMemcpyDeviceToHost));
+  if (m.status == VH_VOTE_TRUNCATED) return VH_ERR_CAPACITY;
+  if (m.status != VH_VOTE_OK && m.status != VH_VOTE_SKIP) return VH_ERR_UNSUPPORTED;
+  *n = m.kept;
+  const int32_t k = std::min(m.kept, capo);
+  if (k > 0) VH_HIP(hipMemcpy(out, ms_vb.v.pm + (size_t)s * ms_vb.v.cap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost));
+  return m.kept > capo ? VH_ERR_CAPACITY : VH_OK;
+}
+
+// Start the device->host copy of every stream's first cap_per_stream match
+// records and of the S counts, ordered after the emission of the last step,
+// and return at once.  One strided transfer: the copy engine moves it while
+// the next step computes (its emit_matches waits for the download, above).
+int32_t Group::download_async(vh_p_match *out, int32_t cap_per_stream, int32_t *counts) {
+  if (!out || !counts || cap_per_stream < 1) return VH_ERR_INVALID_ARG;
+  if (!allocated || last_method < 0) return VH_ERR_STATE;
+  VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
+  const size_t width = sizeof(vh_p_match) * (size_t)std::min(cap_per_stream, mcap);
+  VH_HIP(hipMemcpy2DAsync(out, sizeof(vh_p_match) * (size_t)cap_per_stream, mt.d_matches, sizeof(vh_p_match) * (size_t)mcap,
+                          width, (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(counts, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(mt.h_overflow, mt.d_overflow, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipEventRecord(ev_down, down_stream));
+  mt.ev_down_valid = true;
+  return VH_OK;
+}
+
+int32_t Group::wait_download() {
+  if (!mt.ev_down_valid) return VH_OK;
+  VH_HIP(hipEventSynchronize(ev_down));
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  for (int32_t s = 0; s < S; s++) if (mt.h_overflow[s]) return VH_ERR_CAPACITY;
+  return VH_OK;
+}
+
+int32_t Group::get_matches(int32_t s, vh_p_match *out, int32_t capo, int32_t *n) {
+  if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!allocated || last_method < 0) return VH_OK;
+  if (host_filtered[s]) {
+    *n = (int32_t)host_matches[s].size();
+    const int32_t k = std::min(*n, capo);
+    if (k) memcpy(out, host_matches[s].data(), sizeof(vh_p_match) * (size_t)k);
+    return *n > capo ? VH_ERR_CAPACITY : VH_OK;
+  }
+  // count and overflow flag of the last launch: host-mapped memory, valid once its emission has run
+  VH_HIP(hipEventSynchronize(ev_post[last_buf]));
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  const int32_t cnt = mt.h_out[last_buf][s].x, ov = mt.h_out[last_buf][s].y;
+  *n = cnt;
+  const int32_t k = std::min(std::min(cnt, mcap), capo);
+  if (k > 0 && mt.h_matches) {
+    memcpy(out, mt.h_matches + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)k);
+  } else if (k > 0) {
+    VH_HIP(hipMemcpyAsync(out, (const uint8_t *)mt.d_matches + (size_t)s * mcap * sizeof(vh_p_match),
+                          sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+    VH_HIP(hipStreamSynchronize(post_stream));
+  }
+  // ov: a feature set of this match exceeded the feature capacity (the records beyond
+  // it were dropped, so the list above comes from a truncated set)
+  return (cnt > capo || cnt > mcap || ov) ? VH_ERR_CAPACITY : VH_OK;
+}
+
+int32_t Group::get_features(int32_t s, int32_t which, int32_t *out12, int32_t capo, int32_t *n) {
+  if (!n || s < 0 || s >= S || which < 0 || which > 3 || capo < 0 || (capo > 0 && !out12)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!allocated) return VH_OK;
+  const int32_t set = vh_row_set(role_args(), s, which);
+  int32_t cnt = 0;
+  VH_HIP(hipMemcpyAsync(&cnt, sets.count + set, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  VH_HIP(hipStreamSynchronize(stream));
+  *n = cnt;
+  const int32_t k = std::min(std::min(cnt, cap), capo);
+  if (k > 0) {
+    VH_HIP(hipMemcpyAsync(out12, sets.feat + (size_t)set * cap * 12, sizeof(int32_t) * 12 * (size_t)k,
+                          hipMemcpyDeviceToHost, stream));
+    VH_HIP(hipStreamSynchronize(stream));
+  }
+  return (cnt > capo || cnt > cap) ? VH_ERR_CAPACITY : VH_OK;
+}
+
+int32_t Group::get_counts(int32_t *nf, int32_t *nm) {
+  if (!allocated) return VH_ERR_STATE;
+  if (nf) {
+    std::vector<int32_t> all(n_sets());
+    VH_HIP(hipMemcpyAsync(all.data(), sets.count, sizeof(int32_t) * all.size(), hipMemcpyDeviceToHost, stream));
+    VH_HIP(hipStreamSynchronize(stream));
+    const VhMatchArgs a = role_args();
+    for (int32_t s = 0; s < S; s++)
+      for (int32_t r = 0; r < 4; r++) nf[4 * s + r] = all[vh_row_set(a, s, r)];
+  }
+  if (nm) {
+    VH_HIP(hipMemcpyAsync(nm, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+    VH_HIP(hipStreamSynchronize(post_stream));
+    for (int32_t s = 0; s < S; s++)
+      if (host_filtered[s]) nm[s] = (int32_t)host_matches[s].size();
+  }
+  return VH_OK;
+}
+
+// All streams' matches in one go: counts first, then one transfer per stream
+// into out[s * cap_per_stream ...], a single wait at the end.
+int32_t Group::get_matches_all(vh_p_match *out, int32_t cap_per_stream, int32_t *counts) {
+  if (!out || !counts || cap_per_stream < 0) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < S; s++) counts[s] = 0;
+  if (!allocated || last_method < 0) return VH_OK;
+  VH_HIP(hipMemcpyAsync(counts, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(mt.h_overflow, mt.d_overflow, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipStreamSynchronize(post_stream));
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  bool over = false;
+  for (int32_t s = 0; s < S; s++) over = over || mt.h_overflow[s] != 0;
+  for (int32_t s = 0; s < S; s++) {
+    if (host_filtered[s]) {
+      counts[s] = (int32_t)host_matches[s].size();
+      const int32_t k = std::min(counts[s], cap_per_stream);
+      if (k) memcpy(out + (size_t)s * cap_per_stream, host_matches[s].data(), sizeof(vh_p_match) * (size_t)k);
+      over = over || counts[s] > cap_per_stream;
+      continue;
+    }
+    const int32_t k = std::min(std::min(counts[s], mcap), cap_per_stream);
+    over = over || counts[s] > cap_per_stream || counts[s] > mcap;
+    if (k > 0)
+      VH_HIP(hipMemcpyAsync(out + (size_t)s * cap_per_stream, (const uint8_t *)mt.d_matches + (size_t)s * mcap * sizeof(vh_p_match),
+                            sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+  }
+  VH_HIP(hipStreamSynchronize(post_stream));
+  return over ? VH_ERR_CAPACITY : VH_OK;
+}
+
+// Bring stream s's current matches to the host (no-op if already there).
+int32_t Group::fetch_matches(int32_t s) {
+  if (s < 0 || s >= S) return VH_ERR_INVALID_ARG;
+  if (!allocated || last_method < 0) return VH_ERR_STATE;
+  if (host_filtered[s]) return VH_OK;
+  int32_t n = 0;
+  int32_t rc = get_matches(s, nullptr, 0, &n);
+  if (rc != VH_OK && rc != VH_ERR_CAPACITY) return rc;
+  if (n > mcap) return VH_ERR_CAPACITY;
+  std::vector<vh_p_match> pm((size_t)n);
+  if ((rc = get_matches(s, n ? pm.data() : nullptr, n, &n))) return rc;  // VH_ERR_CAPACITY: a feature set overflowed
+  host_matches[s].swap(pm);
+  host_filtered[s] = 1;
+  return VH_OK;
+}
+
+// removeOutliers (remove_outliers.cpp:4-94) on streams [0, S): host work, one
+// stream per task, `threads` workers.  Stereo records carry no previous-frame
+// position (u1p = -1), so the flow vote only applies to flow and quad matches.
+int32_t Group::remove_outliers(int32_t s_lo, int32_t s_hi, int32_t threads) {
+  if (!allocated || last_method < 0) return VH_ERR_STATE;
+  if (last_method == VH_METHOD_STEREO) return VH_OK;
+  for (int32_t s = s_lo; s < s_hi; s++) {
+    const int32_t rc = fetch_matches(s);
+    if (rc) return rc;
+  }
+  std::atomic<int32_t> failed(0);
+  for_each_stream(s_lo, s_hi, threads, [&](int32_t s) {
+    std::vector<vh_p_match> &pm = host_matches[s];
+    int32_t kept = 0;
+    if (vh_remove_outliers_pm(pm.data(), (int32_t)pm.size(), &kept) != VH_OK) { failed = 1; return; }
+    pm.resize((size_t)kept);
+  });
+  return failed ? VH_ERR_INVALID_ARG : VH_OK;
+}
+
+// The shared end of the group estimators, on the post stream behind the kernels: the results, and the verdict on the
+// lists they came from -- a truncated match list or feature set yields a pose of the truncated data: say so, as every
+// get_matches path does.
+int32_t Group::estimate_results(double *tr, int32_t *ok, int32_t *ninl) {
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipMemcpyAsync(tr, ego.d_ego_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(ok, ego.d_ego_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(ninl, ego.d_ego_ok + S, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  std::vector<int32_t> cnt((size_t)S);
+  VH_HIP(hipMemcpyAsync(cnt.data(), mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(mt.h_overflow, mt.d_overflow, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipStreamSynchronize(post_stream));
+  for (int32_t s = 0; s < S; s++) if (cnt[s] > mcap || mt.h_overflow[s]) return VH_ERR_CAPACITY;
+  return VH_OK;
+}
+
+// VisualOdometryStereo::estimateMotion on the device-resident quad match lists of every stream (scratch: EgoScratch)
+int32_t Group::estimate_motion(const vh_ego_params *e, const int32_t *rand3, double *tr, int32_t *ok, int32_t *ninl) {
+  if (!e || !rand3 || !tr || !ok || !ninl || e->ransac_iters < 1) return VH_ERR_INVALID_ARG;
+  if (!allocated || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
+  const size_t nr = (size_t)S * e->ransac_iters * 3;
+  int32_t rc;
+  if (!ego.d_ego_xyz) {
+    if ((rc = dmalloc(&ego.d_ego_xyz, (size_t)S * mcap * 4, false))) return rc;
+    if (!ego.d_ego_tr) {
+      if ((rc = dmalloc(&ego.d_ego_tr, 6 * (size_t)S, false))) return rc;
+      if ((rc = dmalloc(&ego.d_ego_ok, 2 * (size_t)S, false))) return rc;
+    }
+  }
+  if (ego.ego_rand_n < nr) {  // (the old block stays in `allocs` until the group is released: a few KB per change of ransac_iters)
+    if ((rc = dmalloc(&ego.d_ego_rand, nr, false))) return rc;
+    ego.ego_rand_n = nr;
+  }
+  VH_HIP(hipMemcpyAsync(ego.d_ego_rand, rand3, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
+  vh_launch_ego(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_ego_rand, ego.d_ego_xyz, mcap, ego.d_ego_tr, ego.d_ego_ok,
+                ego.d_ego_ok + S, nullptr, 0, post_stream);
+  return estimate_results(tr, ok, ninl);
+}
+
+// VisualOdometryMono::estimateMotion on the device-resident match lists of every stream
+int32_t Group::estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl) {
+  if (!e || !rand8 || !tr || !ok || !ninl || e->ransac_iters < 1) return VH_ERR_INVALID_ARG;
+  if (!allocated || (last_method != VH_METHOD_FLOW && last_method != VH_METHOD_QUAD)) return VH_ERR_STATE;
+  const size_t nr = (size_t)S * e->ransac_iters * 8;
+  int32_t rc;
+  if ((int64_t)S * e->ransac_iters > (int64_t)1 << 31) return VH_ERR_UNSUPPORTED;
+  if (!ego.d_mono_scratch || ego.mono_scratch_iters < e->ransac_iters) {
+    if ((rc = dmalloc(&ego.d_mono_scratch, (size_t)vh_mono_scratch_bytes(S, mcap, e->ransac_iters), false))) return rc;
+    ego.mono_scratch_iters = e->ransac_iters;
+    if (!ego.d_ego_tr) {
+      if ((rc = dmalloc(&ego.d_ego_tr, 6 * (size_t)S, false))) return rc;
+      if ((rc = dmalloc(&ego.d_ego_ok, 2 * (size_t)S, false))) return rc;
+    }
+  }
+  if (ego.mono_rand_n < nr) {
+    if ((rc = dmalloc(&ego.d_mono_rand, nr, false))) return rc;
+    ego.mono_rand_n = nr;
+  }
+  VH_HIP(hipMemcpyAsync(ego.d_mono_rand, rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
+  vh_launch_mono(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_mono_rand, ego.d_mono_scratch, mcap, ego.d_ego_tr,
+                 ego.d_ego_ok, ego.d_ego_ok + S, nullptr, 0, post_stream);
+  return estimate_results(tr, ok, ninl);
+}
+
+// ---- the steps after matching, pipelined -----------------------------------
+// What the reference's loop does after Matcher::matching -- removeOutliers (src/matcher.cpp:108),
+// bucketFeatures (src/viso_stereo.cpp:41-43 -> matcher.cpp:140-187), estimateMotion
+// (src/viso_stereo.cpp:49-51) -- for every stream of the group: post_begin() starts the download of the
+// step's match lists into one of two page-locked slots and returns; post_finish() runs the Delaunay
+// vote and the bucketing of a begun step on `threads` host threads (one stream per task), uploads the
+// bucketed lists (a few hundred records per stream) and runs the batched egomotion kernel on them.
+// A caller that issues step t+1 before finishing step t has the host work of t running beside the
+// GPU work of t+1.
+
+int32_t Group::post_begin(int32_t cap_ps) {
+  if (cap_ps < 1) return VH_ERR_INVALID_ARG;
+  if (!allocated || last_method < 0) return VH_ERR_STATE;
+  PostSlot &sl = post.slot[post_seq & 1];
+  cap_ps = std::min(cap_ps, mcap);
+  if (sl.cap_ps < cap_ps) {
+    VH_HIP(sl.h_pm.alloc((size_t)S * cap_ps, hipHostMallocDefault));
+    sl.cap_ps = cap_ps;
+  }
+  if (!sl.h_cnt) VH_HIP(sl.h_cnt.alloc(2 * (size_t)S, hipHostMallocDefault));
+  VH_HIP(sl.ev.create());
+  VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
+  sl.width = cap_ps;
+  VH_HIP(hipMemcpy2DAsync(sl.h_pm, sizeof(vh_p_match) * (size_t)sl.cap_ps, mt.d_matches, sizeof(vh_p_match) * (size_t)mcap,
+                          sizeof(vh_p_match) * (size_t)cap_ps, (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(sl.h_cnt, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(sl.h_cnt + S, mt.d_overflow, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipEventRecord(sl.ev, down_stream));
+  // the next step's emission must not overwrite the lists before they have left (as vh_group_download_matches_async)
+  VH_HIP(hipEventRecord(ev_down, down_stream)); mt.ev_down_valid = true;
+  sl.pending = true; sl.method = last_method;
+  post_seq++;
+  return VH_OK;
+}
+
+// (e: the stereo estimator with rand3, or mono: the monocular one with rand8 -- at most one of them)
+int32_t Group::post_finish(int32_t age, int32_t max_features, float bw, float bh, int32_t threads, const vh_ego_params *e, const int32_t *rand3,
+                    const vh_mono_params *mono, const int32_t *rand8,
+                    double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts, double *host_ms) {
+  if (age < 0 || age > 1 || max_features < 1 || !(bw > 0) || !(bh > 0) || threads < 1 || (e && mono)) return VH_ERR_INVALID_ARG;
+  if (e && (!rand3 || !tr || !ok || !ninl || e->ransac_iters < 1)) return VH_ERR_INVALID_ARG;
+  if (mono && (!rand8 || !tr || !ok || !ninl || mono->ransac_iters < 1 || (int64_t)S * mono->ransac_iters > (int64_t)1 << 31)) return VH_ERR_INVALID_ARG;
+  if (post_seq - 1 - age < 0) return VH_ERR_STATE;
+  PostSlot &sl = post.slot[(post_seq - 1 - age) & 1];
+  if (!sl.pending) return VH_ERR_STATE;
+  if (e && sl.method != VH_METHOD_QUAD) return VH_ERR_STATE;       // the stereo estimator needs both cameras of both frames
+  if (mono && sl.method == VH_METHOD_STEREO) return VH_ERR_STATE;  // the monocular one the left camera of both frames
+  int64_t need = 0;
+  { const int32_t rb = bucket_need(max_features, bw, bh, &need); if (rb) return rb; }  // (a bucket below one pixel is refused: the grid would not fit any index type)
+  VH_HIP(hipEventSynchronize(sl.ev));
+  sl.pending = false;
+  for (int32_t s = 0; s < S; s++)
+    if (sl.h_cnt[s] > sl.width || sl.h_cnt[S + s]) return VH_ERR_CAPACITY;  // a list longer than what was downloaded / a truncated feature set
+  if (post.bcap < need) {
+    for (void *old : {(void *)post.d_bucket, (void *)post.d_post_xyz}) dfree(old);  // (the superseded blocks: a caller raising max_features step by step must not pile them up)
+    post.d_bucket = nullptr; post.d_post_xyz = nullptr;
+    VH_HIP(post.h_bucket.alloc((size_t)S * need, hipHostMallocDefault));
+    if (!post.h_bcnt) VH_HIP(post.h_bcnt.alloc((size_t)S, hipHostMallocDefault));
+    int32_t rc;
+    if ((rc = dmalloc((uint8_t **)&post.d_bucket, sizeof(vh_p_match) * (size_t)S * need, false))) return rc;
+    if (!post.d_bcnt && (rc = dmalloc(&post.d_bcnt, (size_t)S, false))) return rc;
+    if ((rc = dmalloc(&post.d_post_xyz, (size_t)S * need * 4, false))) return rc;
+    if (!post.d_post_tr) { if ((rc = dmalloc(&post.d_post_tr, 6 * (size_t)S, false))) return rc; if ((rc = dmalloc(&post.d_post_ok, 2 * (size_t)S, false))) return rc; }
+    post.bcap = (int32_t)need;
+    post.post_mono_iters = 0;  // (the monocular scratch is sized by post.bcap as well)
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  std::atomic<int32_t> failed(0);
+  const bool vote = sl.method != VH_METHOD_STEREO;  // stereo records carry no previous-frame position (as remove_outliers())
+  for_each_stream(0, S, threads, [&](int32_t s) {
+    thread_local std::vector<int32_t> scratch;
+    vh_p_match *pm = sl.h_pm + (size_t)s * sl.cap_ps;
+    int32_t n = sl.h_cnt[s];
+    if (vote && vh_remove_outliers_pm(pm, n, &n) != VH_OK) { failed = 1; return; }
+    post.h_bcnt[s] = bucket_records(pm, n, max_features, bw, bh, post.h_bucket + (size_t)s * post.bcap, post.bcap, scratch);
+  });
+  if (host_ms) *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  if (failed) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < S; s++) if (post.h_bcnt[s] > post.bcap) return VH_ERR_CAPACITY;
+  if (out_counts) for (int32_t s = 0; s < S; s++) out_counts[s] = post.h_bcnt[s];
+  if (out) {
+    for (int32_t s = 0; s < S; s++) {
+      if (post.h_bcnt[s] > out_cap) return VH_ERR_CAPACITY;
+      memcpy(out + (size_t)s * out_cap, post.h_bucket + (size_t)s * post.bcap, sizeof(vh_p_match) * (size_t)post.h_bcnt[s]);
+    }
+  }
+  if (!e && !mono) return VH_OK;
+  const size_t nr = e ? (size_t)S * e->ransac_iters * 3 : (size_t)S * mono->ransac_iters * 8;
+  if (post.post_rand_n < nr) { int32_t rc = dmalloc(&post.d_post_rand, nr, false); if (rc) return rc; post.post_rand_n = nr; }
+  if (mono && post.post_mono_iters < mono->ransac_iters) {
+    int32_t rc = dmalloc(&post.d_post_mono, (size_t)vh_mono_scratch_bytes(S, post.bcap, mono->ransac_iters), false);
+    if (rc) return rc;
+    post.post_mono_iters = mono->ransac_iters;
+  }
+  // the bucketed lists go up as one block; everything on the download stream, beside the next step's kernels
+  VH_HIP(hipMemcpyAsync(post.d_bucket, post.h_bucket, sizeof(vh_p_match) * (size_t)S * post.bcap, hipMemcpyHostToDevice, down_stream));
+  VH_HIP(hipMemcpyAsync(post.d_bcnt, post.h_bcnt, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, down_stream));
+  VH_HIP(hipMemcpyAsync(post.d_post_rand, e ? rand3 : rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, down_stream));
+  if (e) vh_launch_ego(*e, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_xyz, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
+  else vh_launch_mono(*mono, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_mono, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipMemcpyAsync(tr, post.d_post_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(ok, post.d_post_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipMemcpyAsync(ninl, post.d_post_ok + S, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
+  VH_HIP(hipStreamSynchronize(down_stream));
+  static const bool timing = [] { const char *ev_ = getenv("VH_POST_TIMING"); return ev_ && ev_[0] == '1'; }();
+  if (timing) fprintf(stderr, "post_finish: host %.2f ms, upload + ego + results %.2f ms\n",
+                      host_ms ? *host_ms : -1.0, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() - (host_ms ? *host_ms : 0.0));
+  return VH_OK;
+}
+
+// ---- the steps after matching ON THE DEVICE ---------------------------------
+// removeOutliers -> bucketFeatures -> estimateMotion without the host: kernels_vote.hip.  The triangulation
+// under the vote is a sequential chain per list that takes tens of milliseconds as a GPU lane, so the
+// throughput comes from lists in flight: post_begin_device() moves the step's S lists into the current
+// BATCH (the matcher's buffer is free again at once); a batch of `vote_steps` steps is launched as one
+// kernel sequence over vote_steps * S lists on one of a few low-priority streams (their own hardware
+// queues: the long sweep kernel never stands in front of the matcher's kernels), and up to
+// `vote_batches` batches are in flight.  post_finish_device(age) hands out the results of the step begun
+// `age` begins ago, waiting for its batch if it has to -- a caller that stays vote_steps * (vote_batches - 1)
+// steps ahead never waits.
+
+int32_t Group::post_device_config(int32_t steps_per_batch, int32_t batches, int32_t lanes) {
+  if (steps_per_batch < 1 || steps_per_batch > 256 || batches < 1 || batches > 64 || lanes < 1 || lanes > 64) return VH_ERR_INVALID_ARG;
+  for (auto &b : vbatch) if (b.busy) return VH_ERR_STATE;  // steps begun whose results have not been handed out
+  vote_release();
+  vote_steps = steps_per_batch; vote_batches = batches; vote_lanes = lanes;
+  return VH_OK;
+}
+
+// bucket grid of Matcher::bucketFeatures on this group's images: floor(u_max / bw) + 1 columns, floor(v_max / bh) + 1 rows (matcher.cpp:150-151)
+int32_t Group::bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid) const {
+  if (max_features < 1 || !(bw >= 1) || !(bh >= 1)) return VH_ERR_INVALID_ARG;
+  const int64_t cols = (int64_t)floorf((float)(dims[0] - 1) / bw) + 1, rows = (int64_t)floorf((float)(dims[1] - 1) / bh) + 1;
+  if (cols * rows > (1 << 20)) return VH_ERR_UNSUPPORTED;
+  *need = std::min<int64_t>(cols * rows * max_features, mcap);
+  if (grid) *grid = cols * rows;
+  return VH_OK;
+}
+
+int32_t Group::vote_launch(VoteBatch &b, int32_t index) {
+  if (b.launched || b.steps == 0) return VH_OK;
+  hipStream_t vs = vote_stream[index % kVoteStreams];
+  VhVote v = b.vb.v;
+  v.P = b.steps * S;
+  VH_HIP(hipStreamWaitEvent(vs, b.ev_prep, 0));
+  vh_launch_vote(v, vote_lanes, b.max_features, b.bw, b.bh, b.vb.lfsr, b.vb.lfsr_n, b.vb.out, b.vb.out_cap, b.vb.out_count, nullptr, vs);
+  VH_HIP(hipGetLastError());
+  if (b.has_ego) vh_launch_ego(b.ego, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
+  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
+  VH_HIP(hipGetLastError());
+  if (b.has_ego || b.has_mono) {
+    VH_HIP(hipMemcpyAsync(b.h_tr, b.d_tr, sizeof(double) * 6 * (size_t)v.P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(b.h_ok, b.d_ok, sizeof(int32_t) * 2 * (size_t)v.P, hipMemcpyDeviceToHost, vs));
+  }
+  VH_HIP(hipMemcpyAsync(b.h_cnt, b.vb.out_count, sizeof(int32_t) * (size_t)v.P, hipMemcpyDeviceToHost, vs));
+  VH_HIP(hipMemcpyAsync(b.h_meta, b.vb.v.meta, sizeof(VhVoteMeta) * (size_t)v.P, hipMemcpyDeviceToHost, vs));
+  if (b.want_lists) VH_HIP(hipMemcpyAsync(b.h_out, b.vb.out, sizeof(vh_p_match) * (size_t)v.P * b.vb.out_cap, hipMemcpyDeviceToHost, vs));
+  VH_HIP(hipEventRecord(b.ev_done, vs));
+  static const bool serial_vote = [] { const char *ev = getenv("VH_VOTE_SERIAL"); return ev && ev[0] == '1'; }();
+  if (serial_vote) VH_HIP(hipStreamWaitEvent(stream, b.ev_done, 0));  // experiment: the matcher's next step waits for this batch
+  b.launched = true;
+  return VH_OK;
+}
+
+int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw, float bh, const vh_ego_params *e, const int32_t *rand3,
+                          const vh_mono_params *mono, const int32_t *rand8, int32_t want_lists) {
+  if (cap_ps < 1 || (e && mono)) return VH_ERR_INVALID_ARG;
+  if (e && (!rand3 || e->ransac_iters < 1)) return VH_ERR_INVALID_ARG;
+  if (mono && (!rand8 || mono->ransac_iters < 1 || (int64_t)S * vote_steps * mono->ransac_iters > (int64_t)1 << 31)) return VH_ERR_INVALID_ARG;
+  if ((int64_t)S * vote_steps > 65535) return VH_ERR_UNSUPPORTED;  // (the tally and the monocular kernels put the list on grid.y: fewer steps per batch)
+  if (!allocated || last_method < 0) return VH_ERR_STATE;
+  if (e && last_method != VH_METHOD_QUAD) return VH_ERR_STATE;        // the stereo estimator needs both cameras of both frames
+  if (mono && last_method == VH_METHOD_STEREO) return VH_ERR_STATE;   // the monocular one the left camera of both frames
+  int64_t need = 0, grid = 0;
+  int32_t rc = bucket_need(max_features, bw, bh, &need, &grid);
+  if (rc) return rc;
+  cap_ps = std::min(cap_ps, mcap);
+  if (cap_ps > VH_VOTE_LIST_MAX) return VH_ERR_UNSUPPORTED;  // (16-bit hull links; the sweep's angular hash has VH_VOTE_HASH_MAX slots in LDS)
+  if (vbatch.empty()) {
+    // The ring is allocated batch by batch on first use: it must fit the device NOW, or a later begin call -- with steps
+    // already moved -- fails in hipMalloc.  Steps per batch are halved until vote_batches batches fit 80 % of the free
+    // memory; if a single step per batch does not fit, nothing has moved yet and the caller is told so.
+    size_t free_b = 0, total_b = 0;
+    VH_HIP(hipMemGetInfo(&free_b, &total_b));
+    const auto ring_bytes = [&](int32_t steps) {
+      const int32_t P = steps * S;
+      const size_t post = (e ? sizeof(double) * 4 * (size_t)P * (size_t)need : 0) + (mono ? (size_t)vh_mono_scratch_bytes(P, (int32_t)need, mono->ransac_iters) : 0) +
+                          sizeof(double) * 6 * (size_t)P + sizeof(int32_t) * 2 * (size_t)P +
+                          sizeof(int32_t) * (size_t)steps * (e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0));
+      return (double)vote_batches * (double)(VhVoteBuffers::bytes_for(P, cap_ps, (int32_t)need, (int32_t)grid) + post);
+    };
+    int32_t steps = vote_steps;
+    while (steps > 1 && ring_bytes(steps) > 0.8 * (double)free_b) steps = (steps + 1) / 2;
+    if (ring_bytes(steps) > 0.8 * (double)free_b) {
+      t_last_error = "the post stage's ring of batches does not fit the device's free memory even at one step per batch";
+      return VH_ERR_CAPACITY;
+    }
+    vote_steps = steps;
+    vbatch.resize((size_t)vote_batches);
+    vstep.assign((size_t)vote_steps * vote_batches, VoteStep{});
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    static const int prio_env = [] { const char *ev = getenv("VH_VOTE_STREAM_PRIO"); return ev ? atoi(ev) : 1; }();  // 1: lowest, 0: normal, -1: highest
+    const int prio = prio_env > 0 ? prio_lo : (prio_env < 0 ? prio_hi : 0);
+    for (int k = 0; k < kVoteStreams; k++)
+      if (!vote_stream[k]) VH_HIP(vote_stream[k].create(prio));
+    for (auto &b : vbatch) { VH_HIP(b.ev_prep.create()); VH_HIP(b.ev_done.create()); }
+  }
+  VoteBatch *b = &vbatch[(size_t)vote_cur];
+  const size_t rand_per_step = e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0);
+  const auto same = [&](const VoteBatch &q) {
+    return q.method == last_method && q.max_features == max_features && q.bw == bw && q.bh == bh && q.has_ego == (e != nullptr) &&
+           q.has_mono == (mono != nullptr) && (!e || memcmp(&q.ego, e, sizeof(*e)) == 0) && (!mono || memcmp(&q.mono, mono, sizeof(*mono)) == 0) &&
+           q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0);
+  };
+  if (b->steps > 0 && (b->launched || b->steps >= vote_steps || !same(*b))) {  // the batch is closed (full, flushed, or configured differently): next one
+    if ((rc = vote_launch(*b, vote_cur))) return rc;
+    const int32_t next = (vote_cur + 1) % vote_batches;
+    // the ring has come round: the next batch's results must have been handed out (checked before anything moves, so
+    // that the caller can finish those steps and begin this one again)
+    if (vbatch[(size_t)next].launched && vbatch[(size_t)next].busy && vbatch[(size_t)next].handed < vbatch[(size_t)next].steps) return VH_ERR_STATE;
+    vote_cur = next;
+    b = &vbatch[(size_t)vote_cur];
+  }
+  if (b->steps == 0 || b->launched) {  // start the batch
+    if (b->launched) {  // a batch of the previous round: its kernels must be done
+      if (b->busy && b->handed < b->steps) return VH_ERR_STATE;
+      VH_HIP(hipEventSynchronize(b->ev_done));
+    }
+    b->steps = 0; b->launched = false; b->busy = false; b->handed = 0;
+    const int32_t P = vote_steps * S;
+    if (b->vb.v.cap < cap_ps || b->vb.out_cap < need || b->vb.v.P < P || b->vb.v.nb_max < grid) {
+      if (b->vb.block) {  // a batch grows (longer lists than the ring was sized for): only if the difference fits
+        size_t free_b = 0, total_b = 0;
+        VH_HIP(hipMemGetInfo(&free_b, &total_b));
+        const size_t want = VhVoteBuffers::bytes_for(P, cap_ps, (int32_t)need, (int32_t)grid);
+        if (want > b->vb.bytes && want - b->vb.bytes > free_b) { t_last_error = "the post stage's batch cannot grow: device memory exhausted"; return VH_ERR_CAPACITY; }
+      }
+      b->vb.release();
+      VH_HIP(b->vb.alloc(P, cap_ps, (int32_t)need, (int32_t)grid));
+      VH_HIP(b->vb.upload_lfsr());
+    }
+    const int32_t ocap = b->vb.out_cap;
+    const auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t b_rand = up(sizeof(int32_t) * rand_per_step * vote_steps), b_xyz = up(e ? sizeof(double) * 4 * (size_t)P * ocap : 0), b_tr = up(sizeof(double) * 6 * (size_t)P),
+                 b_ok = up(sizeof(int32_t) * 2 * (size_t)P), b_mono = mono ? (size_t)vh_mono_scratch_bytes(P, ocap, mono->ransac_iters) : 0;
+    if (b->block_bytes < b_rand + b_xyz + b_tr + b_ok + b_mono || b->rand_per_step != rand_per_step) {
+      b->block_bytes = 0;
+      VH_HIP(b->block.alloc(b_rand + b_xyz + b_tr + b_ok + b_mono + 256));
+      b->block_bytes = b_rand + b_xyz + b_tr + b_ok + b_mono;
+    }
+    uint8_t *blk = b->block.as<uint8_t>();
+    b->d_rand = (int32_t *)blk; b->d_xyz = (double *)(blk + b_rand); b->d_tr = (double *)(blk + b_rand + b_xyz);
+    b->d_ok = (int32_t *)(blk + b_rand + b_xyz + b_tr); b->d_mono = blk + b_rand + b_xyz + b_tr + b_ok;
+    b->rand_per_step = rand_per_step;
+    if (b->h_rand_ints < rand_per_step * (size_t)vote_steps) {
+      b->h_rand_ints = 0;
+      VH_HIP(b->h_rand.alloc(rand_per_step * (size_t)vote_steps, hipHostMallocDefault));
+      b->h_rand_ints = rand_per_step * (size_t)vote_steps;
+    }
+    if (b->h_lists < P) {
+      b->h_lists = 0;
+      VH_HIP(b->h_tr.alloc(6 * (size_t)P, hipHostMallocDefault));
+      VH_HIP(b->h_ok.alloc(2 * (size_t)P, hipHostMallocDefault));
+      VH_HIP(b->h_cnt.alloc((size_t)P, hipHostMallocDefault));
+      VH_HIP(b->h_meta.alloc((size_t)P, hipHostMallocDefault));
+      b->h_lists = P;
+    }
+    if (want_lists && (!b->h_out || b->h_out_cap < ocap)) {
+      VH_HIP(b->h_out.alloc((size_t)P * ocap, hipHostMallocDefault));
+      b->h_out_cap = ocap;
+    }
+    b->method = last_method; b->max_features = max_features; b->bw = bw; b->bh = bh; b->has_ego = e != nullptr; b->has_mono = mono != nullptr;
+    if (e) b->ego = *e;
+    if (mono) b->mono = *mono;
+    b->want_lists = want_lists != 0;
+  }
+  // the step's lists leave the matcher's buffer behind the emission that wrote them; the next emission waits for that (ev_down)
+  VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
+  vh_launch_vote_prep(b->vb.v, b->steps * S, S, (const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, mt.d_overflow, last_method != VH_METHOD_STEREO ? 1 : 0, down_stream);
+  VH_HIP(hipGetLastError());
+  if (rand_per_step) {
+    // through the batch's page-locked slot of this step: an asynchronous copy from the caller's pageable array would
+    // make the host wait until the stream reaches it (behind the step's emission), and the array is only borrowed
+    int32_t *hr = b->h_rand + rand_per_step * (size_t)b->steps;
+    memcpy(hr, e ? rand3 : rand8, sizeof(int32_t) * rand_per_step);
+    VH_HIP(hipMemcpyAsync(b->d_rand + rand_per_step * (size_t)b->steps, hr, sizeof(int32_t) * rand_per_step, hipMemcpyHostToDevice, down_stream));
+  }
+  VH_HIP(hipEventRecord(b->ev_prep, down_stream));
+  VH_HIP(hipEventRecord(ev_down, down_stream)); mt.ev_down_valid = true;
+  VoteStep &st = vstep[(size_t)(post_dev_seq % (int64_t)vstep.size())];
+  st.batch = vote_cur; st.pos = b->steps; st.open = true;
+  b->steps++; b->busy = true;
+  post_dev_seq++;
+  if (b->steps >= vote_steps) return vote_launch(*b, vote_cur);
+  return VH_OK;
+}
+
+int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts) {
+  if (age < 0 || (out && out_cap < 1)) return VH_ERR_INVALID_ARG;
+  if (vstep.empty() || post_dev_seq - 1 - age < 0 || age >= (int64_t)vstep.size()) return VH_ERR_STATE;
+  VoteStep &st = vstep[(size_t)((post_dev_seq - 1 - age) % (int64_t)vstep.size())];
+  if (!st.open) return VH_ERR_STATE;
+  VoteBatch &b = vbatch[(size_t)st.batch];
+  int32_t rc = vote_launch(b, st.batch);  // (a batch that is not full yet is closed and launched now)
+  if (rc) return rc;
+  VH_HIP(hipEventSynchronize(b.ev_done));
+  st.open = false;
+  b.handed++;
+  if (b.handed >= b.steps) b.busy = false;
+  const size_t p0 = (size_t)st.pos * S, P = (size_t)b.steps * S;
+  if ((b.has_ego || b.has_mono) && (!tr || !ok || !ninl)) return VH_ERR_INVALID_ARG;
+  if (out && !b.want_lists) return VH_ERR_STATE;
+  if (b.has_ego || b.has_mono) {
+    memcpy(tr, b.h_tr + 6 * p0, sizeof(double) * 6 * (size_t)S);
+    memcpy(ok, b.h_ok + p0, sizeof(int32_t) * (size_t)S);
+    memcpy(ninl, b.h_ok + P + p0, sizeof(int32_t) * (size_t)S);
+  }
+  if (out_counts) memcpy(out_counts, b.h_cnt + p0, sizeof(int32_t) * (size_t)S);
+  // One refused list does not void the step: the healthy streams are delivered, a refused stream reports
+  // ok = 0, n_inliers = 0, tr = 0, counts = -1, and the call returns the error (capacity before unsupported).
+  int32_t ret = VH_OK;
+  for (int32_t s = 0; s < S; s++) {
+    const VhVoteMeta &m = b.h_meta[p0 + s];
+    const bool bad = m.status != VH_VOTE_OK && m.status != VH_VOTE_SKIP;
+    if (m.status == VH_VOTE_TRUNCATED) ret = VH_ERR_CAPACITY;
+    else if (bad && ret == VH_OK) ret = VH_ERR_UNSUPPORTED;
+    if (bad) {
+      if (b.has_ego || b.has_mono) { for (int k = 0; k < 6; k++) tr[6 * (size_t)s + k] = 0.0; ok[s] = 0; ninl[s] = 0; }
+      if (out_counts) out_counts[s] = -1;
+      continue;
+    }
+    if (out) {
+      const int32_t k = b.h_cnt[p0 + s];
+      if (k > out_cap) { ret = VH_ERR_CAPACITY; if (out_counts) out_counts[s] = -1; continue; }
+      memcpy(out + (size_t)s * out_cap, b.h_out + (p0 + s) * (size_t)b.vb.out_cap, sizeof(vh_p_match) * (size_t)k);
+    }
+  }
+  return ret;
+}
+
+uint32_t lfsr_next(uint32_t x) { return vh_lfsr_next(x); }  // (vh_vote.h: shared with the device form of the shuffle)
+
+// Matcher::bucketFeatures (matcher.cpp:140-187) without the fixed
+// buckets[126][256] capacity.
+void bucket_host(std::vector<vh_p_match> &pm, int32_t max_features, float bw, float bh) {
+  float u_max = 0, v_max = 0;
+  for (auto &m : pm) { if (m.u1c > u_max) u_max = m.u1c; if (m.v1c > v_max) v_max = m.v1c; }
+  const int32_t cols = (int32_t)floorf(u_max / bw) + 1, rows = (int32_t)floorf(v_max / bh) + 1;
+  std::vector<std::vector<vh_p_match>> buckets((size_t)cols * rows);
+  for (auto &m : pm) {
+    const int32_t u = (int32_t)floorf(m.u1c / bw), v = (int32_t)floorf(m.v1c / bh);
+    buckets[(size_t)v * cols + u].push_back(m);
+  }
+  pm.clear();
+  uint32_t rnd = 5;
+  for (auto &b : buckets) {
+    const int32_t len = (int32_t)b.size();
+    for (int32_t i = 1; i < len; i++) {  // random_shuffle, matcher.cpp:126-138
+      const int32_t j = (int32_t)(rnd % (uint32_t)(i + 1));
+      rnd = lfsr_next(rnd);
+      std::swap(b[i], b[j]);
+    }
+    for (int32_t j = 0, k = 0; j < len; j++) { pm.push_back(b[j]); if (++k >= max_features) break; }
+  }
+}
+
+int32_t bucket_records(const vh_p_match *pm, int32_t n, int32_t max_features, float bw, float bh, vh_p_match *out, int32_t out_cap,
+                       std::vector<int32_t> &work) {
+  float u_max = 0, v_max = 0;
+  for (int32_t i = 0; i < n; i++) { if (pm[i].u1c > u_max) u_max = pm[i].u1c; if (pm[i].v1c > v_max) v_max = pm[i].v1c; }
+  const int32_t cols = (int32_t)floorf(u_max / bw) + 1, rows = (int32_t)floorf(v_max / bh) + 1, nb = cols * rows;
+  // counting sort of the record indices by bucket (row-major), stable: the reference appends in list order
+  work.assign((size_t)nb + 1 + (size_t)n, 0);
+  int32_t *start = work.data(), *idx = work.data() + nb + 1;
+  const auto bucket_of = [&](const vh_p_match &m) { return (int32_t)floorf(m.v1c / bh) * cols + (int32_t)floorf(m.u1c / bw); };
+  for (int32_t i = 0; i < n; i++) start[bucket_of(pm[i]) + 1]++;
+  for (int32_t b = 0; b < nb; b++) start[b + 1] += start[b];
+  {
+    std::vector<int32_t> cur(start, start + nb);
+    for (int32_t i = 0; i < n; i++) idx[cur[bucket_of(pm[i])]++] = i;
+  }
+  uint32_t rnd = 5;
+  int32_t kept = 0;
+  for (int32_t b = 0; b < nb; b++) {
+    int32_t *v = idx + start[b];
+    const int32_t len = start[b + 1] - start[b];
+    for (int32_t i = 1; i < len; i++) {  // random_shuffle, matcher.cpp:126-138
+      const int32_t j = (int32_t)(rnd % (uint32_t)(i + 1));
+      rnd = lfsr_next(rnd);
+      std::swap(v[i], v[j]);
+    }
+    for (int32_t j = 0, k = 0; j < len; j++) { if (kept < out_cap) out[kept] = pm[v[j]]; kept++; if (++k >= max_features) break; }
+  }
+  return kept;
+}
+
+int32_t prior_statistics(const vh_params &p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges) {
+  const float bs = (float)p.match_binsize, R = (float)p.match_radius;
+  const int32_t ubn = (int32_t)ceilf((float)dims[0] / bs), vbn = (int32_t)ceilf((float)dims[1] / bs);  // matcher.cpp:282-283
+  const int32_t nst = method == VH_METHOD_QUAD ? 4 : 2;
+  const size_t nb = (size_t)ubn * vbn;
+  std::vector<uint8_t> seen(nb, 0);
+  for (size_t k = 0; k < nb * 16; k++) ranges[k] = (k & 1) ? R : -R;
+  for (int32_t i = 0; i < n; i++) {
+    const vh_p_match &m = pm[i];
+    float d[8] = {0, 0, 0, 0, 0, 0, 0, 0}, u, v;
+    if (method == VH_METHOD_FLOW) {
+      d[0] = m.u1p - m.u1c; d[1] = m.v1p - m.v1c; d[2] = m.u1c - m.u1p; d[3] = m.v1c - m.v1p;
+      u = m.u1c; v = m.v1c;
+    } else if (method == VH_METHOD_STEREO) {
+      d[0] = m.u2c - m.u1c; d[2] = m.u1c - m.u2c;
+      u = m.u1c; v = m.v1c;
+    } else {
+      d[0] = m.u2p - m.u1p; d[2] = m.u2c - m.u2p; d[3] = m.v2c - m.v2p; d[4] = m.u1c - m.u2c; d[6] = m.u1p - m.u1c; d[7] = m.v1p - m.v1c;
+      u = m.u1p; v = m.v1p;
+    }
+    bool finite = std::isfinite(u) && std::isfinite(v);
+    for (int32_t k = 0; k < 2 * nst; k++) finite = finite && std::isfinite(d[k]);
+    if (!finite) return VH_ERR_INVALID_ARG;
+    // the bin of the reference point, kept in float until it is inside [-1, bin count] (any finite coordinate)
+    const int32_t ub = (int32_t)std::min(std::max(floorf(u / bs), -1.0f), (float)ubn);
+    const int32_t vb = (int32_t)std::min(std::max(floorf(v / bs), -1.0f), (float)vbn);
+    const auto clampi = [](int32_t x, int32_t nbin) { return std::min(std::max(x, 0), nbin - 1); };
+    for (int32_t y = clampi(vb - 1, vbn); y <= clampi(vb + 1, vbn); y++)
+      for (int32_t x = clampi(ub - 1, ubn); x <= clampi(ub + 1, ubn); x++) {
+        const size_t b = (size_t)y * ubn + x;
+        float *r = ranges + b * 16;
+        for (int32_t st = 0; st < nst; st++)
+          for (int32_t ax = 0; ax < 2; ax++) {
+            float &lo = r[4 * st + 2 * ax], &hi = r[4 * st + 2 * ax + 1];
+            const float x_ = d[2 * st + ax];
+            if (!seen[b]) { lo = x_; hi = x_; }
+            else { lo = std::min(lo, x_); hi = std::max(hi, x_); }
+          }
+        seen[b] = 1;
+      }
+  }
+  for (size_t b = 0; b < nb; b++) {
+    if (!seen[b]) continue;  // no observation: +-radius, not widened
+    for (int32_t st = 0; st < nst; st++)
+      for (int32_t ax = 0; ax < 2; ax++) {
+        float &lo = ranges[b * 16 + 4 * st + 2 * ax], &hi = ranges[b * 16 + 4 * st + 2 * ax + 1];
+        const float dd = hi - lo;
+        if (dd < 20.0f) { const float h = ceilf((20.0f - dd) / 2.0f); lo -= h; hi += h; }
+      }
+  }
+  return VH_OK;
+}
+
+}  // namespace vh_engine

@@ -577,7 +577,7 @@ def test_flow_search_tested_loop_path(gpu):
 
 @pytest.mark.gpu
 def test_search_loop_policy_follows_the_data(pkg, ob, oracle, gpu, monkeypatch):
-    """engine.hip: choose_loop.  Frames whose features have partners keep the speculative search loops
+    """engine_match.hip: choose_loop.  Frames whose features have partners keep the speculative search loops
     (few winners fall outside their window); independent noise images -- no feature has a partner -- push
     the observed share of second searches far over the 6.5 % threshold and the tested loops take over;
     partnered frames bring the speculative ones back.  The match lists equal the oracle's in every phase."""

@@ -64,7 +64,7 @@ def tiles(f):
     return int(sum(-(-int((f[:, 3] == c).sum()) // TILE_Q) for c in range(4)))
 
 
-QUERY_SETS = {0: (2, 0), 1: (2, 3), 2: (0, 1, 3, 2)}  # engine.hip match_args: the query set of every pass
+QUERY_SETS = {0: (2, 0), 1: (2, 3), 2: (0, 1, 3, 2)}  # engine_match.hip match_args: the query set of every pass
 
 
 def pmap(fn, items):
@@ -225,7 +225,7 @@ def sparse_frame(img, W, H):
 
 @pytest.mark.parametrize("method", [2, 0, 1], ids=["quad", "flow", "stereo"])
 def test_tile_hint_sparse_to_dense(method, pkg, ob, oracle, gpu):
-    """engine.hip: match_queued sizes the searches' grid of a non-serial group (S >= 3, nms_n <= 4) from the tiles an
+    """engine_match.hip: match_queued sizes the searches' grid of a non-serial group (S >= 3, nms_n <= 4) from the tiles an
     earlier launch saw (tiles_hint).  After a read-back of a step on nearly flat frames, a step on densely textured
     frames holds many times the tiles of that grid: every wave walks several tiles.  Then back to sparse frames."""
     S, W, H = 4, 640, 240
@@ -243,7 +243,7 @@ def test_tile_hint_sparse_to_dense(method, pkg, ob, oracle, gpu):
     npass = 4 if method == 2 else 2
     g = pkg.StreamGroup(S, p)
 
-    def hint(tp, tc):  # engine.hip: choose_loop -- tiles_hint from the fullest stream's query sets
+    def hint(tp, tc):  # engine_match.hip: choose_loop -- tiles_hint from the fullest stream's query sets
         nq = max(sum(len(fr.quad(s, tp, tc)[q]) for q in QUERY_SETS[method]) for s in range(S))
         return nq // npass // TILE_Q + 4
 

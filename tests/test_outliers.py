@@ -560,7 +560,7 @@ def test_device_post_stage_ring_discipline(pkg, ob, oracle, gpu):
 @pytest.mark.gpu
 def test_device_post_stage_ring_is_sized_against_free_memory(pkg, ob, oracle, gpu):
     """The ring of batches is allocated lazily, so the FIRST begin call sizes it against the device's free memory
-    (csrc/engine.hip: post_begin_device): steps per batch are halved until `batches` batches fit 80 % of it, and when even
+    (csrc/engine_post.hip: post_begin_device): steps per batch are halved until `batches` batches fit 80 % of it, and when even
     one step per batch does not fit the call returns VH_ERR_CAPACITY before anything has moved -- the step's lists are
     still in the matcher's buffer and a smaller shape goes through."""
     import ctypes as C
@@ -646,7 +646,7 @@ def test_device_post_stage_leaves_stereo_lists_unvoted(pkg, ob, oracle, gpu):
 
 @pytest.mark.gpu
 def test_device_post_stage_time_sliced(gpu):
-    """VH_VOTE_SERIAL=1 (csrc/engine.hip vote_launch: the matcher's next step waits for the batch's vote instead of
+    """VH_VOTE_SERIAL=1 (csrc/engine_post.hip vote_launch: the matcher's next step waits for the batch's vote instead of
     running beside it; an experiment switch, profiles/EXPERIMENTS.md): the same results -- the device post-stage tests
     of this file once more on that path."""
     import os

@@ -340,3 +340,63 @@ def test_child_refinement_checking_build(pkg, gpu):
     assert os.path.exists(pkg.CHECK_LIB_PATH), "build() makes it"
     r = run_child({"VISO_HIP_LIB": pkg.CHECK_LIB_PATH, "VH_SUBBATCH": "3"}, "groups_and_sequence or stateless")
     assert "VH_CHECK" not in r.stderr
+
+
+@pytest.mark.gpu
+def test_failed_first_push_leaves_nothing_behind(pkg, ob, oracle, gpu):
+    """A first pushBack whose k-th device allocation fails (engine.hip: ensure / allocate, the staging blocks of push_host)
+    releases everything it made: deviceBytes() is 0 right after, and the handle then computes what an undisturbed one
+    does, in the same memory.  320 x 160, S = 2 (serial: the host-mapped match block is on the path), refinement = 1 and
+    half_resolution = 1 so that their blocks are too; skip = 0, the middle, and the last allocation of the push."""
+    kw = dict(refinement=1, half_resolution=1)
+    p, po = pkg.Params.default(**kw), ob.Params.default(**kw)
+    dims = [W, H, pkg.synth.bytes_per_line(W)]
+    S = 2
+    fr = [pkg.synth.stereo_sequence(W, H, 3, disparity=6, blur=4, seed=31 + s) for s in range(S)]
+    push = lambda g, t: g.pushBack(np.stack([fr[s][t][0] for s in range(S)]), np.stack([fr[s][t][1] for s in range(S)]), dims)
+
+    def finish(g):  # two more pushes and a quad match -> the lists and the memory held
+        for t in (1, 2):
+            push(g, t)
+        g.matchFeatures(pkg.METHOD_QUAD)
+        out = [g.getMatches(s) for s in range(S)], g.deviceBytes()
+        g.close()
+        return out
+
+    g = pkg.StreamGroup(S, p)
+    push(g, 0)
+    clean, clean_bytes = finish(g)
+    assert all(len(pm) >= 20 for pm in clean), [len(pm) for pm in clean]
+    want, raw = expected(oracle, po, dims, pkg.METHOD_QUAD, fr[0][1], fr[0][2], 1)
+    assert clean[0].tobytes() == want.tobytes()
+
+    n_alloc = None  # allocations of a first push: the smallest skip at which it succeeds
+    for skip in range(64):
+        g = pkg.StreamGroup(S, p)
+        g.debugFailAllocAfter(skip)
+        try:
+            push(g, 0)
+            n_alloc = skip
+        except pkg.VisoHipError as e:
+            assert e.code == pkg.VH_ERR_HIP, skip
+        g.close()
+        if n_alloc is not None:
+            break
+    assert n_alloc is not None and n_alloc >= 3, n_alloc
+    for skip in (0, n_alloc // 2, n_alloc - 1):
+        g = pkg.StreamGroup(S, p)
+        g.debugFailAllocAfter(skip)
+        with pytest.raises(pkg.VisoHipError) as e:
+            push(g, 0)
+        assert e.value.code == pkg.VH_ERR_HIP and g.deviceBytes() == 0, skip
+        push(g, 0)
+        got, got_bytes = finish(g)
+        assert got_bytes == clean_bytes, (skip, got_bytes, clean_bytes)
+        for s in range(S):
+            assert got[s].tobytes() == clean[s].tobytes(), (skip, s)
+
+
+@pytest.mark.gpu
+def test_child_failed_first_push_on_poisoned_buffers(gpu):
+    """The same with VH_POISON=1: buffers that are not zero-initialised at allocation start as 0xA5 bytes."""
+    run_child({"VH_POISON": "1"}, "failed_first_push_leaves")
