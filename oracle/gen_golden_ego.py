@@ -30,3 +30,20 @@ for name, (n, seed, outliers, noise, kw) in {
     out[name + "__ok"] = np.array(int(ok)); out[name + "__tr"] = tr; out[name + "__inliers"] = inl
     print(name, ok, len(inl), tr)
 np.savez_compressed(os.path.join(ROOT, "tests", "golden", "egomotion.npz"), **out)
+
+# tests/golden/egomotion_edges.npz: the reference on one scene of every kind tests/test_egomotion_edges.py adds
+# (egomotion_scene.stereo_edge_cases: list lengths and iteration counts at the kernel's chunk boundaries, ties,
+# failure paths, degenerate geometry, parameters)
+from egomotion_scene import stereo_edge_cases
+out = {}
+for name, (pm, kw) in stereo_edge_cases(ob.P_MATCH_DTYPE).items():
+    e = ob.EgoParams.default() if kw is None else ob.EgoParams.default(**kw)
+    ok, tr, inl = ref.estimate_motion_stereo(e, pm)
+    ok2, tr2, inl2 = oracle.estimate_motion_stereo(e, pm, oracle.draw_samples(len(pm), e.ransac_iters))
+    assert ok == ok2 and tr.tobytes() == tr2.tobytes() and np.array_equal(inl, inl2), name
+    out[name + "__pm"] = pm.view(np.uint8).reshape(len(pm), 48)
+    out[name + "__ok"] = np.array(int(ok)); out[name + "__tr"] = tr; out[name + "__inliers"] = inl.astype(np.int16)
+    print(name, ok, len(inl), tr)
+path = os.path.join(ROOT, "tests", "golden", "egomotion_edges.npz")
+np.savez_compressed(path, **out)
+print("wrote", path, os.path.getsize(path), "bytes")

@@ -46,3 +46,21 @@ for k, (m, n) in enumerate([(3, 3), (3, 3), (4, 4), (8, 9), (8, 9), (40, 9), (4,
     out[f"svd{k}__a"] = a; out[f"svd{k}__U"] = U; out[f"svd{k}__W"] = W; out[f"svd{k}__V"] = V
 np.savez_compressed(os.path.join(ROOT, "tests", "golden", "mono.npz"), **out)
 print("wrote tests/golden/mono.npz", os.path.getsize(os.path.join(ROOT, "tests", "golden", "mono.npz")), "bytes")
+
+# tests/golden/mono_edges.npz: the reference on one scene of every kind tests/test_mono_edges.py adds
+# (egomotion_scene.mono_edge_cases)
+from egomotion_scene import mono_edge_cases
+out = {}
+for name, (pm, kw) in mono_edge_cases(ob.P_MATCH_DTYPE).items():
+    e = ob.MonoParams.default() if kw is None else ob.MonoParams.default(**kw)
+    n = len(pm)
+    ok, tr, inl = ref.estimate_motion_mono(e, pm)
+    samples = oracle.draw_samples_n(n, 8, e.ransac_iters) if n >= 10 else np.zeros((e.ransac_iters, 8), np.int32)
+    ok2, tr2, inl2 = oracle.estimate_motion_mono(e, pm, samples)
+    assert ok == ok2 and tr.tobytes() == tr2.tobytes() and np.array_equal(inl, inl2), name
+    out[name + "__pm"] = pm.view(np.uint8).reshape(len(pm), 48)
+    out[name + "__ok"] = np.array(int(ok)); out[name + "__tr"] = tr; out[name + "__inliers"] = inl.astype(np.int16)
+    print(name, ok, len(inl), tr)
+path = os.path.join(ROOT, "tests", "golden", "mono_edges.npz")
+np.savez_compressed(path, **out)
+print("wrote", path, os.path.getsize(path), "bytes")

@@ -18,8 +18,9 @@ from oracle import binding as ob  # noqa: E402
 ob.build(ref=True)
 rec = ob.ReferenceRecorder(ob.Reference())
 ob.RecordedReference = lambda path=None: rec  # the `reference` fixture hands the tests the live, recording reference
-rc = pytest.main([os.path.join(ROOT, "tests", f) for f in ("test_egomotion.py", "test_mono.py", "test_oracle.py", "test_outliers.py")]
+rc = pytest.main([os.path.join(ROOT, "tests", f) for f in ("test_egomotion.py", "test_mono.py", "test_oracle.py", "test_outliers.py",
+                                                                "test_egomotion_edges.py", "test_mono_edges.py")]
                  + ["-q", "-m", "not gpu", "-p", "no:cacheprovider"])
 assert rc == 0, "the tests must pass against the live reference before its answers are recorded"
 rec.save(ob.REFERENCE_ANSWERS)
-print(len(rec.answers), "calls recorded,", os.path.getsize(ob.REFERENCE_ANSWERS), "bytes:", ob.REFERENCE_ANSWERS)
+print(len(rec.answers), "calls recorded:", ob.REFERENCE_ANSWERS + "_*.npz")
