@@ -29,7 +29,7 @@
 //    its winner -- and the few queries whose winner lies outside their own window are searched
 //    again exactly, in groups sharing one walk (finish_tile / RedoGroup).  Either way the result
 //    is findMatch's; engine.hip picks the form per launch from the observed share of such queries.
-#include "vh_dev.h"
+#include "vh_findmatch.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -59,9 +59,6 @@ extern "C" int32_t vh_debug_flow_stats(unsigned long long *out, int32_t reset) {
 
 namespace {
 
-// features of a set that are in its bin order (the set's true count, s.count, can be larger: capacity)
-__device__ __forceinline__ int32_t indexed_count(const VhSets &s, int32_t set) { return s.bin_start[(int64_t)set * (s.nbins + 1) + s.nbins]; }
-
 __device__ __forceinline__ int32_t wave_min(int32_t v) {
 #pragma unroll
   for (int32_t d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
@@ -71,17 +68,6 @@ __device__ __forceinline__ int32_t wave_max(int32_t v) {
 #pragma unroll
   for (int32_t d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
   return v;
-}
-
-typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ us2 as_us2(uint32_t x) { return __builtin_bit_cast(us2, x); }
-__device__ __forceinline__ uint32_t as_u32(us2 x) { return __builtin_bit_cast(uint32_t, x); }
-
-__device__ __forceinline__ uint32_t sad4(uint32_t a, uint32_t b, uint32_t acc) {
-  return __builtin_amdgcn_sad_u8(a, b, acc);  // v_sad_u8: 4 byte-wise |a-b| summed into acc
-}
-__device__ __forceinline__ uint32_t sad4hi(uint32_t a, uint32_t b, uint32_t acc) {
-  return __builtin_amdgcn_sad_hi_u8(a, b, acc);  // v_sad_hi_u8: the same sum added at bit 16 of acc
 }
 
 // All-reduce over each 16-lane row of the wave with DPP row rotations (no LDS, no
@@ -118,24 +104,18 @@ __device__ __forceinline__ int32_t ld_uniform_i32(const int32_t *p) { return __b
 
 // The candidate stream of a tile of the flow search: every candidate of class c in
 // the bins [UB0, UB1] x [VB0, VB1] (u-bin major, as Matcher::findMatch visits them,
-// matcher.cpp:243-246), handed to `consume` in chunks of <= 64 consecutive positions,
-// one record per lane (lane j: candidate min(pc+j, p1-1), so the lanes past the end
-// of a column repeat its last candidate).  Software-pipelined: the column table
-// (first/last position of up to 64 columns, one column per lane) costs one round
-// trip per batch of columns, and the records of chunk k+1 are in flight while
-// `consume` works on chunk k.  With 16..32 queries per tile a chunk is only a few
-// hundred cycles of work, less than one L2 round trip; unpipelined, those round
-// trips (two per column for the table, one per chunk for the records) bounded
-// small tiles.
-//   consume(pc, p1, pa0, pa1, pl, gu, g0, g1): chunk [pc, min(pc+64, p1)) of a column
-//   ending at p1; [pa0, pa1) = its positions inside EVERY query's window (TESTED
-//   only; pa0 > pa1 marks a column that is not inside every query's u window);
-//   pl/gu/g0/g1 = this lane's candidate position, u|v<<16 (NEED_UV only) and descriptor.
-template <bool TESTED, bool NEED_UV, class Consume>
-__device__ __forceinline__ void walk_region(const VhSets &s, const int32_t *__restrict__ cbs, const uint32_t *__restrict__ cuv,
-                                            const uint4 *__restrict__ cdesc, int32_t c, int32_t UB0, int32_t UB1, int32_t VB0,
-                                            int32_t VB1, int32_t ULO_MAX, int32_t UHI_MIN, int32_t VA0, int32_t VA1,
-                                            Consume consume) {
+// matcher.cpp:243-246), in chunks of <= 64 consecutive positions of one column.
+// walk_columns is the part the two walkers below share: the column table (first/last
+// position of up to 64 columns, one column per lane, one round trip per batch of
+// columns) and the chunk cursor over it.  How a chunk's records travel is theirs:
+//   first(pc, p1): start the first chunk [pc, min(pc+64, p1)) of a batch on its way
+//   step(pc, p1, pa0, pa1, more, npc, np1): if `more`, start the next chunk [npc, ..)
+//   of a column ending at np1, then wait for and consume chunk [pc, min(pc+64, p1)) of
+//   a column ending at p1; [pa0, pa1) = its positions inside EVERY query's window
+//   (TESTED only; pa0 > pa1 marks a column that is not inside every query's u window).
+template <bool TESTED, class First, class Step>
+__device__ __forceinline__ void walk_columns(const VhSets &s, const int32_t *__restrict__ cbs, int32_t c, int32_t UB0, int32_t UB1, int32_t VB0,
+                                             int32_t VB1, int32_t ULO_MAX, int32_t UHI_MIN, int32_t VA0, int32_t VA1, First first, Step step) {
   const int32_t lane = threadIdx.x & 63;
   // When the v range covers every v-bin (2*radius >= H, as at KITTI size), the columns
   // [UB0, UB1] are one contiguous run of positions: walk it as a single column -- fewer,
@@ -168,26 +148,48 @@ __device__ __forceinline__ void walk_region(const VhSets &s, const int32_t *__re
       return true;
     };
     if (!advance()) continue;
-    int32_t pl = min(pc + lane, p1 - 1);
-    uint32_t gu = 0;
-    if (NEED_UV) gu = cuv[pl];
-    uint4 g0 = cdesc[2 * (int64_t)pl], g1 = cdesc[2 * (int64_t)pl + 1];
+    first(pc, p1);
     for (;;) {
-      const int32_t c_pc = pc, c_p1 = p1, c_ci = ci, c_pl = pl;
-      const uint32_t c_gu = gu;
-      const uint4 c_g0 = g0, c_g1 = g1;
+      const int32_t c_pc = pc, c_p1 = p1, c_ci = ci;
       const bool more = advance();
-      if (more) {  // next chunk's records: in flight while this one is consumed
-        pl = min(pc + lane, p1 - 1);
-        if (NEED_UV) gu = cuv[pl];
-        g0 = cdesc[2 * (int64_t)pl]; g1 = cdesc[2 * (int64_t)pl + 1];
-      }
       int32_t pa0 = 1, pa1 = 0;
       if (TESTED) { pa0 = __builtin_amdgcn_readlane(t_a0, c_ci); pa1 = __builtin_amdgcn_readlane(t_a1, c_ci); }
-      consume(c_pc, c_p1, pa0, pa1, c_pl, c_gu, c_g0, c_g1);
+      step(c_pc, c_p1, pa0, pa1, more, pc, p1);
       if (!more) break;
     }
   }
+}
+
+// The stream through registers, one record per lane (lane j: candidate min(pc+j, p1-1), so the lanes past the end
+// of a column repeat its last candidate).  Software-pipelined: the records of chunk k+1 are in flight while
+// `consume` works on chunk k.  With 16..32 queries per tile a chunk is only a few
+// hundred cycles of work, less than one L2 round trip; unpipelined, those round
+// trips (two per column for the table, one per chunk for the records) bounded
+// small tiles.
+//   consume(pc, p1, pa0, pa1, pl, gu, g0, g1): pl/gu/g0/g1 = this lane's candidate position, u|v<<16 (NEED_UV only)
+//   and descriptor.
+template <bool TESTED, bool NEED_UV, class Consume>
+__device__ __forceinline__ void walk_region(const VhSets &s, const int32_t *__restrict__ cbs, const uint32_t *__restrict__ cuv,
+                                            const uint4 *__restrict__ cdesc, int32_t c, int32_t UB0, int32_t UB1, int32_t VB0,
+                                            int32_t VB1, int32_t ULO_MAX, int32_t UHI_MIN, int32_t VA0, int32_t VA1,
+                                            Consume consume) {
+  const int32_t lane = threadIdx.x & 63;
+  int32_t pl = 0;
+  uint32_t gu = 0;
+  uint4 g0, g1;
+  const auto load = [&](int32_t pc, int32_t p1) __attribute__((always_inline)) {
+    pl = min(pc + lane, p1 - 1);
+    if (NEED_UV) gu = cuv[pl];
+    g0 = cdesc[2 * (int64_t)pl]; g1 = cdesc[2 * (int64_t)pl + 1];
+  };
+  walk_columns<TESTED>(s, cbs, c, UB0, UB1, VB0, VB1, ULO_MAX, UHI_MIN, VA0, VA1, load,
+    [&](int32_t pc, int32_t p1, int32_t pa0, int32_t pa1, bool more, int32_t npc, int32_t np1) __attribute__((always_inline)) {
+      const int32_t c_pl = pl;
+      const uint32_t c_gu = gu;
+      const uint4 c_g0 = g0, c_g1 = g1;
+      if (more) load(npc, np1);  // next chunk's records: in flight while this one is consumed
+      consume(pc, p1, pa0, pa1, c_pl, c_gu, c_g0, c_g1);
+    });
 }
 
 // LDS-DMA (gfx950 global_load_lds_*): a wave-instruction copies 64 x 16 (or 4) bytes from per-lane global
@@ -205,9 +207,9 @@ __device__ __forceinline__ uint32_t lds_addr(const void *p) {
   return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void *)p);
 }
 
-// walk_region for the flow tiles (the stream is consumed from LDS): the same chunk cursor, but the records of a
-// chunk travel global -> LDS by LDS-DMA into one of two wave-private buffers (wD: 2 x {64 first halves | 64 second
-// halves}, wU: 2 x 64 u|v<<16 words, TESTED only), chunk k+1 in flight while `consume` reads chunk k.  No staging
+// The stream for the flow tiles, consumed from LDS: the records of a chunk travel global -> LDS by LDS-DMA into one
+// of two wave-private buffers (wD: 2 x {64 first halves | 64 second halves}, wU: 2 x 64 u|v<<16 words, TESTED only),
+// chunk k+1 in flight while `consume` reads chunk k.  No staging
 // registers, no register copies of a software pipeline, no ds_write: ~10 instead of ~35 VALU instructions per chunk.
 //   consume(pc, p1, pa0, pa1, cD, cU): chunk [pc, min(pc+64, p1)) staged at cD / cU (slot j: candidate min(pc+j, p1-1))
 template <bool TESTED, class Consume>
@@ -215,62 +217,34 @@ __device__ __forceinline__ void walk_region_lds(const VhSets &s, const int32_t *
                                                 const uint4 *__restrict__ cdesc, int32_t c, int32_t UB0, int32_t UB1, int32_t VB0,
                                                 int32_t VB1, int32_t ULO_MAX, int32_t UHI_MIN, int32_t VA0, int32_t VA1,
                                                 uint4 *wD, uint32_t *wU, Consume consume) {
-  const int32_t lane = threadIdx.x & 63;
   const uint32_t ldsD = lds_addr(wD), ldsU = lds_addr(wU);
-  const uint32_t lane32 = (uint32_t)lane * 32u;
-  const bool merged = !TESTED && VB0 == 0 && VB1 == s.vbn - 1;
-  const int32_t UB1w = merged ? UB0 : UB1;
-  for (int32_t cb = UB0; cb <= UB1w; cb += 64) {
-    const int32_t ncb = min(64, UB1w - cb + 1);
-    int32_t t_p0 = 0, t_p1 = 0, t_a0 = 0, t_a1 = 0;
-    if (lane < ncb) {
-      const int32_t row = (c * s.ubn + cb + lane) * s.vbn;
-      t_p0 = ld_off(cbs, (uint32_t)(row + VB0) * 4u);
-      t_p1 = ld_off(cbs, (uint32_t)(merged ? (c * s.ubn + UB1 + 1) * s.vbn : row + VB1 + 1) * 4u);
-      if (TESTED) {
-        const int32_t ubx = cb + lane;
-        const bool in_ = ubx * s.binsize >= ULO_MAX && ubx * s.binsize + s.binsize - 1 <= UHI_MIN;
-        t_a0 = in_ ? ((VA0 <= VA1) ? cbs[row + VA0] : t_p1) : 1;
-        t_a1 = in_ ? ((VA0 <= VA1) ? cbs[row + VA1 + 1] : t_p1) : 0;
-      }
-    }
-    int32_t ci = -1, pc = -64, p1 = 0;
-    const auto advance = [&]() -> bool {
-      pc += 64;
-      while (pc >= p1) {
-        if (++ci >= ncb) return false;
-        pc = __builtin_amdgcn_readlane(t_p0, ci); p1 = __builtin_amdgcn_readlane(t_p1, ci);
-      }
-      return true;
-    };
-    const auto issue = [&](int32_t b) {  // chunk [pc, p1) -> buffer b
-      // 32 * min(pc + lane, p1 - 1) with the scalar terms shifted on the scalar unit: one add and one min per chunk
-      const uint32_t off = min((uint32_t)pc * 32u + lane32, (uint32_t)(p1 - 1) * 32u);
-      glds16(cdesc, off, ldsD + (uint32_t)b * 2048u); glds16(cdesc, off + 16u, ldsD + (uint32_t)b * 2048u + 1024u);
-      if (TESTED) glds4(cuv, off >> 3, ldsU + (uint32_t)b * 256u);
-    };
-    if (!advance()) continue;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the buffers by an earlier walk has returned
-    int32_t buf = 0;
-    issue(0);
-    for (;;) {
-      const int32_t c_pc = pc, c_p1 = p1, c_ci = ci, c_buf = buf;
-      const bool more = advance();
+  const uint32_t lane32 = (uint32_t)(threadIdx.x & 63) * 32u;
+  const auto issue = [&](int32_t b, int32_t pc, int32_t p1) __attribute__((always_inline)) {  // chunk [pc, p1) -> buffer b
+    // 32 * min(pc + lane, p1 - 1) with the scalar terms shifted on the scalar unit: one add and one min per chunk
+    const uint32_t off = min((uint32_t)pc * 32u + lane32, (uint32_t)(p1 - 1) * 32u);
+    glds16(cdesc, off, ldsD + (uint32_t)b * 2048u); glds16(cdesc, off + 16u, ldsD + (uint32_t)b * 2048u + 1024u);
+    if (TESTED) glds4(cuv, off >> 3, ldsU + (uint32_t)b * 256u);
+  };
+  int32_t buf = 0;
+  walk_columns<TESTED>(s, cbs, c, UB0, UB1, VB0, VB1, ULO_MAX, UHI_MIN, VA0, VA1,
+    [&](int32_t pc, int32_t p1) __attribute__((always_inline)) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // every read of the buffers by an earlier walk has returned
+      buf = 0;
+      issue(0, pc, p1);
+    },
+    [&](int32_t pc, int32_t p1, int32_t pa0, int32_t pa1, bool more, int32_t npc, int32_t np1) __attribute__((always_inline)) {
+      const int32_t c_buf = buf;
       if (more) {
         buf ^= 1;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // chunk k-1, the last reader of this buffer, is consumed
-        issue(buf);
+        issue(buf, npc, np1);
         if (TESTED) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // chunk k has landed (k+1 may be in flight)
         else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      int32_t pa0 = 1, pa1 = 0;
-      if (TESTED) { pa0 = __builtin_amdgcn_readlane(t_a0, c_ci); pa1 = __builtin_amdgcn_readlane(t_a1, c_ci); }
-      consume(c_pc, c_p1, pa0, pa1, (const uint4 *)(wD + c_buf * 128), (const uint32_t *)(wU + c_buf * 64));
-      if (!more) break;
-    }
-  }
+      consume(pc, p1, pa0, pa1, (const uint4 *)(wD + c_buf * 128), (const uint32_t *)(wU + c_buf * 64));
+    });
 }
 
 // One candidate (this lane's) against ONE wave-uniform query with the literal accept
@@ -278,12 +252,9 @@ __device__ __forceinline__ void walk_region_lds(const VhSets &s, const int32_t *
 // The slow, exact path behind the speculative searches below (lanes over candidates).
 __device__ __forceinline__ uint64_t tested_key_uniform_query(const uint32_t (&qd)[8], us2 lo2, us2 span2, uint32_t uv2,
                                                              const uint4 &b0, const uint4 &b1, uint32_t relpos) {
-  const us2 t = as_us2(uv2) - lo2;
-  const us2 m = __builtin_elementwise_min(t, span2);
-  uint32_t sad = sad4(qd[0], b0.x, 0);
-  sad = sad4(qd[1], b0.y, sad); sad = sad4(qd[2], b0.z, sad); sad = sad4(qd[3], b0.w, sad);
-  sad = sad4(qd[4], b1.x, sad); sad = sad4(qd[5], b1.y, sad); sad = sad4(qd[6], b1.z, sad); sad = sad4(qd[7], b1.w, sad);
-  return as_u32(t) != as_u32(m) ? ~0ull : (((uint64_t)sad << 32) | relpos);
+  const bool out = outside_window(uv2, lo2, span2);
+  const uint32_t sad = sad32(make_uint4(qd[0], qd[1], qd[2], qd[3]), make_uint4(qd[4], qd[5], qd[6], qd[7]), b0, b1, 0);
+  return out ? ~0ull : (((uint64_t)sad << 32) | relpos);
 }
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t k, int32_t d) {
   const uint32_t lo = (uint32_t)__shfl_xor((int32_t)(uint32_t)k, d), hi = (uint32_t)__shfl_xor((int32_t)(uint32_t)(k >> 32), d);
@@ -309,15 +280,8 @@ template <int KM> struct KeyT { typedef uint32_t type; };
 template <> struct KeyT<KEY_64> { typedef uint64_t type; };
 template <int KM>
 __device__ __forceinline__ typename KeyT<KM>::type sad_key(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1, uint32_t seed) {
-  if (KM == KEY_HI16) {
-    uint32_t key = sad4hi(a0.x, b0.x, seed);
-    key = sad4hi(a0.y, b0.y, key); key = sad4hi(a0.z, b0.z, key); key = sad4hi(a0.w, b0.w, key);
-    key = sad4hi(a1.x, b1.x, key); key = sad4hi(a1.y, b1.y, key); key = sad4hi(a1.z, b1.z, key); key = sad4hi(a1.w, b1.w, key);
-    return (typename KeyT<KM>::type)key;
-  }
-  uint32_t sad = sad4(a0.x, b0.x, 0);
-  sad = sad4(a0.y, b0.y, sad); sad = sad4(a0.z, b0.z, sad); sad = sad4(a0.w, b0.w, sad);
-  sad = sad4(a1.x, b1.x, sad); sad = sad4(a1.y, b1.y, sad); sad = sad4(a1.z, b1.z, sad); sad = sad4(a1.w, b1.w, sad);
+  if (KM == KEY_HI16) return (typename KeyT<KM>::type)sad32<true>(a0, a1, b0, b1, seed);
+  const uint32_t sad = sad32(a0, a1, b0, b1, 0);
   if (KM == KEY_W19) return (typename KeyT<KM>::type)((sad << 19) | seed);
   return (typename KeyT<KM>::type)(((uint64_t)sad << 32) | seed);
 }
@@ -398,7 +362,7 @@ __device__ __forceinline__ bool redo_take(uint64_t &todo, const uint4 (&a0)[Q], 
     g.qd[k][6] = __builtin_amdgcn_readlane(x1.z, fl); g.qd[k][7] = __builtin_amdgcn_readlane(x1.w, fl);
     const uint32_t quv1 = __builtin_amdgcn_readlane(xu, fl);
     const int32_t u1 = (int32_t)(quv1 & 0xFFFF), v1 = (int32_t)(quv1 >> 16);
-    g.lo2[k] = us2{(unsigned short)(u1 - radius), (unsigned short)(v1 - rv)};
+    g.lo2[k] = window_lo2(quv1, radius, rv);
     g.lane[k] = fl; g.n = k + 1;
     g.umin = min(g.umin, u1); g.umax = max(g.umax, u1); g.vmin = min(g.vmin, v1); g.vmax = max(g.vmax, v1);
   }
@@ -435,7 +399,7 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
   const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
   const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
   const int32_t rv = FLOW ? a.radius : a.disp_tol;
-  const us2 span2 = {(unsigned short)(2 * a.radius), (unsigned short)(2 * rv)};
+  const us2 span2 = window_span2(a.radius, rv);
   const int32_t *__restrict__ cidx = s.s_idx + (int64_t)cset * s.cap;
   const int32_t *__restrict__ qidx = s.s_idx + (int64_t)qset * s.cap;
   int32_t *__restrict__ tbl = best + ((int64_t)stream * 4 + a.pass[pass].slot) * s.cap;
@@ -453,12 +417,8 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
     int32_t wp = o.wp;
     VH_CHECK_RANGE(s, 7, wp, 0, pcnt);
     res = pbase + wp;
-    if (SPEC) {  // the winner over the walked region: inside this query's own window?
-      const us2 lo2 = as_us2(uv1) - us2{(unsigned short)a.radius, (unsigned short)rv};
-      const us2 t = as_us2(ld_off(cuv, (uint32_t)res * 4u)) - lo2;
-      const us2 m = __builtin_elementwise_min(t, span2);
-      fail = as_u32(t) != as_u32(m);
-    }
+    // the winner over the walked region: inside this query's own window?
+    if (SPEC) fail = outside_window(ld_off(cuv, (uint32_t)res * 4u), window_lo2(uv1, a.radius, rv), span2);
   }
   if (SPEC) {
     uint64_t todo = __ballot(fail);
@@ -472,13 +432,9 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
 #pragma unroll
         for (int32_t k = 0; k < VH_REDO_G; k++) kk[k] = ~0ull;
         if (FLOW) {
-          const auto bin_of = [&](int32_t x, int32_t nb) -> int32_t {
-            const uint32_t xx = (uint32_t)max(x, 0);
-            return min((int32_t)(s.binsize == 1 ? xx : __umulhi(xx, s.inv_binsize)), nb - 1);
-          };
-          // the union of the group's own bin ranges (matcher.cpp:237-240)
-          walk_region<false, true>(s, cbs, cuv, cdesc, c, bin_of(g.umin - a.radius, s.ubn), bin_of(g.umax + a.radius, s.ubn),
-                                   bin_of(g.vmin - rv, s.vbn), bin_of(g.vmax + rv, s.vbn), 0, 0, 0, 0,
+          // the union of the group's own bin ranges
+          const VhBins b = bins_of_interest(s, VhWindow{g.umin - a.radius, g.umax + a.radius, g.vmin - rv, g.vmax + rv});
+          walk_region<false, true>(s, cbs, cuv, cdesc, c, b.ub0, b.ub1, b.vb0, b.vb1, 0, 0, 0, 0,
             [&](int32_t, int32_t, int32_t, int32_t, int32_t pl, uint32_t gu, const uint4 &g0, const uint4 &g1) {
 #pragma unroll
               for (int32_t k = 0; k < VH_REDO_G; k++)
@@ -545,7 +501,7 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
 // out-of-window candidate resembled the query more than every in-window one:
 // 0.5 % of the queries on the benchmark frames, ~10 % with two grey levels of
 // sensor noise added, where most features have no true partner) the query is
-// searched again by the whole wave with the literal test (flow_query_by_wave).
+// searched again with the literal test, in groups sharing one walk (finish_tile: RedoGroup / redo_take).
 // Results are identical either way; only the time depends on the data.
 // !SPEC keeps the tested loop: three accept-test classes per bin as in round 1.
 //
@@ -570,9 +526,9 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
   const int32_t rv = a.pass[pass].flow ? a.radius : a.disp_tol;
 
-  bool valid[Q];
-  uint4 a0[Q], a1[Q];
-  uint32_t uv1[Q];
+  bool (&valid)[Q] = out.valid;  // the lane's queries live in the tile's result
+  uint4 (&a0)[Q] = out.a0, (&a1)[Q] = out.a1;
+  uint32_t (&uv1)[Q] = out.uv1;
   int32_t v_lo[Q];
   us2 lo2[Q];
   typedef typename KeyT<KM>::type key_t;
@@ -581,7 +537,7 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   int32_t umin = 0x7FFFFFFF, umax = -1, vmin = 0x7FFFFFFF, vmax = -1;
   // [q0, q1) are SNAKE indices (kernels_bin.hip: make_tiles): inside the column [A, B) of the query set's bin order
   // the index k is the position k (even column) or A + B - 1 - k (odd column).  Column starts from col0 on, one per lane.
-  int32_t qp[Q];
+  int32_t (&qp)[Q] = out.qpos;
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
     const int32_t q = q0 + L * qi + l;
@@ -613,13 +569,9 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     uv1[qi] = ld_off(quv, (uint32_t)ql * 4u);
     a0[qi] = ld_off(qdesc, (uint32_t)ql * 32u); a1[qi] = ld_off(qdesc, (uint32_t)ql * 32u + 16u);
     const int32_t u1 = uv1[qi] & 0xFFFF, v1 = uv1[qi] >> 16;
-    // search window (matcher.cpp:231-234; stereo: v narrowed to +-disp_tolerance).
-    // Accept test of matcher.cpp:249 in packed 16-bit arithmetic: with
-    // t = (u2,v2) - (u_lo,v_lo) (mod 2^16 per half), the candidate is inside the
-    // window iff t.u <= 2*radius and t.v <= 2*rv, i.e. iff min(t, span) == t.
-    // Exact because coordinates are < 2^14 and radii <= 2^14 (|u2-u1|+r < 2^15).
+    // search window (matcher.cpp:231-234; stereo: v narrowed to +-disp_tolerance), packed as vh_findmatch.h says
     v_lo[qi] = v1 - rv;
-    lo2[qi] = us2{(unsigned short)(u1 - a.radius), (unsigned short)v_lo[qi]};
+    lo2[qi] = window_lo2(uv1[qi], a.radius, rv);
     best_key[qi] = KNONE;
     // (lanes past q1 repeat query q0: it is valid, so the extrema are unchanged)
     umin = min(umin, u1); umax = max(umax, u1); vmin = min(vmin, v1); vmax = max(vmax, v1);
@@ -629,16 +581,11 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   umax = __builtin_amdgcn_readfirstlane(row16_allreduce<true>(umax));
   vmin = __builtin_amdgcn_readfirstlane(row16_allreduce<false>(vmin));
   vmax = __builtin_amdgcn_readfirstlane(row16_allreduce<true>(vmax));
-  // bins of interest of the union window (matcher.cpp:237-240; for x<0 the clamp to 0
-  // makes the truncating division equivalent to the reference's floor); the bin of a
-  // coordinate is monotone, so the union's bins follow from the extreme queries
-  const auto bin_of = [&](int32_t x, int32_t nb) -> int32_t {
-    const uint32_t xx = (uint32_t)max(x, 0);
-    return min((int32_t)(s.binsize == 1 ? xx : __umulhi(xx, s.inv_binsize)), nb - 1);
-  };
-  const int32_t UB0 = bin_of(umin - a.radius, s.ubn), UB1 = bin_of(umax + a.radius, s.ubn);
-  const int32_t VB0 = bin_of(vmin - rv, s.vbn), VB1 = bin_of(vmax + rv, s.vbn);
-  const us2 span2 = {(unsigned short)(2 * a.radius), (unsigned short)(2 * rv)};
+  // bins of interest of the union window: the bin of a coordinate is monotone, so the union's bins follow from the
+  // extreme queries
+  const VhBins ub = bins_of_interest(s, VhWindow{umin - a.radius, umax + a.radius, vmin - rv, vmax + rv});
+  const int32_t UB0 = ub.ub0, UB1 = ub.ub1, VB0 = ub.vb0, VB1 = ub.vb1;
+  const us2 span2 = window_span2(a.radius, rv);
   // (tested loop) columns whose pixel range [ub*bs, ub*bs+bs-1] is inside EVERY query's u
   // window, and v-bins [VA0, VA1] whose pixel rows lie inside EVERY query's v window: in
   // an interior column their candidates need no accept test at all
@@ -653,9 +600,7 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     constexpr int TEST = decltype(test)::value;
     bool out = false;
     if (TEST == 2) {
-      const us2 t = as_us2(uv2) - lo2[qi];
-      const us2 m = __builtin_elementwise_min(t, span2);
-      out = as_u32(t) != as_u32(m);
+      out = outside_window(uv2, lo2[qi], span2);
     } else if (TEST == 1) {
       out = (uint32_t)((int32_t)(uv2 >> 16) - v_lo[qi]) > (uint32_t)(2 * rv);
     }
@@ -712,11 +657,23 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     });
   // join the phases: lanes l, l+L, l+2L, .. hold partial minima of the same query
   out.wp = join_phases<Q, P, KM>(best_key);
-#pragma unroll
-  for (int32_t qi = 0; qi < Q; qi++) {
-    out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
-    out.qpos[qi] = qp[qi];
-  }
+}
+
+// What surrounds a tile of either kind of pass: the class's span of candidate positions, the key encoding it needs
+// (resolved once: tile(key mode constant, pbase, pcnt, out) is flow_tile or rows_tile), and the end of the tile.
+template <bool SPEC, bool FLOW, class Tile>
+__device__ __forceinline__ void search_tile(const VhSets &s, const VhMatchArgs &a, int32_t pass, int32_t stream, int32_t qset, int32_t cset,
+                                            int32_t c, int32_t *__restrict__ best, int32_t *__restrict__ redo_count, Tile tile) {
+  // candidates of class c occupy the contiguous positions [pbase, pend) of the bin order
+  const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
+  const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
+  const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
+  const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
+  TileOut<VH_FLOW_Q> out;
+  if (km == KEY_HI16) tile(std::integral_constant<int, KEY_HI16>{}, pbase, pend - pbase, out);
+  else if (km == KEY_W19) tile(std::integral_constant<int, KEY_W19>{}, pbase, pend - pbase, out);
+  else tile(std::integral_constant<int, KEY_64>{}, pbase, pend - pbase, out);
+  finish_tile<VH_FLOW_Q, VH_FLOW_P, SPEC, FLOW>(s, a, pass, stream, qset, cset, c, pbase, pend - pbase, out, best, redo_count);
 }
 
 template <bool SPEC>
@@ -729,16 +686,10 @@ __device__ __forceinline__ void flow_pass(const VhSets &s, const VhMatchArgs &a,
     const i32x4 t = ld_uniform((const i32x4 *)(s.tiles + (int64_t)qset * s.max_tiles + tile));
     const int32_t q0 = __builtin_amdgcn_readfirstlane(t.x), q1 = __builtin_amdgcn_readfirstlane(t.y);
     const int32_t c = __builtin_amdgcn_readfirstlane(t.z), col0 = __builtin_amdgcn_readfirstlane(t.w);
-    // candidates of class c occupy the contiguous positions [pbase, pend) of the bin order
-    const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-    const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
-    const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
-    const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
-    TileOut<VH_FLOW_Q> out;
-    if (km == KEY_HI16) flow_tile<VH_FLOW_Q, VH_FLOW_P, KEY_HI16, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pend - pbase, wD, wU, out);
-    else if (km == KEY_W19) flow_tile<VH_FLOW_Q, VH_FLOW_P, KEY_W19, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pend - pbase, wD, wU, out);
-    else flow_tile<VH_FLOW_Q, VH_FLOW_P, KEY_64, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pend - pbase, wD, wU, out);
-    finish_tile<VH_FLOW_Q, VH_FLOW_P, SPEC, true>(s, a, pass, stream, qset, cset, c, pbase, pend - pbase, out, best, redo_count);
+    search_tile<SPEC, true>(s, a, pass, stream, qset, cset, c, best, redo_count,
+      [&](auto km, int32_t pbase, int32_t pcnt, TileOut<VH_FLOW_Q> &out) __attribute__((always_inline)) {
+        flow_tile<VH_FLOW_Q, VH_FLOW_P, decltype(km)::value, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pcnt, wD, wU, out);
+      });
   }
 }
 
@@ -753,8 +704,8 @@ __device__ __forceinline__ void flow_pass(const VhSets &s, const VhMatchArgs &a,
 // as in the flow search (flow_tile), Q queries per lane.  The search is
 // speculative in the same way: no accept test in the loop (the stream holds every
 // u of those rows, the window only +-match_radius of them), the winner is tested
-// once, and a query whose winner lies outside its window is searched again by the
-// whole wave over its own bins (flow_query_by_wave).  The key carries the
+// once, and a query whose winner lies outside its window is searched again over
+// its group's own rows (finish_tile: RedoGroup / redo_take).  The key carries the
 // candidate's BIN-order position (staged next to its descriptor), so the minimum
 // is findMatch's first minimum in (u_bin, v_bin, list) order no matter in which
 // order the rows are walked.  Round 1 used 64-query tiles with the test in the
@@ -777,14 +728,14 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
   const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
   const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
 
-  bool valid[Q];
-  uint4 a0[Q], a1[Q];
-  uint32_t uv1[Q];
-  int32_t qp[Q];
+  bool (&valid)[Q] = out.valid;  // the lane's queries live in the tile's result
+  uint4 (&a0)[Q] = out.a0, (&a1)[Q] = out.a1;
+  uint32_t (&uv1)[Q] = out.uv1;
+  int32_t (&qp)[Q] = out.qpos;
   typedef typename KeyT<KM>::type key_t;
   key_t best_key[Q];
   us2 lo2[Q];
-  const us2 span2 = {(unsigned short)(2 * a.radius), (unsigned short)(2 * a.disp_tol)};
+  const us2 span2 = window_span2(a.radius, a.disp_tol);
   int32_t vmin = 0x7FFFFFFF, vmax = -1;
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
@@ -794,8 +745,8 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
     VH_CHECK_RANGE(s, 1, qp[qi], 0, s.cap);
     uv1[qi] = ld_off(quv, (uint32_t)qp[qi] * 4u);
     a0[qi] = ld_off(qdesc, (uint32_t)qp[qi] * 32u); a1[qi] = ld_off(qdesc, (uint32_t)qp[qi] * 32u + 16u);
-    const int32_t u1 = uv1[qi] & 0xFFFF, v1 = uv1[qi] >> 16;
-    lo2[qi] = us2{(unsigned short)(u1 - a.radius), (unsigned short)(v1 - a.disp_tol)};  // accept test as in flow_tile
+    const int32_t v1 = uv1[qi] >> 16;
+    lo2[qi] = window_lo2(uv1[qi], a.radius, a.disp_tol);
     best_key[qi] = (key_t)~(key_t)0;
     vmin = min(vmin, v1); vmax = max(vmax, v1);
   }
@@ -830,10 +781,9 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
 #pragma unroll
       for (int32_t qi = 0; qi < Q; qi++) {
         key_t kA = sad_key<KM>(a0[qi], a1[qi], dA0, dA1, sA), kB = sad_key<KM>(a0[qi], a1[qi], dB0, dB1, sB);
-        if (!SPEC) {  // the literal accept test (matcher.cpp:249) per pair
-          const us2 tA = as_us2(uA) - lo2[qi], tB = as_us2(uB) - lo2[qi];
-          kA = as_u32(tA) != as_u32(__builtin_elementwise_min(tA, span2)) ? (key_t)~(key_t)0 : kA;
-          kB = as_u32(tB) != as_u32(__builtin_elementwise_min(tB, span2)) ? (key_t)~(key_t)0 : kB;
+        if (!SPEC) {  // the accept test (matcher.cpp:249) per pair
+          kA = outside_window(uA, lo2[qi], span2) ? (key_t)~(key_t)0 : kA;
+          kB = outside_window(uB, lo2[qi], span2) ? (key_t)~(key_t)0 : kB;
         }
         best_key[qi] = min(min(kA, kB), best_key[qi]);
       }
@@ -842,11 +792,6 @@ __device__ __forceinline__ void rows_tile(const VhSets &s, const VhMatchArgs &a,
   }
   // join the phases
   out.wp = join_phases<Q, P, KM>(best_key);
-#pragma unroll
-  for (int32_t qi = 0; qi < Q; qi++) {
-    out.a0[qi] = a0[qi]; out.a1[qi] = a1[qi]; out.uv1[qi] = uv1[qi]; out.valid[qi] = valid[qi];
-    out.qpos[qi] = qp[qi];
-  }
 }
 
 template <bool SPEC>
@@ -868,15 +813,10 @@ __device__ __forceinline__ void rows_pass(const VhSets &s, const VhMatchArgs &a,
       if (c < 0) t -= nt;
     }
     if (c < 0) break;  // past the last tile (uniform)
-    const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-    const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
-    const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
-    const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
-    TileOut<VH_FLOW_Q> out;
-    if (km == KEY_HI16) rows_tile<VH_FLOW_Q, VH_FLOW_P, KEY_HI16, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pend - pbase, wD, wU, wV, out);
-    else if (km == KEY_W19) rows_tile<VH_FLOW_Q, VH_FLOW_P, KEY_W19, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pend - pbase, wD, wU, wV, out);
-    else rows_tile<VH_FLOW_Q, VH_FLOW_P, KEY_64, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pend - pbase, wD, wU, wV, out);
-    finish_tile<VH_FLOW_Q, VH_FLOW_P, SPEC, false>(s, a, pass, stream, qset, cset, c, pbase, pend - pbase, out, best, redo_count);
+    search_tile<SPEC, false>(s, a, pass, stream, qset, cset, c, best, redo_count,
+      [&](auto km, int32_t pbase, int32_t pcnt, TileOut<VH_FLOW_Q> &out) __attribute__((always_inline)) {
+        rows_tile<VH_FLOW_Q, VH_FLOW_P, decltype(km)::value, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pcnt, wD, wU, wV, out);
+      });
   }
 }
 
@@ -910,252 +850,8 @@ match_kernel(VhSets s, VhMatchArgs a, int32_t *__restrict__ best, int32_t *__res
   else rows_pass<SPEC>(s, a, pass, stream, qset, cset, wD, wU, wV, best, redo_count);
 }
 
-// ------------------------------------------------------------ match (prior term)
-// findMatch with the u_,v_ distance term (matcher.cpp:257-262).  The cost is no
-// longer an integer, so the key trick does not apply: one lane per query walks
-// its own bin range in the reference's order (u_bin, v_bin, list position) and
-// keeps the first strict minimum, all in double exactly as the reference
-// (sqrt is the correctly rounded IEEE one; du*du+dv*dv is exact in double).
-__global__ void match_prior_kernel(VhSets s, VhMatchArgs a, double u_, double v_, int32_t *__restrict__ best) {
-  const int32_t qset = vh_row_set(a, 0, a.pass[0].qset);
-  const int32_t cset = vh_row_set(a, 0, a.pass[0].cset);
-  const int32_t nq = indexed_count(s, qset);
-  const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nq) return;
-  const int32_t *q = s.feat + ((int64_t)qset * s.cap + i) * 12;
-  const int32_t u1 = q[0], v1 = q[1], c = q[3];
-  const uint4 a0 = *(const uint4 *)(q + 4), a1 = *(const uint4 *)(q + 8);
-  const int32_t rv = a.pass[0].flow ? a.radius : a.disp_tol;
-  const int32_t u_lo = u1 - a.radius, u_hi = u1 + a.radius, v_lo = v1 - rv, v_hi = v1 + rv;
-  const int32_t ub0 = min(max(u_lo, 0) / s.binsize, s.ubn - 1), ub1 = min(max(u_hi, 0) / s.binsize, s.ubn - 1);
-  const int32_t vb0 = min(max(v_lo, 0) / s.binsize, s.vbn - 1), vb1 = min(max(v_hi, 0) / s.binsize, s.vbn - 1);
-  const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-  const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
-  const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
-  double min_cost = 10000000;  // matcher.cpp:222
-  int32_t min_pos = -1;
-  for (int32_t ub = ub0; ub <= ub1; ub++) {
-    const int32_t row = (c * s.ubn + ub) * s.vbn;
-    for (int32_t p = cbs[row + vb0]; p < cbs[row + vb1 + 1]; p++) {
-      const uint32_t uv2 = cuv[p];
-      const int32_t u2 = uv2 & 0xFFFF, v2 = uv2 >> 16;
-      if (u2 < u_lo || u2 > u_hi || v2 < v_lo || v2 > v_hi) continue;
-      const uint4 b0 = cdesc[2 * (int64_t)p], b1 = cdesc[2 * (int64_t)p + 1];
-      uint32_t sad = sad4(a0.x, b0.x, 0);
-      sad = sad4(a0.y, b0.y, sad); sad = sad4(a0.z, b0.z, sad); sad = sad4(a0.w, b0.w, sad);
-      sad = sad4(a1.x, b1.x, sad); sad = sad4(a1.y, b1.y, sad); sad = sad4(a1.z, b1.z, sad); sad = sad4(a1.w, b1.w, sad);
-      double cost = (double)sad;
-      if (u_ >= 0 && v_ >= 0) {
-        const double du = (double)u2 - u_, dv = (double)v2 - v_;
-        cost += 4 * sqrt(du * du + dv * dv);
-      }
-      if (cost < min_cost) { min_cost = cost; min_pos = p; }
-    }
-  }
-  best[i] = min_pos >= 0 ? s.s_idx[(int64_t)cset * s.cap + min_pos] : 0;
-}
-
-// Survivors per emission chunk: one atomic per wave (the 64 lanes of a wave hold
-// consecutive features of one 256-feature chunk), not one per lane -- 64
-// same-address atomics per wave made the chain kernel 8x slower.
-__device__ __forceinline__ void count_chunk(bool keep, int32_t *counter) {
-  const uint64_t bal = __ballot(keep);
-  if (bal && (threadIdx.x & 63) == (uint32_t)__builtin_ctzll(bal)) atomicAdd(counter, (int32_t)__popcll(bal));
-}
-
-// ---------------------------------------------------------------------- chain
-// Follows the circle of each driving feature through the per-pass tables and
-// records the index tuple (i1p,i2p,i1c,i2c), or z=-2 when the circle does not
-// close / the disparity test fails.
-//   flow   (matcher.cpp:308-336): 1c ->1p ->1c
-//   stereo (stock libviso2): 1c ->2c ->1c, u1c >= u2c
-//   quad   (stock libviso2): 1p ->2p ->2c ->1c ->1p,
-//                                             u1p >= u2p and u1c >= u2c
-// For flow the reference additionally keeps only the FIRST match per pixel of
-// the current image (mask M, matcher.cpp:331-334): every closing feature bids
-// for its pixel with atomicMax(epoch << 24 | (2^24 - 1 - i1c)); the lowest i1c of
-// this epoch wins, and no clearing between frames is needed.
-__global__ void chain_kernel(VhSets s, VhMatchArgs a, int32_t method, const int32_t *__restrict__ best,
-                             int4 *__restrict__ chain, uint32_t *__restrict__ mask, uint32_t epoch,
-                             int32_t *__restrict__ mchunk, int32_t nchm) {
-  const int32_t stream = blockIdx.y;
-  const int32_t set1p = vh_row_set(a, stream, 0), set2p = vh_row_set(a, stream, 1);
-  const int32_t set1c = vh_row_set(a, stream, 2), set2c = vh_row_set(a, stream, 3);
-  const int32_t n1p = indexed_count(s, set1p), n2p = indexed_count(s, set2p);
-  const int32_t n1c = indexed_count(s, set1c), n2c = indexed_count(s, set2c);
-  const int32_t *__restrict__ T = best + (int64_t)stream * 4 * s.cap;
-  const int64_t cap = s.cap;
-  // coordinates in reference order, 4 B per feature (the 48-byte records would cost a 64-byte sector per look-up)
-  const uint32_t *__restrict__ uv1p = s.f_uv + (int64_t)set1p * cap, *__restrict__ uv2p = s.f_uv + (int64_t)set2p * cap;
-  const uint32_t *__restrict__ uv1c = s.f_uv + (int64_t)set1c * cap, *__restrict__ uv2c = s.f_uv + (int64_t)set2c * cap;
-  int4 *__restrict__ out = chain + 2 * (int64_t)stream * s.cap;
-  const int32_t ndrive = (method == 2) ? n1p : n1c;
-  for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ndrive; i += gridDim.x * blockDim.x) {
-    int4 r = make_int4(-1, -1, -2, -1), c = make_int4(0, 0, 0, 0);
-    if (method == 0) {
-      if (n1p > 0) {
-        const int32_t i1p = T[0 * cap + i];
-        const int32_t i1c2 = T[1 * cap + i1p];
-        if (i1c2 == i) {
-          r = make_int4(i1p, -1, i, -1);
-          c.x = (int32_t)uv1p[i1p]; c.z = (int32_t)uv1c[i];
-          atomicMax(&mask[(int64_t)stream * s.W * s.H + (int64_t)((uint32_t)c.z >> 16) * s.W + ((uint32_t)c.z & 0xFFFFu)],
-                    (epoch << VH_MASK_IDX_BITS) | (((1u << VH_MASK_IDX_BITS) - 1u) - (uint32_t)i));
-        }
-      }
-    } else if (method == 1) {
-      if (n2c > 0) {
-        const int32_t i2c = T[0 * cap + i];
-        const int32_t i1c2 = T[1 * cap + i2c];
-        c.z = (int32_t)uv1c[i]; c.w = (int32_t)uv2c[i2c];
-        if (i1c2 == i && ((uint32_t)c.z & 0xFFFFu) >= ((uint32_t)c.w & 0xFFFFu)) r = make_int4(-1, -1, i, i2c);
-      }
-    } else {
-      if (n2p > 0 && n1c > 0 && n2c > 0) {
-        const int32_t i2p = T[0 * cap + i];
-        const int32_t i2c = T[1 * cap + (a.prior ? i : i2p)];
-        const int32_t i1c = T[2 * cap + i2c];
-        const int32_t i1p2 = T[3 * cap + i1c];
-        c = make_int4((int32_t)uv1p[i], (int32_t)uv2p[i2p], (int32_t)uv1c[i1c], (int32_t)uv2c[i2c]);
-        const uint32_t u1p = (uint32_t)c.x & 0xFFFFu, u2p = (uint32_t)c.y & 0xFFFFu, u1c = (uint32_t)c.z & 0xFFFFu, u2c = (uint32_t)c.w & 0xFFFFu;
-        if (i1p2 == i && u1p >= u2p && u1c >= u2c) r = make_int4(i, i2p, i1c, i2c);
-      }
-    }
-    out[2 * (int64_t)i] = r; out[2 * (int64_t)i + 1] = c;
-    if (method != 0) count_chunk(r.z >= 0, mchunk + stream * nchm + (i >> 8));
-  }
-}
-
-// ------------------------------------------------------------------ flow_keep
-// Flow only: after every closing feature has bid for its pixel, keep the winner
-// (the reference's first writer, matcher.cpp:331-334), drop the others, and
-// count the survivors per emission chunk.
-__global__ void flow_keep_kernel(VhSets s, VhMatchArgs a, int4 *__restrict__ chain,
-                                 const uint32_t *__restrict__ mask, uint32_t epoch,
-                                 int32_t *__restrict__ mchunk, int32_t nchm) {
-  const int32_t stream = blockIdx.y;
-  const int32_t set1c = vh_row_set(a, stream, 2);
-  const int32_t n1c = indexed_count(s, set1c);
-  int4 *__restrict__ ch = chain + 2 * (int64_t)stream * s.cap;
-  for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n1c; i += gridDim.x * blockDim.x) {
-    const int4 r = ch[2 * (int64_t)i];
-    const uint32_t uv = (uint32_t)ch[2 * (int64_t)i + 1].z;
-    const bool win = r.z >= 0 && mask[(int64_t)stream * s.W * s.H + (int64_t)(uv >> 16) * s.W + (uv & 0xFFFFu)] ==
-                                     ((epoch << VH_MASK_IDX_BITS) | (((1u << VH_MASK_IDX_BITS) - 1u) - (uint32_t)i));
-    if (r.z >= 0 && !win) ch[2 * (int64_t)i].z = -2;
-    count_chunk(win, mchunk + stream * nchm + (i >> 8));
-  }
-}
-
-// --------------------------------------------------------------- emit_matches
-// One 256-thread workgroup per 256 driving features: ordered compaction of the closed
-// circles into p_match records (48 B, src/matcher.h:89-104), in ascending order
-// of the driving feature index as the reference's loops emit them.  The offset of
-// a chunk is the sum of the survivor counts of the chunks before it.
-// REFINED (refinement > 0): the coordinates of a kept entry come from ref (kernels_refine.hip) instead of the chain.
-template <bool REFINED>
-__global__ void __launch_bounds__(256)
-emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restrict__ chain,
-                    float *__restrict__ matches, int32_t mcap, int32_t *__restrict__ match_count,
-                    int32_t *__restrict__ overflow, const int32_t *__restrict__ mchunk, int32_t nchm,
-                    int32_t *__restrict__ redo, int32_t *__restrict__ mchunk_next, int4 *__restrict__ host_out,
-                    float *__restrict__ host_matches, const float4 *__restrict__ ref) {
-  __shared__ int32_t sWave[4];
-  __shared__ int32_t sBase;
-  const int32_t chunk = blockIdx.x, stream = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // the chunk counters of the NEXT launch (the other buffer; its last reader, the emission before this one, is done)
-  // are zeroed here instead of by a memset of their own: two fill kernels and a launch gap per step
-  if (tid == 0) mchunk_next[stream * nchm + chunk] = 0;
-  int32_t sets[4];
-#pragma unroll
-  for (int32_t r = 0; r < 4; r++) sets[r] = vh_row_set(a, stream, r);
-  const int32_t drive = (method == 2) ? sets[0] : sets[2];
-  const int32_t n = indexed_count(s, drive);
-  if (chunk * 256 >= n && chunk != nchm - 1) return;
-  const int4 *__restrict__ ch = chain + 2 * (int64_t)stream * s.cap;
-  float *__restrict__ out = matches + (int64_t)stream * mcap * 12;
-  // matches emitted by earlier chunks
-  int32_t part = 0;
-  for (int32_t k = tid; k < chunk; k += 256) part += mchunk[stream * nchm + k];
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-  if (lane == 0) sWave[w] = part;
-  __syncthreads();
-  if (tid == 0) { int32_t t = 0; for (int32_t k = 0; k < 4; k++) t += sWave[k]; sBase = t; }
-  __syncthreads();
-  const int32_t base = sBase;
-  __syncthreads();
-
-  const int32_t i = chunk * 256 + tid;
-  int4 r = make_int4(-1, -1, -2, -1), c = make_int4(0, 0, 0, 0);
-  if (i < n) { r = ch[2 * (int64_t)i]; c = ch[2 * (int64_t)i + 1]; }
-  const bool keep = r.z >= 0;
-  uint32_t rec[12];
-#pragma unroll
-  for (int32_t k = 0; k < 12; k++) rec[k] = (k % 3 == 2) ? 0xFFFFFFFFu : __float_as_uint(-1.0f);
-  if (keep) {
-    const int32_t idx[4] = {r.x, r.y, r.z, r.w};
-    const uint32_t uv[4] = {(uint32_t)c.x, (uint32_t)c.y, (uint32_t)c.z, (uint32_t)c.w};
-    float q[8];
-    if (REFINED) {
-      const float4 q0 = ref[2 * ((int64_t)stream * s.cap + i)], q1 = ref[2 * ((int64_t)stream * s.cap + i) + 1];
-      q[0] = q0.x; q[1] = q0.y; q[2] = q0.z; q[3] = q0.w; q[4] = q1.x; q[5] = q1.y; q[6] = q1.z; q[7] = q1.w;
-    }
-#pragma unroll
-    for (int32_t k = 0; k < 4; k++) {
-      if (idx[k] >= 0) {
-        rec[3 * k + 0] = __float_as_uint(REFINED ? q[2 * k] : (float)(uv[k] & 0xFFFFu));
-        rec[3 * k + 1] = __float_as_uint(REFINED ? q[2 * k + 1] : (float)(uv[k] >> 16));
-      }
-      rec[3 * k + 2] = (uint32_t)idx[k];
-    }
-  }
-  const uint64_t bal = __ballot(keep);
-  const int32_t before = __popcll(bal & ((1ull << lane) - 1));
-  if (lane == 0) sWave[w] = __popcll(bal);
-  __syncthreads();
-  int32_t woff = 0, tot = 0;
-#pragma unroll
-  for (int32_t k = 0; k < 4; k++) { const int32_t c = sWave[k]; if (k < w) woff += c; tot += c; }
-  const int32_t pos = base + woff + before;
-  if (keep && pos < mcap) {
-    uint4 *o = (uint4 *)(out + (int64_t)pos * 12);
-    o[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);
-    o[1] = make_uint4(rec[4], rec[5], rec[6], rec[7]);
-    o[2] = make_uint4(rec[8], rec[9], rec[10], rec[11]);
-    if (host_matches) {  // small groups: the records also go straight to host-mapped memory (no download before getMatches)
-      uint4 *h = (uint4 *)(host_matches + ((int64_t)stream * mcap + pos) * 12);
-      h[0] = o[0]; h[1] = o[1]; h[2] = o[2];
-    }
-  }
-  if (chunk == nchm - 1 && tid == 0) {
-    match_count[stream] = base + tot;
-    // a set this method read held more features than the capacity: the matching ran on
-    // its first `cap` records only, which the host reports as VH_ERR_CAPACITY
-    int32_t ov = 0;
-#pragma unroll
-    for (int32_t r = 0; r < 4; r++) {
-      const bool used = method == 2 || r == 2 || (method == 0 && r == 0) || (method == 1 && r == 3);
-      if (used && s.count[sets[r]] > s.cap) ov = 1;
-    }
-    overflow[stream] = ov;
-    // statistics of this launch for the host's loop policy: queries searched again / queries searched
-    int32_t nq = 0;
-#pragma unroll
-    for (int32_t k = 0; k < 4; k++) if (k < a.npass) nq += indexed_count(s, vh_row_set(a, stream, a.pass[k].qset));
-    // count, overflow flag and the launch's statistics also go straight to host-mapped memory: the host reads
-    // them after the launch's event instead of through small device->host copies (each a blit kernel + a round trip)
-    host_out[stream] = make_int4(base + tot, ov, redo[stream], nq);
-    redo[stream] = 0;
-  }
-}
-
 }  // namespace
 
-void vh_launch_match_prior(const VhSets &s, const VhMatchArgs &a, double u_, double v_, int32_t *best,
-                           hipStream_t st) {
-  hipLaunchKernelGGL(match_prior_kernel, dim3((s.cap + 127) / 128), dim3(128), 0, st, s, a, u_, v_, best);
-}
 void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32_t *redo, int32_t speculative, int32_t grid_x,
                      int32_t lds_bytes, hipStream_t st) {
   if (!a.npass) return;
@@ -1190,31 +886,4 @@ void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32
   const int32_t pad = pad_env >= 0 ? pad_env : (wgs > 0 || grid_x <= 0 || lds_bytes <= 0 || have == 0 || (size_t)lds_bytes <= have ? 0 : (int32_t)((size_t)lds_bytes - have));
   if (speculative) hipLaunchKernelGGL(match_kernel<true>, grid, dim3(256), pad, st, s, m, best, redo);
   else hipLaunchKernelGGL(match_kernel<false>, grid, dim3(256), pad, st, s, m, best, redo);
-}
-void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *best,
-                     int4 *chain, uint32_t *mask, uint32_t epoch, int32_t *mchunk, hipStream_t st) {
-  const int32_t nchm = (s.cap + 255) / 256;
-  dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.rows);
-  hipLaunchKernelGGL(chain_kernel, grid, dim3(256), 0, st, s, a, method, best, chain, mask, epoch, mchunk, nchm);
-  if (method == 0) vh_launch_flow_keep(s, a, chain, mask, epoch, mchunk, st);
-}
-void vh_launch_flow_keep(const VhSets &s, const VhMatchArgs &a, int4 *chain, const uint32_t *mask, uint32_t epoch, int32_t *mchunk,
-                         hipStream_t st) {
-  const int32_t nchm = (s.cap + 255) / 256;
-  dim3 grid(std::min(std::max(s.cap / 1024, 8), 256), a.rows);
-  hipLaunchKernelGGL(flow_keep_kernel, grid, dim3(256), 0, st, s, a, chain, mask, epoch, mchunk, nchm);
-}
-void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
-                            void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,
-                            const int32_t *mchunk, int32_t *redo, int32_t *mchunk_next, void *host_out, void *host_matches,
-                            const float4 *ref, hipStream_t st) {
-  const int32_t nchm = (s.cap + 255) / 256;
-  // every row of the handle, a.rows or not: the rows a sequence chunk leaves empty read the empty set here and report 0
-  // matches (their chain tables were not written, their chunk counters are zero), and their counters are reset
-  if (ref)
-    hipLaunchKernelGGL(emit_matches_kernel<true>, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
-                       (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches, ref);
-  else
-    hipLaunchKernelGGL(emit_matches_kernel<false>, dim3(nchm, a.S), dim3(256), 0, st, s, a, method, chain,
-                       (float *)matches, mcap, match_count, overflow, mchunk, nchm, redo, mchunk_next, (int4 *)host_out, (float *)host_matches, ref);
 }

@@ -12,7 +12,7 @@
 //   refine_records  the same hops on caller-owned records (vh_refine_matches)
 //
 // Built with -ffp-contract=off: every double and float rounding step of the sub-pixel fit is part of the result.
-#include "vh_dev.h"
+#include "vh_findmatch.h"
 #include "../../include/viso_hip.h"
 
 #include <algorithm>
@@ -220,7 +220,7 @@ __global__ void __launch_bounds__(256) refine_chain_kernel(VhSets s, VhMatchArgs
     P[r] = Planes{rf.du + (int64_t)set[r] * rf.plane, rf.dv + (int64_t)set[r] * rf.plane};
   }
   const int32_t drive = method == 2 ? set[0] : set[2];
-  const int32_t n = s.bin_start[(int64_t)drive * (s.nbins + 1) + s.nbins];  // the indexed count, as the chain kernel's
+  const int32_t n = indexed_count(s, drive);
   int4 *__restrict__ ch = chain + 2 * (int64_t)row * s.cap;
   float4 *__restrict__ out = ref + 2 * (int64_t)row * s.cap;
   // the grid covers whole waves of consecutive features, so the 64 lanes of a wave share one 256-feature chunk

@@ -221,21 +221,22 @@ void vh_launch_bin_sort(const VhSets &s, int32_t set0, int32_t nsets, int32_t st
 void vh_launch_ref_index(const VhSets &s, int32_t set, int32_t *bin_start_ref, int32_t *list_ref,
                          hipStream_t st);
 
+// findMatch with one prediction for every query of pass 0 (kernels_prior.hip)
 void vh_launch_match_prior(const VhSets &s, const VhMatchArgs &a, double u_, double v_, int32_t *best,
                            hipStream_t st);
-// grid_x: workgroups per (pass, stream) row (<= 0: one per 4 tiles of the capacity-sized tile list); lds_bytes: LDS a workgroup
+// (kernels_match.hip) grid_x: workgroups per (pass, stream) row (<= 0: one per 4 tiles of the capacity-sized tile list); lds_bytes: LDS a workgroup
 // is to occupy, static part included (<= 0: the static part only) -- see the launcher for what both are for
 void vh_launch_match(const VhSets &s, const VhMatchArgs &a, int32_t *best, int32_t *redo, int32_t speculative, int32_t grid_x,
                      int32_t lds_bytes, hipStream_t st);
 void vh_launch_quad_prior(const VhSets &s, const VhMatchArgs &a, const double *tr, double f, double cu, double cv, double base, int32_t *best,
                           hipStream_t st);
-// chain: [stream][cap][2] int4 = {i1p,i2p,i1c,i2c} (z = -2: no match), {uv1p,uv2p,uv1c,uv2c}
+// (kernels_chain.hip) chain: [stream][cap][2] int4 = {i1p,i2p,i1c,i2c} (z = -2: no match), {uv1p,uv2p,uv1c,uv2c}
 void vh_launch_chain(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *best,
                      int4 *chain, uint32_t *mask, uint32_t epoch, int32_t *mchunk, hipStream_t st);
 // the flow method's second half of the chain step (first-writer pixel mask): what vh_launch_chain ends with
 void vh_launch_flow_keep(const VhSets &s, const VhMatchArgs &a, int4 *chain, const uint32_t *mask, uint32_t epoch, int32_t *mchunk,
                          hipStream_t st);
-// pass 2 of multi-stage matching (kernels_ranged.hip): the whole circle per driving feature inside the ranges of the
+// pass 2 of multi-stage matching (kernels_chain.hip): the whole circle per driving feature inside the ranges of the
 // driver's statistics bin, ranges [row][ubn * vbn][4 stages]{u_min, u_max, v_min, v_max}; writes what vh_launch_chain's
 // first kernel writes (flow: vh_launch_flow_keep follows)
 void vh_launch_ranged_circle(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *ranges, int4 *chain, uint32_t *mask,

@@ -66,6 +66,68 @@ def test_find_match_prior_term(pkg, ob, oracle, gpu):
         assert np.array_equal(pkg.match_all_prior(pg, dims, z["max2c"], z["max2p"], u_, v_, flow=flow), want)
 
 
+def _prior_split(A, B, u0, n=100000):
+    """A prediction (u_, v_) beside the perpendicular bisector of the pixels A and B at which 4 * sqrt(du * du + dv * dv)
+    orders the two differently when the sum rounds twice (each product, then the sum: the reference's x86 build) and
+    when a compiler contracts it to one product and a fused multiply-add, in either order; scans n neighbouring doubles
+    of u_ around u0.  -> (u_, v_, index of the two-rounding winner) or None."""
+    import math
+    from fractions import Fraction as Fr
+    (ax, ay), (bx, by) = A, B
+    v_ = ay + (((bx - ax) ** 2 + (by - ay) ** 2) / 2.0 - (u0 - ax) * (bx - ax)) / (by - ay)
+    two = lambda du, dv: du * du + dv * dv
+    fused = lambda du, dv: (float(Fr(du) * Fr(du) + Fr(dv * dv)), float(Fr(dv) * Fr(dv) + Fr(du * du)))
+    winner = lambda sa, sb: 1 if 4 * math.sqrt(sb) < 4 * math.sqrt(sa) else 0  # first strict minimum: A is visited first
+    us = u0 + np.arange(-n // 2, n // 2) * np.spacing(u0)  # (exact: one binade)
+    sa, sb = two(ax - us, ay - v_), two(bx - us, by - v_)
+    for k in np.flatnonzero(np.abs(sa - sb) <= 4 * np.spacing(sa)):  # elsewhere one rounding more or less decides nothing
+        u_ = float(us[k])
+        da, db = (ax - u_, ay - v_), (bx - u_, by - v_)
+        w2, fa, fb = winner(two(*da), two(*db)), fused(*da), fused(*db)
+        if all(winner(fa[j], fb[j]) != w2 for j in (0, 1)):
+            return u_, v_, w2
+    return None
+
+
+def test_find_match_prior_term_rounds_twice(pkg, ob, oracle, gpu):
+    """The distance term with predictions that are not dyadic: du * du + dv * dv rounds twice (src/matcher.cpp:259-261
+    on the reference's x86 build; the oracle and kernels_prior.hip are built without contraction).  One query and two
+    candidates A, B with the query's descriptor, so the cost is the distance term alone, and a prediction at which the
+    fused sum picks the other candidate."""
+    W, H = 320, 240
+    dims = [W, H, pkg.synth.bytes_per_line(W)]
+    p, po = pkg.Params.default(), ob.Params.default()
+    rec = lambda u, v: [u, v, 0, 0] + [0x10203040 + k for k in range(8)]
+    uq, vq = 100, 100
+    found = None
+    for A, B, u0 in (((100, 99), (101, 102), 30.3), ((100, 98), (102, 101), 40.7), ((99, 99), (100, 102), 20.9)):
+        found = _prior_split(A, B, u0)
+        if found:
+            break
+    assert found, "no prediction separates two roundings from one among 10^5 neighbouring doubles of three A/B pairs"
+    u_, v_, w2 = found
+    bs = po.match_binsize
+    assert (A[0] // bs, A[1] // bs) < (B[0] // bs, B[1] // bs)  # A comes first in bin order (u-bin major)
+    q, cand = np.array([rec(uq, vq)], np.int32), np.array([rec(*A), rec(*B)], np.int32)
+    for flow in (True, False):
+        rv = po.match_radius if flow else po.match_disp_tolerance
+        assert all(abs(x - uq) <= po.match_radius and abs(y - vq) <= rv for x, y in (A, B))
+        want = oracle.match_all_prior(po, dims, q, cand, u_, v_, flow=flow)
+        assert want[0] == w2, (u_, v_, flow)
+        assert np.array_equal(pkg.match_all_prior(p, dims, q, cand, u_, v_, flow=flow), want), (u_, v_, flow)
+
+
+@pytest.mark.parametrize("uv", [(10.1, 300.3), (123.456, 77.7), (0.3, 1e-3)])
+def test_find_match_prior_term_non_dyadic(uv, pkg, ob, oracle, gpu):
+    """Ordinary predictions that no binary fraction represents, on the golden sets, against the oracle."""
+    _, dims, Ip, Ic, z = load_golden("small_default", pkg, pkg.Params)
+    po = ob.Params.default(match_radius=90, match_binsize=37)
+    pg = pkg.Params.default(match_radius=90, match_binsize=37)
+    for flow in (True, False):
+        want = oracle.match_all_prior(po, dims, z["max2c"], z["max2p"], uv[0], uv[1], flow=flow)
+        assert np.array_equal(pkg.match_all_prior(pg, dims, z["max2c"], z["max2p"], uv[0], uv[1], flow=flow), want), flow
+
+
 @pytest.mark.parametrize("case", ["kitti_1241x376", "seq_1024x284"])
 def test_known_answers_full_size(case, pkg, oracle, gpu):
     """SURVEY Appendix-B sizes through the stateful Matcher surface (mono flow = configs[0])."""

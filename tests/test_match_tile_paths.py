@@ -99,8 +99,35 @@ def case_noise(pkg, ob, oracle):
     return over, dims, f
 
 
+def case_wide_unmerged_regions(pkg, ob, oracle):
+    """Bins of 2 px and a radius of 70 px: the own window of every query away from the left and right borders spans
+    71 u-bin columns, more than one batch of the walkers' 64-column table, and the features are kept to a band of rows
+    whose windows never reach the top row of bins, so no region -- of a tile or of a group of second searches -- is the
+    single merged run of positions that KITTI-sized frames walk.  Noise images, as in case_noise: the second searches
+    walk such regions too."""
+    W, H = 480, 256
+    b, r = 2, 70
+    over = {"match_binsize": b, "match_radius": r}
+    po = ob.Params.default(**over)
+    dims = [W, H, pkg.synth.bytes_per_line(W)]
+    assert 2 * r // b + 1 > 64 and 2 * r + b < H
+    rng = np.random.default_rng(5)
+    f = _feats(oracle, po, dims, [rng.integers(0, 256, (H, dims[2]), dtype=np.uint8) for _ in range(4)])
+    f = [np.ascontiguousarray(a[(a[:, 1] >= 100) & (a[:, 1] <= 140)]) for a in f]
+    vbn = (H + b - 1) // b
+    for a in f:
+        u, v = a[:, 0], a[:, 1]
+        inner = (u >= r) & (u + r <= W - 1)
+        assert inner.sum() > 4 * TILE_Q and ((u[inner] + r) // b - (u[inner] - r) // b + 1).min() > 64
+        # any union of these windows starts below the first row of bins and ends above the last: never all v-bins
+        assert (v.min() - r) // b > 0 and (v.max() + r) // b < vbn - 1
+        assert min(_class_counts(a)) > TILE_Q, _class_counts(a)
+    return over, dims, f
+
+
 CASES = {"partial_last_tile": case_partial_last_tile, "empty_class": case_empty_class,
-         "three_or_more_columns": case_three_or_more_columns, "noise": case_noise}
+         "three_or_more_columns": case_three_or_more_columns, "noise": case_noise,
+         "wide_unmerged_regions": case_wide_unmerged_regions}
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
