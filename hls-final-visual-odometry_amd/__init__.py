@@ -72,6 +72,7 @@ ABI_SYMBOLS = (
     "vh_set_multi_stage_device", "vh_group_set_multi_stage_device", "vh_prior_statistics_device",
     "vh_set_track_linking", "vh_group_set_track_linking", "vh_get_tracks", "vh_group_get_tracks", "vh_group_get_tracks_all",
     "vh_group_tracks_device", "vh_link_tracks", "vh_track_carry_free", "vh_group_debug_fail_alloc_after",
+    "vh_default_recon_params", "vh_reconstruct_tracks", "vh_reconstruct_last_kernel_ms",
 )
 
 
@@ -123,6 +124,25 @@ class MonoParams(C.Structure):
                 raise AttributeError(k)
             setattr(e, k, v)
         return e
+
+
+class ReconParams(C.Structure):
+    """Reconstruction's calibration and update's thresholds (reference src/reconstruction.h:55, :66)."""
+    _fields_ = [("f", C.c_double), ("cu", C.c_double), ("cv", C.c_double), ("point_type", C.c_int32), ("min_track_length", C.c_int32),
+                ("max_dist", C.c_double), ("min_angle", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw):
+        r = cls(f=1.0, cu=0.0, cv=0.0, point_type=1, min_track_length=2, max_dist=30.0, min_angle=2.0)
+        for k, v in kw.items():
+            if not hasattr(r, k):
+                raise AttributeError(k)
+            setattr(r, k, v)
+        return r
+
+
+#: vh_reconstruct_tracks' status values (include/viso_hip.h), in the order Reconstruction::update tests them
+RECON_ACCEPTED, RECON_SHORT, RECON_INFINITY, RECON_TYPE, RECON_NOT_REFINED, RECON_FAR_OR_NARROW = range(6)
 
 
 #: Matcher::p_match (reference src/matcher.h:89-104), 48 bytes
@@ -224,6 +244,7 @@ def _lib():
             "vh_group_get_tracks_all": [vp, vp, i32, vp], "vh_group_tracks_device": [vp, vp, vp],
             "vh_link_tracks": [i32, i32, vp, i64, vp, i32, vp, vp, vp],
             "vh_group_debug_fail_alloc_after": [vp, i32],
+            "vh_reconstruct_tracks": [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -231,6 +252,10 @@ def _lib():
             fn.restype = None if name.endswith("destroy") else i32
         lib.vh_track_carry_free.argtypes = [vp]
         lib.vh_track_carry_free.restype = None
+        lib.vh_default_recon_params.argtypes = [vp]
+        lib.vh_default_recon_params.restype = None
+        lib.vh_reconstruct_last_kernel_ms.argtypes = []
+        lib.vh_reconstruct_last_kernel_ms.restype = f64
         lib.vh_group_device_bytes.argtypes = [vp]
         lib.vh_group_device_bytes.restype = i64
         _LIB = lib
@@ -904,6 +929,108 @@ def link_tracks(lists, n_index: int, carry: "TrackCarry | None" = None, device: 
     _check(_lib().vh_link_tracks(device, n, _ptr(pm), stride, _ptr(counts), int(n_index), carry._h if carry is not None else None,
                                  C.byref(h), _ptr(out)), "vh_link_tracks")
     return [out[l, :counts[l]].copy() for l in range(n)], TrackCarry(h)
+
+
+def reconstruct_tracks(recon: ReconParams, Trs, first_frame, offsets, pixels, n_frames: int | None = None, metrics: bool = True,
+                       device: int = 0):
+    """What Reconstruction::update computes for its lost tracks (reference src/reconstruction.cpp:131-142), for all given
+    tracks in one launch (vh_reconstruct_tracks).  Trs [n_frames - 1, 4, 4]: the Tr of update k (frame k -> k + 1); track t
+    was seen in frames first_frame[t] .. at pixels[offsets[t]:offsets[t + 1]] = (u, v).
+    -> (points [n, 3] float32, status [n] int32 (RECON_*), metrics [n, 2] float64 (distance, angle) or None)."""
+    tr = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 16)
+    first = np.ascontiguousarray(first_frame, dtype=np.int32).reshape(-1)
+    off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+    px = np.ascontiguousarray(pixels, dtype=np.float32).reshape(-1, 2)
+    n = len(first)
+    if len(off) != n + 1 or (n > 0 and len(px) < off[-1]):
+        raise ValueError(f"reconstruct_tracks: {n} tracks need {n + 1} offsets and offsets[-1] pixels (got {len(off)}, {len(px)})")
+    nf = tr.shape[0] + 1 if n_frames is None else int(n_frames)
+    if tr.shape[0] < nf - 1:
+        raise ValueError(f"reconstruct_tracks: {nf} frames need {nf - 1} Trs (got {tr.shape[0]})")
+    pts = np.zeros((n, 3), np.float32); st = np.zeros(n, np.int32)
+    met = np.zeros((n, 2), np.float64) if metrics else None
+    _check(_lib().vh_reconstruct_tracks(C.byref(recon), int(device), nf, _ptr(tr), n, _ptr(first), _ptr(off), _ptr(px), _ptr(pts),
+                                        _ptr(st), _ptr(met)), "vh_reconstruct_tracks")
+    return pts, st, met
+
+
+def reconstruct_last_kernel_ms() -> float:
+    """Device time of the kernel of this thread's last reconstruct_tracks call (HIP events), -1 before the first."""
+    return float(_lib().vh_reconstruct_last_kernel_ms())
+
+
+class Reconstruction:
+    """Host mirror of the reference's `Reconstruction` (src/reconstruction.h:35-110): setCalibration, update, getPoints.
+    The association of matches to tracks is update's, statement for statement (src/reconstruction.cpp:72-145), on the
+    host; every lost track's point is computed on the GPU (reconstruct_tracks).  updateMany runs several consecutive
+    updates with ONE launch: points never feed back into the association, so the result is that of the single updates.
+    The entry is stateless: every call rebuilds the tables of all frames so far on the host (a third of a microsecond per
+    frame), so update() once per frame costs O(N^2) of that over a drive of N frames; prefer updateMany per chunk."""
+
+    def __init__(self, device: int = 0):
+        self.device = int(device)
+        self.recon = ReconParams.default()
+        self.Trs = []      # Tr of every update so far: frame k -> k + 1
+        self.tracks = []   # active tracks: [pixels (list of (u, v)), first_frame, last_frame, last_idx]
+        self.points = []   # accepted points, float32 [3] each
+
+    def setCalibration(self, f: float, cu: float, cv: float):
+        self.recon.f, self.recon.cu, self.recon.cv = float(f), float(cu), float(cv)
+
+    def associate(self, p_matched, current_frame: int):
+        """src/reconstruction.cpp:75-145 without the points: extends / starts tracks from one match list and returns the
+        lost tracks, in track order, as (first_frame, pixels).  The reference indexes its table with i1p and last_idx
+        unchecked; here a match with i1p < 0 starts a new track and a track with last_idx < 0 is not entered."""
+        pm = np.ascontiguousarray(p_matched, dtype=P_MATCH_DTYPE)
+        tracks = self.tracks
+        track_idx_max = 0
+        if len(pm):
+            track_idx_max = max(track_idx_max, int(pm["i1p"].max()))
+        for t in tracks:
+            if t[3] > track_idx_max:
+                track_idx_max = t[3]
+        track_idx = [-1] * (track_idx_max + 1)
+        for i, t in enumerate(tracks):
+            if t[3] >= 0:
+                track_idx[t[3]] = i          # in track order: the later track wins a shared last_idx
+        for i1p, i1c, u1p, v1p, u1c, v1c in zip(pm["i1p"].tolist(), pm["i1c"].tolist(), pm["u1p"], pm["v1p"], pm["u1c"], pm["v1c"]):
+            idx = track_idx[i1p] if i1p >= 0 else -1
+            if idx >= 0 and tracks[idx][2] == current_frame - 1:
+                t = tracks[idx]
+                t[0].append((u1c, v1c)); t[2] = current_frame; t[3] = i1c
+            else:
+                tracks.append([[(u1p, v1p), (u1c, v1c)], current_frame - 1, current_frame, i1c])
+        lost = [(t[1], t[0]) for t in tracks if t[2] != current_frame]
+        self.tracks = [t for t in tracks if t[2] == current_frame]
+        return lost
+
+    def updateMany(self, lists, Trs, point_type: int = 1, min_track_length: int = 2, max_dist: float = 30.0, min_angle: float = 2.0):
+        """len(lists) consecutive updates; the lost tracks of all of them are solved in one launch."""
+        Trs = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 4, 4)
+        if len(Trs) != len(lists):
+            raise ValueError(f"updateMany: {len(lists)} lists need as many Trs (got {len(Trs)})")
+        lost = []
+        for pm, Tr in zip(lists, Trs):
+            self.Trs.append(Tr.copy())
+            lost += self.associate(pm, len(self.Trs))
+        if not lost:
+            return
+        r = self.recon
+        r.point_type, r.min_track_length, r.max_dist, r.min_angle = int(point_type), int(min_track_length), float(max_dist), float(min_angle)
+        first = np.array([f for f, _ in lost], np.int32)
+        offsets = np.zeros(len(lost) + 1, np.int32)
+        offsets[1:] = np.cumsum([len(px) for _, px in lost])
+        pixels = np.array([uv for _, px in lost for uv in px], np.float32).reshape(-1, 2)
+        pts, st, _ = reconstruct_tracks(r, np.array(self.Trs), first, offsets, pixels, metrics=False, device=self.device)
+        self.points += [p for p in pts[st == RECON_ACCEPTED]]
+
+    def update(self, p_matched, Tr, point_type: int = 1, min_track_length: int = 2, max_dist: float = 30.0, min_angle: float = 2.0):
+        """Reconstruction::update (src/reconstruction.cpp:59-151)."""
+        self.updateMany([p_matched], [Tr], point_type, min_track_length, max_dist, min_angle)
+
+    def getPoints(self) -> np.ndarray:
+        """-> [n, 3] float32 (point3d x, y, z), in the order the reference appends them."""
+        return np.array(self.points, np.float32).reshape(-1, 3)
 
 
 def match(param: Params, dims, method: int, m1p=None, m2p=None, m1c=None, m2c=None, device: int = 0, cap=None):

@@ -610,6 +610,58 @@ int32_t vh_group_post_finish_mono(vh_group *g, int32_t age, int32_t max_features
                                   int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed, int32_t cap_per_stream,
                                   int32_t *counts, double *host_ms);
 
+/* ---- reconstruction: 3-d points from lost feature tracks (csrc/kernels_recon.hip) ----------------- */
+
+/* Reconstruction's calibration and the four thresholds of Reconstruction::update (src/reconstruction.h:55, :66). */
+typedef struct vh_recon_params {
+  double f, cu, cv;          /* setCalibration: focal length, principal point (pixels) */
+  int32_t point_type;        /* 0 = everything, 1 = road and above, 2 = only above the road */
+  int32_t min_track_length;  /* frames a feature must have been tracked for; negative: every track is SHORT (the reference
+                                compares it with pixels.size() unsigned, src/reconstruction.cpp:131) */
+  double max_dist;           /* largest distance from the camera of the track's middle frame (meters) */
+  double min_angle;          /* smallest angle between the first and the last ray (degrees) */
+} vh_recon_params;
+/* f = 1, cu = cv = 0 (the constructor's K = eye(3)); 1, 2, 30, 2 (src/reconstruction.h:66). */
+void vh_default_recon_params(vh_recon_params *r);
+
+/* What became of a track, in the order Reconstruction::update tests (src/reconstruction.cpp:131-141). */
+#define VH_RECON_ACCEPTED 0
+#define VH_RECON_SHORT 1         /* fewer than min_track_length frames */
+#define VH_RECON_INFINITY 2      /* initPoint false: |w| < 1e-10 */
+#define VH_RECON_TYPE 3          /* pointType < point_type (-1: not more than 1 m in front of the first or the last camera) */
+#define VH_RECON_NOT_REFINED 4   /* refinePoint false: a projection with c*c < 1e-10, a singular system, no convergence in 22 updates */
+#define VH_RECON_FAR_OR_NARROW 5 /* pointDistance >= max_dist or rayAngle <= min_angle */
+
+/* What Reconstruction::update computes for every lost track (src/reconstruction.cpp:131-142: initPoint, pointType,
+ * refinePoint, pointDistance, rayAngle), for n_tracks tracks of one drive in ONE launch, one GPU lane per track.
+ * The drive has frames 0 .. n_frames-1; Tr[k] (row-major 4x4) is the Tr handed to update number k, the motion frame
+ * k -> k+1 (src/viso.h:80-86).  The per-frame tables Tr_total, Tr_inv_total, P_total are built on the host from r and
+ * Tr exactly as the constructor, setCalibration and update build them (src/reconstruction.cpp:27-70).  A singular Tr
+ * is not an error: Matrix::inv hands out what its elimination left, and the tracks that read it fail the kernel's tests.
+ * Track t was seen in frames first_frame[t] .. first_frame[t] + len - 1, len = offsets[t+1] - offsets[t], at
+ * pixels[offsets[t] ..][2] = (u, v) per frame.  Association (which match extends which track) stays with the caller:
+ * include/viso_hip_reconstruction.hpp and the Python package restate Reconstruction::update's.
+ * Outputs, in input order: status[t] = VH_RECON_*; points[t][3] = the point as the reference's `p` stood when the track's
+ * fate was decided (ACCEPTED, FAR_OR_NARROW: refined; NOT_REFINED: after the last update; TYPE: initPoint's; SHORT,
+ * INFINITY: 0); metrics[t][2] (nullable) = (pointDistance, rayAngle) for ACCEPTED and FAR_OR_NARROW, else 0.
+ * points and metrics[.][0] equal the reference's bit for bit; the ray angle uses the device's acos and agrees to rounding,
+ * so a track whose angle lies within rounding of min_angle may be classified differently.
+ * VH_ERR_INVALID_ARG: null pointers, n_frames < 1, n_tracks < 0, offsets[0] < 0, a track with len < 1, first_frame < 0 or
+ * first_frame + len > n_frames.  n_tracks == 0: VH_OK, nothing is launched and no device is needed.
+ * Stateless: device buffers live for the call, and the tables of ALL n_frames frames are rebuilt on the host on every
+ * call -- two 4x4 Gauss-Jordan inversions and two products per frame, a third of a microsecond -- and uploaded (256 bytes per
+ * frame).  A caller that runs one call per update of a drive of N updates pays O(N^2) of that in total (N = 10 000:
+ * some twenty seconds over the drive); one call per chunk of k updates (updateMany of the classes) divides it by k. */
+int32_t vh_reconstruct_tracks(const vh_recon_params *r, int32_t device, int32_t n_frames, const double *Tr, int32_t n_tracks,
+                              const int32_t *first_frame, const int32_t *offsets, const float *pixels, float *points, int32_t *status,
+                              double *metrics);
+/* Device time in milliseconds of the kernel of this thread's last successful vh_reconstruct_tracks (HIP events around the
+ * launch; transfers excluded), -1 before the first.  A permanent part of the ABI, the counterpart of sweep_ms of
+ * vh_remove_outliers_device and of vh_group_profile_read for the handles: the entry is synchronous and owns its buffers,
+ * so a caller's own events could only time the whole call, transfers included.  Its price is two events per call
+ * (microseconds beside the call's seven transfers) and one thread-local double; tools/reconstruct_rate.py reads it. */
+double vh_reconstruct_last_kernel_ms(void);
+
 /* Which form of the search loops the group currently runs and the last observed share of
  * queries the speculative form had to search again (-1 before the first report).  The
  * searches are exact either way; the library switches between a speculative loop (no accept
