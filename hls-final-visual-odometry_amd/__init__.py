@@ -73,6 +73,7 @@ ABI_SYMBOLS = (
     "vh_set_track_linking", "vh_group_set_track_linking", "vh_get_tracks", "vh_group_get_tracks", "vh_group_get_tracks_all",
     "vh_group_tracks_device", "vh_link_tracks", "vh_track_carry_free", "vh_group_debug_fail_alloc_after",
     "vh_default_recon_params", "vh_reconstruct_tracks", "vh_reconstruct_last_kernel_ms",
+    "vh_sequence_set_reconstruction", "vh_sequence_reconstruct", "vh_sequence_get_recon_tracks", "vh_reconstruct_lists",
 )
 
 
@@ -143,6 +144,8 @@ class ReconParams(C.Structure):
 
 #: vh_reconstruct_tracks' status values (include/viso_hip.h), in the order Reconstruction::update tests them
 RECON_ACCEPTED, RECON_SHORT, RECON_INFINITY, RECON_TYPE, RECON_NOT_REFINED, RECON_FAR_OR_NARROW = range(6)
+#: a lost track older than the history of a sequence handle's reconstruction: not solved
+RECON_HISTORY = 6
 
 
 #: Matcher::p_match (reference src/matcher.h:89-104), 48 bytes
@@ -155,6 +158,11 @@ P_MATCH_DTYPE = np.dtype([
 
 #: vh_track (include/viso_hip.h), 24 bytes: one per match record of a tracked list
 TRACK = np.dtype([("birth_frame", "<i8"), ("birth_pos", "<i4"), ("age", "<i4"), ("prev", "<i4"), ("reserved", "<i4")])
+
+
+#: vh_recon_track (include/viso_hip.h), 56 bytes: one per lost track of SequenceGroup.reconstruct / reconstruct_lists
+RECON_TRACK = np.dtype([("birth_frame", "<i8"), ("birth_pos", "<i4"), ("frames", "<i4"), ("lost_frame", "<i8"), ("status", "<i4"),
+                        ("point", "<f4", (3,)), ("distance", "<f8"), ("angle", "<f8")])
 
 
 class VisoHipError(RuntimeError):
@@ -245,6 +253,9 @@ def _lib():
             "vh_link_tracks": [i32, i32, vp, i64, vp, i32, vp, vp, vp],
             "vh_group_debug_fail_alloc_after": [vp, i32],
             "vh_reconstruct_tracks": [vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp],
+            "vh_sequence_set_reconstruction": [vp, vp, i32], "vh_sequence_reconstruct": [vp, vp, vp, vp],
+            "vh_sequence_get_recon_tracks": [vp, vp, i32, vp],
+            "vh_reconstruct_lists": [vp, i32, i32, vp, i64, vp, i32, vp, vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -770,6 +781,25 @@ class SequenceGroup(StreamGroup):
         assert tr.shape[0] == n, (tr.shape, n)
         _check(_lib().vh_group_match_features_prior(self._h, int(method), _ptr(tr)), "vh_group_match_features_prior")
 
+    def setReconstruction(self, recon: "ReconParams | None", history_frames: int = 0):
+        """3-d points from the tracks that end, gathered on the device (vh_sequence_set_reconstruction): before the first
+        push only; switches track linking on.  history_frames >= 1: lost tracks older than that come back RECON_HISTORY.
+        recon None: off."""
+        _check(_lib().vh_sequence_set_reconstruction(self._h, C.byref(recon) if recon is not None else None, int(history_frames)),
+               "vh_sequence_set_reconstruction")
+
+    def reconstruct(self, Trs) -> np.ndarray:
+        """The lost tracks of the chunk of the last match call (vh_sequence_reconstruct), once per matched chunk, before the
+        next match call.  Trs [rows, 4, 4]: the motion frame F+r-1 -> F+r per row of that chunk (rows without a pair are not
+        read).  -> RECON_TRACK array sorted by (lost_frame, birth_frame, birth_pos)."""
+        tr = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 16)
+        nt, na = C.c_int32(0), C.c_int32(0)
+        _check(_lib().vh_sequence_reconstruct(self._h, _ptr(tr) if len(tr) else None, C.byref(nt), C.byref(na)), "vh_sequence_reconstruct")
+        out = np.zeros(nt.value, RECON_TRACK)
+        n = C.c_int32(0)
+        _check(_lib().vh_sequence_get_recon_tracks(self._h, _ptr(out) if nt.value else None, nt.value, C.byref(n)), "vh_sequence_get_recon_tracks")
+        return out[:n.value]
+
 
 # ------------------------------------------------------------------ stateless primitives
 def compute_features(param: Params, img, dims, device: int = 0, planes: bool = False, cap: int | None = None):
@@ -952,6 +982,28 @@ def reconstruct_tracks(recon: ReconParams, Trs, first_frame, offsets, pixels, n_
     _check(_lib().vh_reconstruct_tracks(C.byref(recon), int(device), nf, _ptr(tr), n, _ptr(first), _ptr(off), _ptr(px), _ptr(pts),
                                         _ptr(st), _ptr(met)), "vh_reconstruct_tracks")
     return pts, st, met
+
+
+def reconstruct_lists(recon: ReconParams, lists, Trs, n_index: int, device: int = 0) -> np.ndarray:
+    """A whole fresh drive from caller-owned match lists (vh_reconstruct_lists): list l is update l of a new
+    Reconstruction, Trs[l] its Tr; linked by the rule of link_tracks, every lost track gathered and solved on the device.
+    -> RECON_TRACK array sorted by (lost_frame, birth_frame, birth_pos)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in lists]
+    n = len(lists)
+    tr = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 16)
+    if tr.shape[0] != n:
+        raise ValueError(f"reconstruct_lists: {n} lists need as many Trs (got {tr.shape[0]})")
+    stride = max([len(m) for m in lists] + [1])
+    pm = np.zeros((n, stride), P_MATCH_DTYPE)
+    for l, m in enumerate(lists):
+        pm[l, :len(m)] = m
+    counts = np.array([len(m) for m in lists], np.int32)
+    cap = int(counts.sum())   # every record ends at most one track
+    out = np.zeros(max(cap, 1), RECON_TRACK)
+    got = C.c_int32(0)
+    _check(_lib().vh_reconstruct_lists(C.byref(recon), int(device), n, _ptr(pm), stride, _ptr(counts), int(n_index), _ptr(tr), _ptr(out), cap,
+                                       C.byref(got)), "vh_reconstruct_lists")
+    return out[:got.value].copy()
 
 
 def reconstruct_last_kernel_ms() -> float:

@@ -8,6 +8,7 @@
 #include "vh_dev.h"
 #include "../../include/viso_hip.h"
 #include "vh_vote.h"
+#include "vh_recon.h"
 
 #include <algorithm>
 #include <chrono>
@@ -202,6 +203,45 @@ struct Ranges {
   HostBlock<int32_t> h_ranges;   // page-locked staging
 };
 
+// The per-frame tables of Reconstruction (vh_recon.h), built one frame at a time (engine_recon.hip: recon_table_push)
+struct ReconTable {
+  double total[16], inv[16];   // Tr_total.back() and its inverse
+  int64_t first = 0;           // frame of frames[0]
+  std::vector<double> frames;  // VH_RECON_FRAME_DOUBLES per frame
+  int64_t count() const { return (int64_t)(frames.size() / VH_RECON_FRAME_DOUBLES); }
+};
+// Reconstruction on a sequence handle (vh_sequence_set_reconstruction; engine_recon.hip): the
+// ring of compact records and the gather buffers, outside the arena (the gather buffers grow), counted in `bytes`.
+// vh_reconstruct_lists runs on a transient one.
+struct ReconHistory {
+  bool on = false;
+  vh_recon_params params{};
+  int32_t history = 0;
+  // the chunk of the last match call, recorded when it was queued
+  bool m_valid = false, m_done = false;
+  int64_t m_first = 0;
+  int32_t m_lo = 0, m_rows = 0;
+  int32_t pushes_since_match = 0;
+  // the chain of lists stored so far: unbroken up to frame `last`; has_pending: the list of frame `last` is in the ring
+  bool chain = false, has_pending = false;
+  int64_t last = 0;
+  ReconTable table;
+  std::vector<vh_recon_track> result;
+  int32_t accepted = 0;
+  // device
+  DeviceBlock b_ring, b_count, b_totals;
+  int32_t ring_slots = 0, ring_cap = 0;
+  struct Grown { DeviceBlock b; size_t bytes = 0; } g_tails, g_first, g_off, g_order, g_px, g_pts, g_st, g_met, g_frames;
+  int64_t bytes = 0;
+  void drop_chain() { chain = has_pending = false; }
+  void release_device() {  // (the work using it must have completed)
+    b_ring = DeviceBlock(); b_count = DeviceBlock(); b_totals = DeviceBlock();
+    for (Grown *g : {&g_tails, &g_first, &g_off, &g_order, &g_px, &g_pts, &g_st, &g_met, &g_frames}) { g->b = DeviceBlock(); g->bytes = 0; }
+    ring_slots = ring_cap = 0; bytes = 0;
+    drop_chain(); m_valid = m_done = false;
+  }
+};
+
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
 struct VoteBatch {
   VoteBuffers vb;
@@ -348,6 +388,7 @@ struct Group {
   Ranges rg;
   VoteBuffers ms_vb;
   std::vector<VoteBatch> vbatch;
+  ReconHistory rh;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
   // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
   // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
@@ -406,6 +447,7 @@ struct Group {
   int32_t multi_stage_ranges_device(int32_t method);
   int32_t load_ranges(const float *ranges);
   int32_t match(int32_t method, const double *tr16 = nullptr, bool ranged = false);
+  int32_t match_call(int32_t method, const double *tr16, bool ranged);
   int32_t match_queued(int32_t method, const double *tr16, const int32_t *ranges);
   int32_t mask_epoch(hipStream_t st);
   int32_t match_post(int32_t method, const VhMatchArgs &a, int32_t buf, bool ranged, bool spec);
@@ -420,6 +462,13 @@ struct Group {
   int32_t get_tracks(int32_t s, vh_track *out, int32_t capo, int32_t *n);
   int32_t get_tracks_all(vh_track *out, int32_t cap_per_stream, int32_t *counts);
   int32_t load_features(int32_t role, const int32_t *m, int32_t n);
+
+  // ---- engine_recon.hip ----
+  void recon_pushed(bool first);
+  void recon_before_link();
+  void recon_matched(const VhMatchArgs &a);
+  void recon_match_failed() { rh.m_valid = false; rh.drop_chain(); }
+  int32_t reconstruct(const double *Tr, int32_t *n_tracks, int32_t *n_accepted);
 
   // ---- engine_post.hip ----
   int32_t get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n);
@@ -462,6 +511,16 @@ struct Scope {
 int32_t check_params(const vh_params *p);
 int32_t select_device(int32_t device);
 int32_t group_new(const vh_params *p, int32_t device, int32_t S, int32_t mf, int32_t mm, Group **out);
+// engine_api.hip
+// The lists of vh_link_tracks / vh_reconstruct_lists uploaded and linked as the rows of one chain; the blocks are the caller's.
+struct LinkedLists {
+  std::vector<DeviceBlock> blocks;
+  vh_p_match *d_pm = nullptr; vh_track *d_trk = nullptr; int32_t *d_cnt = nullptr; uint32_t *d_check = nullptr;
+  int32_t lcap = 0;
+  int64_t serial0 = 0;
+};
+int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index, const vh_p_match *carry_pm,
+                          const vh_track *carry_trk, int32_t carry_count, int64_t carry_serial, bool has_carry, LinkedLists &out);
 // engine_post.hip
 // Matcher::bucketFeatures (matcher.cpp:140-187) on the records pm[0, n): the selected records are written to
 // out (at most out_cap of them) in the reference's order; returns how many the reference would keep.

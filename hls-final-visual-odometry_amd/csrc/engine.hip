@@ -56,6 +56,7 @@ int32_t Group::check_violation() {
 // everything allocate() and the calls after it made, so that the next ensure() starts from nothing (the work using it must have completed)
 void Group::release() {
   vote_release();
+  rh.release_device();
   allocs.clear(); device_bytes = 0;
   sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {};
   allocated = false;
@@ -275,6 +276,7 @@ int32_t Group::push_device(const void *dI1, const void *dI2, int64_t stride, con
   else {
     failed = false;
     trk_pushed(pair_cur != old_cur, old_frames == 0, seq_n);
+    recon_pushed(old_frames == 0);
     if (seq) { seq_n_prev = seq_n; seq_n = rows; seq_first = seq_total; seq_total += rows; }
   }
   return rc;

@@ -103,6 +103,66 @@ static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac
   return VH_OK;
 }
 
+// (arguments validated and the device selected by the caller)
+int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index, const vh_p_match *carry_pm,
+                          const vh_track *carry_trk, int32_t ccnt, int64_t carry_serial, bool has_carry, LinkedLists &out) {
+  int32_t cmax = 0;
+  for (int32_t l = 0; l < n_lists; l++) cmax = std::max(cmax, counts[l]);
+  const int32_t lcap = std::max(std::max(cmax, ccnt), 1), slots = n_lists + 1, cslot = n_lists;
+  std::vector<DeviceBlock> &blocks = out.blocks;
+  const auto alloc = [&](void **ptr, size_t bytes) { blocks.emplace_back(); const hipError_t e = blocks.back().alloc(bytes); *ptr = blocks.back().p; return e; };
+  vh_p_match *d_pm = nullptr; vh_track *d_trk = nullptr; uint32_t *d_tc = nullptr, *d_tp = nullptr, *d_check = nullptr; int32_t *d_cnt = nullptr, *d_scnt = nullptr;
+  VH_HIP(alloc((void **)&d_pm, sizeof(vh_p_match) * (size_t)slots * lcap));
+  VH_HIP(alloc((void **)&d_trk, sizeof(vh_track) * (size_t)slots * lcap));
+  VH_HIP(alloc((void **)&d_tc, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(alloc((void **)&d_tp, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(alloc((void **)&d_cnt, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(alloc((void **)&d_scnt, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(alloc((void **)&d_check, sizeof(uint32_t) * 4));
+  VH_HIP(hipMemset(d_tc, 0, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(hipMemset(d_tp, 0, sizeof(uint32_t) * (size_t)slots * n_index));
+  VH_HIP(hipMemset(d_scnt, 0, sizeof(int32_t) * (size_t)slots));
+  VH_HIP(hipMemset(d_check, 0, sizeof(uint32_t) * 4));
+  std::vector<int32_t> hc(counts, counts + n_lists);
+  hc.push_back(ccnt);
+  VH_HIP(hipMemcpy(d_cnt, hc.data(), sizeof(int32_t) * (size_t)slots, hipMemcpyHostToDevice));
+  for (int32_t l = 0; l < n_lists; l++)
+    if (counts[l]) VH_HIP(hipMemcpy(d_pm + (size_t)l * lcap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  VhTrackArgs t{};
+  t.pm = d_pm; t.pm_stride = lcap; t.counts = d_cnt; t.count_cap = lcap; t.n_index = n_index;
+  t.tab_c = d_tc; t.tab_p = d_tp; t.trk = d_trk; t.trk_stride = lcap; t.slot_count = d_scnt; t.check = d_check;
+  t.chain = 1; t.epoch = 1; t.pred_epoch = 1; t.pred0 = -1;
+  if (has_carry) {  // the carry's list bids for its table in the slot behind the lists; its tracks are final
+    if (ccnt) {
+      VH_HIP(hipMemcpy(d_pm + (size_t)cslot * lcap, carry_pm, sizeof(vh_p_match) * (size_t)ccnt, hipMemcpyHostToDevice));
+    }
+    VhTrackArgs c = t;
+    c.pm = d_pm + (size_t)cslot * lcap; c.counts = d_cnt + cslot; c.rows = 1; c.slot0 = cslot; c.tab_p = d_tp + (size_t)cslot * n_index;
+    vh_launch_track_scatter(c, nullptr);
+    if (ccnt) VH_HIP(hipMemcpyAsync(d_trk + (size_t)cslot * lcap, carry_trk, sizeof(vh_track) * (size_t)ccnt, hipMemcpyHostToDevice, nullptr));
+    t.pred0 = cslot;
+  }
+  t.rows = n_lists; t.slot0 = 0; t.serial0 = has_carry ? carry_serial : 0;
+  vh_launch_track_scatter(t, nullptr);
+  vh_launch_track_link(t, nullptr);
+  vh_launch_track_rank(t, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+#ifdef VH_CHECK
+  {
+    uint32_t c[4] = {0, 0, 0, 0};
+    VH_HIP(hipMemcpy(c, d_check, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[0]) {
+      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
+      fflush(stderr);
+      abort();
+    }
+  }
+#endif
+  out.d_pm = d_pm; out.d_trk = d_trk; out.d_cnt = d_cnt; out.d_check = d_check; out.lcap = lcap; out.serial0 = t.serial0;
+  return VH_OK;
+}
+
 }  // namespace vh_engine
 
 using namespace vh_engine;
@@ -162,6 +222,7 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
   if (gq->sparse) b += vh_group_device_bytes((const vh_group *)gq->sparse.get());  // the sparse sets of multi-stage matching
   b += (int64_t)gq->ms_vb.bytes;                                             // and the voted sparse lists of its device mode
   for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes;
+  b += gq->rh.bytes;                                                         // the ring and the gather buffers of reconstruction
   return b;
 }
 int32_t vh_group_push_back_device(vh_group *g, const void *dI1, const void *dI2, int64_t stride_bytes,
@@ -306,6 +367,7 @@ int32_t vh_group_set_track_linking(vh_group *g, int32_t on) {
   Group *gq = (Group *)g;
   if (!gq) return VH_ERR_INVALID_ARG;
   if (gq->allocated) return VH_ERR_STATE;  // before the first push only: every list since the first frame has its place in the chain
+  if (!on && gq->rh.on) return VH_ERR_STATE;  // reconstruction reads the tracks (vh_sequence_set_reconstruction)
   gq->trk_on = on != 0;
   return VH_OK;
 }
@@ -353,64 +415,16 @@ int32_t vh_link_tracks(int32_t device, int32_t n_lists, const vh_p_match *pm, in
   if (cmax > (int32_t)VH_TRACK_POS_MASK || (int64_t)n_lists + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;  // (positions share a table entry with the epoch; rows are a grid dimension)
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  const int32_t ccnt = carry_in ? (int32_t)carry_in->pm.size() : 0;
-  const int32_t lcap = std::max(std::max(cmax, ccnt), 1), slots = n_lists + 1, cslot = n_lists;
-  std::vector<DeviceBlock> blocks;
-  const auto alloc = [&](void **ptr, size_t bytes) { blocks.emplace_back(); const hipError_t e = blocks.back().alloc(bytes); *ptr = blocks.back().p; return e; };
-  vh_p_match *d_pm = nullptr; vh_track *d_trk = nullptr; uint32_t *d_tc = nullptr, *d_tp = nullptr, *d_check = nullptr; int32_t *d_cnt = nullptr, *d_scnt = nullptr;
-  VH_HIP(alloc((void **)&d_pm, sizeof(vh_p_match) * (size_t)slots * lcap));
-  VH_HIP(alloc((void **)&d_trk, sizeof(vh_track) * (size_t)slots * lcap));
-  VH_HIP(alloc((void **)&d_tc, sizeof(uint32_t) * (size_t)slots * n_index));
-  VH_HIP(alloc((void **)&d_tp, sizeof(uint32_t) * (size_t)slots * n_index));
-  VH_HIP(alloc((void **)&d_cnt, sizeof(int32_t) * (size_t)slots));
-  VH_HIP(alloc((void **)&d_scnt, sizeof(int32_t) * (size_t)slots));
-  VH_HIP(alloc((void **)&d_check, sizeof(uint32_t) * 4));
-  VH_HIP(hipMemset(d_tc, 0, sizeof(uint32_t) * (size_t)slots * n_index));
-  VH_HIP(hipMemset(d_tp, 0, sizeof(uint32_t) * (size_t)slots * n_index));
-  VH_HIP(hipMemset(d_scnt, 0, sizeof(int32_t) * (size_t)slots));
-  VH_HIP(hipMemset(d_check, 0, sizeof(uint32_t) * 4));
-  std::vector<int32_t> hc(counts, counts + n_lists);
-  hc.push_back(ccnt);
-  VH_HIP(hipMemcpy(d_cnt, hc.data(), sizeof(int32_t) * (size_t)slots, hipMemcpyHostToDevice));
+  LinkedLists ll;
+  const int32_t rl = link_lists_device(n_lists, pm, stride, counts, n_index, carry_in ? carry_in->pm.data() : nullptr, carry_in ? carry_in->trk.data() : nullptr,
+                                       carry_in ? (int32_t)carry_in->pm.size() : 0, carry_in ? carry_in->next_serial : 0, carry_in != nullptr, ll);
+  if (rl) return rl;
   for (int32_t l = 0; l < n_lists; l++)
-    if (counts[l]) VH_HIP(hipMemcpy(d_pm + (size_t)l * lcap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
-  VhTrackArgs t{};
-  t.pm = d_pm; t.pm_stride = lcap; t.counts = d_cnt; t.count_cap = lcap; t.n_index = n_index;
-  t.tab_c = d_tc; t.tab_p = d_tp; t.trk = d_trk; t.trk_stride = lcap; t.slot_count = d_scnt; t.check = d_check;
-  t.chain = 1; t.epoch = 1; t.pred_epoch = 1; t.pred0 = -1;
-  if (carry_in) {  // the carry's list bids for its table in the slot behind the lists; its tracks are final
-    if (ccnt) {
-      VH_HIP(hipMemcpy(d_pm + (size_t)cslot * lcap, carry_in->pm.data(), sizeof(vh_p_match) * (size_t)ccnt, hipMemcpyHostToDevice));
-    }
-    VhTrackArgs c = t;
-    c.pm = d_pm + (size_t)cslot * lcap; c.counts = d_cnt + cslot; c.rows = 1; c.slot0 = cslot; c.tab_p = d_tp + (size_t)cslot * n_index;
-    vh_launch_track_scatter(c, nullptr);
-    if (ccnt) VH_HIP(hipMemcpyAsync(d_trk + (size_t)cslot * lcap, carry_in->trk.data(), sizeof(vh_track) * (size_t)ccnt, hipMemcpyHostToDevice, nullptr));
-    t.pred0 = cslot;
-  }
-  t.rows = n_lists; t.slot0 = 0; t.serial0 = carry_in ? carry_in->next_serial : 0;
-  vh_launch_track_scatter(t, nullptr);
-  vh_launch_track_link(t, nullptr);
-  vh_launch_track_rank(t, nullptr);
-  VH_HIP(hipGetLastError());
-  VH_HIP(hipDeviceSynchronize());
-#ifdef VH_CHECK
-  {
-    uint32_t c[4] = {0, 0, 0, 0};
-    VH_HIP(hipMemcpy(c, d_check, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[0]) {
-      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
-      fflush(stderr);
-      abort();
-    }
-  }
-#endif
-  for (int32_t l = 0; l < n_lists; l++)
-    if (counts[l]) VH_HIP(hipMemcpy(out + (size_t)l * stride, d_trk + (size_t)l * lcap, sizeof(vh_track) * (size_t)counts[l], hipMemcpyDeviceToHost));
+    if (counts[l]) VH_HIP(hipMemcpy(out + (size_t)l * stride, ll.d_trk + (size_t)l * ll.lcap, sizeof(vh_track) * (size_t)counts[l], hipMemcpyDeviceToHost));
   if (carry_out) {
     vh_track_carry *c = new vh_track_carry();
     const int32_t last = n_lists - 1;
-    c->next_serial = t.serial0 + n_lists;
+    c->next_serial = ll.serial0 + n_lists;
     if (counts[last]) {
       c->pm.assign(pm + (size_t)last * stride, pm + (size_t)last * stride + counts[last]);
       c->trk.assign(out + (size_t)last * stride, out + (size_t)last * stride + counts[last]);

@@ -149,6 +149,12 @@ int32_t Group::load_ranges(const float *ranges) {
 // ranged: search inside the ranges load_ranges() queued (vh_match_ranged); a handle with multi-stage matching on
 // produces its own (multi_stage_ranges)
 int32_t Group::match(int32_t method, const double *tr16, bool ranged) {
+  const int32_t rc = match_call(method, tr16, ranged);
+  if (rc && rh.on) recon_match_failed();  // (reconstruction: every failed match call is a break)
+  return rc;
+}
+
+int32_t Group::match_call(int32_t method, const double *tr16, bool ranged) {
   if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
   if (!allocated || failed) return VH_ERR_STATE;
   if (sparse && tr16) return VH_ERR_UNSUPPORTED;  // the motion prior does not combine with multi-stage matching
@@ -265,7 +271,9 @@ int32_t Group::match_post(int32_t method, const VhMatchArgs &a, int32_t buf, boo
                            mt.d_mchunk2[buf ^ 1], (int4 *)mt.h_out[buf].dev, mt.h_matches.dev, ref, ps);
   }
   VH_HIP(hipGetLastError());
+  recon_before_link();
   if (trk_on) { const int32_t rt = trk_queue(a, ps); if (rt) return rt; }
+  recon_matched(a);
   // (re-searched, searched) of this launch are read from mt.h_out[buf] by a later choose_loop(); the ranged search reports nothing
   mt.stats_pending[buf] = true; mt.stats_was_spec[buf] = spec; mt.stats_npass[buf] = a.npass;
   VH_HIP(hipEventRecord(ev_post[buf], ps)); ev_post_valid[buf] = true;

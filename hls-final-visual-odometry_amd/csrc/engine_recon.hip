@@ -1,10 +1,12 @@
-// engine_recon.hip -- the host half of vh_reconstruct_tracks (include/viso_hip.h): argument checks, the per-frame
-// tables of Reconstruction (reference src/reconstruction.cpp:27-70) and the transfers around kernels_recon.hip.
+// engine_recon.hip -- the host half of reconstruction (include/viso_hip.h): the per-frame tables of Reconstruction
+// (reference src/reconstruction.cpp:27-70), vh_reconstruct_tracks and its transfers around kernels_recon.hip, and
+// reconstruction from tracked lists -- a sequence handle's (vh_sequence_reconstruct) or the caller's
+// (vh_reconstruct_lists) -- through kernels_recon_gather.hip.
 // Built with -ffp-contract=off: the tables are part of the bit-for-bit contract.
 #include "engine.h"
-#include "vh_recon.h"
 
 #include <numeric>
+#include <optional>
 
 using namespace vh_engine;
 
@@ -62,7 +64,235 @@ void matrix_mul(const double *A, const double *B, int32_t m, int32_t kk, int32_t
 
 thread_local double t_recon_kernel_ms = -1.0;
 
+// The tables of the constructor, setCalibration and update (src/reconstruction.cpp:27-70) for one more frame: Tr == null
+// starts the drive (frame `origin`: Tr_total[0] = Tr_inv_total[0] = eye(4)), otherwise Tr is the motion from the last frame.
+void recon_table_push(const vh_recon_params &r, ReconTable &t, const double *Tr, int64_t origin = 0) {
+  const double K[9] = {r.f, 0, r.cu, 0, r.f, r.cv, 0, 0, 1};
+  double *total = t.total, *inv = t.inv;
+  if (!Tr) {
+    t.frames.clear(); t.first = origin;
+    for (int32_t i = 0; i < 16; i++) total[i] = inv[i] = i % 5 == 0 ? 1.0 : 0.0;
+  } else {
+    double ti[16], cur[16];
+    matrix_inv4(Tr, ti);
+    matrix_mul(total, ti, 4, 4, 4, 4, cur);  // Tr_total.back() * Matrix::inv(Tr)
+    memcpy(total, cur, sizeof(t.total));
+    matrix_inv4(total, inv);                 // Tr_inv_total; the same inverse again is what P_total takes its rows from
+  }
+  t.frames.resize(t.frames.size() + VH_RECON_FRAME_DOUBLES, 0.0);
+  double *f = t.frames.data() + t.frames.size() - VH_RECON_FRAME_DOUBLES;
+  matrix_mul(K, inv, 3, 3, 4, 4, f + VH_RECON_P);  // K * (.).getMat(0,0,2,3): rows 0..2 of the 4 x 4
+  memcpy(f + VH_RECON_TINV, inv, sizeof(t.inv));
+  for (int32_t i = 0; i < 3; i++) f[VH_RECON_C + i] = total[4 * i + 3];
+}
+
+// row 1 of Tr_cam_road (src/reconstruction.cpp:43-53)
+void recon_road(double road[4]) {
+  const double cam_pitch = -0.08, cam_height = 1.6;
+  road[0] = 0.0; road[1] = +cos(cam_pitch); road[2] = -sin(cam_pitch); road[3] = -cam_height;
+}
+
+// ---- reconstruction from tracked lists ------------------------------------------------------------------------------
+// gq: the handle (profile scopes, the allocation test hook), or null for vh_reconstruct_lists
+bool recon_refused(Group *gq) { return gq && gq->alloc_refused(); }
+// VH_POISON=1 (test aid, as Group::dmalloc): a fresh buffer holds 0xA5 bytes
+hipError_t recon_poison(void *q, size_t bytes) {
+  static const bool poison = [] { const char *e = getenv("VH_POISON"); return e && e[0] == '1'; }();
+  return poison ? hipMemset(q, 0xA5, bytes) : hipSuccess;
+}
+
+int32_t recon_grow(ReconHistory &h, Group *gq, ReconHistory::Grown &g, size_t need) {
+  if (g.bytes >= need && g.b.p) return VH_OK;
+  if (recon_refused(gq)) return VH_ERR_HIP;
+  DeviceBlock nb;
+  const size_t want = need + need / 4 + 256;
+  VH_HIP(nb.alloc(want));
+  VH_HIP(recon_poison(nb.p, want));
+  h.bytes += (int64_t)want - (int64_t)g.bytes;
+  g.b = std::move(nb);  // (the old block goes with nb: its readers finished with the last call, which was synchronous)
+  g.bytes = want;
+  return VH_OK;
+}
+
+int32_t recon_ensure_ring(ReconHistory &h, Group *gq, int32_t slots, int32_t cap) {
+  if (h.b_ring.p) return VH_OK;
+  const size_t b_ring = sizeof(VhReconRec) * (size_t)slots * cap, b_count = sizeof(int32_t) * (size_t)slots, b_tot = sizeof(unsigned long long) * 5;
+  DeviceBlock ring, count, totals;
+  if (recon_refused(gq)) return VH_ERR_HIP;
+  VH_HIP(ring.alloc(b_ring));
+  if (recon_refused(gq)) return VH_ERR_HIP;
+  VH_HIP(count.alloc(b_count));
+  if (recon_refused(gq)) return VH_ERR_HIP;
+  VH_HIP(totals.alloc(b_tot));
+  VH_HIP(recon_poison(ring.p, b_ring));
+  VH_HIP(hipMemset(count.p, 0, b_count));
+  h.b_ring = std::move(ring); h.b_count = std::move(count); h.b_totals = std::move(totals);
+  h.ring_slots = slots; h.ring_cap = cap;
+  h.bytes += (int64_t)(b_ring + b_count + b_tot);
+  return VH_OK;
+}
+
+// store -> tails (count) -> grow -> tails (append) -> gather -> solve -> the sorted records.  `a` names the lists, the
+// tail range and `check`; nothing of `h` but its buffers changes, so a failed call can simply be made again.
+int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs a, const ReconTable &tab, const vh_recon_params &r,
+                  std::vector<vh_recon_track> &out, int32_t *accepted) {
+  a.ring = h.b_ring.as<VhReconRec>(); a.ring_count = h.b_count.as<int32_t>(); a.ring_slots = h.ring_slots; a.ring_cap = h.ring_cap;
+  a.totals = h.b_totals.as<unsigned long long>();
+  out.clear(); *accepted = 0;
+  VH_HIP(hipMemsetAsync(a.totals, 0, sizeof(unsigned long long) * 5, st));
+  { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_store", st); vh_launch_recon_store(a, st); }
+  { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_tails", st); vh_launch_recon_tails(a, 0, st); }
+  VH_HIP(hipGetLastError());
+  unsigned long long tot[5] = {0, 0, 0, 0, 0};
+  VH_HIP(hipMemcpyAsync(tot, a.totals, sizeof(unsigned long long) * 3, hipMemcpyDeviceToHost, st));
+  VH_HIP(hipStreamSynchronize(st));
+  if (tot[0] >= (1ull << 24) || tot[2] >= (1ull << 24) || tot[1] > (unsigned long long)INT32_MAX) return VH_ERR_UNSUPPORTED;  // (the appending atomic packs both; offsets are 32 bits)
+  const int32_t ns = (int32_t)tot[0], nt = ns + (int32_t)tot[2];
+  const size_t n_px = (size_t)tot[1];
+  a.n_solved = ns; a.n_tails = nt; a.n_pixels = (int64_t)n_px;
+  // the window of the tables the tracks can reach: a track of a list since tail_lo began at most `history` frames before it
+  a.window0 = std::max(tab.first, a.tail_lo - a.history);
+  const size_t w_doubles = (size_t)(tab.first + tab.count() - a.window0) * VH_RECON_FRAME_DOUBLES;
+  int32_t rc;
+  if ((rc = recon_grow(h, gq, h.g_tails, sizeof(VhReconTail) * (size_t)nt))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_first, sizeof(int32_t) * (size_t)ns))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_off, sizeof(int32_t) * ((size_t)ns + 1)))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_order, sizeof(int32_t) * (size_t)ns))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_px, sizeof(float) * 2 * n_px))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_pts, sizeof(float) * 3 * (size_t)ns))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_st, sizeof(int32_t) * (size_t)ns))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_met, sizeof(double) * 2 * (size_t)ns))) return rc;
+  if ((rc = recon_grow(h, gq, h.g_frames, sizeof(double) * w_doubles))) return rc;
+  if (nt == 0) return VH_OK;
+  a.tails = h.g_tails.b.as<VhReconTail>(); a.first_frame = h.g_first.b.as<int32_t>(); a.offsets = h.g_off.b.as<int32_t>();
+  a.order = h.g_order.b.as<int32_t>(); a.pixels = h.g_px.b.as<float>();
+  VH_HIP(hipMemcpyAsync(h.g_frames.b.p, tab.frames.data() + (size_t)(a.window0 - tab.first) * VH_RECON_FRAME_DOUBLES, sizeof(double) * w_doubles,
+                        hipMemcpyHostToDevice, st));
+  { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_tails", st); vh_launch_recon_tails(a, 1, st); }
+  { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_gather", st); vh_launch_recon_gather(a, st); }
+  double road[4];
+  recon_road(road);
+  {
+    std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_solve", st);
+    vh_launch_recon(r, road, h.g_frames.b.as<double>(), ns, a.order, a.first_frame, a.offsets, a.pixels, h.g_pts.b.as<float>(), h.g_st.b.as<int32_t>(),
+                    h.g_met.b.as<double>(), st);
+  }
+  VH_HIP(hipGetLastError());
+  std::vector<VhReconTail> tails((size_t)nt);
+  std::vector<float> pts(3 * (size_t)ns);
+  std::vector<int32_t> stat((size_t)ns);
+  std::vector<double> met(2 * (size_t)ns);
+  VH_HIP(hipMemcpyAsync(tails.data(), a.tails, sizeof(VhReconTail) * (size_t)nt, hipMemcpyDeviceToHost, st));
+  if (ns) {
+    VH_HIP(hipMemcpyAsync(pts.data(), h.g_pts.b.p, sizeof(float) * 3 * (size_t)ns, hipMemcpyDeviceToHost, st));
+    VH_HIP(hipMemcpyAsync(stat.data(), h.g_st.b.p, sizeof(int32_t) * (size_t)ns, hipMemcpyDeviceToHost, st));
+    VH_HIP(hipMemcpyAsync(met.data(), h.g_met.b.p, sizeof(double) * 2 * (size_t)ns, hipMemcpyDeviceToHost, st));
+  }
+  VH_HIP(hipStreamSynchronize(st));
+#ifdef VH_CHECK
+  if (a.check) {
+    uint32_t c[4] = {0, 0, 0, 0};
+    VH_HIP(hipMemcpy(c, a.check, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[0]) {
+      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
+      fflush(stderr);
+      abort();
+    }
+  }
+#endif
+  out.resize((size_t)nt);
+  for (int32_t t = 0; t < nt; t++) {
+    vh_recon_track &o = out[(size_t)t];
+    const VhReconTail &q = tails[(size_t)t];
+    memset(&o, 0, sizeof(o));
+    o.birth_frame = q.birth_frame; o.birth_pos = q.birth_pos; o.frames = q.frames; o.lost_frame = q.lost_frame;
+    if (t >= ns) { o.status = VH_RECON_HISTORY; continue; }
+    o.status = stat[(size_t)t];
+    for (int32_t i = 0; i < 3; i++) o.point[i] = pts[3 * (size_t)t + i];
+    o.distance = met[2 * (size_t)t]; o.angle = met[2 * (size_t)t + 1];
+  }
+  std::sort(out.begin(), out.end(), [](const vh_recon_track &x, const vh_recon_track &y) {
+    if (x.lost_frame != y.lost_frame) return x.lost_frame < y.lost_frame;
+    if (x.birth_frame != y.birth_frame) return x.birth_frame < y.birth_frame;
+    return x.birth_pos < y.birth_pos;
+  });
+  for (const vh_recon_track &o : out) *accepted += o.status == VH_RECON_ACCEPTED ? 1 : 0;
+  return VH_OK;
+}
+
+// the getters' capacity rule
+int32_t recon_copy_out(const std::vector<vh_recon_track> &res, vh_recon_track *out, int32_t cap, int32_t *n) {
+  *n = (int32_t)res.size();
+  const size_t k = std::min(res.size(), (size_t)cap);
+  if (k) memcpy(out, res.data(), sizeof(vh_recon_track) * k);
+  return res.size() > (size_t)cap ? VH_ERR_CAPACITY : VH_OK;
+}
+
 }  // namespace
+
+// ---- the handle's state (breaks) -------------------------------------------------------------
+namespace vh_engine {
+
+// a push has succeeded; first: the ring of feature sets starts again (first push, new dims)
+void Group::recon_pushed(bool first) {
+  if (!rh.on) return;
+  if (first) { rh.drop_chain(); rh.m_valid = rh.m_done = false; rh.pushes_since_match = 0; }
+  rh.pushes_since_match++;
+}
+
+// Before the lists of a match call are linked.  The chain goes on only if this is the first match call on the chunk
+// pushed right after a chunk that was matched AND reconstructed; every other order is a break.  A break also takes the
+// predecessor away from the track linking, so that vh_track's age and birth -- which the ring stores -- describe the
+// same tracks as the reconstruction: both start again at this chunk.
+void Group::recon_before_link() {
+  if (!rh.on) return;
+  const bool again = rh.pushes_since_match == 0;
+  const bool goes_on = again ? (rh.m_valid && !rh.m_done) : (rh.pushes_since_match == 1 && rh.m_valid && rh.m_done && rh.chain);
+  if (again && goes_on) return;  // the chunk's lists are replaced: the ring has none of them yet
+  if (!goes_on) { rh.drop_chain(); trk_pred_valid = false; trk_carry_src = -1; }
+}
+
+void Group::recon_matched(const VhMatchArgs &a) {
+  if (!rh.on) return;
+  rh.m_valid = true; rh.m_done = false; rh.m_first = seq_first; rh.m_lo = a.seq_lo; rh.m_rows = a.rows; rh.pushes_since_match = 0;
+}
+
+int32_t Group::reconstruct(const double *Tr, int32_t *n_tracks, int32_t *n_accepted) {
+  if (!n_tracks || !n_accepted) return VH_ERR_INVALID_ARG;
+  *n_tracks = *n_accepted = 0;
+  if (!seq || !rh.on || !allocated || !rh.m_valid || rh.m_done) return VH_ERR_STATE;  // (a push since the match call changes nothing)
+  const int64_t F = rh.m_first;
+  const int32_t lo = rh.m_lo, rows = rh.m_rows;
+  if (lo < rows && !Tr) return VH_ERR_INVALID_ARG;
+  if (rh.chain && rh.last != F + lo - 1) rh.drop_chain();  // (cannot happen: recon_before_link keeps the two in step)
+  int32_t rc = recon_ensure_ring(rh, this, rh.history + S, mcap);
+  if (rc) return rc;
+  ReconTable tab;
+  if (rh.chain) tab = rh.table;
+  else recon_table_push(rh.params, tab, nullptr, F + lo - 1);
+  for (int32_t r = lo; r < rows; r++) recon_table_push(rh.params, tab, Tr + 16 * (size_t)r);
+  const bool pred = rh.chain && rh.has_pending;
+  VhReconGatherArgs a{};
+  a.pm = (const vh_p_match *)mt.d_matches; a.pm_stride = mcap; a.counts = mt.d_match_count; a.count_cap = mcap;
+  a.trk = tk.d_trk; a.trk_stride = mcap;
+  a.row_lo = lo; a.rows = rows; a.frame0 = F; a.pred_valid = pred ? 1 : 0; a.history = rh.history;
+  a.tail_lo = pred ? F + lo - 1 : F + lo; a.tail_hi = F + rows - 1;
+  a.check = sets.check;
+  if (lo < rows) {
+    // behind the emission and the linking of the match call, on their stream
+    if ((rc = recon_run(rh, this, post_stream, a, tab, rh.params, rh.result, &rh.accepted))) return rc;
+  } else { rh.result.clear(); rh.accepted = 0; }
+  // the next call reaches back `history` frames from its first tail, the list of frame F + rows - 1
+  const int64_t keep = std::max(tab.first, F + rows - 1 - rh.history - 1);
+  tab.frames.erase(tab.frames.begin(), tab.frames.begin() + (size_t)(keep - tab.first) * VH_RECON_FRAME_DOUBLES);
+  tab.first = keep;
+  rh.table = std::move(tab);
+  rh.chain = true; rh.has_pending = lo < rows; rh.last = F + rows - 1; rh.m_done = true;
+  *n_tracks = (int32_t)rh.result.size(); *n_accepted = rh.accepted;
+  return VH_OK;
+}
+
+}  // namespace vh_engine
 
 extern "C" {
 
@@ -90,26 +320,11 @@ int32_t vh_reconstruct_tracks(const vh_recon_params *r, int32_t device, int32_t 
   if (rc) return rc;
 
   // the tables of the constructor, setCalibration and update (src/reconstruction.cpp:27-70), frame by frame
-  std::vector<double> frames((size_t)n_frames * VH_RECON_FRAME_DOUBLES, 0.0);
-  const double K[9] = {r->f, 0, r->cu, 0, r->f, r->cv, 0, 0, 1};
-  double total[16], inv[16];
-  for (int32_t i = 0; i < 16; i++) total[i] = inv[i] = i % 5 == 0 ? 1.0 : 0.0;  // Tr_total[0] = Tr_inv_total[0] = eye(4)
-  for (int32_t k = 0; k < n_frames; k++) {
-    if (k > 0) {
-      double ti[16], cur[16];
-      matrix_inv4(Tr + (size_t)(k - 1) * 16, ti);
-      matrix_mul(total, ti, 4, 4, 4, 4, cur);  // Tr_total.back() * Matrix::inv(Tr)
-      memcpy(total, cur, sizeof(total));
-      matrix_inv4(total, inv);                 // Tr_inv_total; the same inverse again is what P_total takes its rows from
-    }
-    double *f = frames.data() + (size_t)k * VH_RECON_FRAME_DOUBLES;
-    matrix_mul(K, inv, 3, 3, 4, 4, f + VH_RECON_P);  // K * (.).getMat(0,0,2,3): rows 0..2 of the 4 x 4
-    memcpy(f + VH_RECON_TINV, inv, sizeof(inv));
-    for (int32_t i = 0; i < 3; i++) f[VH_RECON_C + i] = total[4 * i + 3];
-  }
-  // row 1 of Tr_cam_road (src/reconstruction.cpp:43-53)
-  const double cam_pitch = -0.08, cam_height = 1.6;
-  const double road[4] = {0.0, +cos(cam_pitch), -sin(cam_pitch), -cam_height};
+  ReconTable tab;
+  for (int32_t k = 0; k < n_frames; k++) recon_table_push(*r, tab, k ? Tr + (size_t)(k - 1) * 16 : nullptr);
+  const std::vector<double> &frames = tab.frames;
+  double road[4];
+  recon_road(road);
 
   // longest tracks first, so that the lanes of a wave run the same number of frames; outputs go to the track's own index
   std::vector<int32_t> order((size_t)n_tracks);
@@ -153,6 +368,66 @@ int32_t vh_reconstruct_tracks(const vh_recon_params *r, int32_t device, int32_t 
   VH_HIP(hipMemcpy(status, b_st.p, sizeof(int32_t) * (size_t)n_tracks, hipMemcpyDeviceToHost));
   if (metrics) VH_HIP(hipMemcpy(metrics, b_met.p, sizeof(double) * 2 * (size_t)n_tracks, hipMemcpyDeviceToHost));
   return VH_OK;
+}
+
+int32_t vh_sequence_set_reconstruction(vh_group *g, const vh_recon_params *r, int32_t history_frames) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (!gq->seq) return VH_ERR_UNSUPPORTED;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: every list since the first frame has its place in the ring
+  if (!r) { gq->rh.on = false; return VH_OK; }
+  if (history_frames < 1) return VH_ERR_INVALID_ARG;
+  gq->rh.on = true; gq->rh.params = *r; gq->rh.history = history_frames;
+  gq->trk_on = true;
+  return VH_OK;
+}
+
+int32_t vh_sequence_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, int32_t *n_accepted) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (hipSetDevice(gq->device) != hipSuccess) { t_last_error = "hipSetDevice"; return VH_ERR_HIP; }
+  return gq->reconstruct(Tr, n_tracks, n_accepted);
+}
+
+int32_t vh_sequence_get_recon_tracks(vh_group *g, vh_recon_track *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g;
+  if (!gq || !n || cap < 0 || (cap > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!gq->rh.on || !gq->rh.m_done) return VH_ERR_STATE;
+  return recon_copy_out(gq->rh.result, out, cap, n);
+}
+
+int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts,
+                             int32_t n_index, const double *Tr, vh_recon_track *out, int32_t cap, int32_t *n) {
+  if (!r || !n || n_lists < 0 || cap < 0 || (cap > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (n_lists == 0) return VH_OK;
+  if (!counts || !Tr || stride < 0 || n_index < 1) return VH_ERR_INVALID_ARG;
+  int32_t cmax = 0;
+  for (int32_t l = 0; l < n_lists; l++) {
+    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
+    cmax = std::max(cmax, counts[l]);
+  }
+  if (cmax > 0 && !pm) return VH_ERR_INVALID_ARG;
+  if (cmax > (int32_t)VH_TRACK_POS_MASK || (int64_t)n_lists + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;  // (as vh_link_tracks)
+  int32_t rc = select_device(device);
+  if (rc) return rc;
+  LinkedLists ll;
+  if ((rc = link_lists_device(n_lists, pm, stride, counts, n_index, nullptr, nullptr, 0, 0, false, ll))) return rc;
+  ReconHistory h;  // a whole fresh drive: list l is the list of frame l + 1, nothing is older than the history
+  if ((rc = recon_ensure_ring(h, nullptr, n_lists, ll.lcap))) return rc;
+  ReconTable tab;
+  recon_table_push(*r, tab, nullptr);
+  for (int32_t l = 0; l < n_lists; l++) recon_table_push(*r, tab, Tr + 16 * (size_t)l);
+  VhReconGatherArgs a{};
+  a.pm = ll.d_pm; a.pm_stride = ll.lcap; a.counts = ll.d_cnt; a.count_cap = ll.lcap; a.trk = ll.d_trk; a.trk_stride = ll.lcap;
+  a.row_lo = 0; a.rows = n_lists; a.frame0 = 1; a.pred_valid = 0; a.history = n_lists;
+  a.tail_lo = 1; a.tail_hi = n_lists;
+  a.check = ll.d_check;
+  std::vector<vh_recon_track> res;
+  int32_t accepted = 0;
+  if ((rc = recon_run(h, nullptr, nullptr, a, tab, *r, res, &accepted))) return rc;
+  return recon_copy_out(res, out, cap, n);
 }
 
 }  // extern "C"

@@ -115,7 +115,8 @@ struct VhSets {
 // (engine.hip: check_violation) -- loud, but without a wild access on a shared GPU.
 //   codes: 1 rows_tile query position, 2 rows_tile candidate position, 3 row re-search candidate
 //          position, 4 bin_sort row slot, 5 emit_features stage slot, 6 bin_sort staged bin length,
-//          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position
+//          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position,
+//          10 recon_store predecessor position of a continued mark, 11 recon_gather position followed through the ring
 #ifdef VH_CHECK
 #define VH_CHECK_RANGE(s_, code_, x_, lo_, hi_)                                          \
   do {                                                                                   \
@@ -312,6 +313,55 @@ void vh_launch_track_link(const VhTrackArgs &t, hipStream_t st);
 void vh_launch_track_rank(const VhTrackArgs &t, hipStream_t st);
 void vh_launch_track_copy(const VhTrackArgs &t, int32_t src, int32_t dst, hipStream_t st);
 void vh_launch_track_retag(uint32_t *tab, int64_t n_index, int64_t n_slots, int64_t keep0, int64_t keep1, uint32_t live, hipStream_t st);
+
+// Reconstruction from the lists of a handle or of vh_reconstruct_lists (kernels_recon_gather.hip).
+// The ring keeps, per list of the last `ring_slots` frames, one 32-byte record per match record: the list of frame f (the
+// pair f - 1 -> f) lives in slot f % ring_slots.  Both halves of a record are aligned 16-byte vectors; a step of the
+// gather's walk reads one record, and recon_tails reads only the second half.
+struct VhReconRec {
+  float u1p, v1p, u1c, v1c;  // the left camera's pixels in frames f - 1 and f
+  int32_t prev;              // vh_track::prev: position of the continued record in the list of frame f - 1, -1: a head
+  int32_t age;               // vh_track::age: records of the track up to this one
+  int32_t birth_pos;         // vh_track::birth_pos (the birth frame is f - age + 1)
+  int32_t cont;              // 1: a record of the list of frame f + 1 continues this one
+};
+// one lost track, appended by recon_tails (solved tracks from the front of the array, VH_RECON_HISTORY ones from its end)
+struct VhReconTail {
+  int64_t lost_frame, birth_frame;
+  int32_t birth_pos, frames;  // frames = age + 1
+  int32_t pos;                // of the track's last record, in the list of frame lost_frame - 1
+  int32_t px_off;             // first of its `frames` pixels in the gathered array; -1: older than the history, not gathered
+};
+struct VhReconGatherArgs {
+  // recon_store: the lists of rows [row_lo, rows) of a launch and their tracks, addressed as VhTrackArgs does; row r is frame0 + r
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *counts;
+  int32_t count_cap;
+  const vh_track *trk;       // row r at trk + r * trk_stride
+  int64_t trk_stride;
+  int32_t row_lo, rows;
+  int64_t frame0;
+  int32_t pred_valid;        // 0: the list of row_lo has no predecessor in the ring -- its records are stored as heads
+  VhReconRec *ring;          // [ring_slots][ring_cap]
+  int32_t *ring_count;       // [ring_slots]
+  int32_t ring_slots, ring_cap, history;
+  // recon_tails: the lists of frames [tail_lo, tail_hi) have a successor now; totals = {solved tracks, their pixels,
+  // history tracks} of the counting mode, then {solved tracks << 40 | pixels, history tracks} of the appending mode
+  int64_t tail_lo, tail_hi;
+  unsigned long long *totals;
+  VhReconTail *tails;        // [n_tails]
+  int32_t n_tails, n_solved;
+  int64_t n_pixels;
+  // recon_gather: the arrays recon_kernel reads (vh_recon.h); first_frame counts from frame `window0`
+  int64_t window0;
+  int32_t *first_frame, *offsets, *order;
+  float *pixels;
+  uint32_t *check;           // VH_CHECK builds: {violations, code, value, bound}
+};
+void vh_launch_recon_store(const VhReconGatherArgs &a, hipStream_t st);                // the copy, then the continued marks
+void vh_launch_recon_tails(const VhReconGatherArgs &a, int32_t append, hipStream_t st);
+void vh_launch_recon_gather(const VhReconGatherArgs &a, hipStream_t st);
 
 struct vh_ego_params;
 void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,

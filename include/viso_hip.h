@@ -662,6 +662,67 @@ int32_t vh_reconstruct_tracks(const vh_recon_params *r, int32_t device, int32_t 
  * (microseconds beside the call's seven transfers) and one thread-local double; tools/reconstruct_rate.py reads it. */
 double vh_reconstruct_last_kernel_ms(void);
 
+/* ---- reconstruction on a sequence handle: lost tracks gathered on the device (csrc/kernels_recon_gather.hip, DESIGN.md
+ * section 4.8).  The handle already holds the match lists and their vh_track chains on the device; with this switch it
+ * also keeps a ring of compact records (32 bytes per match record: the four left-camera floats, prev, age, birth_pos and
+ * a "continued" mark) for the lists of the last history_frames + max_frames frames, and vh_sequence_reconstruct turns
+ * every track that ended into one vh_recon_track without moving a list to the host.
+ *   Contract: THE LINK RULE of vh_track above decides which record continues which.  Reconstruction::update
+ *   (src/reconstruction.cpp:75-145) extends a track when a match's i1p equals the track's last_idx: the first match in
+ *   list order with a given i1p continues the track, a second one starts a new track, and of two tracks ending in the
+ *   same feature the later one in track order wins.  Track order is (birth update, position in that list), so lost tracks
+ *   leave an update in ascending (birth_frame, birth_pos).  The link rule agrees on the first point and on the order; it
+ *   differs only when a predecessor list holds the same i1c twice (the link rule takes the lowest position, the reference
+ *   the later track).  The result equals Reconstruction::update point for point whenever every list's i1c values are
+ *   distinct.
+ *   Frames: reconstruction frame k is frame k of the sequence (vh_sequence_position).  The list of row r of a chunk pushed
+ *   at position F is the list of the update whose current_frame is F + r, and Tr[r] is that update's Tr, the motion
+ *   F+r-1 -> F+r.  A track whose last record sits in the list of frame c-1 and is continued by no record of the list of
+ *   frame c is lost at frame c; it was seen in frames birth_frame-1 (the head's u1p, v1p) .. c-1, age + 1 frames.  The
+ *   last list of a chunk stays pending until the next chunk's row 0 shows what it continues; tracks alive at the end of
+ *   a drive are never emitted, as in the reference.
+ *   History: a lost track with age > history_frames is not solved: status VH_RECON_HISTORY, zeros for point and metrics.
+ *   Breaks: the reconstruction starts again, as a new Reconstruction constructed at the frame before the chunk's first
+ *   list, when the chunk's dims differ, when a chunk in between was never matched, after a failed match call, when the
+ *   previous chunk was matched but not reconstructed, and when a chunk is matched again after it was reconstructed.
+ *   Pending tracks and the history are dropped, not solved.  A break also takes the predecessor away from the track
+ *   linking: with reconstruction on, vh_track's birth and age start again wherever the reconstruction does.  Matching a
+ *   chunk again BEFORE its reconstruct call only replaces its lists. */
+#define VH_RECON_HISTORY 6       /* older than history_frames: not solved */
+typedef struct vh_recon_track {  /* 56 bytes */
+  int64_t birth_frame;           /* (birth_frame, birth_pos): the vh_track id */
+  int32_t birth_pos;
+  int32_t frames;                /* age + 1 */
+  int64_t lost_frame;
+  int32_t status;                /* VH_RECON_* */
+  float point[3];                /* as points of vh_reconstruct_tracks */
+  double distance, angle;        /* as metrics of vh_reconstruct_tracks */
+} vh_recon_track;
+/* Before the first push only (VH_ERR_STATE afterwards); sequence handles only (VH_ERR_UNSUPPORTED on a plain group).
+ * r == NULL switches the feature off; otherwise history_frames < 1 is VH_ERR_INVALID_ARG (there is no default).  It
+ * switches track linking on; vh_group_set_track_linking(g, 0) returns VH_ERR_STATE while reconstruction is on.
+ * Off (the default): nothing is allocated or launched.  On: 32 * max_matches bytes per ring slot, history_frames +
+ * max_frames slots, plus the gather buffers (they grow with the lost tracks of a call), allocated by the first
+ * vh_sequence_reconstruct and counted by vh_group_device_bytes. */
+int32_t vh_sequence_set_reconstruction(vh_group *g, const vh_recon_params *r, int32_t history_frames);
+/* The lost tracks of the chunk of the last match call: legal once per matched chunk, from the return of that match call
+ * until the next match call -- also after the next chunk has been pushed, so that its detection runs beside this call;
+ * otherwise VH_ERR_STATE.  Tr[rows][16]: one row-major motion per row of that chunk (rows that hold no pair are not read).
+ * Synchronous: waits for the match and the linking, runs recon_store, recon_tails, recon_gather and recon_kernel, and keeps
+ * the records, sorted by (lost_frame, birth_frame, birth_pos), until the next call.  *n_tracks = records, *n_accepted =
+ * those with VH_RECON_ACCEPTED: their points, in order, are what the reference appends to `points` over the same updates.
+ * A failed allocation returns VH_ERR_HIP and changes nothing: the call may be made again. */
+int32_t vh_sequence_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, int32_t *n_accepted);
+/* The records of the last vh_sequence_reconstruct under the getters' capacity rule: VH_ERR_CAPACITY with the true count
+ * in *n and the first cap records written. */
+int32_t vh_sequence_get_recon_tracks(vh_group *g, vh_recon_track *out, int32_t cap, int32_t *n);
+/* The same kernels on caller-owned lists (host pointers, laid out as for vh_link_tracks): a whole fresh drive in one call,
+ * list l is update l of a new Reconstruction (the list of frame l + 1) and Tr[l] its Tr.  The history is n_lists deep, so
+ * no record is VH_RECON_HISTORY; there is no carry.  The path for voted or bucketed lists.  Argument errors as
+ * vh_link_tracks and vh_reconstruct_tracks; n_lists == 0: VH_OK, *n = 0, no device needed; capacity rule as above. */
+int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride,
+                             const int32_t *counts, int32_t n_index, const double *Tr, vh_recon_track *out, int32_t cap, int32_t *n);
+
 /* Which form of the search loops the group currently runs and the last observed share of
  * queries the speculative form had to search again (-1 before the first report).  The
  * searches are exact either way; the library switches between a speculative loop (no accept
@@ -685,6 +746,7 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  * ("detect_nms", "emit_features", "bin_hist", "bin_scan", "bin_fill",
  *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine";
  *  with track linking "track_scatter", "track_link", "track_rank" and, once per chunk of a sequence handle, "track_carry";
+ *  with reconstruction on a sequence handle "recon_store", "recon_tails", "recon_gather", "recon_solve", per vh_sequence_reconstruct;
  *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place)
