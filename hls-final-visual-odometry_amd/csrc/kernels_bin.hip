@@ -14,6 +14,7 @@
 // Matcher::findMatch visits candidates (src/matcher.cpp:243-246) is simply
 // ascending position -- the first-minimum tie-break becomes "lowest position".
 #include "vh_dev.h"
+#include "vh_wave.h"
 #include <algorithm>
 
 // Threads of the one-workgroup-per-set scan.  256, not 1024: a 1024-thread
@@ -68,15 +69,6 @@ __global__ void bin_hist_kernel(VhSets s, int32_t set0) {
   }
 }
 
-__device__ __forceinline__ int32_t scan_wave_inclusive(int32_t v) {
-#pragma unroll
-  for (int32_t d = 1; d < 64; d <<= 1) {
-    const int32_t t = __shfl_up(v, d);
-    if ((int32_t)(threadIdx.x & 63) >= d) v += t;
-  }
-  return v;
-}
-
 // Workgroup-wide exclusive scan of load(0..n-1): every element i is handed to
 // emit(i, prefix, value); returns the total.  EPT consecutive elements per lane
 // and trip, a wave scan of the lane sums and one LDS exchange of the
@@ -91,7 +83,7 @@ __device__ __forceinline__ int32_t scan_exclusive(int32_t n, int32_t *sWave, Loa
     int32_t mine = 0;
 #pragma unroll
     for (int32_t k = 0; k < EPT; k++) { v[k] = (b + k < n) ? load(b + k) : 0; mine += v[k]; }
-    const int32_t incl = scan_wave_inclusive(mine);
+    const int32_t incl = vh_wave_scan(mine);
     if ((tid & 63) == 63) sWave[w] = incl;
     __syncthreads();
     int32_t before = 0, total = 0;

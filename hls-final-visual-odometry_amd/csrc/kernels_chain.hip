@@ -13,6 +13,7 @@
 // The rules around the hops (circle below) are the same, and both kernels write the same things: index tuple,
 // coordinate tuple, pixel-mask bid, survivors per emission chunk.  flow_keep, refine and emit_matches follow either.
 #include "vh_findmatch.h"
+#include "vh_wave.h"
 #include <algorithm>
 
 #ifndef VH_RANGED_G
@@ -131,11 +132,7 @@ __device__ __forceinline__ int32_t find_ranged(const VhSets &s, int32_t qset, in
       }
     }
   }
-#pragma unroll
-  for (int32_t d = VH_RANGED_G / 2; d >= 1; d >>= 1) {
-    const unsigned long long o = __shfl_xor(key, d);
-    key = o < key ? o : key;
-  }
+  key = vh_wave_min_u64<VH_RANGED_G>(key);
   return key == ~0ull ? 0 : s.s_idx[(int64_t)cset * cap + (uint32_t)key];
 }
 
@@ -214,8 +211,7 @@ emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restr
   // matches emitted by earlier chunks
   int32_t part = 0;
   for (int32_t k = tid; k < chunk; k += 256) part += mchunk[stream * nchm + k];
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+  part = vh_wave_sum(part);
   if (lane == 0) sWave[w] = part;
   __syncthreads();
   if (tid == 0) { int32_t t = 0; for (int32_t k = 0; k < 4; k++) t += sWave[k]; sBase = t; }
@@ -247,14 +243,8 @@ emit_matches_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restr
       rec[3 * k + 2] = (uint32_t)idx[k];
     }
   }
-  const uint64_t bal = __ballot(keep);
-  const int32_t before = __popcll(bal & ((1ull << lane) - 1));
-  if (lane == 0) sWave[w] = __popcll(bal);
-  __syncthreads();
-  int32_t woff = 0, tot = 0;
-#pragma unroll
-  for (int32_t k = 0; k < 4; k++) { const int32_t c = sWave[k]; if (k < w) woff += c; tot += c; }
-  const int32_t pos = base + woff + before;
+  const VhCompact cp = vh_compact4(keep, sWave, w, lane);
+  const int32_t pos = base + cp.pos, tot = cp.total;
   if (keep && pos < mcap) {
     uint4 *o = (uint4 *)(out + (int64_t)pos * 12);
     o[0] = make_uint4(rec[0], rec[1], rec[2], rec[3]);

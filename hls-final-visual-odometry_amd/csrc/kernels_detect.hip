@@ -33,6 +33,7 @@
 //   Debug builds: -DVH_EMIT_TIMING[=2] puts phase clocks into emit_features
 //                 [detect_nms_fast] (tools/emit_timing.py).
 #include "vh_dev.h"
+#include "vh_wave.h"
 #include <type_traits>
 
 namespace {
@@ -516,7 +517,7 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
       for (int32_t t = 0; t < 4; t++) {
         const int32_t mm = t & 1;
         const uint32_t first = ((base >> (16 * mm)) & 0xFFFFu) + (t >= 2 ? (mm ? n1 : n0) : 0u);
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal[t] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal[t], 0u));
+        const uint32_t rank = (uint32_t)vh_wave_rank(bal[t]);
         if (cand[t]) sQueue[mm * 512 + first + rank] = (uint32_t)tid | ((uint32_t)t << 8) | (ext[t] << 16);
       }
     }
@@ -622,15 +623,6 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
 // output order).  Phase A: ordered compaction of the chunk's survivors into an
 // LDS list; phase B: 16 lanes per survivor compute its descriptor from the
 // image and the 12-word record is stored with 48-byte-contiguous writes.
-__device__ __forceinline__ int32_t wave_incl_scan(int32_t v) {
-#pragma unroll
-  for (int32_t d = 1; d < 64; d <<= 1) {
-    const int32_t t = __shfl_up(v, d);
-    if ((int32_t)(threadIdx.x & 63) >= d) v += t;
-  }
-  return v;
-}
-
 // sample-point offsets of the 16 (du,dv) pairs, byte order of matcher.cpp:482-513
 __constant__ int8_t c_desc_dx[16] = {-3, -3, -1, -1, +3, +3, +1, +1, -1, -1, +1, +1, -5, -5, +5, +5};
 __constant__ int8_t c_desc_dy[16] = {-1, +1, -1, +1, -1, +1, -1, +1, -5, +5, -5, +5, -3, +3, -3, +3};
@@ -678,9 +670,8 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
     if (chunk * VH_CHUNK + tid * BPL + k >= g.nblocks) clo[k] = chi[k] = ~0u;
     mine += ((clo[k] & 0xFFFFu) != VH_NO_CODE) + ((clo[k] >> 16) != VH_NO_CODE) + ((chi[k] & 0xFFFFu) != VH_NO_CODE) + ((chi[k] >> 16) != VH_NO_CODE);
   }
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
-  const int32_t incl = wave_incl_scan(mine);
+  part = vh_wave_sum(part);
+  const int32_t incl = vh_wave_scan(mine);
   if ((tid & 63) == 63) { sWave[tid >> 6] = incl; sWaveP[tid >> 6] = part; }
   __syncthreads();
   const int32_t base = sWaveP[0] + sWaveP[1] + sWaveP[2] + sWaveP[3];

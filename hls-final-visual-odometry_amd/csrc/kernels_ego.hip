@@ -4,7 +4,7 @@
 //   VisualOdometryStereo::estimateMotion              (reference src/viso_stereo.cpp:54-157)
 //   ...::getInlier / updateParameters / computeObservations / computeResidualsAndJacobian
 //                                                     (src/viso_stereo.cpp:159-330)
-//   Matrix::solve on the 6x6 normal equations         (src/matrix.cpp:417-504)
+//   Matrix::solve on the 6x6 normal equations         (src/matrix.cpp:417-504; vh_gauss_jordan.h)
 //   VisualOdometry::getRandomSample(N,3)              (src/viso.cpp:86-106), from caller-supplied rand() values
 //
 // One 256-thread workgroup per stream, double precision throughout, built with
@@ -24,6 +24,9 @@
 #include "vh_dev.h"
 #include "../../include/viso_hip.h"
 #include <math.h>
+#include "vh_wave.h"
+#define SVD_HD __device__ __forceinline__
+#include "vh_gauss_jordan.h"
 
 namespace {
 
@@ -97,78 +100,18 @@ __device__ __forceinline__ void ego_accumulate(const vh_ego_params &e, const Ego
   }
 }
 
-// Matrix::solve for the 6x6 system (src/matrix.cpp:417-504): Gauss-Jordan with full pivoting,
-// singular below 1e-20.  acc as produced by ego_accumulate; on success b = the solution.
-// Every array index is a compile-time constant after unrolling -- the pivot's row and column (data-dependent in
-// the original) select among the six rows / columns by predicates -- so the system lives in registers: with
-// dynamic indices it sat in private memory, and the 22 dependent solves of a hypothesis were 85 % of the
-// kernel (1.2 of 1.4 ms per batch of bucketed lists, tools/ego_phases.py).  The arithmetic applied to the
-// elements, and its order, are the original's.
-__device__ bool ego_solve(const double acc[27], double b[6]) {
+// Matrix::solve for the 6x6 normal equations: acc as produced by ego_accumulate is unpacked into the full symmetric
+// matrix, vh_gauss_jordan.h does the rest; on success b = the solution.
+__device__ bool ego_solve(const double acc[27], double (&b)[6]) {
   double A[6][6];
-  {
-    int32_t k = 0;
+  int32_t k = 0;
 #pragma unroll
-    for (int32_t m = 0; m < 6; m++)
+  for (int32_t m = 0; m < 6; m++)
 #pragma unroll
-      for (int32_t n = m; n < 6; n++) { A[m][n] = acc[k]; A[n][m] = acc[k]; k++; }
+    for (int32_t n = m; n < 6; n++) { A[m][n] = acc[k]; A[n][m] = acc[k]; k++; }
 #pragma unroll
-    for (int32_t m = 0; m < 6; m++) b[m] = acc[21 + m];
-  }
-  int32_t ipiv[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int32_t i = 0; i < 6; i++) {
-    double big = 0.0;
-    int32_t irow = 0, icol = 0;
-#pragma unroll
-    for (int32_t j = 0; j < 6; j++)
-#pragma unroll
-      for (int32_t k = 0; k < 6; k++) {
-        const double v = fabs(A[j][k]);
-        if (ipiv[j] != 1 && ipiv[k] == 0 && v >= big) { big = v; irow = j; icol = k; }
-      }
-#pragma unroll
-    for (int32_t q = 0; q < 6; q++) ipiv[q] += q == icol ? 1 : 0;
-    // rows irow and icol change places (nothing moves when they are the same row)
-    double ri[6], rc[6], bi = 0.0, bc = 0.0;
-#pragma unroll
-    for (int32_t l = 0; l < 6; l++) { ri[l] = 0.0; rc[l] = 0.0; }
-#pragma unroll
-    for (int32_t r = 0; r < 6; r++) {
-#pragma unroll
-      for (int32_t l = 0; l < 6; l++) { ri[l] = r == irow ? A[r][l] : ri[l]; rc[l] = r == icol ? A[r][l] : rc[l]; }
-      bi = r == irow ? b[r] : bi; bc = r == icol ? b[r] : bc;
-    }
-#pragma unroll
-    for (int32_t r = 0; r < 6; r++) {
-#pragma unroll
-      for (int32_t l = 0; l < 6; l++) A[r][l] = r == icol ? ri[l] : (r == irow ? rc[l] : A[r][l]);
-      b[r] = r == icol ? bi : (r == irow ? bc : b[r]);
-    }
-    // the pivot row (now row icol) is ri, its right-hand side bi
-    double piv = 0.0;
-#pragma unroll
-    for (int32_t l = 0; l < 6; l++) piv = l == icol ? ri[l] : piv;
-    if (fabs(piv) < 1e-20) return false;
-    const double pivinv = 1.0 / piv;
-#pragma unroll
-    for (int32_t l = 0; l < 6; l++) ri[l] = (l == icol ? 1.0 : ri[l]) * pivinv;
-    bi *= pivinv;
-#pragma unroll
-    for (int32_t ll = 0; ll < 6; ll++) {
-      double dum = 0.0;
-#pragma unroll
-      for (int32_t l = 0; l < 6; l++) dum = l == icol ? A[ll][l] : dum;
-      const bool prow = ll == icol;
-#pragma unroll
-      for (int32_t l = 0; l < 6; l++) {
-        const double cur = l == icol ? 0.0 : A[ll][l];
-        A[ll][l] = prow ? ri[l] : cur - ri[l] * dum;
-      }
-      b[ll] = prow ? bi : b[ll] - bi * dum;
-    }
-  }
-  return true;
+  for (int32_t m = 0; m < 6; m++) b[m] = acc[21 + m];
+  return vh_gauss_jordan<6>(A, b);
 }
 
 __device__ __forceinline__ EgoObs ego_load(const vh_p_match *pm, const double *X, const double *Y, const double *Z, int32_t i) {
@@ -209,8 +152,9 @@ ego_kernel(vh_ego_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_s
   __shared__ int32_t sWave[EGO_T / 64], sFlag, sBase;
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // matches of this stream: a slice of a concatenated list (offsets) or a fixed-stride slot with a device-side count
-  const vh_p_match *pm = offsets ? pm_base + offsets[s] : pm_base + (int64_t)s * pm_stride;
-  const int32_t n = offsets ? offsets[s + 1] - offsets[s] : min(counts[s], count_cap);
+  const VhList L = vh_list(s, pm_base, pm_stride, offsets, counts, count_cap);
+  const vh_p_match *pm = L.pm;
+  const int32_t n = L.n;
   double *X = xyz + (int64_t)s * xyz_stride * 4, *Y = X + xyz_stride, *Z = Y + xyz_stride, *F = Z + xyz_stride;  // F: inlier flags of the winner
   int32_t *inl = inl_out ? inl_out + (offsets ? (int64_t)offsets[s] : (int64_t)s * inl_stride) : nullptr;
   if (n < 6) {  // src/viso_stereo.cpp:68-69
@@ -276,12 +220,7 @@ ego_kernel(vh_ego_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_s
       }
     }
     // 3. the best hypothesis so far: wave arg max, then across waves
-    unsigned long long best = key;
-#pragma unroll
-    for (int32_t d = 32; d >= 1; d >>= 1) {
-      const unsigned long long other = ((unsigned long long)(uint32_t)__shfl_xor((int32_t)(best >> 32), d) << 32) | (uint32_t)__shfl_xor((int32_t)(uint32_t)best, d);
-      best = other > best ? other : best;
-    }
+    const unsigned long long best = vh_wave_max_u64(key);
     if (lane == 0 && best) atomicMax(&sBestKey, best);
     __syncthreads();
     if (key && key == sBestKey) for (int32_t m = 0; m < 6; m++) sTr[m] = t6[m];  // unique: the hypothesis number is part of the key
@@ -302,14 +241,10 @@ ego_kernel(vh_ego_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_s
       const int32_t i = i0 + tid;
       const bool in_ = i < n && ego_is_inlier(e, R, tr, ego_load(pm, X, Y, Z, i));
       if (i < n) F[i] = in_ ? 1.0 : 0.0;
-      const uint64_t bal = __ballot(in_);
-      if (lane == 0) sWave[w] = __popcll(bal);
+      const VhCompact c = vh_compact4(in_, sWave, w, lane);
+      if (in_ && inl) inl[sBase + c.pos] = i;
       __syncthreads();
-      int32_t off = sBase;
-      for (int32_t q = 0; q < w; q++) off += sWave[q];
-      if (in_ && inl) inl[off + __popcll(bal & ((1ull << lane) - 1))] = i;
-      __syncthreads();
-      if (tid == 0) sBase += sWave[0] + sWave[1] + sWave[2] + sWave[3];
+      if (tid == 0) sBase += c.total;
       __syncthreads();
     }
   }
@@ -328,9 +263,7 @@ ego_kernel(vh_ego_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_s
         if (F[i] != 0.0) ego_accumulate(e, R, tr, o, acc);  // the inlier set of the RANSAC winner, fixed
       }
       for (int32_t q = 0; q < 27; q++) {
-        double v = acc[q];
-#pragma unroll
-        for (int32_t d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+        const double v = vh_wave_sum(acc[q]);
         if (lane == 0) sAcc[w][q] = v;
       }
       __syncthreads();

@@ -30,6 +30,7 @@
 //    again exactly, in groups sharing one walk (finish_tile / RedoGroup).  Either way the result
 //    is findMatch's; engine.hip picks the form per launch from the observed share of such queries.
 #include "vh_findmatch.h"
+#include "vh_wave.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -58,17 +59,6 @@ extern "C" int32_t vh_debug_flow_stats(unsigned long long *out, int32_t reset) {
 #endif
 
 namespace {
-
-__device__ __forceinline__ int32_t wave_min(int32_t v) {
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) v = min(v, __shfl_xor(v, d));
-  return v;
-}
-__device__ __forceinline__ int32_t wave_max(int32_t v) {
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d));
-  return v;
-}
 
 // All-reduce over each 16-lane row of the wave with DPP row rotations (no LDS, no
 // bpermute): afterwards every lane holds the extremum of its row.
@@ -256,15 +246,6 @@ __device__ __forceinline__ uint64_t tested_key_uniform_query(const uint32_t (&qd
   const uint32_t sad = sad32(make_uint4(qd[0], qd[1], qd[2], qd[3]), make_uint4(qd[4], qd[5], qd[6], qd[7]), b0, b1, 0);
   return out ? ~0ull : (((uint64_t)sad << 32) | relpos);
 }
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t k, int32_t d) {
-  const uint32_t lo = (uint32_t)__shfl_xor((int32_t)(uint32_t)k, d), hi = (uint32_t)__shfl_xor((int32_t)(uint32_t)(k >> 32), d);
-  return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t k) {
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) k = min(k, shfl_xor_u64(k, d));
-  return k;
-}
 
 // Match keys.  The minimum of (SAD, bin-order position relative to the first position of
 // the class) in lexicographic order is findMatch's first strict minimum (matcher.cpp:264),
@@ -310,7 +291,7 @@ __device__ __forceinline__ int32_t join_phases(const typename KeyT<KM>::type (&b
     for (int32_t qi = 0; qi < Q; qi++) {
       k[qi] = (uint64_t)best_key[qi];
 #pragma unroll
-      for (int32_t d = 16; d < 64; d <<= 1) k[qi] = min(k[qi], shfl_xor_u64(k[qi], d));
+      for (int32_t d = 16; d < 64; d <<= 1) k[qi] = min(k[qi], vh_shfl_xor_u64(k[qi], d));
     }
     const uint64_t kk = (threadIdx.x & 32) ? k[1] : k[0];
     return kk == ~0ull ? -1 : (int32_t)(uint32_t)kk;
@@ -459,7 +440,7 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
 #pragma unroll
         for (int32_t k = 0; k < VH_REDO_G; k++)
           if (k < g.n) {
-            const uint64_t kf = wave_min_u64(kk[k]);
+            const uint64_t kf = vh_wave_min_u64(kk[k]);
             int32_t wp = (int32_t)(uint32_t)kf;
             if (kf != ~0ull) VH_CHECK_RANGE(s, 7, wp, 0, pcnt);
             if (lane == g.lane[k]) res = kf == ~0ull ? -1 : pbase + wp;

@@ -35,6 +35,7 @@
 #include <math.h>
 #define SVD_HD __device__ __forceinline__
 #include "svd_static.h"
+#include "vh_wave.h"
 
 namespace {
 
@@ -261,8 +262,9 @@ __host__ __device__ inline int64_t mono_per_list(int64_t cap) { return (236 * ca
 __device__ __forceinline__ MonoList mono_list(int32_t s, const vh_p_match *pm_base, int64_t pm_stride, const int32_t *offsets,
                                               const int32_t *counts, int32_t count_cap, uint8_t *scratch, int64_t cap) {
   MonoList L;
-  L.pm = offsets ? pm_base + offsets[s] : pm_base + (int64_t)s * pm_stride;
-  L.n = offsets ? offsets[s + 1] - offsets[s] : min(counts[s], count_cap);
+  const VhList l = vh_list(s, pm_base, pm_stride, offsets, counts, count_cap);
+  L.pm = l.pm;
+  L.n = l.n;
   uint8_t *b = scratch + (int64_t)s * mono_per_list(cap);
   L.pn = (float4 *)b; b += 16 * cap;
   L.A = (double *)b; b += 72 * cap;
@@ -781,18 +783,14 @@ mono_final_a_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, in
     for (int32_t i0 = 0; i0 < N; i0 += MONO_T) {
       const int32_t i = i0 + tid;
       const bool in_ = i < N && sampson_inlier(F, L.pn[min(i, N - 1)], e.inlier_threshold);
-      const uint64_t bal = __ballot(in_);
-      if (lane == 0) sWave[wv] = __popcll(bal);
-      __syncthreads();
-      int32_t off = sBase;
-      for (int32_t q = 0; q < wv; q++) off += sWave[q];
+      const VhCompact c = vh_compact4(in_, sWave, wv, lane);
       if (in_) {
-        const int32_t p = off + __popcll(bal & ((1ull << lane) - 1));
+        const int32_t p = sBase + c.pos;
         L.idx[p] = i;
         if (inl) inl[p] = i;
       }
       __syncthreads();
-      if (tid == 0) sBase += sWave[0] + sWave[1] + sWave[2] + sWave[3];
+      if (tid == 0) sBase += c.total;
       __syncthreads();
     }
   }
@@ -938,20 +936,16 @@ mono_final_c_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, in
       if (wq != 0) { x = Xb[i] / wq; y = Xb[(int64_t)cap + i] / wq; z = Xb[(int64_t)2 * cap + i] / wq; }
     }
     const bool front = i < N && z > 0;
-    const uint64_t bal = __ballot(front);
-    if (lane == 0) sWave[wv] = __popcll(bal);
-    __syncthreads();
-    int32_t off = sBase;
-    for (int32_t q = 0; q < wv; q++) off += sWave[q];
+    const VhCompact c = vh_compact4(front, sWave, wv, lane);
     if (front) {
-      const int32_t p = off + __popcll(bal & ((1ull << lane) - 1));
+      const int32_t p = sBase + c.pos;
       L.dist[p] = fabs(x) + fabs(y) + fabs(z);
       double dd = 0.0;
       dd += n0 * y; dd += n1 * z;
       L.d[p] = dd;
     }
     __syncthreads();
-    if (tid == 0) sBase += sWave[0] + sWave[1] + sWave[2] + sWave[3];
+    if (tid == 0) sBase += c.total;
     __syncthreads();
   }
   const int32_t np = sBase;

@@ -6,7 +6,7 @@
 //   Reconstruction::pointType                       (src/reconstruction.cpp:235-261)
 //   Reconstruction::refinePoint / updatePoint / computeObservations / computePredictionsAndJacobian
 //                                                   (src/reconstruction.cpp:184-207, 263-349)
-//   Matrix::solve on the 3x3 normal equations       (src/matrix.cpp:417-504)
+//   Matrix::solve on the 3x3 normal equations       (src/matrix.cpp:417-504; vh_gauss_jordan.h)
 //   Reconstruction::pointDistance, rayAngle         (src/reconstruction.cpp:209-233)
 // The tables the reference keeps per frame (P_total, Tr_inv_total, Tr_total) come from the host (vh_recon.h).
 //
@@ -17,77 +17,18 @@
 // hands the tracks out sorted by length (order[]), so that the lanes of a wave run the same number of frames.
 // The Jacobian is not stored: frame by frame, its two rows are added to the nine sums, which is the order in which
 // the reference's loops over i = 0 .. 2 len - 1 add them.  All per-lane arrays are indexed by compile-time constants after
-// unrolling (svd_static.h; recon_solve3 as ego_solve of kernels_ego.hip), so they live in registers.
+// unrolling (svd_static.h, vh_gauss_jordan.h), so they live in registers.
 // The only device-library functions are sqrt (correctly rounded) and acos (the ray angle: to rounding, not bit for bit).
 #include "vh_recon.h"
 #include "../../include/viso_hip.h"
 #include <math.h>
 #define SVD_HD __device__ __forceinline__
 #include "svd_static.h"
+#include "vh_gauss_jordan.h"
 
 namespace {
 
 #define RECON_T 64
-
-// Matrix::solve (src/matrix.cpp:417-504) for the 3x3 system: Gauss-Jordan with full pivoting, singular below 1e-20.
-// The pivot's row and column select among the three rows / columns by predicates; the arithmetic and its order are the
-// original's.  A is the full matrix (the reference fills all nine entries; A[m][n] and A[n][m] are the same sums).
-__device__ __forceinline__ bool recon_solve3(double (&A)[3][3], double (&b)[3]) {
-  int32_t ipiv[3] = {0, 0, 0};
-  int32_t irow = 0, icol = 0;  // (kept from pivot to pivot, as the original's are: a search that finds nothing -- NaN -- reuses them)
-#pragma unroll
-  for (int32_t i = 0; i < 3; i++) {
-    double big = 0.0;
-#pragma unroll
-    for (int32_t j = 0; j < 3; j++)
-#pragma unroll
-      for (int32_t k = 0; k < 3; k++) {
-        const double v = fabs(A[j][k]);
-        if (ipiv[j] != 1 && ipiv[k] == 0 && v >= big) { big = v; irow = j; icol = k; }
-      }
-#pragma unroll
-    for (int32_t q = 0; q < 3; q++) ipiv[q] += q == icol ? 1 : 0;
-    // rows irow and icol change places (nothing moves when they are the same row)
-    double ri[3], rc[3], bi = 0.0, bc = 0.0;
-#pragma unroll
-    for (int32_t l = 0; l < 3; l++) { ri[l] = 0.0; rc[l] = 0.0; }
-#pragma unroll
-    for (int32_t r = 0; r < 3; r++) {
-#pragma unroll
-      for (int32_t l = 0; l < 3; l++) { ri[l] = r == irow ? A[r][l] : ri[l]; rc[l] = r == icol ? A[r][l] : rc[l]; }
-      bi = r == irow ? b[r] : bi; bc = r == icol ? b[r] : bc;
-    }
-#pragma unroll
-    for (int32_t r = 0; r < 3; r++) {
-#pragma unroll
-      for (int32_t l = 0; l < 3; l++) A[r][l] = r == icol ? ri[l] : (r == irow ? rc[l] : A[r][l]);
-      b[r] = r == icol ? bi : (r == irow ? bc : b[r]);
-    }
-    // the pivot row (now row icol) is ri, its right-hand side bi
-    double piv = 0.0;
-#pragma unroll
-    for (int32_t l = 0; l < 3; l++) piv = l == icol ? ri[l] : piv;
-    if (fabs(piv) < 1e-20) return false;
-    const double pivinv = 1.0 / piv;
-#pragma unroll
-    for (int32_t l = 0; l < 3; l++) ri[l] = (l == icol ? 1.0 : ri[l]) * pivinv;
-    bi *= pivinv;
-#pragma unroll
-    for (int32_t ll = 0; ll < 3; ll++) {
-      double dum = 0.0;
-#pragma unroll
-      for (int32_t l = 0; l < 3; l++) dum = l == icol ? A[ll][l] : dum;
-      const bool prow = ll == icol;
-#pragma unroll
-      for (int32_t l = 0; l < 3; l++) {
-        const double cur = l == icol ? 0.0 : A[ll][l];
-        A[ll][l] = prow ? ri[l] : cur - ri[l] * dum;
-      }
-      b[ll] = prow ? bi : b[ll] - bi * dum;
-    }
-  }
-  return true;
-}
 
 // row `row` of (4x4 M) * (x, y, z, 1) in Matrix::operator*'s order (src/matrix.cpp:271-276): C = 0, C += A[i][k] * B[k], k ascending
 __device__ __forceinline__ double recon_row4(const double *M, int32_t row, double x, double y, double z, double w) {
@@ -177,7 +118,7 @@ recon_kernel(vh_recon_params r, double road0, double road1, double road2, double
         updated = false;
         if (!singular) {
           double A[3][3] = {{A00, A01, A02}, {A01, A11, A12}, {A02, A12, A22}}, B[3] = {B0, B1, B2};
-          if (recon_solve3(A, B)) {
+          if (vh_gauss_jordan<3>(A, B)) {
 #pragma unroll
             for (int32_t i = 0; i < 3; i++) p[i] = (float)((double)p[i] + 1.0 * B[i]);
             converged = fabs(B[0]) < 1e-5 && fabs(B[1]) < 1e-5 && fabs(B[2]) < 1e-5;

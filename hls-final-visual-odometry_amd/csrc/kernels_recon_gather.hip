@@ -17,6 +17,7 @@
 // Gather / scatter kernels bound by random sectors (as kernels_track.hip): a walk step is one dependent 32-byte record.
 // Every store is a plain vector store.  Indices that address a STORE are bounded in the shipped build too.
 #include "vh_dev.h"
+#include "vh_wave.h"
 #include "../../include/viso_hip.h"
 
 #include <algorithm>
@@ -62,19 +63,6 @@ __global__ void __launch_bounds__(256) recon_mark_kernel(VhReconGatherArgs a) {
   }
 }
 
-__device__ inline int32_t wave_scan(int32_t v) {  // inclusive, over the 64 lanes
-  const int32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int32_t d = 1; d < 64; d <<= 1) {
-    const int32_t o = __shfl_up(v, d, 64);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-__device__ inline int32_t lanes_below(uint64_t mask) {
-  return (int32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
-
 template <int APPEND> __global__ void __launch_bounds__(256) recon_tails_kernel(VhReconGatherArgs a) {
   const int64_t frame = a.tail_lo + blockIdx.y;
   const int32_t slot = rg_slot(a, frame), n = a.ring_count[slot], lane = threadIdx.x & 63;
@@ -86,7 +74,7 @@ template <int APPEND> __global__ void __launch_bounds__(256) recon_tails_kernel(
     const bool lost = h.w == 0, old = lost && h.y > a.history, solved = lost && !old;
     const uint64_t m_solved = __ballot(solved), m_old = __ballot(old);
     if ((m_solved | m_old) == 0) continue;
-    const int32_t frames = h.y + 1, incl = wave_scan(solved ? frames : 0), px = __shfl(incl, 63, 64);
+    const int32_t frames = h.y + 1, incl = vh_wave_scan(solved ? frames : 0), px = __shfl(incl, 63, 64);
     const int32_t ns = __popcll(m_solved), no = __popcll(m_old);
     if (!APPEND) {
       if (lane == 0) {
@@ -105,11 +93,11 @@ template <int APPEND> __global__ void __launch_bounds__(256) recon_tails_kernel(
     VhReconTail t;
     t.lost_frame = frame + 1; t.birth_frame = frame - h.y + 1; t.birth_pos = h.z; t.frames = frames; t.pos = j;
     if (solved) {
-      const int64_t idx = (int64_t)(b >> 40) + lanes_below(m_solved), off = (int64_t)(b & ((1ull << 40) - 1)) + incl - frames;
+      const int64_t idx = (int64_t)(b >> 40) + vh_wave_rank(m_solved), off = (int64_t)(b & ((1ull << 40) - 1)) + incl - frames;
       t.px_off = (int32_t)off;
       if (idx < a.n_solved && off + frames <= a.n_pixels) a.tails[idx] = t;
     } else if (old) {
-      const int64_t idx = (int64_t)a.n_tails - 1 - ((int64_t)ob + lanes_below(m_old));
+      const int64_t idx = (int64_t)a.n_tails - 1 - ((int64_t)ob + vh_wave_rank(m_old));
       t.px_off = -1;
       if (idx >= a.n_solved && idx < a.n_tails) a.tails[idx] = t;
     }

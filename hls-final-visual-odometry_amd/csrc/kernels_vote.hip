@@ -26,6 +26,7 @@
 //
 // Built with -ffp-contract=off (Makefile): every float product-sum rounds as on the reference's x86 build.
 #include "vh_dev.h"
+#include "vh_wave.h"
 #include "../../include/viso_hip.h"
 #define VH_SH_DEVICE 1
 #include "vh_vote.h"  // (includes sweep_hull.h in its 16-bit-link form)
@@ -35,33 +36,6 @@ namespace {
 
 using vh_sh::kNone;
 using vh_sh::Pt;
-
-__device__ __forceinline__ uint64_t lanes_below() { return (1ull << (threadIdx.x & 63)) - 1ull; }
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-    const uint64_t o = ((uint64_t)hi << 32) | lo;
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int32_t wave_sum_i32(int32_t v) {
-#pragma unroll
-  for (int32_t d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-// inclusive prefix sum over the wave's lanes
-__device__ __forceinline__ int32_t wave_scan_i32(int32_t v) {
-  const int32_t lane = threadIdx.x & 63;
-#pragma unroll
-  for (int32_t d = 1; d < 64; d <<= 1) {
-    const int32_t o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
 
 // Stable least-significant-digit radix sort of n (key, value) pairs by ONE wave, 8 bits per pass.
 // a holds the input; a and b are the ping-pong buffers; the result is in the returned buffer.
@@ -85,7 +59,7 @@ __device__ uint2 *wave_radix_sort(uint2 *a, uint2 *b, int32_t n, uint32_t *hist,
     const uint32_t *h = hist + 256 * pass;
     const uint32_t c0 = h[4 * lane], c1 = h[4 * lane + 1], c2 = h[4 * lane + 2], c3 = h[4 * lane + 3];
     if (__ballot(c0 == (uint32_t)n || c1 == (uint32_t)n || c2 == (uint32_t)n || c3 == (uint32_t)n)) continue;  // one digit holds them all
-    const int32_t incl = wave_scan_i32((int32_t)(c0 + c1 + c2 + c3));
+    const int32_t incl = vh_wave_scan((int32_t)(c0 + c1 + c2 + c3));
     uint32_t run = (uint32_t)incl - (c0 + c1 + c2 + c3);
     base[4 * lane] = run; run += c0;
     base[4 * lane + 1] = run; run += c1;
@@ -104,7 +78,7 @@ __device__ uint2 *wave_radix_sort(uint2 *a, uint2 *b, int32_t n, uint32_t *hist,
         const uint64_t m = __ballot((digit >> bit) & 1u);
         peers &= ((digit >> bit) & 1u) ? m : ~m;
       }
-      const int32_t rank = __popcll(peers & lanes_below());
+      const int32_t rank = vh_wave_rank(peers);
       const uint32_t at = live ? base[digit] : 0;
       __syncthreads();  // every lane has read its digit's cursor before the first lane of each group advances it
       if (live && rank == 0) base[digit] = at + (uint32_t)__popcll(peers);
@@ -181,7 +155,7 @@ __global__ __launch_bounds__(64) void vote_order_kernel(VhVote vt) {
       best = k < best ? k : best;
     }
   }
-  best = wave_min_u64(best);
+  best = vh_wave_min_u64(best);
   if (__ballot(!plain) || best == ~0ull) {  // NaN or infinite coordinates: not a list this matcher produces
     if (lane == 0) { m.status = VH_VOTE_UNSUPPORTED; }
     return;
@@ -209,7 +183,7 @@ __global__ __launch_bounds__(64) void vote_order_kernel(VhVote vt) {
       best = k < best ? k : best;
     }
   }
-  best = wave_min_u64(best);
+  best = vh_wave_min_u64(best);
   int32_t s1 = kNone, s2 = kNone;
   if (best != ~0ull) {
     s1 = (int32_t)(uint32_t)best;
@@ -224,7 +198,7 @@ __global__ __launch_bounds__(64) void vote_order_kernel(VhVote vt) {
         best = k < best ? k : best;
       }
     }
-    best = wave_min_u64(best);
+    best = vh_wave_min_u64(best);
     if (best != ~0ull) s2 = (int32_t)(uint32_t)best;
   }
   // the seeds' ranks
@@ -350,7 +324,7 @@ __global__ __launch_bounds__(64) void vote_select_kernel(VhVote vt, int32_t max_
       if (keep) { const int4 *q = (const int4 *)(pm + i); w0 = q[0]; w1 = q[1]; w2 = q[2]; }
       const uint64_t mask = __ballot(keep);
       __syncthreads();  // (the step's loads have landed before its stores go out)
-      if (keep) { int4 *d = (int4 *)(pm + kept + __popcll(mask & lanes_below())); d[0] = w0; d[1] = w1; d[2] = w2; }
+      if (keep) { int4 *d = (int4 *)(pm + kept + vh_wave_rank(mask)); d[0] = w0; d[1] = w1; d[2] = w2; }
       kept += __popcll(mask);
       __syncthreads();
     }
@@ -407,7 +381,7 @@ __global__ __launch_bounds__(64) void vote_select_kernel(VhVote vt, int32_t max_
     const int32_t b = b0 + lane;
     const int32_t len = b < nb ? bstart[b + 1] : 0;
     const int32_t steps = len > 1 ? len - 1 : 0, take = len < max_features ? len : max_features;
-    const int32_t i_len = wave_scan_i32(len), i_steps = wave_scan_i32(steps), i_take = wave_scan_i32(take);
+    const int32_t i_len = vh_wave_scan(len), i_steps = vh_wave_scan(steps), i_take = vh_wave_scan(take);
     __syncthreads();
     if (b < nb) { bstart[b] = run_start + i_len - len; boff[b] = run_off + i_steps - steps; bout[b] = run_out + i_take - take; }
     run_start += __shfl(i_len, 63); run_off += __shfl(i_steps, 63); run_out += __shfl(i_take, 63);

@@ -33,6 +33,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/viso_hip.h"
 
 #define VH_MARGIN 7          // src/matcher.cpp:38
 #ifndef VH_CHUNK
@@ -362,6 +363,20 @@ struct VhReconGatherArgs {
 void vh_launch_recon_store(const VhReconGatherArgs &a, hipStream_t st);                // the copy, then the continued marks
 void vh_launch_recon_tails(const VhReconGatherArgs &a, int32_t append, hipStream_t st);
 void vh_launch_recon_gather(const VhReconGatherArgs &a, hipStream_t st);
+
+// The match list of problem s of an estimator launch (vh_launch_ego, vh_launch_mono): a slice of one concatenated list
+// (offsets, n_sets + 1 entries) or a fixed-stride slot whose count lives on the device (counts, clamped to count_cap).
+struct VhList {
+  const vh_p_match *pm;
+  int32_t n;
+};
+__device__ __forceinline__ VhList vh_list(int32_t s, const vh_p_match *pm_base, int64_t pm_stride, const int32_t *offsets,
+                                          const int32_t *counts, int32_t count_cap) {
+  VhList L;
+  L.pm = offsets ? pm_base + offsets[s] : pm_base + (int64_t)s * pm_stride;
+  L.n = offsets ? offsets[s + 1] - offsets[s] : min(counts[s], count_cap);
+  return L;
+}
 
 struct vh_ego_params;
 void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,

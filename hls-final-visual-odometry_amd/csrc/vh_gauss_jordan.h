@@ -1,0 +1,80 @@
+// vh_gauss_jordan.h -- Matrix::solve (reference src/matrix.cpp:417-504) for an N x N system with one right-hand side:
+// Gauss-Jordan elimination with full pivoting, singular below 1e-20.  On success b holds the solution (A is destroyed).
+//
+// Every array index is a compile-time constant after unrolling -- the pivot's row and column (data-dependent in the
+// original) select among the N rows / columns by predicates -- so the system lives in registers: with dynamic indices
+// the 6x6 system of the stereo estimator sat in private memory, and the 22 dependent solves of a hypothesis were 85 %
+// of ego_kernel (1.2 of 1.4 ms per batch of bucketed lists, tools/ego_phases.py).  The arithmetic applied to the
+// elements, and its order, are the original's.  A is the full matrix (the reference fills all N * N entries).
+//
+// irow / icol are declared outside the loop over the pivots, where the original declares them (src/matrix.cpp:435):
+// a pivot search selects an entry whenever it looks at one that is not NaN (`>= big` with big = 0), so they keep a
+// value from the pivot before only when every candidate entry of a step is NaN -- and then the original reuses it.
+// (Its first step would read them uninitialised; here they start at 0.)
+//
+// Host and device: SVD_HD as in svd_static.h (tests/cpp/gauss_jordan_check.cpp compiles this header for the host).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#ifndef SVD_HD
+#define SVD_HD inline
+#endif
+
+template <int N> SVD_HD bool vh_gauss_jordan(double (&A)[N][N], double (&b)[N]) {
+  int32_t ipiv[N];
+#pragma unroll
+  for (int32_t q = 0; q < N; q++) ipiv[q] = 0;
+  int32_t irow = 0, icol = 0;
+#pragma unroll
+  for (int32_t i = 0; i < N; i++) {
+    double big = 0.0;
+#pragma unroll
+    for (int32_t j = 0; j < N; j++)
+#pragma unroll
+      for (int32_t k = 0; k < N; k++) {
+        const double v = fabs(A[j][k]);
+        if (ipiv[j] != 1 && ipiv[k] == 0 && v >= big) { big = v; irow = j; icol = k; }
+      }
+#pragma unroll
+    for (int32_t q = 0; q < N; q++) ipiv[q] += q == icol ? 1 : 0;
+    // rows irow and icol change places (nothing moves when they are the same row)
+    double ri[N], rc[N], bi = 0.0, bc = 0.0;
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) { ri[l] = 0.0; rc[l] = 0.0; }
+#pragma unroll
+    for (int32_t r = 0; r < N; r++) {
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) { ri[l] = r == irow ? A[r][l] : ri[l]; rc[l] = r == icol ? A[r][l] : rc[l]; }
+      bi = r == irow ? b[r] : bi; bc = r == icol ? b[r] : bc;
+    }
+#pragma unroll
+    for (int32_t r = 0; r < N; r++) {
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) A[r][l] = r == icol ? ri[l] : (r == irow ? rc[l] : A[r][l]);
+      b[r] = r == icol ? bi : (r == irow ? bc : b[r]);
+    }
+    // the pivot row (now row icol) is ri, its right-hand side bi
+    double piv = 0.0;
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) piv = l == icol ? ri[l] : piv;
+    if (fabs(piv) < 1e-20) return false;
+    const double pivinv = 1.0 / piv;
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) ri[l] = (l == icol ? 1.0 : ri[l]) * pivinv;
+    bi *= pivinv;
+#pragma unroll
+    for (int32_t ll = 0; ll < N; ll++) {
+      double dum = 0.0;
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) dum = l == icol ? A[ll][l] : dum;
+      const bool prow = ll == icol;
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) {
+        const double cur = l == icol ? 0.0 : A[ll][l];
+        A[ll][l] = prow ? ri[l] : cur - ri[l] * dum;
+      }
+      b[ll] = prow ? bi : b[ll] - bi * dum;
+    }
+  }
+  return true;
+}

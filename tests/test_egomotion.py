@@ -64,6 +64,26 @@ def test_oracle_estimate_motion_golden(name, ob, oracle):
     assert ok_o == ok and np.array_equal(inl_o, inl) and tr_o.tobytes() == tr.tobytes()
 
 
+def test_gauss_jordan_header_equals_the_solvers_it_replaced(tmp_path):
+    """csrc/vh_gauss_jordan.h (the one Matrix::solve of ego_kernel's 6x6 and recon_kernel's 3x3 normal equations)
+    compiled for the host with -ffp-contract=off: bit-identical to verbatim copies of the two solvers it replaced and to
+    Matrix::solve with dynamic indices on 4 000 random symmetric systems per size and on the edge systems (zero matrix,
+    singular below 1e-20, off-diagonal pivots in every step, equal-magnitude ties).  Where every candidate of a pivot
+    search is NaN it equals Matrix::solve, which keeps the row and column of the pivot before; the former 6x6 solver
+    went back to (0, 0) there and gives other (NaN) components on one of the three such systems
+    (tests/cpp/gauss_jordan_check.cpp)."""
+    import os
+    import subprocess
+    from conftest import ROOT
+    exe = str(tmp_path / "gauss_jordan_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", os.path.join(ROOT, "tests", "cpp", "gauss_jordan_check.cpp"),
+                           "-lm", "-o", exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("\n0 failures"), r.stdout + r.stderr
+    assert r.stdout.count("0 differ from the former solver, 0 from Matrix::solve") == 4, r.stdout
+    assert "NaN systems, 0 differ from Matrix::solve, 1 of 3 from the former solver" in r.stdout, r.stdout
+
+
 def _rand3(ob, ego, n_sets):
     """rand() after srand(0), one fresh sequence per list (as one fresh VisualOdometryStereo per list would draw)."""
     r = ob.glibc_rand_after_srand0(3 * ego.ransac_iters).reshape(ego.ransac_iters, 3)

@@ -153,13 +153,14 @@ def test_invert_draw_any_order(ob, oracle):
 
 # ------------------------------------------------------------------------------------------------------------ GPU
 
-LENGTHS = [0, 5, 6, 7, 8, 255, 256, 257, 511, 512, 513, 768, 769]
+LENGTHS = [0, 5, 6, 7, 8, 255, 256, 257, 511, 512, 513, 768, 769, 63, 64, 65]  # (appended: the lists before keep their rand() rows)
 
 
 @pytest.mark.gpu
 def test_gpu_list_lengths_around_the_chunks(pkg, ob, oracle, gpu):
-    """One batch of lists of 0 .. 769 matches, 30 % outliers (inlier lists that cross the 256-chunks at assorted
-    offsets), at 64 hypotheses; a second one at inlier_threshold 10 with a noise-free, outlier-free list of exactly
+    """One batch of lists of 0 .. 769 matches (lengths around the 64-lane waves and the 256-thread trips of the ordered
+    compaction), 30 % outliers (inlier lists that cross the 256-chunks at assorted offsets), at 64 hypotheses; a second
+    one at inlier_threshold 10 with a noise-free, outlier-free list of exactly
     512 and one of 513 whose every match is an inlier (every chunk full; asserted on the oracle)."""
     lists = [es.scene(ob.P_MATCH_DTYPE, n, 400 + n, outliers=0.0 if n < 9 else 0.3, noise=0.0 if n < 9 else 0.2)[0] for n in LENGTHS]
     raw = np.random.default_rng(11).integers(0, 2 ** 31 - 1, (len(lists), 64, 3)).astype(np.int32)

@@ -168,10 +168,13 @@ def test_gpu_mono_shortest_lists(pkg, ob, oracle, gpu):
 @pytest.mark.gpu
 def test_gpu_mono_lds_global_switch(pkg, ob, oracle, gpu):
     """Noise-free, outlier-free scenes of 639, 640 and 641 matches, every match an inlier (asserted): the refit system of
-    the first two lives in LDS, the third takes the global-memory path."""
-    lists = [es.mono_two_motion_scene(ob.P_MATCH_DTYPE, n, 0, 90)[0] for n in (639, 640, 641)]
-    want = _compare(pkg, ob, oracle, dict(es.MONO_KITTI, ransac_iters=128), lists, _glibc(ob, 128, 3), "lds switch")
-    assert [len(w[2]) for w in want] == [639, 640, 641] and all(w[0] for w in want)
+    the first two lives in LDS, the third takes the global-memory path.  In the same batch, lists whose lengths -- and,
+    every match being an inlier, whose inlier lists -- end at the 64-lane waves and the 256-thread trips of the ordered
+    compaction."""
+    lengths = (63, 64, 65, 255, 256, 257, 513, 639, 640, 641)
+    lists = [es.mono_two_motion_scene(ob.P_MATCH_DTYPE, n, 0, 90)[0] for n in lengths]
+    want = _compare(pkg, ob, oracle, dict(es.MONO_KITTI, ransac_iters=128), lists, _glibc(ob, 128, len(lengths)), "lds switch")
+    assert [len(w[2]) for w in want] == list(lengths) and all(w[0] for w in want)
 
 
 @pytest.mark.gpu
