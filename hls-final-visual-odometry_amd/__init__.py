@@ -74,6 +74,8 @@ ABI_SYMBOLS = (
     "vh_group_tracks_device", "vh_link_tracks", "vh_track_carry_free", "vh_group_debug_fail_alloc_after",
     "vh_default_recon_params", "vh_reconstruct_tracks", "vh_reconstruct_last_kernel_ms",
     "vh_sequence_set_reconstruction", "vh_sequence_reconstruct", "vh_sequence_get_recon_tracks", "vh_reconstruct_lists",
+    "vh_group_set_reconstruction", "vh_group_reconstruct", "vh_group_get_recon_tracks", "vh_group_get_recon_counts",
+    "vh_group_debug_reconstruct_lists",
 )
 
 
@@ -256,6 +258,9 @@ def _lib():
             "vh_sequence_set_reconstruction": [vp, vp, i32], "vh_sequence_reconstruct": [vp, vp, vp, vp],
             "vh_sequence_get_recon_tracks": [vp, vp, i32, vp],
             "vh_reconstruct_lists": [vp, i32, i32, vp, i64, vp, i32, vp, vp, i32, vp],
+            "vh_group_set_reconstruction": [vp, vp, i32], "vh_group_reconstruct": [vp, vp, vp, vp],
+            "vh_group_get_recon_tracks": [vp, i32, vp, i32, vp], "vh_group_get_recon_counts": [vp, vp, vp],
+            "vh_group_debug_reconstruct_lists": [vp, i32, i32, i32, vp, i64, vp, i32, vp, vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -713,6 +718,36 @@ class StreamGroup:
         _check(_lib().vh_group_search_stats(self._h, C.byref(sp), C.byref(rate)), "vh_group_search_stats")
         return bool(sp.value), rate.value
 
+    def setReconstruction(self, recon: "ReconParams | None", history_steps: int = 0):
+        """3-d points from the tracks that end, per stream and step, gathered on the device (vh_group_set_reconstruction):
+        before the first push only; switches track linking on.  history_steps >= 1: lost tracks older than that come back
+        RECON_HISTORY.  recon None: off."""
+        _check(_lib().vh_group_set_reconstruction(self._h, C.byref(recon) if recon is not None else None, int(history_steps)),
+               "vh_group_set_reconstruction")
+
+    def reconstruct(self, Trs) -> list:
+        """The lost tracks of the step of the last match call (vh_group_reconstruct), once per match call, before the next
+        one.  Trs [S, 4, 4]: every stream's motion over this step.  -> S RECON_TRACK arrays, each sorted by (lost_frame,
+        birth_frame, birth_pos)."""
+        tr = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 16)
+        assert tr.shape[0] == self.S, (tr.shape, self.S)
+        nt, na = C.c_int32(0), C.c_int32(0)
+        _check(_lib().vh_group_reconstruct(self._h, _ptr(tr), C.byref(nt), C.byref(na)), "vh_group_reconstruct")
+        counts = self.getReconCounts()[0]
+        out = []
+        for s in range(self.S):
+            rec = np.zeros(int(counts[s]), RECON_TRACK)
+            n = C.c_int32(0)
+            _check(_lib().vh_group_get_recon_tracks(self._h, s, _ptr(rec) if len(rec) else None, len(rec), C.byref(n)), "vh_group_get_recon_tracks")
+            out.append(rec[:n.value])
+        return out
+
+    def getReconCounts(self):
+        """-> (records [S], accepted records [S]) of the last reconstruct call."""
+        nt, na = np.zeros(self.S, np.int32), np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_get_recon_counts(self._h, _ptr(nt), _ptr(na)), "vh_group_get_recon_counts")
+        return nt, na
+
     def debugFailNextAlloc(self):
         """Test hook: the group's next device allocation fails once."""
         _check(_lib().vh_group_debug_fail_next_alloc(self._h), "vh_group_debug_fail_next_alloc")
@@ -1004,6 +1039,27 @@ def reconstruct_lists(recon: ReconParams, lists, Trs, n_index: int, device: int 
     _check(_lib().vh_reconstruct_lists(C.byref(recon), int(device), n, _ptr(pm), stride, _ptr(counts), int(n_index), _ptr(tr), _ptr(out), cap,
                                        C.byref(got)), "vh_reconstruct_lists")
     return out[:got.value].copy()
+
+
+def debug_group_reconstruct_lists(recon: ReconParams, streams, Trs, n_index: int, device: int = 0) -> list:
+    """Test hook (vh_group_debug_reconstruct_lists): the group form of the gather kernels on caller-owned lists.  streams:
+    S sequences of n lists each, Trs [S, n, 4, 4]; every stream a fresh drive, all through one kernel sequence.
+    -> S RECON_TRACK arrays."""
+    S, n = len(streams), len(streams[0])
+    tr = np.ascontiguousarray(Trs, dtype=np.float64).reshape(-1, 16)
+    assert all(len(ls) == n for ls in streams) and tr.shape[0] == S * n, (S, n, tr.shape)
+    stride = max(1, max(len(m) for ls in streams for m in ls))
+    pm = np.zeros((S * n, stride), P_MATCH_DTYPE)
+    for k, m in enumerate(m for ls in streams for m in ls):
+        pm[k, :len(m)] = m
+    counts = np.array([len(m) for ls in streams for m in ls], np.int32)
+    cap = int(counts.sum())
+    out = np.zeros(max(cap, 1), RECON_TRACK)
+    got = np.zeros(S, np.int32)
+    _check(_lib().vh_group_debug_reconstruct_lists(C.byref(recon), int(device), S, n, _ptr(pm), stride, _ptr(counts), int(n_index), _ptr(tr),
+                                                   _ptr(out), cap, _ptr(got)), "vh_group_debug_reconstruct_lists")
+    ends = np.cumsum(got)
+    return [out[e - c:e].copy() for e, c in zip(ends, got)]
 
 
 def reconstruct_last_kernel_ms() -> float:

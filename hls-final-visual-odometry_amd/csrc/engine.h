@@ -210,34 +210,36 @@ struct ReconTable {
   std::vector<double> frames;  // VH_RECON_FRAME_DOUBLES per frame
   int64_t count() const { return (int64_t)(frames.size() / VH_RECON_FRAME_DOUBLES); }
 };
-// Reconstruction on a sequence handle (vh_sequence_set_reconstruction; engine_recon.hip): the
-// ring of compact records and the gather buffers, outside the arena (the gather buffers grow), counted in `bytes`.
-// vh_reconstruct_lists runs on a transient one.
+// Reconstruction on a sequence handle or a group (vh_sequence_set_reconstruction, vh_group_set_reconstruction;
+// engine_recon.hip, DESIGN.md sections 4.8 and 4.9): the ring of compact records and the gather buffers, outside the
+// arena (the gather buffers grow), counted in `bytes`.  vh_reconstruct_lists runs on a transient one.
+// A "frame" is a frame of a sequence handle or a step of a group; it holds `lists` lists: 1, or one per stream.
 struct ReconHistory {
   bool on = false;
   vh_recon_params params{};
   int32_t history = 0;
-  // the chunk of the last match call, recorded when it was queued
+  // the chunk (group: the step, a chunk of one row) of the last match call, recorded when it was queued
   bool m_valid = false, m_done = false;
+  bool replaced = false;  // group: a replace push since the last match call -- the next lists have no predecessor
   int64_t m_first = 0;
-  int32_t m_lo = 0, m_rows = 0;
+  int32_t m_lo = 0, m_rows = 0, m_buf = 0;  // (m_buf: group, the track buffer of that step's lists)
   int32_t pushes_since_match = 0;
   // the chain of lists stored so far: unbroken up to frame `last`; has_pending: the list of frame `last` is in the ring
   bool chain = false, has_pending = false;
   int64_t last = 0;
-  ReconTable table;
-  std::vector<vh_recon_track> result;
-  int32_t accepted = 0;
+  std::vector<ReconTable> tables;      // one per stream, all over the same frames
+  std::vector<vh_recon_track> result;  // of the last call: stream after stream, each sorted
+  std::vector<int32_t> res_off, accepted;  // [lists + 1] where each stream's records begin / [lists] its accepted ones
   // device
   DeviceBlock b_ring, b_count, b_totals;
-  int32_t ring_slots = 0, ring_cap = 0;
+  int32_t ring_slots = 0, ring_lists = 0, ring_cap = 0;  // frames, lists per frame, records per list
   struct Grown { DeviceBlock b; size_t bytes = 0; } g_tails, g_first, g_off, g_order, g_px, g_pts, g_st, g_met, g_frames;
   int64_t bytes = 0;
   void drop_chain() { chain = has_pending = false; }
   void release_device() {  // (the work using it must have completed)
     b_ring = DeviceBlock(); b_count = DeviceBlock(); b_totals = DeviceBlock();
     for (Grown *g : {&g_tails, &g_first, &g_off, &g_order, &g_px, &g_pts, &g_st, &g_met, &g_frames}) { g->b = DeviceBlock(); g->bytes = 0; }
-    ring_slots = ring_cap = 0; bytes = 0;
+    ring_slots = ring_lists = ring_cap = 0; bytes = 0;
     drop_chain(); m_valid = m_done = false;
   }
 };
@@ -464,10 +466,11 @@ struct Group {
   int32_t load_features(int32_t role, const int32_t *m, int32_t n);
 
   // ---- engine_recon.hip ----
-  void recon_pushed(bool first);
+  void recon_pushed(bool first, bool shifted);
   void recon_before_link();
   void recon_matched(const VhMatchArgs &a);
   void recon_match_failed() { rh.m_valid = false; rh.drop_chain(); }
+  int32_t recon_lists() const { return seq ? 1 : S; }  // lists per frame
   int32_t reconstruct(const double *Tr, int32_t *n_tracks, int32_t *n_accepted);
 
   // ---- engine_post.hip ----

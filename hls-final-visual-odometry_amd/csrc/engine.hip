@@ -276,7 +276,7 @@ int32_t Group::push_device(const void *dI1, const void *dI2, int64_t stride, con
   else {
     failed = false;
     trk_pushed(pair_cur != old_cur, old_frames == 0, seq_n);
-    recon_pushed(old_frames == 0);
+    recon_pushed(old_frames == 0, pair_cur != old_cur);
     if (seq) { seq_n_prev = seq_n; seq_n = rows; seq_first = seq_total; seq_total += rows; }
   }
   return rc;

@@ -1,7 +1,8 @@
 // engine_recon.hip -- the host half of reconstruction (include/viso_hip.h): the per-frame tables of Reconstruction
 // (reference src/reconstruction.cpp:27-70), vh_reconstruct_tracks and its transfers around kernels_recon.hip, and
 // reconstruction from tracked lists -- a sequence handle's (vh_sequence_reconstruct) or the caller's
-// (vh_reconstruct_lists) -- through kernels_recon_gather.hip.
+// (vh_reconstruct_lists) -- through kernels_recon_gather.hip, and the same for the S streams of
+// a group stepped together (vh_group_reconstruct, section 4.9): one store, tails, gather and solve sequence per step.
 // Built with -ffp-contract=off: the tables are part of the bit-for-bit contract.
 #include "engine.h"
 
@@ -114,9 +115,10 @@ int32_t recon_grow(ReconHistory &h, Group *gq, ReconHistory::Grown &g, size_t ne
   return VH_OK;
 }
 
-int32_t recon_ensure_ring(ReconHistory &h, Group *gq, int32_t slots, int32_t cap) {
+// slots frames of `lists` lists of cap records
+int32_t recon_ensure_ring(ReconHistory &h, Group *gq, int32_t slots, int32_t lists, int32_t cap) {
   if (h.b_ring.p) return VH_OK;
-  const size_t b_ring = sizeof(VhReconRec) * (size_t)slots * cap, b_count = sizeof(int32_t) * (size_t)slots, b_tot = sizeof(unsigned long long) * 5;
+  const size_t b_ring = sizeof(VhReconRec) * (size_t)slots * lists * cap, b_count = sizeof(int32_t) * (size_t)slots * lists, b_tot = sizeof(unsigned long long) * 5;
   DeviceBlock ring, count, totals;
   if (recon_refused(gq)) return VH_ERR_HIP;
   VH_HIP(ring.alloc(b_ring));
@@ -127,18 +129,23 @@ int32_t recon_ensure_ring(ReconHistory &h, Group *gq, int32_t slots, int32_t cap
   VH_HIP(recon_poison(ring.p, b_ring));
   VH_HIP(hipMemset(count.p, 0, b_count));
   h.b_ring = std::move(ring); h.b_count = std::move(count); h.b_totals = std::move(totals);
-  h.ring_slots = slots; h.ring_cap = cap;
+  h.ring_slots = slots; h.ring_lists = lists; h.ring_cap = cap;
   h.bytes += (int64_t)(b_ring + b_count + b_tot);
   return VH_OK;
 }
 
 // store -> tails (count) -> grow -> tails (append) -> gather -> solve -> the sorted records.  `a` names the lists, the
 // tail range and `check`; nothing of `h` but its buffers changes, so a failed call can simply be made again.
-int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs a, const ReconTable &tab, const vh_recon_params &r,
-                  std::vector<vh_recon_track> &out, int32_t *accepted) {
+// tabs: one table per stream (h.ring_lists of them), all over the same frames.  out: stream after stream, stream s's
+// records at [off[s], off[s + 1]), each sorted by (lost_frame, birth_frame, birth_pos); accepted: per stream.
+int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs a, const ReconTable *tabs, const vh_recon_params &r,
+                  std::vector<vh_recon_track> &out, std::vector<int32_t> &off, std::vector<int32_t> &accepted) {
+  const int32_t L = h.ring_lists;
+  const ReconTable &tab = tabs[0];
   a.ring = h.b_ring.as<VhReconRec>(); a.ring_count = h.b_count.as<int32_t>(); a.ring_slots = h.ring_slots; a.ring_cap = h.ring_cap;
+  a.lists_per_frame = L;
   a.totals = h.b_totals.as<unsigned long long>();
-  out.clear(); *accepted = 0;
+  out.clear(); off.assign((size_t)L + 1, 0); accepted.assign((size_t)L, 0);
   VH_HIP(hipMemsetAsync(a.totals, 0, sizeof(unsigned long long) * 5, st));
   { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_store", st); vh_launch_recon_store(a, st); }
   { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_tails", st); vh_launch_recon_tails(a, 0, st); }
@@ -152,7 +159,8 @@ int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs 
   a.n_solved = ns; a.n_tails = nt; a.n_pixels = (int64_t)n_px;
   // the window of the tables the tracks can reach: a track of a list since tail_lo began at most `history` frames before it
   a.window0 = std::max(tab.first, a.tail_lo - a.history);
-  const size_t w_doubles = (size_t)(tab.first + tab.count() - a.window0) * VH_RECON_FRAME_DOUBLES;
+  a.window = (int32_t)(tab.first + tab.count() - a.window0);
+  const size_t w_one = (size_t)a.window * VH_RECON_FRAME_DOUBLES, w_doubles = w_one * (size_t)L;  // a window per stream, stream after stream
   int32_t rc;
   if ((rc = recon_grow(h, gq, h.g_tails, sizeof(VhReconTail) * (size_t)nt))) return rc;
   if ((rc = recon_grow(h, gq, h.g_first, sizeof(int32_t) * (size_t)ns))) return rc;
@@ -166,8 +174,15 @@ int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs 
   if (nt == 0) return VH_OK;
   a.tails = h.g_tails.b.as<VhReconTail>(); a.first_frame = h.g_first.b.as<int32_t>(); a.offsets = h.g_off.b.as<int32_t>();
   a.order = h.g_order.b.as<int32_t>(); a.pixels = h.g_px.b.as<float>();
-  VH_HIP(hipMemcpyAsync(h.g_frames.b.p, tab.frames.data() + (size_t)(a.window0 - tab.first) * VH_RECON_FRAME_DOUBLES, sizeof(double) * w_doubles,
-                        hipMemcpyHostToDevice, st));
+  const size_t w_skip = (size_t)(a.window0 - tab.first) * VH_RECON_FRAME_DOUBLES;
+  std::vector<double> windows;  // (lives until the synchronisation below)
+  const double *w_src = tab.frames.data() + w_skip;
+  if (L > 1) {
+    windows.resize(w_doubles);
+    for (int32_t s = 0; s < L; s++) memcpy(windows.data() + w_one * (size_t)s, tabs[s].frames.data() + w_skip, sizeof(double) * w_one);
+    w_src = windows.data();
+  }
+  VH_HIP(hipMemcpyAsync(h.g_frames.b.p, w_src, sizeof(double) * w_doubles, hipMemcpyHostToDevice, st));
   { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_tails", st); vh_launch_recon_tails(a, 1, st); }
   { std::optional<Scope> sc; if (gq) sc.emplace(gq, "recon_gather", st); vh_launch_recon_gather(a, st); }
   double road[4];
@@ -200,32 +215,40 @@ int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs 
     }
   }
 #endif
+  std::vector<int32_t> order((size_t)nt);
+  std::iota(order.begin(), order.end(), 0);
+  std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+    const VhReconTail &p = tails[(size_t)x], &q = tails[(size_t)y];
+    if (p.stream != q.stream) return p.stream < q.stream;
+    if (p.lost_off != q.lost_off) return p.lost_off < q.lost_off;
+    if (p.birth_off != q.birth_off) return p.birth_off < q.birth_off;
+    return p.birth_pos < q.birth_pos;
+  });
   out.resize((size_t)nt);
-  for (int32_t t = 0; t < nt; t++) {
-    vh_recon_track &o = out[(size_t)t];
+  for (int32_t k = 0; k < nt; k++) {
+    const int32_t t = order[(size_t)k];
+    vh_recon_track &o = out[(size_t)k];
     const VhReconTail &q = tails[(size_t)t];
+    if (q.stream < 0 || q.stream >= L) { t_last_error = "recon_tails: a record of no stream"; return VH_ERR_HIP; }  // (never)
+    off[(size_t)q.stream + 1]++;
     memset(&o, 0, sizeof(o));
-    o.birth_frame = q.birth_frame; o.birth_pos = q.birth_pos; o.frames = q.frames; o.lost_frame = q.lost_frame;
+    o.birth_frame = a.window0 + q.birth_off; o.birth_pos = q.birth_pos; o.frames = q.frames; o.lost_frame = a.window0 + q.lost_off;
     if (t >= ns) { o.status = VH_RECON_HISTORY; continue; }
     o.status = stat[(size_t)t];
     for (int32_t i = 0; i < 3; i++) o.point[i] = pts[3 * (size_t)t + i];
     o.distance = met[2 * (size_t)t]; o.angle = met[2 * (size_t)t + 1];
+    accepted[(size_t)q.stream] += o.status == VH_RECON_ACCEPTED ? 1 : 0;
   }
-  std::sort(out.begin(), out.end(), [](const vh_recon_track &x, const vh_recon_track &y) {
-    if (x.lost_frame != y.lost_frame) return x.lost_frame < y.lost_frame;
-    if (x.birth_frame != y.birth_frame) return x.birth_frame < y.birth_frame;
-    return x.birth_pos < y.birth_pos;
-  });
-  for (const vh_recon_track &o : out) *accepted += o.status == VH_RECON_ACCEPTED ? 1 : 0;
+  for (int32_t s = 0; s < L; s++) off[(size_t)s + 1] += off[(size_t)s];
   return VH_OK;
 }
 
 // the getters' capacity rule
-int32_t recon_copy_out(const std::vector<vh_recon_track> &res, vh_recon_track *out, int32_t cap, int32_t *n) {
-  *n = (int32_t)res.size();
-  const size_t k = std::min(res.size(), (size_t)cap);
-  if (k) memcpy(out, res.data(), sizeof(vh_recon_track) * k);
-  return res.size() > (size_t)cap ? VH_ERR_CAPACITY : VH_OK;
+int32_t recon_copy_out(const vh_recon_track *res, size_t count, vh_recon_track *out, int32_t cap, int32_t *n) {
+  *n = (int32_t)count;
+  const size_t k = std::min(count, (size_t)cap);
+  if (k) memcpy(out, res, sizeof(vh_recon_track) * k);
+  return count > (size_t)cap ? VH_ERR_CAPACITY : VH_OK;
 }
 
 }  // namespace
@@ -234,9 +257,11 @@ int32_t recon_copy_out(const std::vector<vh_recon_track> &res, vh_recon_track *o
 namespace vh_engine {
 
 // a push has succeeded; first: the ring of feature sets starts again (first push, new dims)
-void Group::recon_pushed(bool first) {
+// shifted: the push brought a new step (group: false for a replace push, which keeps the step and voids its lists)
+void Group::recon_pushed(bool first, bool shifted) {
   if (!rh.on) return;
-  if (first) { rh.drop_chain(); rh.m_valid = rh.m_done = false; rh.pushes_since_match = 0; }
+  if (first) { rh.drop_chain(); rh.m_valid = rh.m_done = false; rh.pushes_since_match = 0; rh.replaced = false; }
+  if (!seq && !first && !shifted) { rh.replaced = true; return; }
   rh.pushes_since_match++;
 }
 
@@ -247,48 +272,61 @@ void Group::recon_pushed(bool first) {
 void Group::recon_before_link() {
   if (!rh.on) return;
   const bool again = rh.pushes_since_match == 0;
-  const bool goes_on = again ? (rh.m_valid && !rh.m_done) : (rh.pushes_since_match == 1 && rh.m_valid && rh.m_done && rh.chain);
+  bool goes_on = again ? (rh.m_valid && !rh.m_done) : (rh.pushes_since_match == 1 && rh.m_valid && rh.m_done && rh.chain);
+  // group: the linking contract gives the lists of a replaced frame no predecessor, and a push covers every stream
+  if (rh.replaced) { goes_on = false; rh.replaced = false; }
   if (again && goes_on) return;  // the chunk's lists are replaced: the ring has none of them yet
   if (!goes_on) { rh.drop_chain(); trk_pred_valid = false; trk_carry_src = -1; }
 }
 
 void Group::recon_matched(const VhMatchArgs &a) {
   if (!rh.on) return;
-  rh.m_valid = true; rh.m_done = false; rh.m_first = seq_first; rh.m_lo = a.seq_lo; rh.m_rows = a.rows; rh.pushes_since_match = 0;
+  rh.m_valid = true; rh.m_done = false; rh.pushes_since_match = 0;
+  if (seq) { rh.m_first = seq_first; rh.m_lo = a.seq_lo; rh.m_rows = a.rows; return; }
+  // group: a chunk of one row, the step with push serial trk_serial; the first push's step holds no pair.  The buffer of
+  // its tracks is recorded too: the next push may come before the reconstruct call, and it changes trk_cur
+  rh.m_first = trk_serial; rh.m_lo = trk_serial == 0 ? 1 : 0; rh.m_rows = 1; rh.m_buf = trk_cur;
 }
 
 int32_t Group::reconstruct(const double *Tr, int32_t *n_tracks, int32_t *n_accepted) {
   if (!n_tracks || !n_accepted) return VH_ERR_INVALID_ARG;
   *n_tracks = *n_accepted = 0;
-  if (!seq || !rh.on || !allocated || !rh.m_valid || rh.m_done) return VH_ERR_STATE;  // (a push since the match call changes nothing)
+  if (!rh.on || !allocated || !rh.m_valid || rh.m_done) return VH_ERR_STATE;  // (a push since the match call changes nothing)
   const int64_t F = rh.m_first;
   const int32_t lo = rh.m_lo, rows = rh.m_rows;
   if (lo < rows && !Tr) return VH_ERR_INVALID_ARG;
   if (rh.chain && rh.last != F + lo - 1) rh.drop_chain();  // (cannot happen: recon_before_link keeps the two in step)
-  int32_t rc = recon_ensure_ring(rh, this, rh.history + S, mcap);
+  // The list axis: a sequence handle holds one camera, its rows are frames; a group holds S cameras, its one row is the
+  // step -- the list of (row r, stream s) is list r + s * stride of the handle's arrays, and its motion Tr[r + s * stride]
+  const int32_t L = recon_lists();
+  const int64_t stride = seq ? 0 : 1;
+  int32_t rc = recon_ensure_ring(rh, this, seq ? rh.history + S : rh.history + 1, L, mcap);
   if (rc) return rc;
-  ReconTable tab;
-  if (rh.chain) tab = rh.table;
-  else recon_table_push(rh.params, tab, nullptr, F + lo - 1);
-  for (int32_t r = lo; r < rows; r++) recon_table_push(rh.params, tab, Tr + 16 * (size_t)r);
+  std::vector<ReconTable> tabs;
+  if (rh.chain) tabs = rh.tables;
+  else { tabs.resize((size_t)L); for (ReconTable &t : tabs) recon_table_push(rh.params, t, nullptr, F + lo - 1); }
+  for (int32_t s = 0; s < L; s++)
+    for (int32_t r = lo; r < rows; r++) recon_table_push(rh.params, tabs[(size_t)s], Tr + 16 * (size_t)(r + s * stride));
   const bool pred = rh.chain && rh.has_pending;
   VhReconGatherArgs a{};
   a.pm = (const vh_p_match *)mt.d_matches; a.pm_stride = mcap; a.counts = mt.d_match_count; a.count_cap = mcap;
-  a.trk = tk.d_trk; a.trk_stride = mcap;
+  a.trk = tk.d_trk + (seq ? 0 : (size_t)rh.m_buf * S * mcap); a.trk_stride = mcap; a.stream_stride = stride;
   a.row_lo = lo; a.rows = rows; a.frame0 = F; a.pred_valid = pred ? 1 : 0; a.history = rh.history;
   a.tail_lo = pred ? F + lo - 1 : F + lo; a.tail_hi = F + rows - 1;
   a.check = sets.check;
   if (lo < rows) {
     // behind the emission and the linking of the match call, on their stream
-    if ((rc = recon_run(rh, this, post_stream, a, tab, rh.params, rh.result, &rh.accepted))) return rc;
-  } else { rh.result.clear(); rh.accepted = 0; }
+    if ((rc = recon_run(rh, this, post_stream, a, tabs.data(), rh.params, rh.result, rh.res_off, rh.accepted))) return rc;
+  } else { rh.result.clear(); rh.res_off.assign((size_t)L + 1, 0); rh.accepted.assign((size_t)L, 0); }
   // the next call reaches back `history` frames from its first tail, the list of frame F + rows - 1
-  const int64_t keep = std::max(tab.first, F + rows - 1 - rh.history - 1);
-  tab.frames.erase(tab.frames.begin(), tab.frames.begin() + (size_t)(keep - tab.first) * VH_RECON_FRAME_DOUBLES);
-  tab.first = keep;
-  rh.table = std::move(tab);
+  for (ReconTable &tab : tabs) {
+    const int64_t keep = std::max(tab.first, F + rows - 1 - rh.history - 1);
+    tab.frames.erase(tab.frames.begin(), tab.frames.begin() + (size_t)(keep - tab.first) * VH_RECON_FRAME_DOUBLES);
+    tab.first = keep;
+  }
+  rh.tables = std::move(tabs);
   rh.chain = true; rh.has_pending = lo < rows; rh.last = F + rows - 1; rh.m_done = true;
-  *n_tracks = (int32_t)rh.result.size(); *n_accepted = rh.accepted;
+  *n_tracks = (int32_t)rh.result.size(); *n_accepted = std::accumulate(rh.accepted.begin(), rh.accepted.end(), 0);
   return VH_OK;
 }
 
@@ -386,6 +424,7 @@ int32_t vh_sequence_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks
   Group *gq = (Group *)g;
   if (!gq) return VH_ERR_INVALID_ARG;
   if (hipSetDevice(gq->device) != hipSuccess) { t_last_error = "hipSetDevice"; return VH_ERR_HIP; }
+  if (!gq->seq) { if (n_tracks) *n_tracks = 0; if (n_accepted) *n_accepted = 0; return n_tracks && n_accepted ? VH_ERR_STATE : VH_ERR_INVALID_ARG; }
   return gq->reconstruct(Tr, n_tracks, n_accepted);
 }
 
@@ -393,8 +432,50 @@ int32_t vh_sequence_get_recon_tracks(vh_group *g, vh_recon_track *out, int32_t c
   Group *gq = (Group *)g;
   if (!gq || !n || cap < 0 || (cap > 0 && !out)) return VH_ERR_INVALID_ARG;
   *n = 0;
+  if (!gq->seq || !gq->rh.on || !gq->rh.m_done) return VH_ERR_STATE;  // (a group's records come per stream: vh_group_get_recon_tracks)
+  return recon_copy_out(gq->rh.result.data(), gq->rh.result.size(), out, cap, n);
+}
+
+int32_t vh_group_set_reconstruction(vh_group *g, const vh_recon_params *r, int32_t history_steps) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;  // (a sequence handle keeps its own entry)
+  if (gq->allocated) return VH_ERR_STATE;
+  if (!r) { gq->rh.on = false; return VH_OK; }
+  if (history_steps < 1) return VH_ERR_INVALID_ARG;
+  gq->rh.on = true; gq->rh.params = *r; gq->rh.history = history_steps;
+  gq->trk_on = true;
+  return VH_OK;
+}
+
+int32_t vh_group_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, int32_t *n_accepted) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;
+  if (hipSetDevice(gq->device) != hipSuccess) { t_last_error = "hipSetDevice"; return VH_ERR_HIP; }
+  return gq->reconstruct(Tr, n_tracks, n_accepted);
+}
+
+int32_t vh_group_get_recon_tracks(vh_group *g, int32_t stream, vh_recon_track *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g;
+  if (!gq || !n || cap < 0 || (cap > 0 && !out) || stream < 0 || stream >= gq->S) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;
   if (!gq->rh.on || !gq->rh.m_done) return VH_ERR_STATE;
-  return recon_copy_out(gq->rh.result, out, cap, n);
+  const int32_t lo = gq->rh.res_off[(size_t)stream], hi = gq->rh.res_off[(size_t)stream + 1];
+  return recon_copy_out(gq->rh.result.data() + lo, (size_t)(hi - lo), out, cap, n);
+}
+
+int32_t vh_group_get_recon_counts(vh_group *g, int32_t *n_tracks, int32_t *n_accepted) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;
+  if (!gq->rh.on || !gq->rh.m_done) return VH_ERR_STATE;
+  for (int32_t s = 0; s < gq->S; s++) {
+    if (n_tracks) n_tracks[s] = gq->rh.res_off[(size_t)s + 1] - gq->rh.res_off[(size_t)s];
+    if (n_accepted) n_accepted[s] = gq->rh.accepted[(size_t)s];
+  }
+  return VH_OK;
 }
 
 int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts,
@@ -415,7 +496,7 @@ int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n
   LinkedLists ll;
   if ((rc = link_lists_device(n_lists, pm, stride, counts, n_index, nullptr, nullptr, 0, 0, false, ll))) return rc;
   ReconHistory h;  // a whole fresh drive: list l is the list of frame l + 1, nothing is older than the history
-  if ((rc = recon_ensure_ring(h, nullptr, n_lists, ll.lcap))) return rc;
+  if ((rc = recon_ensure_ring(h, nullptr, n_lists, 1, ll.lcap))) return rc;
   ReconTable tab;
   recon_table_push(*r, tab, nullptr);
   for (int32_t l = 0; l < n_lists; l++) recon_table_push(*r, tab, Tr + 16 * (size_t)l);
@@ -425,9 +506,58 @@ int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n
   a.tail_lo = 1; a.tail_hi = n_lists;
   a.check = ll.d_check;
   std::vector<vh_recon_track> res;
-  int32_t accepted = 0;
-  if ((rc = recon_run(h, nullptr, nullptr, a, tab, *r, res, &accepted))) return rc;
-  return recon_copy_out(res, out, cap, n);
+  std::vector<int32_t> off, accepted;
+  if ((rc = recon_run(h, nullptr, nullptr, a, &tab, *r, res, off, accepted))) return rc;
+  return recon_copy_out(res.data(), res.size(), out, cap, n);
+}
+
+int32_t vh_group_debug_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_streams, int32_t n_lists, const vh_p_match *pm,
+                                         int64_t stride, const int32_t *counts, int32_t n_index, const double *Tr, vh_recon_track *out,
+                                         int32_t cap, int32_t *n) {
+  if (!r || !n || n_streams < 1 || n_lists < 1 || cap < 0 || (cap > 0 && !out) || !counts || !Tr || stride < 0 || n_index < 1) return VH_ERR_INVALID_ARG;
+  const int64_t per = (int64_t)n_lists + 1, total = per * n_streams;  // an empty list behind every stream's: no track crosses it
+  if (total + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;
+  std::vector<int32_t> cnt((size_t)total, 0);
+  std::vector<vh_p_match> rows;
+  int64_t cmax = 0;
+  for (int64_t k = 0; k < (int64_t)n_streams * n_lists; k++) {
+    if (counts[k] < 0 || counts[k] > stride) return VH_ERR_INVALID_ARG;
+    cmax = std::max<int64_t>(cmax, counts[k]);
+  }
+  if (cmax > 0 && !pm) return VH_ERR_INVALID_ARG;
+  if (cmax > (int64_t)VH_TRACK_POS_MASK) return VH_ERR_UNSUPPORTED;
+  const int64_t rs = std::max<int64_t>(cmax, 1);
+  rows.resize((size_t)(total * rs));
+  for (int32_t s = 0; s < n_streams; s++)
+    for (int32_t l = 0; l < n_lists; l++) {
+      const size_t k = (size_t)s * n_lists + l, d = (size_t)(s * per + l);
+      cnt[d] = counts[k];
+      if (counts[k]) memcpy(rows.data() + d * rs, pm + k * (size_t)stride, sizeof(vh_p_match) * (size_t)counts[k]);
+    }
+  int32_t rc = select_device(device);
+  if (rc) return rc;
+  LinkedLists ll;
+  if ((rc = link_lists_device((int32_t)total, rows.data(), rs, cnt.data(), n_index, nullptr, nullptr, 0, 0, false, ll))) return rc;
+  ReconHistory h;
+  if ((rc = recon_ensure_ring(h, nullptr, n_lists, n_streams, ll.lcap))) return rc;
+  std::vector<ReconTable> tabs((size_t)n_streams);
+  for (int32_t s = 0; s < n_streams; s++) {
+    recon_table_push(*r, tabs[(size_t)s], nullptr);
+    for (int32_t l = 0; l < n_lists; l++) recon_table_push(*r, tabs[(size_t)s], Tr + 16 * ((size_t)s * n_lists + l));
+  }
+  VhReconGatherArgs a{};
+  a.pm = ll.d_pm; a.pm_stride = ll.lcap; a.counts = ll.d_cnt; a.count_cap = ll.lcap; a.trk = ll.d_trk; a.trk_stride = ll.lcap;
+  a.stream_stride = per;
+  a.row_lo = 0; a.rows = n_lists; a.frame0 = 1; a.pred_valid = 0; a.history = n_lists;
+  a.tail_lo = 1; a.tail_hi = n_lists;
+  a.check = ll.d_check;
+  std::vector<vh_recon_track> res;
+  std::vector<int32_t> off, accepted;
+  if ((rc = recon_run(h, nullptr, nullptr, a, tabs.data(), *r, res, off, accepted))) return rc;
+  for (int32_t s = 0; s < n_streams; s++) n[s] = off[(size_t)s + 1] - off[(size_t)s];
+  if (res.size() > (size_t)cap) return VH_ERR_CAPACITY;
+  if (!res.empty()) memcpy(out, res.data(), sizeof(vh_recon_track) * res.size());
+  return VH_OK;
 }
 
 }  // extern "C"

@@ -319,6 +319,8 @@ void vh_launch_track_retag(uint32_t *tab, int64_t n_index, int64_t n_slots, int6
 // The ring keeps, per list of the last `ring_slots` frames, one 32-byte record per match record: the list of frame f (the
 // pair f - 1 -> f) lives in slot f % ring_slots.  Both halves of a record are aligned 16-byte vectors; a step of the
 // gather's walk reads one record, and recon_tails reads only the second half.
+// The list axis (section 4.9): a frame holds lists_per_frame lists, one per camera stream (1: a sequence handle,
+// vh_reconstruct_lists; S: a group); the list of (frame f, stream s) lives in slot (f % ring_slots) * lists_per_frame + s.
 struct VhReconRec {
   float u1p, v1p, u1c, v1c;  // the left camera's pixels in frames f - 1 and f
   int32_t prev;              // vh_track::prev: position of the continued record in the list of frame f - 1, -1: a head
@@ -328,24 +330,28 @@ struct VhReconRec {
 };
 // one lost track, appended by recon_tails (solved tracks from the front of the array, VH_RECON_HISTORY ones from its end)
 struct VhReconTail {
-  int64_t lost_frame, birth_frame;
-  int32_t birth_pos, frames;  // frames = age + 1
-  int32_t pos;                // of the track's last record, in the list of frame lost_frame - 1
-  int32_t px_off;             // first of its `frames` pixels in the gathered array; -1: older than the history, not gathered
+  int32_t lost_off, birth_off;  // lost_frame, birth_frame as offsets from the call's window0 (birth_off < 0: only beyond the history)
+  int32_t birth_pos, frames;    // frames = age + 1
+  int32_t pos;                  // of the track's last record, in its stream's list of frame lost_frame - 1
+  int32_t px_off;               // first of its `frames` pixels in the gathered array; -1: older than the history, not gathered
+  int32_t stream, reserved;     // the list axis: 0 on a sequence handle; reserved = 0
 };
 struct VhReconGatherArgs {
-  // recon_store: the lists of rows [row_lo, rows) of a launch and their tracks, addressed as VhTrackArgs does; row r is frame0 + r
+  // recon_store: the lists of rows [row_lo, rows) of a launch and their tracks, addressed as VhTrackArgs does; row r is frame0 + r.
+  // The list of (row r, stream s) is list r + s * stream_stride of pm / counts / trk.
+  int32_t lists_per_frame;
+  int64_t stream_stride;
   const vh_p_match *pm;
   int64_t pm_stride;
   const int32_t *counts;
   int32_t count_cap;
-  const vh_track *trk;       // row r at trk + r * trk_stride
+  const vh_track *trk;       // list l at trk + l * trk_stride
   int64_t trk_stride;
   int32_t row_lo, rows;
   int64_t frame0;
   int32_t pred_valid;        // 0: the list of row_lo has no predecessor in the ring -- its records are stored as heads
-  VhReconRec *ring;          // [ring_slots][ring_cap]
-  int32_t *ring_count;       // [ring_slots]
+  VhReconRec *ring;          // [ring_slots][lists_per_frame][ring_cap]
+  int32_t *ring_count;       // [ring_slots][lists_per_frame]
   int32_t ring_slots, ring_cap, history;
   // recon_tails: the lists of frames [tail_lo, tail_hi) have a successor now; totals = {solved tracks, their pixels,
   // history tracks} of the counting mode, then {solved tracks << 40 | pixels, history tracks} of the appending mode
@@ -354,8 +360,10 @@ struct VhReconGatherArgs {
   VhReconTail *tails;        // [n_tails]
   int32_t n_tails, n_solved;
   int64_t n_pixels;
-  // recon_gather: the arrays recon_kernel reads (vh_recon.h); first_frame counts from frame `window0`
+  // recon_gather: the arrays recon_kernel reads (vh_recon.h); the frame table holds `window` frames from frame `window0`
+  // per stream, stream after stream, and first_frame indexes the concatenation
   int64_t window0;
+  int32_t window;
   int32_t *first_frame, *offsets, *order;
   float *pixels;
   uint32_t *check;           // VH_CHECK builds: {violations, code, value, bound}

@@ -723,6 +723,40 @@ int32_t vh_sequence_get_recon_tracks(vh_group *g, vh_recon_track *out, int32_t c
 int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride,
                              const int32_t *counts, int32_t n_index, const double *Tr, vh_recon_track *out, int32_t cap, int32_t *n);
 
+/* ---- reconstruction on a group: S cameras stepped together, 3-d points per camera and step ----------
+ * The sequence form above with a second axis: a step of the group is one frame of each of its S cameras, the ring keeps
+ * history_steps + 1 steps of S lists, and ONE store, tails, gather and solve sequence per step serves all S streams.
+ * Streams never interact: stream s's records over a drive are what the sequence form gives for stream s's own lists and
+ * motions (the link rule, as stated above).
+ *   Frames: frame k of stream s is the frame with push serial k (the serial vh_track.birth_frame counts in).  Stream s's
+ *   list of a step is the update whose current_frame is that serial, and Tr[s] is its motion.  A track whose last record
+ *   lies in the stream's previous list and that no record of this step's list continues is lost at this step: the previous
+ *   step's lists are the pending ones.  The step of the first push holds no pair: its call reads no Tr and returns nothing.
+ *   History: a lost track with age > history_steps is not solved (VH_RECON_HISTORY, zeros).
+ *   Breaks are per group, as match calls are: the reconstruction of EVERY stream starts again -- pending tracks and the
+ *   history dropped, not solved, and vh_track's birth and age starting again with it -- when dims change, when a step was
+ *   pushed but never matched, after a failed match call, when a step was matched but not reconstructed, and when a step is
+ *   matched again after it was reconstructed.  Matching a step again BEFORE its reconstruct call only replaces the lists.
+ *   A replace push is a break as well: the linking contract gives the lists of a replaced frame no predecessor, and a push
+ *   covers all S streams, so it breaks every stream of the group.
+ * vh_group_set_reconstruction: plain groups only (VH_ERR_UNSUPPORTED on a sequence handle, which keeps its own entry);
+ * before the first push only (VH_ERR_STATE afterwards); r == NULL switches the feature off; otherwise history_steps < 1 is
+ * VH_ERR_INVALID_ARG.  It switches track linking on; vh_group_set_track_linking(g, 0) returns VH_ERR_STATE while it is on.
+ * Off (the default): nothing is allocated or launched.  On: a ring of 32 * max_matches * S * (history_steps + 1) bytes and
+ * a count per slot, allocated by the first vh_group_reconstruct, plus the gather buffers, which only grow; all counted by
+ * vh_group_device_bytes. */
+int32_t vh_group_set_reconstruction(vh_group *g, const vh_recon_params *r, int32_t history_steps);
+/* The lost tracks of the step of the last match call, all streams: legal once per match call, from its return until the
+ * next match call -- also after the next push; otherwise VH_ERR_STATE.  Tr[S][16]: one row-major motion per stream.
+ * Synchronous.  *n_tracks / *n_accepted: the sums over the streams.  A failed allocation returns VH_ERR_HIP before any
+ * host state changed: the call may be made again. */
+int32_t vh_group_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, int32_t *n_accepted);
+/* Stream `stream`'s records of the last vh_group_reconstruct, sorted by (lost_frame, birth_frame, birth_pos), under the
+ * getters' capacity rule: VH_ERR_CAPACITY with the true count in *n and the first cap records written. */
+int32_t vh_group_get_recon_tracks(vh_group *g, int32_t stream, vh_recon_track *out, int32_t cap, int32_t *n);
+/* Per stream the records and the accepted ones of the last vh_group_reconstruct ([S] each; either may be NULL). */
+int32_t vh_group_get_recon_counts(vh_group *g, int32_t *n_tracks, int32_t *n_accepted);
+
 /* Which form of the search loops the group currently runs and the last observed share of
  * queries the speculative form had to search again (-1 before the first report).  The
  * searches are exact either way; the library switches between a speculative loop (no accept
@@ -736,6 +770,14 @@ int32_t vh_group_debug_fail_next_alloc(vh_group *g);
 /* The same after `skip` (>= 0) more allocations have succeeded: a failure in the middle of a call that allocates several
  * buffers (the track tables, then the range tables of multi-stage matching). */
 int32_t vh_group_debug_fail_alloc_after(vh_group *g, int32_t skip);
+/* Test hook: the group form of the reconstruction kernels on caller-owned lists (host pointers), as vh_reconstruct_lists
+ * is their sequence form.  n_streams cameras of n_lists lists each, stream s's list l at pm[(s * n_lists + l) * stride ..
+ * + counts[s * n_lists + l]) with the motion Tr[s * n_lists + l]; every stream is a fresh drive of its own, and all of them
+ * go through one store, tails, gather and solve sequence.  out receives the records stream after stream, each sorted;
+ * n[n_streams] the counts; VH_ERR_CAPACITY if their sum exceeds cap (nothing is written then). */
+int32_t vh_group_debug_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n_streams, int32_t n_lists, const vh_p_match *pm,
+                                         int64_t stride, const int32_t *counts, int32_t n_index, const double *Tr, vh_recon_track *out,
+                                         int32_t cap, int32_t *n);
 /* Test hook: flip-stack entries the device vote's sweep may hold per list (1..31; 0 restores the default, 31), process-wide.
  * With a small value ordinary match lists take the refusal path (VH_ERR_UNSUPPORTED for that list, see
  * vh_remove_outliers_device). */
@@ -746,7 +788,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  * ("detect_nms", "emit_features", "bin_hist", "bin_scan", "bin_fill",
  *  "bin_sort", "match", "chain", "emit_matches"; with refinement > 0 also "refine_planes", "refine";
  *  with track linking "track_scatter", "track_link", "track_rank" and, once per chunk of a sequence handle, "track_carry";
- *  with reconstruction on a sequence handle "recon_store", "recon_tails", "recon_gather", "recon_solve", per vh_sequence_reconstruct;
+ *  with reconstruction on a sequence handle "recon_store", "recon_tails", "recon_gather", "recon_solve", per vh_sequence_reconstruct,
+ *  and the same four on a group, per vh_group_reconstruct;
  *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place)
