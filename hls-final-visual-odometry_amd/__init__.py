@@ -76,6 +76,8 @@ ABI_SYMBOLS = (
     "vh_sequence_set_reconstruction", "vh_sequence_reconstruct", "vh_sequence_get_recon_tracks", "vh_reconstruct_lists",
     "vh_group_set_reconstruction", "vh_group_reconstruct", "vh_group_get_recon_tracks", "vh_group_get_recon_counts",
     "vh_group_debug_reconstruct_lists",
+    "vh_motion_inliers", "vh_group_motion_inliers", "vh_match_inliers", "vh_group_get_inlier_flags", "vh_group_get_inlier_matches",
+    "vh_group_get_inlier_matches_all", "vh_get_inlier_matches", "vh_group_inliers_device",
 )
 
 
@@ -261,6 +263,11 @@ def _lib():
             "vh_group_set_reconstruction": [vp, vp, i32], "vh_group_reconstruct": [vp, vp, vp, vp],
             "vh_group_get_recon_tracks": [vp, i32, vp, i32, vp], "vh_group_get_recon_counts": [vp, vp, vp],
             "vh_group_debug_reconstruct_lists": [vp, i32, i32, i32, vp, i64, vp, i32, vp, vp, i32, vp],
+            "vh_motion_inliers": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_motion_inliers": [vp, vp, vp, vp, vp], "vh_match_inliers": [vp, vp, vp, i32, vp],
+            "vh_group_get_inlier_flags": [vp, i32, vp, i32, vp], "vh_group_get_inlier_matches": [vp, i32, vp, vp, i32, vp],
+            "vh_group_get_inlier_matches_all": [vp, vp, vp, i32, vp], "vh_get_inlier_matches": [vp, vp, vp, i32, vp],
+            "vh_group_inliers_device": [vp, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -429,6 +436,23 @@ class Matcher:
         elif rc != VH_OK:
             raise VisoHipError(rc, "vh_get_tracks")
         return out
+
+    def motionInliers(self, ego: "EgoParams", tr, ok: bool = True) -> int:
+        """VisualOdometryStereo::getInlier on the whole device-resident quad list under tr[6] (vh_match_inliers) -> the
+        number of inliers; getInlierMatches() returns them."""
+        tr = np.ascontiguousarray(tr, np.float64).reshape(6)
+        n = C.c_int32(0)
+        _check(_lib().vh_match_inliers(self._h, C.byref(ego), _ptr(tr), 1 if ok else 0, C.byref(n)), "vh_match_inliers")
+        return n.value
+
+    def getInlierMatches(self):
+        """-> (the inlier records in list order, their positions in getMatches()) of the last motionInliers."""
+        n = C.c_int32(0)
+        _check(_lib().vh_get_inlier_matches(self._h, None, None, 0, C.byref(n)), "vh_get_inlier_matches", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, P_MATCH_DTYPE); pos = np.zeros(n.value, np.int32)
+        if n.value:
+            _check(_lib().vh_get_inlier_matches(self._h, _ptr(out), _ptr(pos), n.value, C.byref(n)), "vh_get_inlier_matches")
+        return out, pos
 
     def getFeatures(self, which: int) -> np.ndarray:
         n = C.c_int32(0)
@@ -634,6 +658,48 @@ class StreamGroup:
         tr = np.zeros((self.S, 6), np.float64); ok = np.zeros(self.S, np.int32); ninl = np.zeros(self.S, np.int32)
         _check(_lib().vh_group_estimate_motion(self._h, C.byref(ego), _ptr(rand3), _ptr(tr), _ptr(ok), _ptr(ninl)), "vh_group_estimate_motion")
         return tr, ok.astype(bool), ninl
+
+    def motionInliers(self, ego: "EgoParams", tr, ok) -> np.ndarray:
+        """VisualOdometryStereo::getInlier (reference src/viso_stereo.cpp:159-177) on every stream's whole device-resident
+        quad list under tr [S, 6] / ok [S], e.g. from estimateMotion (vh_group_motion_inliers) -> inliers per stream [S]."""
+        tr = np.ascontiguousarray(tr, np.float64); ok = np.ascontiguousarray(ok).astype(np.int32)
+        assert tr.shape == (self.S, 6) and ok.shape == (self.S,)
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_motion_inliers(self._h, C.byref(ego), _ptr(tr), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers")
+        return counts
+
+    def getInlierFlags(self, stream: int) -> np.ndarray:
+        """One byte per record of the stream's list: 1 = inlier of the last motionInliers (vh_group_get_inlier_flags)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_group_get_inlier_flags(self._h, stream, None, 0, C.byref(n)), "vh_group_get_inlier_flags", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            _check(_lib().vh_group_get_inlier_flags(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_inlier_flags")
+        return out
+
+    def getInlierMatches(self, stream: int):
+        """-> (the stream's inlier records in list order, their positions in getMatches(stream)) (vh_group_get_inlier_matches)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_group_get_inlier_matches(self._h, stream, None, None, 0, C.byref(n)), "vh_group_get_inlier_matches",
+               allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, P_MATCH_DTYPE); pos = np.zeros(n.value, np.int32)
+        if n.value:
+            _check(_lib().vh_group_get_inlier_matches(self._h, stream, _ptr(out), _ptr(pos), n.value, C.byref(n)), "vh_group_get_inlier_matches")
+        return out, pos
+
+    def getInlierMatchesAll(self, cap_per_stream: int):
+        """-> (records [S, cap_per_stream], positions [S, cap_per_stream], counts [S]) (vh_group_get_inlier_matches_all)."""
+        out = np.zeros((self.S, max(cap_per_stream, 1)), P_MATCH_DTYPE); pos = np.zeros((self.S, max(cap_per_stream, 1)), np.int32)
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_get_inlier_matches_all(self._h, _ptr(out), _ptr(pos), out.shape[1], _ptr(counts)), "vh_group_get_inlier_matches_all")
+        return out, pos, counts
+
+    def inliersDevice(self):
+        """-> (device addresses of stream 0's flags, inlier records and positions, stride in elements): valid until the
+        next matchFeatures (vh_group_inliers_device)."""
+        f = C.c_void_p(); m = C.c_void_p(); q = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_inliers_device(self._h, C.byref(f), C.byref(m), C.byref(q), C.byref(stride)), "vh_group_inliers_device")
+        return f.value, m.value, q.value, stride.value
 
     def postBegin(self, cap_per_stream: int):
         """Start the download of this step's match lists into an internal page-locked slot (vh_group_post_begin)."""
@@ -919,6 +985,26 @@ def estimate_motion_stereo(ego: EgoParams, match_lists, rand3, device: int = 0):
     _check(_lib().vh_estimate_motion_stereo(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(rand3), _ptr(tr), _ptr(ok),
                                             _ptr(ninl), _ptr(inl)), "vh_estimate_motion_stereo")
     return tr, ok.astype(bool), [inl[offsets[s]:offsets[s] + ninl[s]].copy() for s in range(n)]
+
+
+def motion_inliers(ego: EgoParams, match_lists, tr, ok, device: int = 0):
+    """VisualOdometryStereo::getInlier (reference src/viso_stereo.cpp:159-177) on whole quad lists under given motions:
+    `match_lists` (a list of p_match arrays), tr [n, 6], ok [n] (vh_motion_inliers).
+    -> ([flags uint8 per list], n_inliers [n], [inlier records per list], [their positions per list])."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    total = int(offsets[-1])
+    pm = np.concatenate(lists) if total else np.zeros(0, P_MATCH_DTYPE)
+    tr = np.ascontiguousarray(tr, np.float64).reshape(n, 6); ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    flags = np.zeros(max(total, 1), np.uint8); ninl = np.zeros(max(n, 1), np.int32)
+    out = np.zeros(max(total, 1), P_MATCH_DTYPE); pos = np.zeros(max(total, 1), np.int32)
+    _check(_lib().vh_motion_inliers(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(tr), _ptr(ok), _ptr(flags), _ptr(ninl),
+                                    _ptr(out), _ptr(pos)), "vh_motion_inliers")
+    sl = [slice(int(offsets[s]), int(offsets[s]) + int(ninl[s])) for s in range(n)]
+    return ([flags[offsets[s]:offsets[s + 1]].copy() for s in range(n)], ninl[:n],
+            [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0):

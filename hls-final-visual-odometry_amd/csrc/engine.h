@@ -3,6 +3,7 @@
 //   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
+//   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip) and their part of the ABI
 #ifndef VH_ENGINE_H
 #define VH_ENGINE_H
 #include "vh_dev.h"
@@ -244,6 +245,25 @@ struct ReconHistory {
   }
 };
 
+// Motion inliers of the handle's lists (vh_group_motion_inliers; engine_inlier.hip): one arena
+// block, allocated by the first call, cut into the arrays below.  Nothing here exists on a handle that never calls it.
+struct InlierState {
+  uint8_t *d_flags = nullptr;     // [S][mcap]
+  vh_p_match *d_out = nullptr;    // [S][mcap] the inlier records of each list, in list order
+  int32_t *d_src = nullptr;       // [S][mcap] their positions in the list
+  int32_t *d_tiles = nullptr;     // [S][tiles]
+  int32_t *d_ninl = nullptr, *d_ok = nullptr;  // [S]
+  double *d_tr = nullptr;         // [S][6]
+  // a second block, allocated only once a list was replaced on the host (vh_remove_outliers, vh_bucket_features): the
+  // lists as the getters return them, [S][mcap] and their counts [S]
+  vh_p_match *d_host_pm = nullptr;
+  int32_t *d_host_cnt = nullptr;
+  int32_t tiles = 0;
+  bool valid = false, truncated = false;  // a classification exists (of the lists of match call `seq`) / of a truncated list
+  int64_t seq = 0;
+  std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
+};
+
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
 struct VoteBatch {
   VoteBuffers vb;
@@ -391,6 +411,7 @@ struct Group {
   VoteBuffers ms_vb;
   std::vector<VoteBatch> vbatch;
   ReconHistory rh;
+  InlierState inl;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
   // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
   // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
@@ -472,6 +493,13 @@ struct Group {
   void recon_match_failed() { rh.m_valid = false; rh.drop_chain(); }
   int32_t recon_lists() const { return seq ? 1 : S; }  // lists per frame
   int32_t reconstruct(const double *Tr, int32_t *n_tracks, int32_t *n_accepted);
+
+  // ---- engine_inlier.hip ----
+  bool inliers_current() const { return allocated && inl.valid && inl.seq == match_seq; }
+  int32_t motion_inliers(const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts);
+  int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
+  int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
+  int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);
 
   // ---- engine_post.hip ----
   int32_t get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n);

@@ -1,0 +1,234 @@
+// engine_inlier.hip -- motion inliers: VisualOdometryStereo::getInlier on whole lists under a caller-given motion
+// (kernels_inlier.hip), on the device-resident lists of a handle and on caller-owned lists, and its part of the ABI.
+#include "engine.h"
+
+namespace vh_engine {
+
+static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// The arrays of one classification inside one device block: flags | records | positions | tile counts | counts | ok | tr
+struct InlierLayout {
+  size_t o_out, o_src, o_tiles, o_ninl, o_ok, o_tr, bytes;
+  InlierLayout(size_t lists, size_t slots, size_t tiles) {
+    o_out = up256(slots);
+    o_src = o_out + up256(sizeof(vh_p_match) * slots);
+    o_tiles = o_src + up256(sizeof(int32_t) * slots);
+    o_ninl = o_tiles + up256(sizeof(int32_t) * lists * tiles);
+    o_ok = o_ninl + up256(sizeof(int32_t) * lists);
+    o_tr = o_ok + up256(sizeof(int32_t) * lists);
+    bytes = o_tr + up256(sizeof(double) * 6 * lists);
+  }
+};
+
+// the launch grid is lists x tiles workgroups of 256 threads
+static bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
+
+int32_t Group::motion_inliers(const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts) {
+  if (!e || !tr || !ok || !counts) return VH_ERR_INVALID_ARG;
+  if (!allocated || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
+  bool replaced = false;  // the getters serve a host-side list for some stream: that list is classified, from a device copy
+  for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
+  const int32_t tiles = (mcap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
+  if (!inlier_grid_ok(S, tiles)) return VH_ERR_UNSUPPORTED;
+  inl.valid = false;
+  const InlierLayout lay((size_t)S, (size_t)S * mcap, (size_t)tiles);
+  if (!inl.d_flags) {  // one block: a refused allocation leaves nothing behind
+    uint8_t *d = nullptr;
+    const int32_t rc = dmalloc(&d, lay.bytes, false);
+    if (rc) return rc;
+    inl.d_flags = d; inl.d_out = (vh_p_match *)(d + lay.o_out); inl.d_src = (int32_t *)(d + lay.o_src);
+    inl.d_tiles = (int32_t *)(d + lay.o_tiles); inl.d_ninl = (int32_t *)(d + lay.o_ninl); inl.d_ok = (int32_t *)(d + lay.o_ok);
+    inl.d_tr = (double *)(d + lay.o_tr);
+    inl.tiles = tiles;
+  }
+  if (replaced && !inl.d_host_pm) {
+    uint8_t *d = nullptr;
+    const size_t b_pm = up256(sizeof(vh_p_match) * (size_t)S * mcap);
+    const int32_t rc = dmalloc(&d, b_pm + sizeof(int32_t) * (size_t)S, false);
+    if (rc) return rc;
+    inl.d_host_pm = (vh_p_match *)d; inl.d_host_cnt = (int32_t *)(d + b_pm);
+  }
+  inl.n_list.assign((size_t)S, 0); inl.n_inl.assign((size_t)S, 0);
+  // on the post stream, behind the emission of the lists
+  VH_HIP(hipMemcpyAsync(inl.d_tr, tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  const vh_p_match *d_lists = (const vh_p_match *)mt.d_matches;
+  const int32_t *d_counts = mt.d_match_count;
+  std::vector<int32_t> host_cnt;
+  if (replaced) {  // a replaced list is a subset of the device list it came from: it fits the slot
+    host_cnt.assign((size_t)S, 0);
+    VH_HIP(hipMemcpyAsync(inl.d_host_cnt, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
+    for (int32_t s = 0; s < S; s++) {
+      vh_p_match *dst = inl.d_host_pm + (size_t)s * mcap;
+      if (!host_filtered[s]) {
+        VH_HIP(hipMemcpyAsync(dst, d_lists + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)mcap, hipMemcpyDeviceToDevice, post_stream));
+        continue;
+      }
+      host_cnt[s] = (int32_t)std::min<size_t>(host_matches[s].size(), (size_t)mcap);
+      if (host_cnt[s]) VH_HIP(hipMemcpyAsync(dst, host_matches[s].data(), sizeof(vh_p_match) * (size_t)host_cnt[s], hipMemcpyHostToDevice, post_stream));
+      VH_HIP(hipMemcpyAsync(inl.d_host_cnt + s, &host_cnt[s], sizeof(int32_t), hipMemcpyHostToDevice, post_stream));
+    }
+    d_lists = inl.d_host_pm; d_counts = inl.d_host_cnt;
+  }
+  VhInlierArgs a{};
+  a.e = *e;
+  a.pm = d_lists; a.pm_stride = mcap; a.counts = d_counts; a.count_cap = mcap;
+  a.n_lists = S; a.tiles_per_list = inl.tiles;
+  a.tr = inl.d_tr; a.ok = inl.d_ok; a.out_stride = mcap;
+  a.flags = inl.d_flags; a.tile_cnt = inl.d_tiles; a.n_inl = inl.d_ninl; a.out = inl.d_out; a.src_pos = inl.d_src;
+  { Scope sc(this, "inlier_flag", post_stream); vh_launch_inlier_flag(a, post_stream); }
+  { Scope sc(this, "inlier_compact", post_stream); vh_launch_inlier_compact(a, post_stream); }
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipMemcpyAsync(inl.n_inl.data(), inl.d_ninl, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(inl.n_list.data(), d_counts, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(mt.h_overflow, mt.d_overflow, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipStreamSynchronize(post_stream));
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  inl.truncated = false;
+  for (int32_t s = 0; s < S; s++) {
+    if (inl.n_list[s] > mcap || mt.h_overflow[s]) inl.truncated = true;
+    inl.n_list[s] = std::min(inl.n_list[s], mcap);
+    counts[s] = inl.n_inl[s];
+  }
+  inl.valid = true; inl.seq = match_seq;
+  return inl.truncated ? VH_ERR_CAPACITY : VH_OK;
+}
+
+int32_t Group::get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n) {
+  if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!inliers_current()) return VH_ERR_STATE;
+  *n = inl.n_list[s];
+  const int32_t k = std::min(*n, capo);
+  if (k > 0) VH_HIP(hipMemcpy(out, inl.d_flags + (size_t)s * mcap, (size_t)k, hipMemcpyDeviceToHost));
+  return (*n > capo || inl.truncated) ? VH_ERR_CAPACITY : VH_OK;
+}
+
+int32_t Group::get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n) {
+  if (!n || s < 0 || s >= S || capo < 0 || (capo > 0 && !out)) return VH_ERR_INVALID_ARG;
+  *n = 0;
+  if (!inliers_current()) return VH_ERR_STATE;
+  *n = inl.n_inl[s];
+  const int32_t k = std::min(*n, capo);
+  if (k > 0) {
+    VH_HIP(hipMemcpy(out, inl.d_out + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost));
+    if (src_pos) VH_HIP(hipMemcpy(src_pos, inl.d_src + (size_t)s * mcap, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
+  }
+  return (*n > capo || inl.truncated) ? VH_ERR_CAPACITY : VH_OK;
+}
+
+int32_t Group::get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts) {
+  if (!out || !counts || cap_per_stream < 0) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < S; s++) counts[s] = 0;
+  if (!inliers_current()) return VH_ERR_STATE;
+  bool over = inl.truncated;
+  for (int32_t s = 0; s < S; s++) {
+    counts[s] = inl.n_inl[s];
+    over = over || counts[s] > cap_per_stream;
+    const int32_t k = std::min(counts[s], cap_per_stream);
+    if (k <= 0) continue;
+    VH_HIP(hipMemcpyAsync(out + (size_t)s * cap_per_stream, inl.d_out + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+    if (src_pos)
+      VH_HIP(hipMemcpyAsync(src_pos + (size_t)s * cap_per_stream, inl.d_src + (size_t)s * mcap, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+  }
+  VH_HIP(hipStreamSynchronize(post_stream));
+  return over ? VH_ERR_CAPACITY : VH_OK;
+}
+
+}  // namespace vh_engine
+
+using namespace vh_engine;
+
+#define ENTER(gq)                                   \
+  if (!(gq)) return VH_ERR_INVALID_ARG;             \
+  { hipError_t e_ = hipSetDevice((gq)->device);     \
+    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
+
+extern "C" {
+
+int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                          const double *tr, const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm,
+                          int32_t *src_pos) {
+  if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
+  if (n_sets == 0) return VH_OK;
+  if (!offsets || !tr || !ok || !n_inliers || offsets[0] < 0) return VH_ERR_INVALID_ARG;
+  int64_t nmax = 0;
+  for (int32_t s = 0; s < n_sets; s++) {
+    if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
+    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
+  }
+  const int64_t end = offsets[n_sets], total = end - offsets[0];
+  if (total > 0 && (!pm || !flags)) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < n_sets; s++) n_inliers[s] = 0;
+  if (total == 0) return VH_OK;
+  const int64_t tiles = (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
+  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, tiles)) return VH_ERR_UNSUPPORTED;  // (a list longer than any handle holds)
+  const int32_t rc = select_device(device);
+  if (rc) return rc;
+  // one block: the records up to offsets[n_sets] | offsets | the arrays of InlierLayout, addressed by the same offsets
+  const InlierLayout lay((size_t)n_sets, (size_t)end, (size_t)tiles);
+  const size_t o_pm = up256(lay.bytes), o_off = o_pm + up256(sizeof(vh_p_match) * (size_t)end);
+  DeviceBlock blk;
+  VH_HIP(blk.alloc(o_off + sizeof(int32_t) * ((size_t)n_sets + 1)));
+  uint8_t *d = blk.as<uint8_t>();
+  const size_t first = (size_t)offsets[0];
+  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + lay.o_tr, tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + lay.o_ok, ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyHostToDevice));
+  VhInlierArgs a{};
+  a.e = *e;
+  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
+  a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
+  a.tr = (const double *)(d + lay.o_tr); a.ok = (const int32_t *)(d + lay.o_ok);
+  a.flags = d; a.out = (vh_p_match *)(d + lay.o_out); a.src_pos = (int32_t *)(d + lay.o_src);
+  a.tile_cnt = (int32_t *)(d + lay.o_tiles); a.n_inl = (int32_t *)(d + lay.o_ninl);
+  vh_launch_inlier_flag(a, nullptr);
+  vh_launch_inlier_compact(a, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+  VH_HIP(hipMemcpy(n_inliers, a.n_inl, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToHost));
+  VH_HIP(hipMemcpy(flags + first, a.flags + first, (size_t)total, hipMemcpyDeviceToHost));
+  // (the compacted lists: list s's n_inliers[s] records at offsets[s]; what lies behind them in its slice is not written)
+  for (int32_t s = 0; s < n_sets && (inlier_pm || src_pos); s++) {
+    const size_t o = (size_t)offsets[s], k = (size_t)n_inliers[s];
+    if (!k) continue;
+    if (inlier_pm) VH_HIP(hipMemcpy(inlier_pm + o, a.out + o, sizeof(vh_p_match) * k, hipMemcpyDeviceToHost));
+    if (src_pos) VH_HIP(hipMemcpy(src_pos + o, a.src_pos + o, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+  }
+  return VH_OK;
+}
+
+int32_t vh_group_motion_inliers(vh_group *g, const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->motion_inliers(e, tr, ok, counts);
+}
+int32_t vh_match_inliers(vh_matcher *m, const vh_ego_params *e, const double *tr, int32_t ok, int32_t *count) {
+  Group *gq = (Group *)m; ENTER(gq);
+  if (gq->S != 1) return VH_ERR_INVALID_ARG;
+  return gq->motion_inliers(e, tr, &ok, count);
+}
+int32_t vh_group_get_inlier_flags(vh_group *g, int32_t stream, uint8_t *out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->get_inlier_flags(stream, out, cap, n);
+}
+int32_t vh_group_get_inlier_matches(vh_group *g, int32_t stream, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap, int32_t *n) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->get_inlier_matches(stream, pm_out, src_pos_out, cap, n);
+}
+int32_t vh_group_get_inlier_matches_all(vh_group *g, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap_per_stream, int32_t *counts) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->get_inlier_matches_all(pm_out, src_pos_out, cap_per_stream, counts);
+}
+int32_t vh_get_inlier_matches(vh_matcher *m, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap, int32_t *n) {
+  return vh_group_get_inlier_matches((vh_group *)m, 0, pm_out, src_pos_out, cap, n);
+}
+int32_t vh_group_inliers_device(vh_group *g, const uint8_t **d_flags, const vh_p_match **d_matches, const int32_t **d_src_pos, int64_t *stride) {
+  Group *gq = (Group *)g;
+  if (!gq || !d_flags || !d_matches || !d_src_pos || !stride) return VH_ERR_INVALID_ARG;
+  if (!gq->inliers_current()) return VH_ERR_STATE;
+  *d_flags = gq->inl.d_flags; *d_matches = gq->inl.d_out; *d_src_pos = gq->inl.d_src; *stride = gq->mcap;
+  return VH_OK;
+}
+
+}  // extern "C"

@@ -25,45 +25,11 @@
 #include "../../include/viso_hip.h"
 #include <math.h>
 #include "vh_wave.h"
+#include "vh_ego.h"
 #define SVD_HD __device__ __forceinline__
 #include "vh_gauss_jordan.h"
 
 namespace {
-
-struct EgoRot {
-  double r[9], drx[9], dry[9], drz[9];
-};
-
-__device__ __forceinline__ void ego_rot(const double tr[6], EgoRot &R) {
-  const double sx = sin(tr[0]), cx = cos(tr[0]), sy = sin(tr[1]), cy = cos(tr[1]), sz = sin(tr[2]), cz = cos(tr[2]);
-  R.r[0] = +cy * cz; R.r[1] = -cy * sz; R.r[2] = +sy;
-  R.r[3] = +sx * sy * cz + cx * sz; R.r[4] = -sx * sy * sz + cx * cz; R.r[5] = -sx * cy;
-  R.r[6] = -cx * sy * cz + sx * sz; R.r[7] = +cx * sy * sz + sx * cz; R.r[8] = +cx * cy;
-  R.drx[0] = 0; R.drx[1] = 0; R.drx[2] = 0;
-  R.drx[3] = +cx * sy * cz - sx * sz; R.drx[4] = -cx * sy * sz - sx * cz; R.drx[5] = -cx * cy;
-  R.drx[6] = +sx * sy * cz + cx * sz; R.drx[7] = -sx * sy * sz + cx * cz; R.drx[8] = -sx * cy;
-  R.dry[0] = -sy * cz; R.dry[1] = +sy * sz; R.dry[2] = +cy;
-  R.dry[3] = +sx * cy * cz; R.dry[4] = -sx * cy * sz; R.dry[5] = +sx * sy;
-  R.dry[6] = -cx * cy * cz; R.dry[7] = +cx * cy * sz; R.dry[8] = -cx * sy;
-  R.drz[0] = -cy * sz; R.drz[1] = -cy * cz; R.drz[2] = 0;
-  R.drz[3] = -sx * sy * sz + cx * cz; R.drz[4] = -sx * sy * cz - cx * sz; R.drz[5] = 0;
-  R.drz[6] = +cx * sy * sz + sx * cz; R.drz[7] = +cx * sy * cz - sx * sz; R.drz[8] = 0;
-}
-
-struct EgoObs { double u1c, v1c, u2c, v2c, X, Y, Z; };
-
-// prediction of one match under (R, t): p_predict of computeResidualsAndJacobian (src/viso_stereo.cpp:317-321)
-__device__ __forceinline__ void ego_predict(const vh_ego_params &e, const EgoRot &R, const double tr[6], const EgoObs &o, double p[4],
-                                            double &X1c, double &Y1c, double &Z1c) {
-  X1c = R.r[0] * o.X + R.r[1] * o.Y + R.r[2] * o.Z + tr[3];
-  Y1c = R.r[3] * o.X + R.r[4] * o.Y + R.r[5] * o.Z + tr[4];
-  Z1c = R.r[6] * o.X + R.r[7] * o.Y + R.r[8] * o.Z + tr[5];
-  const double X2c = X1c - e.base;
-  p[0] = e.f * X1c / Z1c + e.cu;
-  p[1] = e.f * Y1c / Z1c + e.cv;
-  p[2] = e.f * X2c / Z1c + e.cu;
-  p[3] = e.f * Y1c / Z1c + e.cv;
-}
 
 // Adds the four rows of one match to the normal equations: acc[0..20] = upper triangle of
 // J^T J (row-major, m <= n), acc[21..26] = J^T r; rows in the reference's order (u1, v1, u2, v2).
@@ -119,14 +85,6 @@ __device__ __forceinline__ EgoObs ego_load(const vh_p_match *pm, const double *X
   o.u1c = pm[i].u1c; o.v1c = pm[i].v1c; o.u2c = pm[i].u2c; o.v2c = pm[i].v2c;
   o.X = X[i]; o.Y = Y[i]; o.Z = Z[i];
   return o;
-}
-
-// squared reprojection error test of getInlier (src/viso_stereo.cpp:171-174)
-__device__ __forceinline__ bool ego_is_inlier(const vh_ego_params &e, const EgoRot &R, const double tr[6], const EgoObs &o) {
-  double p[4], a, b, c;
-  ego_predict(e, R, tr, o, p, a, b, c);
-  const double d0 = o.u1c - p[0], d1 = o.v1c - p[1], d2 = o.u2c - p[2], d3 = o.v2c - p[3];
-  return d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3 < e.inlier_threshold * e.inlier_threshold;
 }
 
 #define EGO_T 256

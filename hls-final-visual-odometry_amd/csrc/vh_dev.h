@@ -391,6 +391,28 @@ void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm,
                    const int32_t *counts, int32_t count_cap, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr,
                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st);
 
+// Motion inliers of whole lists (kernels_inlier.hip).  The lists are addressed as vh_list does;
+// flags, out and src_pos of list s begin at offsets[s] (concatenated lists) or at s * out_stride (fixed-stride slots).
+#define VH_INLIER_TILE 1024  // records per workgroup
+struct VhInlierArgs {
+  vh_ego_params e;          // f, cu, cv, base, inlier_threshold (ransac_iters and reweighting are not read)
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_INLIER_TILE)
+  const double *tr;         // [n_lists][6]
+  const int32_t *ok;        // [n_lists]; 0: the list has no inliers (tr is not read)
+  int64_t out_stride;
+  uint8_t *flags;
+  int32_t *tile_cnt;        // [n_lists][tiles_per_list] inliers per tile, then (after the scan) inliers before the tile
+  int32_t *n_inl;           // [n_lists]
+  vh_p_match *out;          // the inlier records in list order
+  int32_t *src_pos;         // position of each in its list
+};
+void vh_launch_inlier_flag(const VhInlierArgs &a, hipStream_t st);
+void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st);  // the scan of the tile counts, then the scatter
+
 struct vh_mono_params;
 int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters);
 void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,

@@ -508,6 +508,55 @@ int32_t vh_estimate_motion_stereo(const vh_ego_params *e, int32_t device, int32_
 int32_t vh_group_estimate_motion(vh_group *g, const vh_ego_params *e, const int32_t *rand3, double *tr, int32_t *ok,
                                  int32_t *n_inliers);
 
+/* ---- motion inliers: which records of whole lists agree with a motion ------------------------------- */
+/* VisualOdometryStereo::getInlier (src/viso_stereo.cpp:159-177) for any quad list and any tr[6] = (rx,ry,rz,tx,ty,tz):
+ * the 3-d point of the previous pair with float df = max(u1p - u2p, 0.0001f) (:83-86), the rotation (:244-250), the
+ * four predicted coordinates (:274-276, :317-321) and the test  sum of the four squared differences to
+ * (u1c, v1c, u2c, v2c) < inlier_threshold^2  -- strict, in double, added left to right, unweighted (`reweighting` and
+ * `ransac_iters` are not read).  A sum that is NaN or infinite (NaN coordinates, Z1c = 0) is "not an inlier", never
+ * an error; a list with ok = 0 has no inliers and its tr is not read; a list of one record is classified like any
+ * other (the N < 6 return belongs to estimateMotion).  The estimators' n_inliers / inliers refer to the (bucketed)
+ * lists they ran on; this classifies the dense lists under the motion they found.
+ * Only sin / cos come from the device library: with a non-zero rotation a record whose sum lies within rounding of
+ * the threshold may be classified differently from a host restatement using libm.
+ *
+ * Stateless: n_sets lists laid out as for vh_estimate_motion_stereo, tr[n_sets][6], ok[n_sets].  flags (one byte
+ * per record, 1 = inlier, indexed like pm, i.e. sized offsets[n_sets]) and n_inliers[n_sets] are written; if not
+ * NULL, inlier_pm and src_pos (both indexed like pm) receive at [offsets[s], offsets[s] + n_inliers[s]) the inlier
+ * records of list s in list order and the position of each in list s -- the rest of each slice is not written.
+ * n_sets == 0 or no records at all: VH_OK, nothing is launched and no device is needed.  VH_ERR_UNSUPPORTED for a
+ * list of more than 2^24 - 1 records or n_sets * ceil(longest / 1024) >= 2^24. */
+int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                          const double *tr, const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm,
+                          int32_t *src_pos);
+/* The same on the device-resident lists of the handle's last match call -- exactly the lists vh_group_get_matches
+ * returns (refined where refinement is on, pass 2 under multi-stage matching): tr[S][6], ok[S] go up, counts[S]
+ * (inliers per stream) comes back; synchronous.  Quad lists only (VH_ERR_STATE otherwise, and before any match, as
+ * vh_group_estimate_motion).  Once vh_remove_outliers / vh_group_remove_outliers / vh_bucket_features replaced a list
+ * on the host, the replaced list -- what the getters return -- is the one classified, from a device copy made by the
+ * call (a second block of 48 bytes per record slot and 4 per stream, allocated when that first happens).  Legal from the return of a match call until the next push or match; a further call with another tr replaces
+ * the result.  Plain groups, sequence handles (rows without a pair: count 0, their tr is not read) and lone matchers.
+ * VH_ERR_CAPACITY when a list or a feature set was truncated (the classification of the truncated list is kept).
+ * The first call allocates 1 + 48 + 4 bytes per record slot (S x max_matches slots), 4 bytes per tile of 1024 slots
+ * and 56 bytes per stream, counted by vh_group_device_bytes; a handle that never calls this allocates and launches
+ * nothing for it.  A failed allocation is VH_ERR_HIP before anything is launched, and the call may be repeated.
+ * Profile scopes: "inlier_flag", "inlier_compact". */
+int32_t vh_group_motion_inliers(vh_group *g, const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts);
+int32_t vh_match_inliers(vh_matcher *m, const vh_ego_params *e, const double *tr, int32_t ok, int32_t *count);
+/* The results of that call, valid until the next match call (VH_ERR_STATE before a classification of the current
+ * lists), under the getters' capacity rule: *n is the full number, at most cap elements are written, VH_ERR_CAPACITY
+ * when there are more.  Flags: one byte per record of the list.  Inlier matches: the inlier records in list order,
+ * and (src_pos_out, nullable) the position of each in the list, so pm_out[k] == list[src_pos_out[k]].  The _all form
+ * writes stream s at [s * cap_per_stream ..] and counts[S]. */
+int32_t vh_group_get_inlier_flags(vh_group *g, int32_t stream, uint8_t *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_inlier_matches(vh_group *g, int32_t stream, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap, int32_t *n);
+int32_t vh_group_get_inlier_matches_all(vh_group *g, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap_per_stream, int32_t *counts);
+int32_t vh_get_inlier_matches(vh_matcher *m, vh_p_match *pm_out, int32_t *src_pos_out, int32_t cap, int32_t *n);
+/* The device arrays themselves, stream s at [s * *stride ..] (elements), valid until the next match call; the
+ * compacted lists are ordinary lists: vh_reconstruct_lists and vh_link_tracks take them once downloaded. */
+int32_t vh_group_inliers_device(vh_group *g, const uint8_t **d_flags, const vh_p_match **d_matches, const int32_t **d_src_pos,
+                                int64_t *stride);
+
 /* ---- the steps after matching, pipelined ------------------------------------------------------------- */
 /* What the reference's loop runs between Matcher::matching and the pose -- removeOutliers (the tail of
  * matchFeatures, src/matcher.cpp:108), bucketFeatures (src/viso_stereo.cpp:41-43 -> src/matcher.cpp:140-187)
