@@ -78,6 +78,8 @@ ABI_SYMBOLS = (
     "vh_group_debug_reconstruct_lists",
     "vh_motion_inliers", "vh_group_motion_inliers", "vh_match_inliers", "vh_group_get_inlier_flags", "vh_group_get_inlier_matches",
     "vh_group_get_inlier_matches_all", "vh_get_inlier_matches", "vh_group_inliers_device",
+    "vh_estimate_motion_mono_model", "vh_group_estimate_motion_mono_model",
+    "vh_motion_inliers_mono", "vh_group_motion_inliers_mono", "vh_match_inliers_mono",
 )
 
 
@@ -129,6 +131,26 @@ class MonoParams(C.Structure):
                 raise AttributeError(k)
             setattr(e, k, v)
         return e
+
+
+class MonoModel(C.Structure):
+    """vh_mono_model: the normalisation and the refit F the mono estimator arrived at (include/viso_hip.h)."""
+    _fields_ = [("c", C.c_double * 4), ("s", C.c_double * 2), ("F", C.c_double * 9), ("valid", C.c_double)]
+
+
+#: numpy layout of vh_mono_model, for arrays of models (one per list / stream)
+MONO_MODEL_DTYPE = np.dtype([("c", "<f8", (4,)), ("s", "<f8", (2,)), ("F", "<f8", (9,)), ("valid", "<f8")])
+
+
+def _models(model, n):
+    """`model` (a MONO_MODEL_DTYPE array, a MonoModel or a sequence of them) as a contiguous MONO_MODEL_DTYPE array [n]."""
+    if isinstance(model, MonoModel):
+        model = [model]
+    if not isinstance(model, np.ndarray):
+        model = np.frombuffer(b"".join(bytes(m) for m in model), MONO_MODEL_DTYPE)
+    model = np.ascontiguousarray(model, MONO_MODEL_DTYPE).reshape(-1)
+    assert len(model) == n, (len(model), n)
+    return model
 
 
 class ReconParams(C.Structure):
@@ -268,6 +290,10 @@ def _lib():
             "vh_group_get_inlier_flags": [vp, i32, vp, i32, vp], "vh_group_get_inlier_matches": [vp, i32, vp, vp, i32, vp],
             "vh_group_get_inlier_matches_all": [vp, vp, vp, i32, vp], "vh_get_inlier_matches": [vp, vp, vp, i32, vp],
             "vh_group_inliers_device": [vp, vp, vp, vp, vp],
+            "vh_estimate_motion_mono_model": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_estimate_motion_mono_model": [vp, vp, vp, vp, vp, vp, vp],
+            "vh_motion_inliers_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_motion_inliers_mono": [vp, vp, vp, vp, vp], "vh_match_inliers_mono": [vp, vp, vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -445,8 +471,16 @@ class Matcher:
         _check(_lib().vh_match_inliers(self._h, C.byref(ego), _ptr(tr), 1 if ok else 0, C.byref(n)), "vh_match_inliers")
         return n.value
 
+    def motionInliersMono(self, mono: "MonoParams", model, ok: bool = True) -> int:
+        """VisualOdometryMono::getInlier on the whole device-resident flow or quad list under a vh_mono_model
+        (vh_match_inliers_mono) -> the number of inliers; getInlierMatches() returns them."""
+        model = _models(model, 1)
+        n = C.c_int32(0)
+        _check(_lib().vh_match_inliers_mono(self._h, C.byref(mono), _ptr(model), 1 if ok else 0, C.byref(n)), "vh_match_inliers_mono")
+        return n.value
+
     def getInlierMatches(self):
-        """-> (the inlier records in list order, their positions in getMatches()) of the last motionInliers."""
+        """-> (the inlier records in list order, their positions in getMatches()) of the last motionInliers(Mono)."""
         n = C.c_int32(0)
         _check(_lib().vh_get_inlier_matches(self._h, None, None, 0, C.byref(n)), "vh_get_inlier_matches", allow=(VH_ERR_CAPACITY,))
         out = np.zeros(n.value, P_MATCH_DTYPE); pos = np.zeros(n.value, np.int32)
@@ -668,6 +702,16 @@ class StreamGroup:
         _check(_lib().vh_group_motion_inliers(self._h, C.byref(ego), _ptr(tr), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers")
         return counts
 
+    def motionInliersMono(self, mono: "MonoParams", model, ok) -> np.ndarray:
+        """VisualOdometryMono::getInlier (reference src/viso_mono.cpp:268-315) on every stream's whole device-resident flow
+        or quad list under model [S] (MONO_MODEL_DTYPE) / ok [S], e.g. from estimateMotionMono(model=True)
+        (vh_group_motion_inliers_mono) -> inliers per stream [S]; the getters are motionInliers'."""
+        model = _models(model, self.S)
+        ok = np.ascontiguousarray(ok).astype(np.int32).reshape(self.S)
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_motion_inliers_mono(self._h, C.byref(mono), _ptr(model), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers_mono")
+        return counts
+
     def getInlierFlags(self, stream: int) -> np.ndarray:
         """One byte per record of the stream's list: 1 = inlier of the last motionInliers (vh_group_get_inlier_flags)."""
         n = C.c_int32(0)
@@ -769,12 +813,18 @@ class StreamGroup:
         lists = [out[s, :max(int(counts[s]), 0)].copy() for s in range(S)] if want_lists else None
         return {"tr": tr, "ok": ok.astype(bool), "n_inliers": ninl, "lists": lists, "counts": counts, "rc": rc}
 
-    def estimateMotionMono(self, mono: "MonoParams", rand8):
+    def estimateMotionMono(self, mono: "MonoParams", rand8, model: bool = False):
         """VisualOdometryMono::estimateMotion (reference src/viso_mono.cpp:41-160) on every stream's device-resident
-        flow (or quad) matches; rand8 [S, ransac_iters, 8] int32 rand() values -> (tr [S,6], ok [S], n_inliers [S])."""
+        flow (or quad) matches; rand8 [S, ransac_iters, 8] int32 rand() values -> (tr [S,6], ok [S], n_inliers [S]);
+        model=True: and the models [S] (MONO_MODEL_DTYPE, vh_group_estimate_motion_mono_model) as a fourth value."""
         rand8 = np.ascontiguousarray(rand8, np.int32)
         assert rand8.shape == (self.S, mono.ransac_iters, 8)
         tr = np.zeros((self.S, 6), np.float64); ok = np.zeros(self.S, np.int32); ninl = np.zeros(self.S, np.int32)
+        if model:
+            mo = np.zeros(self.S, MONO_MODEL_DTYPE)
+            _check(_lib().vh_group_estimate_motion_mono_model(self._h, C.byref(mono), _ptr(rand8), _ptr(tr), _ptr(ok), _ptr(ninl), _ptr(mo)),
+                   "vh_group_estimate_motion_mono_model")
+            return tr, ok.astype(bool), ninl, mo
         _check(_lib().vh_group_estimate_motion_mono(self._h, C.byref(mono), _ptr(rand8), _ptr(tr), _ptr(ok), _ptr(ninl)), "vh_group_estimate_motion_mono")
         return tr, ok.astype(bool), ninl
 
@@ -1007,9 +1057,10 @@ def motion_inliers(ego: EgoParams, match_lists, tr, ok, device: int = 0):
             [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
 
 
-def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0):
+def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):
     """VisualOdometryMono::estimateMotion (reference src/viso_mono.cpp:41-160), batched over `match_lists`;
-    rand8 [n_sets, ransac_iters, 8] int32 rand() values.  -> (tr [n,6], ok [n] bool, [inlier index arrays])."""
+    rand8 [n_sets, ransac_iters, 8] int32 rand() values.  -> (tr [n,6], ok [n] bool, [inlier index arrays]);
+    model=True: and the models [n] (MONO_MODEL_DTYPE, vh_estimate_motion_mono_model) as a fourth value."""
     lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
     n = len(lists)
     offsets = np.zeros(n + 1, np.int32)
@@ -1019,9 +1070,36 @@ def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0):
     assert rand8.shape == (n, mono.ransac_iters, 8)
     tr = np.zeros((n, 6), np.float64); ok = np.zeros(n, np.int32); ninl = np.zeros(n, np.int32)
     inl = np.zeros(max(int(offsets[-1]), 1), np.int32)
-    _check(_lib().vh_estimate_motion_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(rand8), _ptr(tr), _ptr(ok),
-                                          _ptr(ninl), _ptr(inl)), "vh_estimate_motion_mono")
-    return tr, ok.astype(bool), [inl[offsets[s]:offsets[s] + ninl[s]].copy() for s in range(n)]
+    if model:
+        mo = np.zeros(max(n, 1), MONO_MODEL_DTYPE)
+        _check(_lib().vh_estimate_motion_mono_model(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(rand8), _ptr(tr), _ptr(ok),
+                                                    _ptr(ninl), _ptr(inl), _ptr(mo)), "vh_estimate_motion_mono_model")
+    else:
+        _check(_lib().vh_estimate_motion_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(rand8), _ptr(tr), _ptr(ok),
+                                              _ptr(ninl), _ptr(inl)), "vh_estimate_motion_mono")
+    res = (tr, ok.astype(bool), [inl[offsets[s]:offsets[s] + ninl[s]].copy() for s in range(n)])
+    return res + (mo[:n],) if model else res
+
+
+def motion_inliers_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
+    """VisualOdometryMono::getInlier (reference src/viso_mono.cpp:268-315) on whole flow or quad lists under given models:
+    `match_lists` (a list of p_match arrays), model [n] (MONO_MODEL_DTYPE), ok [n] (vh_motion_inliers_mono).
+    -> ([flags uint8 per list], n_inliers [n], [inlier records per list], [their positions per list])."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    total = int(offsets[-1])
+    pm = np.concatenate(lists) if total else np.zeros(0, P_MATCH_DTYPE)
+    model = _models(model, n) if n else np.zeros(1, MONO_MODEL_DTYPE)
+    ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    flags = np.zeros(max(total, 1), np.uint8); ninl = np.zeros(max(n, 1), np.int32)
+    out = np.zeros(max(total, 1), P_MATCH_DTYPE); pos = np.zeros(max(total, 1), np.int32)
+    _check(_lib().vh_motion_inliers_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(flags), _ptr(ninl),
+                                         _ptr(out), _ptr(pos)), "vh_motion_inliers_mono")
+    sl = [slice(int(offsets[s]), int(offsets[s]) + int(ninl[s])) for s in range(n)]
+    return ([flags[offsets[s]:offsets[s + 1]].copy() for s in range(n)], ninl[:n],
+            [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
 
 
 def remove_outliers(pm) -> np.ndarray:

@@ -179,6 +179,7 @@ struct EgoScratch {
   size_t ego_rand_n = 0;
   uint8_t *d_mono_scratch = nullptr;
   int32_t *d_mono_rand = nullptr;
+  vh_mono_model *d_mono_model = nullptr;  // [S] vh_group_estimate_motion_mono_model's output, allocated by its first call
   size_t mono_rand_n = 0;
   int32_t mono_scratch_iters = 0;
 };
@@ -245,6 +246,20 @@ struct ReconHistory {
   }
 };
 
+// Which per-record test a classification launches, with what the caller gave for it: VisualOdometryStereo::getInlier
+// under tr[lists][6], or VisualOdometryMono::getInlier under model[lists].
+struct InlierTest {
+  const vh_ego_params *ego = nullptr;
+  const double *tr = nullptr;
+  const vh_mono_params *mono = nullptr;
+  const vh_mono_model *model = nullptr;
+  bool is_mono = false;
+  static InlierTest stereo(const vh_ego_params *e, const double *tr) { InlierTest t; t.ego = e; t.tr = tr; return t; }
+  static InlierTest monocular(const vh_mono_params *e, const vh_mono_model *m) { InlierTest t; t.mono = e; t.model = m; t.is_mono = true; return t; }
+  bool params_ok() const { return is_mono ? mono != nullptr : ego != nullptr; }
+  bool args_ok() const { return params_ok() && (is_mono ? model != nullptr : tr != nullptr); }
+};
+
 // Motion inliers of the handle's lists (vh_group_motion_inliers; engine_inlier.hip): one arena
 // block, allocated by the first call, cut into the arrays below.  Nothing here exists on a handle that never calls it.
 struct InlierState {
@@ -254,6 +269,7 @@ struct InlierState {
   int32_t *d_tiles = nullptr;     // [S][tiles]
   int32_t *d_ninl = nullptr, *d_ok = nullptr;  // [S]
   double *d_tr = nullptr;         // [S][6]
+  vh_mono_model *d_model = nullptr;  // [S] a block of its own, allocated by the first mono classification
   // a second block, allocated only once a list was replaced on the host (vh_remove_outliers, vh_bucket_features): the
   // lists as the getters return them, [S][mcap] and their counts [S]
   vh_p_match *d_host_pm = nullptr;
@@ -496,7 +512,7 @@ struct Group {
 
   // ---- engine_inlier.hip ----
   bool inliers_current() const { return allocated && inl.valid && inl.seq == match_seq; }
-  int32_t motion_inliers(const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts);
+  int32_t motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts);
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
   int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
   int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);
@@ -512,7 +528,7 @@ struct Group {
   int32_t fetch_matches(int32_t s);
   int32_t remove_outliers(int32_t s_lo, int32_t s_hi, int32_t threads);
   int32_t estimate_motion(const vh_ego_params *e, const int32_t *rand3, double *tr, int32_t *ok, int32_t *ninl);
-  int32_t estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl);
+  int32_t estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl, vh_mono_model *model);
   int32_t estimate_results(double *tr, int32_t *ok, int32_t *ninl);
   int32_t post_begin(int32_t cap_ps);
   int32_t post_finish(int32_t age, int32_t max_features, float bw, float bh, int32_t threads, const vh_ego_params *e, const int32_t *rand3,

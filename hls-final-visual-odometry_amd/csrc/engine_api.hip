@@ -61,10 +61,12 @@ struct EgoWorkLease {
 // The stateless estimators: validation, one device block (matches | offsets | random draws | ok,ninl | inliers | tr |
 // scratch of scratch_bytes(longest list)), the uploads, the kernels through `launch`, the downloads.  unsupported: the
 // verdict of the entry point's own limits, reported once the arguments are known to be valid.
+// extra / extra_bytes (nullable / 0): one more output of the call (the mono models), behind the scratch; `launch` receives its
+// device address as its last argument and the bytes come back with the other results.
 template <class Bytes, class Launch>
 static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac_iters, int32_t draws, bool unsupported, const vh_p_match *pm,
                                   const int32_t *offsets, const int32_t *rnd, double *tr, int32_t *ok, int32_t *n_inliers, int32_t *inliers,
-                                  Bytes scratch_bytes, Launch launch) {
+                                  Bytes scratch_bytes, Launch launch, void *extra = nullptr, size_t extra_bytes = 0) {
   if (n_sets < 1 || !offsets || !rnd || !tr || !ok || !n_inliers || ransac_iters < 1) return VH_ERR_INVALID_ARG;
   if (offsets[0] < 0) return VH_ERR_INVALID_ARG;
   int64_t nmax = 0;
@@ -83,7 +85,8 @@ static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac
   auto up = [](size_t x) { return (x + 255) / 256 * 256; };
   const size_t o_off = up(b_pm), o_r = o_off + up(b_off), o_ok = o_r + up(b_r), o_inl = o_ok + up(b_ok), o_tr = o_inl + up(b_inl), o_scr = o_tr + up(b_tr);
   EgoWorkLease lease;
-  VH_HIP(lease.take(device, o_scr + b_scr));
+  const size_t o_extra = o_scr + up(b_scr);
+  VH_HIP(lease.take(device, extra ? o_extra + extra_bytes : o_scr + b_scr));
   uint8_t *d = lease.d;
   hipError_t er = hipSuccess;
   if (total) er = hipMemcpy(d, pm, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice);
@@ -91,7 +94,7 @@ static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac
   if (er == hipSuccess) er = hipMemcpy(d + o_r, rnd, b_r, hipMemcpyHostToDevice);
   if (er == hipSuccess) {
     launch((const vh_p_match *)d, (const int32_t *)(d + o_off), (const int32_t *)(d + o_r), d + o_scr, cap, (double *)(d + o_tr), (int32_t *)(d + o_ok),
-           (int32_t *)(d + o_inl));
+           (int32_t *)(d + o_inl), extra ? d + o_extra : nullptr);
     er = hipGetLastError();  // (a rejected launch is not reported by the synchronisation)
     if (er == hipSuccess) er = hipDeviceSynchronize();
   }
@@ -99,6 +102,7 @@ static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac
   if (er == hipSuccess) er = hipMemcpy(ok, d + o_ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToHost);
   if (er == hipSuccess) er = hipMemcpy(n_inliers, d + o_ok + sizeof(int32_t) * (size_t)n_sets, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToHost);
   if (er == hipSuccess && inliers && total) er = hipMemcpy(inliers, d + o_inl, sizeof(int32_t) * (size_t)total, hipMemcpyDeviceToHost);
+  if (er == hipSuccess && extra) er = hipMemcpy(extra, d + o_extra, extra_bytes, hipMemcpyDeviceToHost);
   if (er != hipSuccess) { t_last_error = hipGetErrorString(er); return VH_ERR_HIP; }
   return VH_OK;
 }
@@ -636,7 +640,7 @@ int32_t vh_estimate_motion_stereo(const vh_ego_params *e, int32_t device, int32_
   if (!e) return VH_ERR_INVALID_ARG;
   return estimate_stateless(device, n_sets, e->ransac_iters, 3, false, pm, offsets, rand3, tr, ok, n_inliers, inliers,
     [&](int64_t cap) { return sizeof(double) * 4 * (size_t)n_sets * (size_t)cap; },  // xyz + flags
-    [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl) {
+    [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl, uint8_t *) {
       vh_launch_ego(*e, n_sets, d_pm, 0, d_off, nullptr, 0, d_rand, (double *)d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, nullptr);
     });
 }
@@ -685,19 +689,36 @@ void vh_default_mono_params(vh_mono_params *e) {
 int32_t vh_group_estimate_motion_mono(vh_group *g, const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok,
                                       int32_t *n_inliers) {
   Group *gq = (Group *)g; ENTER(gq);
-  return gq->estimate_motion_mono(e, rand8, tr, ok, n_inliers);
+  return gq->estimate_motion_mono(e, rand8, tr, ok, n_inliers, nullptr);
 }
-int32_t vh_estimate_motion_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
-                                const int32_t *offsets, const int32_t *rand8, double *tr, int32_t *ok, int32_t *n_inliers,
-                                int32_t *inliers) {
+int32_t vh_group_estimate_motion_mono_model(vh_group *g, const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok,
+                                            int32_t *n_inliers, vh_mono_model *model) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (!model) return VH_ERR_INVALID_ARG;
+  return gq->estimate_motion_mono(e, rand8, tr, ok, n_inliers, model);
+}
+// model (nullable): the models come back too
+static int32_t estimate_mono_stateless(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                                       const int32_t *rand8, double *tr, int32_t *ok, int32_t *n_inliers, int32_t *inliers, vh_mono_model *model) {
   if (!e) return VH_ERR_INVALID_ARG;
   // (the hypothesis and triangulation kernels put the list on grid.y)
   const bool unsupported = (int64_t)n_sets * e->ransac_iters > (int64_t)1 << 31 || n_sets > 65535;
   return estimate_stateless(device, n_sets, e->ransac_iters, 8, unsupported, pm, offsets, rand8, tr, ok, n_inliers, inliers,
     [&](int64_t cap) { return (size_t)vh_mono_scratch_bytes(n_sets, cap, e->ransac_iters); },  // per-list scratch
-    [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl) {
-      vh_launch_mono(*e, n_sets, d_pm, 0, d_off, nullptr, 0, d_rand, d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, nullptr);
-    });
+    [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl, uint8_t *d_model) {
+      vh_launch_mono(*e, n_sets, d_pm, 0, d_off, nullptr, 0, d_rand, d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, (vh_mono_model *)d_model, nullptr);
+    }, model, model ? sizeof(vh_mono_model) * (size_t)std::max(n_sets, 0) : 0);
+}
+int32_t vh_estimate_motion_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                                const int32_t *offsets, const int32_t *rand8, double *tr, int32_t *ok, int32_t *n_inliers,
+                                int32_t *inliers) {
+  return estimate_mono_stateless(e, device, n_sets, pm, offsets, rand8, tr, ok, n_inliers, inliers, nullptr);
+}
+int32_t vh_estimate_motion_mono_model(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                                      const int32_t *offsets, const int32_t *rand8, double *tr, int32_t *ok, int32_t *n_inliers,
+                                      int32_t *inliers, vh_mono_model *model) {
+  if (!model) return VH_ERR_INVALID_ARG;
+  return estimate_mono_stateless(e, device, n_sets, pm, offsets, rand8, tr, ok, n_inliers, inliers, model);
 }
 
 // ---- stateless primitives ----------------------------------------------------

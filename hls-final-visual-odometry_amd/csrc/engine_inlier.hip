@@ -1,6 +1,8 @@
-// engine_inlier.hip -- motion inliers: VisualOdometryStereo::getInlier on whole lists under a caller-given motion
-// (kernels_inlier.hip), on the device-resident lists of a handle and on caller-owned lists, and its part of the ABI.
+// engine_inlier.hip -- motion inliers: VisualOdometryStereo::getInlier on whole lists under a caller-given motion and
+// VisualOdometryMono::getInlier under a caller-given epipolar model (kernels_inlier.hip), on the device-resident lists
+// of a handle and on caller-owned lists, and its part of the ABI.
 #include "engine.h"
+#include <optional>
 
 namespace vh_engine {
 
@@ -23,16 +25,35 @@ struct InlierLayout {
 // the launch grid is lists x tiles workgroups of 256 threads
 static bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
 
-int32_t Group::motion_inliers(const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts) {
-  if (!e || !tr || !ok || !counts) return VH_ERR_INVALID_ARG;
-  if (!allocated || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
+// The flag pass of either test, then the scan and the scatter both share.  g: the handle whose profile takes the
+// scopes (none for the stateless entries).
+static void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group *g) {
+  std::optional<Scope> sc;
+  if (g) sc.emplace(g, t.is_mono ? "inlier_flag_mono" : "inlier_flag", st);
+  if (t.is_mono) {
+    a.mono_threshold = t.mono->inlier_threshold;
+    vh_launch_inlier_flag_mono(a, st);
+  } else {
+    a.e = *t.ego;
+    vh_launch_inlier_flag(a, st);
+  }
+  sc.reset();
+  if (g) sc.emplace(g, "inlier_compact", st);
+  vh_launch_inlier_compact(a, st);
+}
+
+int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts) {
+  if (!t.args_ok() || !ok || !counts) return VH_ERR_INVALID_ARG;
+  // the stereo test reads the right camera's columns; the mono test the left camera's flow, which flow and quad lists carry
+  if (!allocated || !(last_method == VH_METHOD_QUAD || (t.is_mono && last_method == VH_METHOD_FLOW))) return VH_ERR_STATE;
   bool replaced = false;  // the getters serve a host-side list for some stream: that list is classified, from a device copy
   for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
   const int32_t tiles = (mcap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
   if (!inlier_grid_ok(S, tiles)) return VH_ERR_UNSUPPORTED;
   inl.valid = false;
   const InlierLayout lay((size_t)S, (size_t)S * mcap, (size_t)tiles);
-  if (!inl.d_flags) {  // one block: a refused allocation leaves nothing behind
+  const bool first = !inl.d_flags;
+  if (first) {  // one block: a refused allocation leaves nothing behind
     uint8_t *d = nullptr;
     const int32_t rc = dmalloc(&d, lay.bytes, false);
     if (rc) return rc;
@@ -40,6 +61,16 @@ int32_t Group::motion_inliers(const vh_ego_params *e, const double *tr, const in
     inl.d_tiles = (int32_t *)(d + lay.o_tiles); inl.d_ninl = (int32_t *)(d + lay.o_ninl); inl.d_ok = (int32_t *)(d + lay.o_ok);
     inl.d_tr = (double *)(d + lay.o_tr);
     inl.tiles = tiles;
+  }
+  if (t.is_mono && !inl.d_model) {  // the models of the mono test: a block of their own, so that the stereo path allocates what it always did
+    const int32_t rc = dmalloc(&inl.d_model, (size_t)S, false);
+    if (rc) {
+      if (first) {  // (nothing has used the main block yet, and no other block of `inl` exists) -- the refused call leaves the handle as it found it
+        dfree(inl.d_flags); device_bytes -= (int64_t)lay.bytes;
+        inl = InlierState();
+      }
+      return rc;
+    }
   }
   if (replaced && !inl.d_host_pm) {
     uint8_t *d = nullptr;
@@ -50,7 +81,8 @@ int32_t Group::motion_inliers(const vh_ego_params *e, const double *tr, const in
   }
   inl.n_list.assign((size_t)S, 0); inl.n_inl.assign((size_t)S, 0);
   // on the post stream, behind the emission of the lists
-  VH_HIP(hipMemcpyAsync(inl.d_tr, tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  if (t.is_mono) VH_HIP(hipMemcpyAsync(inl.d_model, t.model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  else VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
   VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
   const vh_p_match *d_lists = (const vh_p_match *)mt.d_matches;
   const int32_t *d_counts = mt.d_match_count;
@@ -71,13 +103,11 @@ int32_t Group::motion_inliers(const vh_ego_params *e, const double *tr, const in
     d_lists = inl.d_host_pm; d_counts = inl.d_host_cnt;
   }
   VhInlierArgs a{};
-  a.e = *e;
   a.pm = d_lists; a.pm_stride = mcap; a.counts = d_counts; a.count_cap = mcap;
   a.n_lists = S; a.tiles_per_list = inl.tiles;
-  a.tr = inl.d_tr; a.ok = inl.d_ok; a.out_stride = mcap;
+  a.tr = t.is_mono ? nullptr : inl.d_tr; a.model = t.is_mono ? inl.d_model : nullptr; a.ok = inl.d_ok; a.out_stride = mcap;
   a.flags = inl.d_flags; a.tile_cnt = inl.d_tiles; a.n_inl = inl.d_ninl; a.out = inl.d_out; a.src_pos = inl.d_src;
-  { Scope sc(this, "inlier_flag", post_stream); vh_launch_inlier_flag(a, post_stream); }
-  { Scope sc(this, "inlier_compact", post_stream); vh_launch_inlier_compact(a, post_stream); }
+  launch_inliers(t, a, post_stream, this);
   VH_HIP(hipGetLastError());
   VH_HIP(hipMemcpyAsync(inl.n_inl.data(), inl.d_ninl, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   VH_HIP(hipMemcpyAsync(inl.n_list.data(), d_counts, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
@@ -144,14 +174,13 @@ using namespace vh_engine;
   { hipError_t e_ = hipSetDevice((gq)->device);     \
     if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
 
-extern "C" {
-
-int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
-                          const double *tr, const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm,
-                          int32_t *src_pos) {
-  if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
+// The stateless classification under either test: validation, one device block, the uploads, the flag launch of the
+// test, the scan and the scatter, the downloads.
+static int32_t inliers_stateless(const InlierTest &t, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                                 const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm, int32_t *src_pos) {
+  if (!t.params_ok() || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
-  if (!offsets || !tr || !ok || !n_inliers || offsets[0] < 0) return VH_ERR_INVALID_ARG;
+  if (!offsets || !t.args_ok() || !ok || !n_inliers || offsets[0] < 0) return VH_ERR_INVALID_ARG;
   int64_t nmax = 0;
   for (int32_t s = 0; s < n_sets; s++) {
     if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
@@ -165,26 +194,28 @@ int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets
   if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, tiles)) return VH_ERR_UNSUPPORTED;  // (a list longer than any handle holds)
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  // one block: the records up to offsets[n_sets] | offsets | the arrays of InlierLayout, addressed by the same offsets
+  // one block: the arrays of InlierLayout, addressed by the same offsets | the records up to offsets[n_sets] | offsets | (mono) the models
   const InlierLayout lay((size_t)n_sets, (size_t)end, (size_t)tiles);
   const size_t o_pm = up256(lay.bytes), o_off = o_pm + up256(sizeof(vh_p_match) * (size_t)end);
+  const size_t o_model = o_off + up256(sizeof(int32_t) * ((size_t)n_sets + 1));
   DeviceBlock blk;
-  VH_HIP(blk.alloc(o_off + sizeof(int32_t) * ((size_t)n_sets + 1)));
+  VH_HIP(blk.alloc(t.is_mono ? o_model + sizeof(vh_mono_model) * (size_t)n_sets : o_off + sizeof(int32_t) * ((size_t)n_sets + 1)));
   uint8_t *d = blk.as<uint8_t>();
   const size_t first = (size_t)offsets[0];
   VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + lay.o_tr, tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
+  if (t.is_mono) VH_HIP(hipMemcpy(d + o_model, t.model, sizeof(vh_mono_model) * (size_t)n_sets, hipMemcpyHostToDevice));
+  else VH_HIP(hipMemcpy(d + lay.o_tr, t.tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + lay.o_ok, ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyHostToDevice));
   VhInlierArgs a{};
-  a.e = *e;
   a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
   a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
-  a.tr = (const double *)(d + lay.o_tr); a.ok = (const int32_t *)(d + lay.o_ok);
+  a.tr = t.is_mono ? nullptr : (const double *)(d + lay.o_tr);  // (each flag kernel reads its own of the two)
+  a.model = t.is_mono ? (const vh_mono_model *)(d + o_model) : nullptr;
+  a.ok = (const int32_t *)(d + lay.o_ok);
   a.flags = d; a.out = (vh_p_match *)(d + lay.o_out); a.src_pos = (int32_t *)(d + lay.o_src);
   a.tile_cnt = (int32_t *)(d + lay.o_tiles); a.n_inl = (int32_t *)(d + lay.o_ninl);
-  vh_launch_inlier_flag(a, nullptr);
-  vh_launch_inlier_compact(a, nullptr);
+  launch_inliers(t, a, nullptr, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
   VH_HIP(hipMemcpy(n_inliers, a.n_inl, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToHost));
@@ -199,14 +230,35 @@ int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets
   return VH_OK;
 }
 
+extern "C" {
+
+int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                          const double *tr, const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm,
+                          int32_t *src_pos) {
+  return inliers_stateless(InlierTest::stereo(e, tr), device, n_sets, pm, offsets, ok, flags, n_inliers, inlier_pm, src_pos);
+}
+int32_t vh_motion_inliers_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                               const vh_mono_model *model, const int32_t *ok, uint8_t *flags, int32_t *n_inliers,
+                               vh_p_match *inlier_pm, int32_t *src_pos) {
+  return inliers_stateless(InlierTest::monocular(e, model), device, n_sets, pm, offsets, ok, flags, n_inliers, inlier_pm, src_pos);
+}
 int32_t vh_group_motion_inliers(vh_group *g, const vh_ego_params *e, const double *tr, const int32_t *ok, int32_t *counts) {
   Group *gq = (Group *)g; ENTER(gq);
-  return gq->motion_inliers(e, tr, ok, counts);
+  return gq->motion_inliers(InlierTest::stereo(e, tr), ok, counts);
 }
 int32_t vh_match_inliers(vh_matcher *m, const vh_ego_params *e, const double *tr, int32_t ok, int32_t *count) {
   Group *gq = (Group *)m; ENTER(gq);
   if (gq->S != 1) return VH_ERR_INVALID_ARG;
-  return gq->motion_inliers(e, tr, &ok, count);
+  return gq->motion_inliers(InlierTest::stereo(e, tr), &ok, count);
+}
+int32_t vh_group_motion_inliers_mono(vh_group *g, const vh_mono_params *e, const vh_mono_model *model, const int32_t *ok, int32_t *counts) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->motion_inliers(InlierTest::monocular(e, model), ok, counts);
+}
+int32_t vh_match_inliers_mono(vh_matcher *m, const vh_mono_params *e, const vh_mono_model *model, int32_t ok, int32_t *count) {
+  Group *gq = (Group *)m; ENTER(gq);
+  if (gq->S != 1) return VH_ERR_INVALID_ARG;
+  return gq->motion_inliers(InlierTest::monocular(e, model), &ok, count);
 }
 int32_t vh_group_get_inlier_flags(vh_group *g, int32_t stream, uint8_t *out, int32_t cap, int32_t *n) {
   Group *gq = (Group *)g; ENTER(gq);

@@ -231,7 +231,8 @@ int32_t Group::estimate_motion(const vh_ego_params *e, const int32_t *rand3, dou
 }
 
 // VisualOdometryMono::estimateMotion on the device-resident match lists of every stream
-int32_t Group::estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl) {
+// (model, nullable: [S] the lists' models come back too, through a device block of 128 bytes per stream allocated on first need)
+int32_t Group::estimate_motion_mono(const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *ninl, vh_mono_model *model) {
   if (!e || !rand8 || !tr || !ok || !ninl || e->ransac_iters < 1) return VH_ERR_INVALID_ARG;
   if (!allocated || (last_method != VH_METHOD_FLOW && last_method != VH_METHOD_QUAD)) return VH_ERR_STATE;
   const size_t nr = (size_t)S * e->ransac_iters * 8;
@@ -249,9 +250,11 @@ int32_t Group::estimate_motion_mono(const vh_mono_params *e, const int32_t *rand
     if ((rc = dmalloc(&ego.d_mono_rand, nr, false))) return rc;
     ego.mono_rand_n = nr;
   }
+  if (model && !ego.d_mono_model && (rc = dmalloc(&ego.d_mono_model, (size_t)S, false))) return rc;
   VH_HIP(hipMemcpyAsync(ego.d_mono_rand, rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
   vh_launch_mono(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_mono_rand, ego.d_mono_scratch, mcap, ego.d_ego_tr,
-                 ego.d_ego_ok, ego.d_ego_ok + S, nullptr, 0, post_stream);
+                 ego.d_ego_ok, ego.d_ego_ok + S, nullptr, 0, model ? ego.d_mono_model : nullptr, post_stream);
+  if (model) VH_HIP(hipMemcpyAsync(model, ego.d_mono_model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyDeviceToHost, post_stream));  // (estimate_results waits for the stream)
   return estimate_results(tr, ok, ninl);
 }
 
@@ -354,7 +357,7 @@ int32_t Group::post_finish(int32_t age, int32_t max_features, float bw, float bh
   VH_HIP(hipMemcpyAsync(post.d_bcnt, post.h_bcnt, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, down_stream));
   VH_HIP(hipMemcpyAsync(post.d_post_rand, e ? rand3 : rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, down_stream));
   if (e) vh_launch_ego(*e, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_xyz, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
-  else vh_launch_mono(*mono, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_mono, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
+  else vh_launch_mono(*mono, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_mono, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, nullptr, down_stream);
   VH_HIP(hipGetLastError());
   VH_HIP(hipMemcpyAsync(tr, post.d_post_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, down_stream));
   VH_HIP(hipMemcpyAsync(ok, post.d_post_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
@@ -404,7 +407,7 @@ int32_t Group::vote_launch(VoteBatch &b, int32_t index) {
   vh_launch_vote(v, vote_lanes, b.max_features, b.bw, b.bh, b.vb.lfsr, b.vb.lfsr_n, b.vb.out, b.vb.out_cap, b.vb.out_count, nullptr, vs);
   VH_HIP(hipGetLastError());
   if (b.has_ego) vh_launch_ego(b.ego, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
-  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
+  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, nullptr, vs);
   VH_HIP(hipGetLastError());
   if (b.has_ego || b.has_mono) {
     VH_HIP(hipMemcpyAsync(b.h_tr, b.d_tr, sizeof(double) * 6 * (size_t)v.P, hipMemcpyDeviceToHost, vs));

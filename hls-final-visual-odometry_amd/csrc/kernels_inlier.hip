@@ -11,6 +11,9 @@
 // A list is cut into tiles of INL_TILE records; a 256-lane workgroup takes one tile, one record per lane and trip:
 //   inlier_flag     the flag of every record (one byte) and the number of inliers of the tile.  A record is read as
 //                   three 16-byte loads, all trips of a lane in flight at once; wave 0 builds the rotation meanwhile.
+//   inlier_flag_mono  the same tiles under VisualOdometryMono::getInlier (src/viso_mono.cpp:268-315) and a vh_mono_model
+//                   per list (vh_mono.h: the estimator's normalisation and Sampson test): two 16-byte loads per record,
+//                   the model by uniform loads, pure double arithmetic and one division.
 //   inlier_scan     one workgroup per list: the tile counts become the tiles' first output positions, their sum the
 //                   list's inlier count.
 //   inlier_compact  a tile's inliers go to their positions (vh_compact4 per trip: thread order is list order), with
@@ -19,6 +22,7 @@
 #include "vh_dev.h"
 #include "vh_wave.h"
 #include "vh_ego.h"
+#include "vh_mono.h"
 
 namespace {
 
@@ -39,28 +43,22 @@ __device__ __forceinline__ InlList inl_list(const VhInlierArgs &a, int32_t s) {
   return r;
 }
 
-__global__ void __launch_bounds__(INL_T)
-inlier_flag_kernel(VhInlierArgs a) {
-  __shared__ double sR[9], sTr[6];
-  __shared__ int32_t sWave[INL_T / 64];
-  const int32_t s = blockIdx.x, tile = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const InlList L = inl_list(a, s);
-  const int32_t i0 = tile * VH_INLIER_TILE;
-  if (i0 >= L.n) return;  // (an empty list reads neither ok nor tr)
-  uint8_t *fl = a.flags + L.out0;
-  int32_t cnt = 0;
-  if (a.ok[s]) {
-    float4 q[INL_R][3];
-#pragma unroll
-    for (int32_t k = 0; k < INL_R; k++) {
-      const int32_t i = i0 + k * INL_T + tid;
-      if (i < L.n) {
-        const float4 *p = (const float4 *)(L.pm + i);
-        q[k][0] = p[0]; q[k][1] = p[1]; q[k][2] = p[2];
-      } else {
-        q[k][0] = q[k][1] = q[k][2] = make_float4(0, 0, 0, 0);
-      }
-    }
+// The per-record test of a flag kernel: what a lane keeps of a record (Rec, from 16-byte loads), what the workgroup
+// prepares once between the loads and the first use (setup), and the test itself.
+// VisualOdometryStereo::getInlier under tr[6] (vh_ego.h): three loads; wave 0 builds the rotation while they are in
+// flight and hands it over through LDS.
+struct InlStereo {
+  struct Rec { float4 q[3]; };
+  EgoRot R;
+  double tr[6];
+  static __device__ __forceinline__ Rec load(const vh_p_match *m) {
+    const float4 *p = (const float4 *)m;
+    Rec r; r.q[0] = p[0]; r.q[1] = p[1]; r.q[2] = p[2];
+    return r;
+  }
+  static __device__ __forceinline__ Rec none() { Rec r; r.q[0] = r.q[1] = r.q[2] = make_float4(0, 0, 0, 0); return r; }
+  __device__ __forceinline__ void setup(const VhInlierArgs &a, int32_t s, int32_t w, int32_t lane) {
+    __shared__ double sR[9], sTr[6];
     if (w == 0) {  // the rotation, once per workgroup
       double t6[6];
       for (int32_t m = 0; m < 6; m++) t6[m] = a.tr[6 * (int64_t)s + m];
@@ -72,18 +70,58 @@ inlier_flag_kernel(VhInlierArgs a) {
       }
     }
     __syncthreads();
-    EgoRot R;
-    double tr[6];
     for (int32_t m = 0; m < 9; m++) R.r[m] = sR[m];
     for (int32_t m = 0; m < 6; m++) tr[m] = sTr[m];
+  }
+  __device__ __forceinline__ bool inlier(const VhInlierArgs &a, const Rec &r) const {
+    // {u1p, v1p, i1p, u2p} {v2p, i2p, u1c, v1c} {i1c, u2c, v2c, i2c}
+    const EgoObs o = ego_observe(a.e, r.q[0].x, r.q[0].y, r.q[0].w, r.q[1].z, r.q[1].w, r.q[2].y, r.q[2].z);
+    return ego_is_inlier(a.e, R, tr, o);  // (a NaN or infinite sum compares false)
+  }
+};
+// VisualOdometryMono::getInlier under a vh_mono_model (vh_mono.h): two loads (the last third of a record is not
+// fetched); the model is the same for the whole workgroup -- 16 doubles at a uniform address, no LDS, no barrier.
+struct InlMono {
+  struct Rec { float4 q[2]; };
+  vh_mono_model m;
+  static __device__ __forceinline__ Rec load(const vh_p_match *pm) {
+    const float4 *p = (const float4 *)pm;
+    Rec r; r.q[0] = p[0]; r.q[1] = p[1];
+    return r;
+  }
+  static __device__ __forceinline__ Rec none() { Rec r; r.q[0] = r.q[1] = make_float4(0, 0, 0, 0); return r; }
+  __device__ __forceinline__ void setup(const VhInlierArgs &a, int32_t s, int32_t, int32_t) { m = a.model[s]; }
+  __device__ __forceinline__ bool inlier(const VhInlierArgs &a, const Rec &r) const {
+    // {u1p, v1p, i1p, u2p} {v2p, i2p, u1c, v1c}
+    return mono_is_inlier(m, r.q[0].x, r.q[0].y, r.q[1].z, r.q[1].w, a.mono_threshold);  // (a NaN or infinite quotient compares false)
+  }
+};
+
+// One tile of one list: the flag of every record and the tile's inlier count -- the skeleton of both flag kernels.
+template <class Test>
+__device__ __forceinline__ void inlier_flag_tile(const VhInlierArgs &a) {
+  __shared__ int32_t sWave[INL_T / 64];
+  const int32_t s = blockIdx.x, tile = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const InlList L = inl_list(a, s);
+  const int32_t i0 = tile * VH_INLIER_TILE;
+  if (i0 >= L.n) return;  // (an empty list reads neither ok nor its motion / model)
+  uint8_t *fl = a.flags + L.out0;
+  int32_t cnt = 0;
+  if (a.ok[s]) {
+    typename Test::Rec q[INL_R];
+#pragma unroll
+    for (int32_t k = 0; k < INL_R; k++) {
+      const int32_t i = i0 + k * INL_T + tid;
+      q[k] = i < L.n ? Test::load(L.pm + i) : Test::none();
+    }
+    Test t;
+    t.setup(a, s, w, lane);
 #pragma unroll
     for (int32_t k = 0; k < INL_R; k++) {
       const int32_t i = i0 + k * INL_T + tid;
       bool in_ = false;
       if (i < L.n) {
-        // {u1p, v1p, i1p, u2p} {v2p, i2p, u1c, v1c} {i1c, u2c, v2c, i2c}
-        const EgoObs o = ego_observe(a.e, q[k][0].x, q[k][0].y, q[k][0].w, q[k][1].z, q[k][1].w, q[k][2].y, q[k][2].z);
-        in_ = ego_is_inlier(a.e, R, tr, o);  // (a NaN or infinite sum compares false)
+        in_ = t.inlier(a, q[k]);
         fl[i] = in_ ? 1 : 0;
       }
       cnt += __popcll(__ballot(in_));
@@ -99,6 +137,12 @@ inlier_flag_kernel(VhInlierArgs a) {
   __syncthreads();
   if (tid == 0) a.tile_cnt[(int64_t)s * a.tiles_per_list + tile] = (sWave[0] + sWave[1]) + (sWave[2] + sWave[3]);
 }
+
+__global__ void __launch_bounds__(INL_T)
+inlier_flag_kernel(VhInlierArgs a) { inlier_flag_tile<InlStereo>(a); }
+
+__global__ void __launch_bounds__(INL_T)
+inlier_flag_mono_kernel(VhInlierArgs a) { inlier_flag_tile<InlMono>(a); }
 
 __global__ void __launch_bounds__(INL_T)
 inlier_scan_kernel(VhInlierArgs a) {
@@ -155,6 +199,9 @@ inlier_compact_kernel(VhInlierArgs a) {
 // grid: a.n_lists x a.tiles_per_list workgroups (the caller keeps the product below 2^24 and tiles_per_list <= 65535)
 void vh_launch_inlier_flag(const VhInlierArgs &a, hipStream_t st) {
   hipLaunchKernelGGL(inlier_flag_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
+}
+void vh_launch_inlier_flag_mono(const VhInlierArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(inlier_flag_mono_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
 }
 void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st) {
   hipLaunchKernelGGL(inlier_scan_kernel, dim3(a.n_lists), dim3(INL_T), 0, st, a);

@@ -36,6 +36,7 @@
 #define SVD_HD __device__ __forceinline__
 #include "svd_static.h"
 #include "vh_wave.h"
+#include "vh_mono.h"
 
 namespace {
 
@@ -236,6 +237,7 @@ __device__ unsigned long long g_mono_t[16];
 
 struct __attribute__((aligned(16))) MonoPoint { double u1, v1, u2, v2; };  // normalised (u1p, v1p, u1c, v1c) as doubles
 
+#define MONO_H_C 19       /* the four centroids mono_norm subtracted (Tp, Tc hold only their products with the scales) */
 // hdr slots written by mono_final_a for mono_tri / mono_final_c
 #define MONO_H_GO 32      /* 1: the later kernels have work (0: mono_final_a already reported the failure) */
 #define MONO_H_NBEST 33
@@ -339,8 +341,8 @@ mono_norm_kernel(const vh_p_match *__restrict__ pm_base, int64_t pm_stride, cons
   for (int32_t i = tid; i < N; i += MONO_T) {
     const vh_p_match &m = L.pm[i];
     float4 q;
-    q.x = (float)((double)m.u1p - cpu); q.y = (float)((double)m.v1p - cpv);
-    q.z = (float)((double)m.u1c - ccu); q.w = (float)((double)m.v1c - ccv);
+    q.x = mono_center(m.u1p, cpu); q.y = mono_center(m.v1p, cpv);
+    q.z = mono_center(m.u1c, ccu); q.w = mono_center(m.v1c, ccv);
     L.pn[i] = q;
     fl[i] = make_float2(sqrtf(q.x * q.x + q.y * q.y), sqrtf(q.z * q.z + q.w * q.w));  // float expressions in the reference
   }
@@ -363,8 +365,8 @@ mono_norm_kernel(const vh_p_match *__restrict__ pm_base, int64_t pm_stride, cons
   sc = sqrt(2.0) * (double)N / sc;
   for (int32_t i = tid; i < N; i += MONO_T) {
     float4 q = L.pn[i];
-    q.x = (float)((double)q.x * sp); q.y = (float)((double)q.y * sp);
-    q.z = (float)((double)q.z * sc); q.w = (float)((double)q.w * sc);
+    q.x = mono_scale(q.x, sp); q.y = mono_scale(q.y, sp);
+    q.z = mono_scale(q.z, sc); q.w = mono_scale(q.w, sc);
     L.pn[i] = q;
     // the same four floats widened once (exact), for mono_hyp's loop over the matches; the refit system's place is free until mono_final
     MonoPoint d4; d4.u1 = q.x; d4.v1 = q.y; d4.u2 = q.z; d4.v2 = q.w;
@@ -374,6 +376,7 @@ mono_norm_kernel(const vh_p_match *__restrict__ pm_base, int64_t pm_stride, cons
     double *Tp = L.hdr, *Tc = L.hdr + 9;
     Tp[0] = sp; Tp[1] = 0; Tp[2] = -sp * cpu; Tp[3] = 0; Tp[4] = sp; Tp[5] = -sp * cpv; Tp[6] = 0; Tp[7] = 0; Tp[8] = 1;
     Tc[0] = sc; Tc[1] = 0; Tc[2] = -sc * ccu; Tc[3] = 0; Tc[4] = sc; Tc[5] = -sc * ccv; Tc[6] = 0; Tc[7] = 0; Tc[8] = 1;
+    L.hdr[MONO_H_C + 0] = cpu; L.hdr[MONO_H_C + 1] = cpv; L.hdr[MONO_H_C + 2] = ccu; L.hdr[MONO_H_C + 3] = ccv;  // (for vh_mono_model)
     L.hdr[18] = 1.0;
   }
 }
@@ -415,15 +418,7 @@ __device__ void sample8(const int32_t *r, int32_t N, int32_t *act) {
   }
 }
 
-// Sampson distance test of getInlier (src/viso_mono.cpp:283-309)
-__device__ __forceinline__ bool sampson_inlier(const double *F, const float4 q, double thr) {
-  const double u1 = q.x, v1 = q.y, u2 = q.z, v2 = q.w;
-  const double Fx1u = F[0] * u1 + F[1] * v1 + F[2], Fx1v = F[3] * u1 + F[4] * v1 + F[5], Fx1w = F[6] * u1 + F[7] * v1 + F[8];
-  const double Ftx2u = F[0] * u2 + F[3] * v2 + F[6], Ftx2v = F[1] * u2 + F[4] * v2 + F[7];
-  const double x2tFx1 = u2 * Fx1u + v2 * Fx1v + Fx1w;
-  const double d = x2tFx1 * x2tFx1 / (Fx1u * Fx1u + Fx1v * Fx1v + Ftx2u * Ftx2u + Ftx2v * Ftx2v);
-  return fabs(d) < thr;
-}
+// (sampson_inlier, the Sampson distance test of getInlier: vh_mono.h)
 
 // The same test for mono_hyp's loop (one lane = one hypothesis, every lane the same match): numerator and denominator
 // as above, operation for operation, but the quotient is formed only when the answer is not already certain.
@@ -746,7 +741,7 @@ __global__ void __launch_bounds__(MONO_T)
 mono_final_a_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_stride, const int32_t *__restrict__ offsets,
                   const int32_t *__restrict__ counts, int32_t count_cap, const int32_t *__restrict__ rand8, uint8_t *__restrict__ scratch,
                   int64_t cap, double *__restrict__ tr_out, int32_t *__restrict__ ok_out, int32_t *__restrict__ ninl_out,
-                  int32_t *__restrict__ inl_out, int64_t inl_stride) {
+                  int32_t *__restrict__ inl_out, int64_t inl_stride, vh_mono_model *__restrict__ model_out) {
   __shared__ double sF[9], sV[81], sX[16];
   // The refit system lives in LDS when it fits (MONO_LDS_ROWS x 9 doubles): the cooperative SVD's sequential sums
   // are chains of dependent accumulations over a column, one load per step -- from global memory each step waited
@@ -760,7 +755,10 @@ mono_final_a_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, in
   const int32_t N = L.n;
   int32_t *inl = inl_out ? inl_out + (offsets ? (int64_t)offsets[s] : (int64_t)s * inl_stride) : nullptr;
   auto fail = [&](int32_t ninl) {
-    if (tid == 0) { ok_out[s] = 0; ninl_out[s] = ninl; for (int32_t q = 0; q < 6; q++) tr_out[6 * s + q] = 0.0; }
+    if (tid == 0) {
+      ok_out[s] = 0; ninl_out[s] = ninl; for (int32_t q = 0; q < 6; q++) tr_out[6 * s + q] = 0.0;
+      if (model_out) { double *mo = (double *)(model_out + s); for (int32_t q = 0; q < 16; q++) mo[q] = 0.0; }  // (no refit: the zero record)
+    }
   };
   if (tid == 0) L.hdr[MONO_H_GO] = 0.0;
   if (L.hdr[18] == 0.0) { fail(0); return; }
@@ -815,6 +813,13 @@ mono_final_a_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, in
     const double K[9] = {e.f, 0, e.cu, 0, e.f, e.cv, 0, 0, 1};
     for (int32_t q = 0; q < 9; q++) F0[q] = sV[q * 9 + 8];
     rank2_3x3(F0, F);
+    if (model_out) {  // the model of the list (vh_mono_model): valid whatever the later stages decide
+      vh_mono_model &mo = model_out[s];
+      for (int32_t q = 0; q < 4; q++) mo.c[q] = L.hdr[MONO_H_C + q];
+      mo.s[0] = L.hdr[0]; mo.s[1] = L.hdr[9];
+      for (int32_t q = 0; q < 9; q++) mo.F[q] = F[q];
+      mo.valid = 1.0;
+    }
     // denormalise, essential matrix, rank 2 again (src/viso_mono.cpp:86-94)
     transpose3(L.hdr + 9, T1); matmul(T1, 3, 3, F, 3, T2); matmul(T2, 3, 3, L.hdr, 3, F);
     transpose3(K, Kt); matmul(Kt, 3, 3, F, 3, T2); matmul(T2, 3, 3, K, 3, E);
@@ -1041,7 +1046,7 @@ int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters)
 
 void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
                     const int32_t *counts, int32_t count_cap, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr,
-                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st) {
+                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st) {
   hipLaunchKernelGGL(mono_norm_kernel, dim3(n_sets), dim3(MONO_T), 0, st, pm, pm_stride, offsets, counts, count_cap, scratch, cap);
   static const int32_t force_signed = [] { const char *v = getenv("VH_MONO_SIGNED"); return v && atoi(v) ? 1 : 0; }();
   const dim3 hgrid((e.ransac_iters + 127) / 128, n_sets);
@@ -1050,7 +1055,7 @@ void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *p
   hipLaunchKernelGGL(mono_hyp_kernel<true>, dim3((uint32_t)(((int64_t)n_sets * e.ransac_iters + 127) / 128)), dim3(128), 0, st, e, pm, pm_stride, offsets,
                      counts, count_cap, rand8, scratch, cap, n_sets, force_signed);
   hipLaunchKernelGGL(mono_final_a_kernel, dim3(n_sets), dim3(MONO_T), 0, st, e, pm, pm_stride, offsets, counts, count_cap, rand8, scratch,
-                     cap, tr, ok, ninl, inl, inl_stride);
+                     cap, tr, ok, ninl, inl, inl_stride, model);
   // (sized for lists as long as the capacity; the workgroups beyond a list's length return at once)
   hipLaunchKernelGGL(mono_tri_kernel, dim3((uint32_t)((cap + 63) / 64), n_sets), dim3(256), 0, st, pm, pm_stride, offsets, counts, count_cap, scratch, cap);
   hipLaunchKernelGGL(mono_final_c_kernel, dim3(n_sets), dim3(MONO_T), 0, st, e, pm, pm_stride, offsets, counts, count_cap, scratch, cap, tr, ok, ninl);

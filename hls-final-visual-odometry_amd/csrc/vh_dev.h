@@ -409,14 +409,19 @@ struct VhInlierArgs {
   int32_t *n_inl;           // [n_lists]
   vh_p_match *out;          // the inlier records in list order
   int32_t *src_pos;         // position of each in its list
+  // inlier_flag_mono (it reads these in the place of e and tr)
+  const vh_mono_model *model;  // [n_lists]; not read where ok = 0
+  double mono_threshold;       // vh_mono_params::inlier_threshold
 };
 void vh_launch_inlier_flag(const VhInlierArgs &a, hipStream_t st);
+void vh_launch_inlier_flag_mono(const VhInlierArgs &a, hipStream_t st);
 void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st);  // the scan of the tile counts, then the scatter
 
 struct vh_mono_params;
 int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters);
+// model (nullable): [n_sets] the normalisation and the refit F of every list (vh_mono_model), written by mono_final_a
 void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
                     const int32_t *counts, int32_t count_cap, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr,
-                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st);
+                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st);
 
 #endif

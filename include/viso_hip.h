@@ -613,6 +613,63 @@ int32_t vh_estimate_motion_mono(const vh_mono_params *e, int32_t device, int32_t
  * (VH_METHOD_FLOW or VH_METHOD_QUAD: both carry the left camera's flow). */
 int32_t vh_group_estimate_motion_mono(vh_group *g, const vh_mono_params *e, const int32_t *rand8, double *tr,
                                       int32_t *ok, int32_t *n_inliers);
+
+/* The epipolar model the estimator arrived at, in its own normalised frame: what is needed to apply its inlier test
+ * (getInlier, src/viso_mono.cpp:268-315) to any other list.  inlier_threshold only has a meaning in this frame, and
+ * F cannot be rebuilt from tr.  16 doubles, 128 bytes. */
+typedef struct vh_mono_model {
+  double c[4];   /* cpu, cpv, ccu, ccv: the centroids normalizeFeaturePoints subtracts (src/viso_mono.cpp:190-200) */
+  double s[2];   /* sp, sc: its two scales (:216-217) */
+  double F[9];   /* the refit F of :80 in the normalised frame, after fundamentalMatrix's rank-2 step, row-major */
+  double valid;  /* 1.0: the estimator reached the refit (>= 10 inliers of the best hypothesis); 0.0: everything above is 0 */
+} vh_mono_model;
+/* vh_estimate_motion_mono / vh_group_estimate_motion_mono with one more output, model[n_sets] / model[S]; tr, ok,
+ * n_inliers and inliers are bit for bit those of the plain entries on the same inputs (the plain entries are these
+ * with model = NULL inside; here NULL is VH_ERR_INVALID_ARG).  valid does not depend on ok: a list that fails after
+ * the refit (too few points in front, median depth above motion_threshold, no chirality solution) has valid = 1 and
+ * a meaningful F; valid = 0 and a zeroed record for fewer than 10 matches, a degenerate scale, or a best hypothesis
+ * with fewer than 10 inliers.  The sign of F is the refit's (Matrix::svd's sign normalisation of the N x 9 system);
+ * the Sampson test is the same for F and -F bit for bit.
+ * The first vh_group_estimate_motion_mono_model call of a handle allocates one block of 128 bytes per stream for this
+ * output, counted by vh_group_device_bytes (beside what vh_group_estimate_motion_mono allocates; the plain entry never
+ * allocates it).
+ * The pipelined post chains (vh_group_post_finish_mono, vh_group_post_begin_device / _finish_device) have no model
+ * output: take the bucketed lists they return through vh_estimate_motion_mono_model. */
+int32_t vh_estimate_motion_mono_model(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                                      const int32_t *offsets, const int32_t *rand8, double *tr, int32_t *ok,
+                                      int32_t *n_inliers, int32_t *inliers, vh_mono_model *model);
+int32_t vh_group_estimate_motion_mono_model(vh_group *g, const vh_mono_params *e, const int32_t *rand8, double *tr,
+                                            int32_t *ok, int32_t *n_inliers, vh_mono_model *model);
+
+/* ---- motion inliers, monocular: which records of whole lists agree with an epipolar model ------------ */
+/* VisualOdometryMono::getInlier (src/viso_mono.cpp:268-315) for any flow or quad list under a vh_mono_model: a record's
+ * (u1p, v1p) is normalised with c[0], c[1], s[0] and its (u1c, v1c) with c[2], c[3], s[1] as normalizeFeaturePoints
+ * does -- q = (float)((double)u - c), then (float)((double)q * s), each rounded to float once -- and the test is
+ * |Sampson distance under F| < inlier_threshold: strict, in double, one division, no transcendental function, so the
+ * flags equal a host restatement byte for byte on every input.  A quotient that is NaN or infinite (NaN coordinates,
+ * a zero denominator, 0/0 under F = 0) is "not an inlier", never an error; a list with ok = 0 has no inliers and its
+ * model is not read (`valid` is never read: pass ok = (int32_t)valid, or the estimator's ok); a list of one record
+ * is classified like any other.  Only inlier_threshold of vh_mono_params is read; the other fields of a record are
+ * not read.
+ *
+ * Stateless: as vh_motion_inliers with model[n_sets] in the place of tr -- same outputs, same limits, and n_sets == 0
+ * or no records at all is VH_OK without a device. */
+int32_t vh_motion_inliers_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                               const int32_t *offsets, const vh_mono_model *model, const int32_t *ok, uint8_t *flags,
+                               int32_t *n_inliers, vh_p_match *inlier_pm, int32_t *src_pos);
+/* The same on the device-resident lists of the handle's last match call, as vh_group_motion_inliers / vh_match_inliers:
+ * model[S], ok[S] go up, counts[S] comes back.  Flow and quad lists (VH_ERR_STATE for stereo lists and before any
+ * match).  Plain groups, sequence handles and lone matchers; refined, multi-stage and host-replaced lists as there.
+ * A handle has ONE result: the getters above (vh_group_get_inlier_flags / _matches / _matches_all,
+ * vh_get_inlier_matches, vh_group_inliers_device) return the last classification of either kind, and a mono
+ * classification replaces a stereo one and the other way round.  The first classification of either kind allocates
+ * the block described at vh_group_motion_inliers; the first mono classification adds one block of 128 bytes per
+ * stream for the models (its own: not the one vh_group_estimate_motion_mono_model keeps for its output).  Both are counted by vh_group_device_bytes; a refused allocation is VH_ERR_HIP before
+ * anything is launched, leaves nothing behind, and the call may be repeated.
+ * Profile scopes: "inlier_flag_mono", "inlier_compact". */
+int32_t vh_group_motion_inliers_mono(vh_group *g, const vh_mono_params *e, const vh_mono_model *model, const int32_t *ok,
+                                     int32_t *counts);
+int32_t vh_match_inliers_mono(vh_matcher *m, const vh_mono_params *e, const vh_mono_model *model, int32_t ok, int32_t *count);
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
