@@ -80,6 +80,7 @@ ABI_SYMBOLS = (
     "vh_group_get_inlier_matches_all", "vh_get_inlier_matches", "vh_group_inliers_device",
     "vh_estimate_motion_mono_model", "vh_group_estimate_motion_mono_model",
     "vh_motion_inliers_mono", "vh_group_motion_inliers_mono", "vh_match_inliers_mono",
+    "vh_refit_motion", "vh_group_refit_motion", "vh_match_refit_motion",
 )
 
 
@@ -294,6 +295,8 @@ def _lib():
             "vh_group_estimate_motion_mono_model": [vp, vp, vp, vp, vp, vp, vp],
             "vh_motion_inliers_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_motion_inliers_mono": [vp, vp, vp, vp, vp], "vh_match_inliers_mono": [vp, vp, vp, i32, vp],
+            "vh_refit_motion": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -478,6 +481,15 @@ class Matcher:
         n = C.c_int32(0)
         _check(_lib().vh_match_inliers_mono(self._h, C.byref(mono), _ptr(model), 1 if ok else 0, C.byref(n)), "vh_match_inliers_mono")
         return n.value
+
+    def refitMotion(self, ego: "EgoParams", reclassify: bool = False):
+        """The reference's final optimisation (src/viso_stereo.cpp:126-139) on ALL inliers of the last motionInliers, from the
+        motion it classified under (vh_match_refit_motion) -> (tr [6], ok, n_updates, count); reclassify: the list is
+        classified again under the refined motion, and count / getInlierMatches() are that classification's."""
+        tr = np.zeros(6, np.float64); ok = C.c_int32(0); nupd = C.c_int32(0); n = C.c_int32(0)
+        _check(_lib().vh_match_refit_motion(self._h, C.byref(ego), 1 if reclassify else 0, _ptr(tr), C.byref(ok), C.byref(nupd), C.byref(n)),
+               "vh_match_refit_motion")
+        return tr, bool(ok.value), nupd.value, n.value
 
     def getInlierMatches(self):
         """-> (the inlier records in list order, their positions in getMatches()) of the last motionInliers(Mono)."""
@@ -701,6 +713,17 @@ class StreamGroup:
         counts = np.zeros(self.S, np.int32)
         _check(_lib().vh_group_motion_inliers(self._h, C.byref(ego), _ptr(tr), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers")
         return counts
+
+    def refitMotion(self, ego: "EgoParams", reclassify: bool = False):
+        """The reference's final optimisation (src/viso_stereo.cpp:126-139) on every stream's compacted inlier list of the last
+        motionInliers, from the tr / ok it classified under (vh_group_refit_motion) -> (tr [S, 6], ok [S], n_updates [S],
+        counts [S]); reclassify: the lists are classified again under the refined motions (queued behind the refit), and
+        counts and the getters are that classification's."""
+        tr = np.zeros((self.S, 6), np.float64); ok = np.zeros(self.S, np.int32); nupd = np.zeros(self.S, np.int32)
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_refit_motion(self._h, C.byref(ego), 1 if reclassify else 0, _ptr(tr), _ptr(ok), _ptr(nupd), _ptr(counts)),
+               "vh_group_refit_motion")
+        return tr, ok.astype(bool), nupd, counts
 
     def motionInliersMono(self, mono: "MonoParams", model, ok) -> np.ndarray:
         """VisualOdometryMono::getInlier (reference src/viso_mono.cpp:268-315) on every stream's whole device-resident flow
@@ -1055,6 +1078,22 @@ def motion_inliers(ego: EgoParams, match_lists, tr, ok, device: int = 0):
     sl = [slice(int(offsets[s]), int(offsets[s]) + int(ninl[s])) for s in range(n)]
     return ([flags[offsets[s]:offsets[s + 1]].copy() for s in range(n)], ninl[:n],
             [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
+
+
+def refit_motion(ego: EgoParams, match_lists, tr, ok, device: int = 0):
+    """The reference's final optimisation (src/viso_stereo.cpp:126-139: updateParameters with eps 1e-8 until it converges, at
+    most 102 times) on whole quad lists, every record active, from the starts tr [n, 6] / ok [n] (vh_refit_motion).
+    -> (tr [n, 6], ok [n] bool, n_updates [n])."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    pm = np.concatenate(lists) if int(offsets[-1]) else np.zeros(0, P_MATCH_DTYPE)
+    tr = np.ascontiguousarray(tr, np.float64).reshape(n, 6); ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    tr_out = np.zeros((max(n, 1), 6), np.float64); ok_out = np.zeros(max(n, 1), np.int32); nupd = np.zeros(max(n, 1), np.int32)
+    _check(_lib().vh_refit_motion(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(tr), _ptr(ok), _ptr(tr_out), _ptr(ok_out),
+                                  _ptr(nupd)), "vh_refit_motion")
+    return tr_out[:n], ok_out[:n].astype(bool), nupd[:n]
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):

@@ -3,7 +3,8 @@
 //   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
-//   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip) and their part of the ABI
+//   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
+//                     their part of the ABI
 #ifndef VH_ENGINE_H
 #define VH_ENGINE_H
 #include "vh_dev.h"
@@ -254,6 +255,7 @@ struct InlierTest {
   const vh_mono_params *mono = nullptr;
   const vh_mono_model *model = nullptr;
   bool is_mono = false;
+  bool on_device = false;  // stereo: tr and ok are what the handle's block holds already (Group::refit_motion); nothing goes up
   static InlierTest stereo(const vh_ego_params *e, const double *tr) { InlierTest t; t.ego = e; t.tr = tr; return t; }
   static InlierTest monocular(const vh_mono_params *e, const vh_mono_model *m) { InlierTest t; t.mono = e; t.model = m; t.is_mono = true; return t; }
   bool params_ok() const { return is_mono ? mono != nullptr : ego != nullptr; }
@@ -275,9 +277,17 @@ struct InlierState {
   vh_p_match *d_host_pm = nullptr;
   int32_t *d_host_cnt = nullptr;
   int32_t tiles = 0;
+  bool mono = false;                      // the classification is a mono one
   bool valid = false, truncated = false;  // a classification exists (of the lists of match call `seq`) / of a truncated list
   int64_t seq = 0;
   std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
+};
+
+// The motion refined on the compacted inlier lists (vh_group_refit_motion; engine_inlier.hip):
+// one arena block, allocated by the first call -- the kernel joins its partial sums in LDS, so the outputs are all of it.
+struct RefitState {
+  double *d_tr = nullptr;                      // [S][6]
+  int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
 };
 
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
@@ -428,6 +438,7 @@ struct Group {
   std::vector<VoteBatch> vbatch;
   ReconHistory rh;
   InlierState inl;
+  RefitState rft;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
   // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
   // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
@@ -513,6 +524,7 @@ struct Group {
   // ---- engine_inlier.hip ----
   bool inliers_current() const { return allocated && inl.valid && inl.seq == match_seq; }
   int32_t motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts);
+  int32_t refit_motion(const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out, int32_t *n_updates, int32_t *counts);
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
   int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
   int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);

@@ -1,6 +1,7 @@
 // engine_inlier.hip -- motion inliers: VisualOdometryStereo::getInlier on whole lists under a caller-given motion and
 // VisualOdometryMono::getInlier under a caller-given epipolar model (kernels_inlier.hip), on the device-resident lists
-// of a handle and on caller-owned lists, and its part of the ABI.
+// of a handle and on caller-owned lists; the stereo motion refined on such lists (kernels_refit.hip: the handle's
+// compacted inlier lists, or caller-owned lists); and their part of the ABI.
 #include "engine.h"
 #include <optional>
 
@@ -43,7 +44,7 @@ static void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st,
 }
 
 int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts) {
-  if (!t.args_ok() || !ok || !counts) return VH_ERR_INVALID_ARG;
+  if (!(t.on_device ? t.params_ok() && !t.is_mono : t.args_ok() && ok) || !counts) return VH_ERR_INVALID_ARG;
   // the stereo test reads the right camera's columns; the mono test the left camera's flow, which flow and quad lists carry
   if (!allocated || !(last_method == VH_METHOD_QUAD || (t.is_mono && last_method == VH_METHOD_FLOW))) return VH_ERR_STATE;
   bool replaced = false;  // the getters serve a host-side list for some stream: that list is classified, from a device copy
@@ -82,8 +83,8 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
   inl.n_list.assign((size_t)S, 0); inl.n_inl.assign((size_t)S, 0);
   // on the post stream, behind the emission of the lists
   if (t.is_mono) VH_HIP(hipMemcpyAsync(inl.d_model, t.model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyHostToDevice, post_stream));
-  else VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
-  VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  else if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
   const vh_p_match *d_lists = (const vh_p_match *)mt.d_matches;
   const int32_t *d_counts = mt.d_match_count;
   std::vector<int32_t> host_cnt;
@@ -120,8 +121,52 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
     inl.n_list[s] = std::min(inl.n_list[s], mcap);
     counts[s] = inl.n_inl[s];
   }
-  inl.valid = true; inl.seq = match_seq;
+  inl.valid = true; inl.seq = match_seq; inl.mono = t.is_mono;
   return inl.truncated ? VH_ERR_CAPACITY : VH_OK;
+}
+
+// The Gauss-Newton loop of src/viso_stereo.cpp:126-139 on the compacted inlier lists of the current stereo classification,
+// from the tr / ok it was made under; reclassify: the classification again under the result, queued behind the refit.
+int32_t Group::refit_motion(const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out, int32_t *n_updates, int32_t *counts) {
+  if (!e || !tr_out || !ok_out || !n_updates || !counts) return VH_ERR_INVALID_ARG;
+  // (a push ends the pair the lists belong to: last_method)
+  if (!inliers_current() || inl.mono || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
+  const size_t o_ok = up256(sizeof(double) * 6 * (size_t)S), o_nupd = o_ok + up256(sizeof(int32_t) * (size_t)S);
+  if (!rft.d_tr) {  // one block: a refused allocation leaves nothing behind
+    uint8_t *d = nullptr;
+    const int32_t rc = dmalloc(&d, o_nupd + up256(sizeof(int32_t) * (size_t)S), false);
+    if (rc) return rc;
+    rft.d_tr = (double *)d; rft.d_ok = (int32_t *)(d + o_ok); rft.d_nupd = (int32_t *)(d + o_nupd);
+  }
+  VhRefitArgs a{};
+  a.e = *e;
+  a.pm = inl.d_out; a.pm_stride = mcap; a.counts = inl.d_ninl; a.count_cap = mcap; a.n_lists = S;
+  a.tr_in = inl.d_tr; a.ok_in = inl.d_ok;
+  a.tr_out = rft.d_tr; a.ok_out = rft.d_ok; a.n_updates = rft.d_nupd;
+  {
+    Scope sc(this, "motion_refit", post_stream);
+    vh_launch_refit(a, post_stream);
+  }
+  VH_HIP(hipGetLastError());
+  // the results come down behind the refit whatever happens to the classification after it
+  VH_HIP(hipMemcpyAsync(tr_out, rft.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(ok_out, rft.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(n_updates, rft.d_nupd, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  if (!reclassify) {
+    for (int32_t s = 0; s < S; s++) counts[s] = inl.n_inl[s];
+    VH_HIP(hipStreamSynchronize(post_stream));
+    return check_violation();
+  }
+  // the refined motion becomes the one the flag kernel reads: the host does not wait in between, and the one wait of the
+  // classification covers the downloads above
+  VH_HIP(hipMemcpyAsync(inl.d_tr, rft.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
+  VH_HIP(hipMemcpyAsync(inl.d_ok, rft.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
+  InlierTest t = InlierTest::stereo(e, nullptr);
+  t.on_device = true;
+  const int32_t rc = motion_inliers(t, nullptr, counts);
+  // (an error there may have returned before its wait: the caller's arrays must be complete when this call returns)
+  if (rc != VH_OK && rc != VH_ERR_CAPACITY) (void)hipStreamSynchronize(post_stream);
+  return rc;
 }
 
 int32_t Group::get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n) {
@@ -230,8 +275,71 @@ static int32_t inliers_stateless(const InlierTest &t, int32_t device, int32_t n_
   return VH_OK;
 }
 
+// The stateless refit: validation as inliers_stateless, one device block (records | offsets | tr, ok in | tr, ok, updates
+// out), one launch.
+static int32_t refit_stateless(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                               const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates) {
+  if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
+  if (n_sets == 0) return VH_OK;
+  if (!offsets || !tr_in || !ok_in || !tr_out || !ok_out || !n_updates || offsets[0] < 0) return VH_ERR_INVALID_ARG;
+  int64_t nmax = 0;
+  for (int32_t s = 0; s < n_sets; s++) {
+    if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
+    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
+  }
+  const int64_t end = offsets[n_sets], total = end - offsets[0];
+  if (total > 0 && !pm) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < n_sets; s++) {
+    ok_out[s] = 0; n_updates[s] = 0;
+    for (int32_t m = 0; m < 6; m++) tr_out[6 * (size_t)s + m] = 0;
+  }
+  if (total == 0) return VH_OK;
+  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
+  const int32_t rc = select_device(device);
+  if (rc) return rc;
+  const size_t lists = (size_t)n_sets;
+  const size_t o_off = up256(sizeof(vh_p_match) * (size_t)end), o_tr = o_off + up256(sizeof(int32_t) * (lists + 1));
+  const size_t o_ok = o_tr + up256(sizeof(double) * 6 * lists), o_tr2 = o_ok + up256(sizeof(int32_t) * lists);
+  const size_t o_ok2 = o_tr2 + up256(sizeof(double) * 6 * lists), o_nupd = o_ok2 + up256(sizeof(int32_t) * lists);
+  DeviceBlock blk;
+  VH_HIP(blk.alloc(o_nupd + sizeof(int32_t) * lists));
+  uint8_t *d = blk.as<uint8_t>();
+  const size_t first = (size_t)offsets[0];
+  VH_HIP(hipMemcpy(d + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_tr, tr_in, sizeof(double) * 6 * lists, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_ok, ok_in, sizeof(int32_t) * lists, hipMemcpyHostToDevice));
+  VhRefitArgs a{};
+  a.e = *e;
+  a.pm = (const vh_p_match *)d; a.offsets = (const int32_t *)(d + o_off); a.n_lists = n_sets;
+  a.tr_in = (const double *)(d + o_tr); a.ok_in = (const int32_t *)(d + o_ok);
+  a.tr_out = (double *)(d + o_tr2); a.ok_out = (int32_t *)(d + o_ok2); a.n_updates = (int32_t *)(d + o_nupd);
+  vh_launch_refit(a, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+  VH_HIP(hipMemcpy(tr_out, a.tr_out, sizeof(double) * 6 * lists, hipMemcpyDeviceToHost));
+  VH_HIP(hipMemcpy(ok_out, a.ok_out, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  VH_HIP(hipMemcpy(n_updates, a.n_updates, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  return VH_OK;
+}
+
 extern "C" {
 
+int32_t vh_refit_motion(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                        const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates) {
+  return refit_stateless(e, device, n_sets, pm, offsets, tr_in, ok_in, tr_out, ok_out, n_updates);
+}
+int32_t vh_group_refit_motion(vh_group *g, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
+                              int32_t *n_updates, int32_t *counts) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->refit_motion(e, reclassify, tr_out, ok_out, n_updates, counts);
+}
+int32_t vh_match_refit_motion(vh_matcher *m, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
+                              int32_t *n_updates, int32_t *count) {
+  Group *gq = (Group *)m; ENTER(gq);
+  if (gq->S != 1) return VH_ERR_INVALID_ARG;
+  return gq->refit_motion(e, reclassify, tr_out, ok_out, n_updates, count);
+}
 int32_t vh_motion_inliers(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
                           const double *tr, const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm,
                           int32_t *src_pos) {

@@ -225,8 +225,11 @@ int32_t Group::estimate_motion(const vh_ego_params *e, const int32_t *rand3, dou
     ego.ego_rand_n = nr;
   }
   VH_HIP(hipMemcpyAsync(ego.d_ego_rand, rand3, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
-  vh_launch_ego(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_ego_rand, ego.d_ego_xyz, mcap, ego.d_ego_tr, ego.d_ego_ok,
-                ego.d_ego_ok + S, nullptr, 0, post_stream);
+  {
+    Scope sc(this, "ego_kernel", post_stream);
+    vh_launch_ego(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_ego_rand, ego.d_ego_xyz, mcap, ego.d_ego_tr, ego.d_ego_ok,
+                  ego.d_ego_ok + S, nullptr, 0, post_stream);
+  }
   return estimate_results(tr, ok, ninl);
 }
 

@@ -417,6 +417,27 @@ void vh_launch_inlier_flag(const VhInlierArgs &a, hipStream_t st);
 void vh_launch_inlier_flag_mono(const VhInlierArgs &a, hipStream_t st);
 void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st);  // the scan of the tile counts, then the scatter
 
+// The stereo motion refined on whole lists (kernels_refit.hip): the Gauss-Newton loop of
+// src/viso_stereo.cpp:126-139 on every record of each list, one workgroup of VH_REFIT_THREADS lanes per list.  The lists
+// are addressed as vh_list does.
+#ifndef VH_REFIT_THREADS
+#define VH_REFIT_THREADS 256
+#endif
+struct VhRefitArgs {
+  vh_ego_params e;          // f, cu, cv, base, reweighting (ransac_iters and inlier_threshold are not read)
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists;
+  const double *tr_in;      // [n_lists][6] the start; not read where ok_in = 0 or the list has fewer than 6 records
+  const int32_t *ok_in;     // [n_lists]
+  double *tr_out;           // [n_lists][6]; zero where ok_out = 0
+  int32_t *ok_out;          // [n_lists]
+  int32_t *n_updates;       // [n_lists] updateParameters calls made: 0 (not started), 1 .. 102
+};
+void vh_launch_refit(const VhRefitArgs &a, hipStream_t st);
+
 struct vh_mono_params;
 int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters);
 // model (nullable): [n_sets] the normalisation and the refit F of every list (vh_mono_model), written by mono_final_a

@@ -557,6 +557,43 @@ int32_t vh_get_inlier_matches(vh_matcher *m, vh_p_match *pm_out, int32_t *src_po
 int32_t vh_group_inliers_device(vh_group *g, const uint8_t **d_flags, const vh_p_match **d_matches, const int32_t **d_src_pos,
                                 int64_t *stride);
 
+/* ---- the stereo motion refined on whole lists (csrc/kernels_refit.hip) ---------------------------------
+ * The "final optimization" of VisualOdometryStereo::estimateMotion (reference src/viso_stereo.cpp:126-139) on any quad
+ * list, EVERY record of it active (pass an inlier list), from a start tr_in[6]: updateParameters(.., 1, 1e-8) until it
+ * reports CONVERGED, at most 102 times.  Double precision; `reweighting` is read, inlier_threshold and ransac_iters
+ * are not.  Per list:
+ *   ok_in == 0 or fewer than 6 records: ok_out = 0, tr_out = 0, n_updates = 0 (tr_in is not read);
+ *   CONVERGED: ok_out = 1, tr_out = the refined motion; Matrix::solve refuses, or still not converged after 102
+ *   updates: ok_out = 0, tr_out = 0.  n_updates = updateParameters calls made (1 .. 102).
+ * The normal equations are summed in parallel in an order that depends on the list's length alone: tr_out agrees with
+ * a sequential evaluation to rounding (not bit for bit), is the same from run to run, and does not depend on the other
+ * lists of the call.  Non-finite records are not an error: they propagate as they do in the reference's arithmetic.
+ *
+ * Stateless: lists laid out as for vh_motion_inliers, tr_in[n_sets][6], ok_in[n_sets] -> tr_out[n_sets][6],
+ * ok_out[n_sets], n_updates[n_sets].  n_sets == 0 or no records at all: VH_OK (outputs zero), nothing is launched and
+ * no device is needed.  Length limits as vh_motion_inliers. */
+int32_t vh_refit_motion(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                        const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates);
+/* The same on the compacted inlier lists of the handle's current STEREO classification (vh_group_motion_inliers /
+ * vh_match_inliers), from the tr / ok that classification was made under -- both are on the device already: nothing
+ * goes up, tr_out[S][6], ok_out[S], n_updates[S] and counts[S] come back; the call is synchronous.  VH_ERR_STATE
+ * before any classification of the current lists, after the next push or match, and when the current result is a
+ * mono classification.  Rows without a pair have ok_out = 0.
+ *   reclassify == 0: the classification is untouched, counts are its counts.
+ *   reclassify != 0: the lists are classified again under tr_out / ok_out with e->inlier_threshold, queued behind the
+ *   refit on the same stream (the host does not wait in between); the getters and vh_group_inliers_device then return
+ *   the refined motion's inliers and counts are theirs (VH_ERR_CAPACITY as vh_group_motion_inliers).  Should that
+ *   classification fail with another error, tr_out / ok_out / n_updates are still delivered and the handle is left
+ *   without a classification (VH_ERR_STATE from the getters) until vh_group_motion_inliers is called again.
+ * Plain groups, sequence handles and lone matchers.  The first call adds one block of 56 bytes per stream (each of
+ * its three arrays rounded up to 256 bytes), counted by vh_group_device_bytes; a handle that never calls it allocates
+ * and launches nothing.  A refused allocation is VH_ERR_HIP before any launch and leaves the handle as it was; the
+ * call may be repeated.  Profile scope: "motion_refit". */
+int32_t vh_group_refit_motion(vh_group *g, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
+                              int32_t *n_updates, int32_t *counts);
+int32_t vh_match_refit_motion(vh_matcher *m, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
+                              int32_t *n_updates, int32_t *count);
+
 /* ---- the steps after matching, pipelined ------------------------------------------------------------- */
 /* What the reference's loop runs between Matcher::matching and the pose -- removeOutliers (the tail of
  * matchFeatures, src/matcher.cpp:108), bucketFeatures (src/viso_stereo.cpp:41-43 -> src/matcher.cpp:140-187)
@@ -898,7 +935,9 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  and the same four on a group, per vh_group_reconstruct;
  *  with multi-stage matching "ranged" (pass 2), the same names with the prefix "sparse_" for the sparse sets'
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
- *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place)
+ *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place;
+ *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
+ *  "motion_refit" per vh_group_refit_motion)
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches);
