@@ -81,6 +81,7 @@ ABI_SYMBOLS = (
     "vh_estimate_motion_mono_model", "vh_group_estimate_motion_mono_model",
     "vh_motion_inliers_mono", "vh_group_motion_inliers_mono", "vh_match_inliers_mono",
     "vh_refit_motion", "vh_group_refit_motion", "vh_match_refit_motion",
+    "vh_group_post_device_dense", "vh_group_post_finish_device_dense",
 )
 
 
@@ -152,6 +153,12 @@ def _models(model, n):
     model = np.ascontiguousarray(model, MONO_MODEL_DTYPE).reshape(-1)
     assert len(model) == n, (len(model), n)
     return model
+
+
+class PostDense(C.Structure):
+    """vh_post_dense: the nullable output pointers of vh_group_post_finish_device_dense (include/viso_hip.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("voted_counts", "inlier_counts", "tr_refit", "ok_refit", "n_updates", "model",
+                                          "voted_pm", "flags", "inlier_pm", "src_pos")]
 
 
 class ReconParams(C.Structure):
@@ -297,6 +304,8 @@ def _lib():
             "vh_group_motion_inliers_mono": [vp, vp, vp, vp, vp], "vh_match_inliers_mono": [vp, vp, vp, i32, vp],
             "vh_refit_motion": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
+            "vh_group_post_device_dense": [vp, i32],
+            "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -807,6 +816,13 @@ class StreamGroup:
         (64 steps per batch, 3 batches, 16 lists per wave: the throughput-optimal shape, up to a second of latency)."""
         _check(_lib().vh_group_post_device_config(self._h, int(steps_per_batch), int(batches), int(lanes_per_wave)), "vh_group_post_device_config")
 
+    def postDeviceDense(self, mode: int):
+        """Dense inliers and the motion refit as stages of the device post chain (vh_group_post_device_dense): 0 off (the
+        default), 1 classify every stream's voted list under the batch's motion, 2 and refit on the inliers (stereo
+        estimator), 3 and classify again under the refined motion.  Not while steps are in flight."""
+        _check(_lib().vh_group_post_device_dense(self._h, int(mode)), "vh_group_post_device_dense")
+        self._dense_mode = int(mode)
+
     def postBeginDevice(self, cap_per_stream: int, max_features: int, bucket_width: float, bucket_height: float,
                         ego: "EgoParams" = None, rand3=None, mono: "MonoParams" = None, rand8=None, want_lists: bool = False):
         """This step's match lists enter the device post stage: removeOutliers -> bucketFeatures -> estimateMotion, all on
@@ -822,19 +838,60 @@ class StreamGroup:
                                                  C.byref(ego) if ego is not None else None, _ptr(r3),
                                                  C.byref(mono) if mono is not None else None, _ptr(r8), 1 if want_lists else 0),
                "vh_group_post_begin_device")
+        # what the steps in flight were begun with: postFinishDevice(dense=...) asks for what such a step produced
+        steps = self.__dict__.setdefault("_dense_steps", [])
+        steps.append((getattr(self, "_dense_mode", 0), mono is not None))
+        del steps[:-(256 * 64)]
 
-    def postFinishDevice(self, age: int, want_lists: bool = False, list_cap: int = 4096, estimator: bool = True, strict: bool = True):
+    def postFinishDevice(self, age: int, want_lists: bool = False, list_cap: int = 4096, estimator: bool = True, strict: bool = True,
+                         dense=None):
         """Results of the step begun `age` begins ago (vh_group_post_finish_device) -> dict(tr, ok, n_inliers, lists, counts).
-        strict=False: a refused list does not raise; its stream reports counts = -1 and the dict carries the code as "rc"."""
+        strict=False: a refused list does not raise; its stream reports counts = -1 and the dict carries the code as "rc".
+        dense (vh_group_post_finish_device_dense, after postDeviceDense(mode >= 1)): a tuple of "counts" -- adds voted_counts
+        [S], inlier_counts [S], with modes 2 and 3 tr_refit [S, 6], ok_refit [S], n_updates [S], with the monocular estimator
+        model [S] -- and "lists" -- adds voted, flags, inliers, src_pos: one array per stream (empty where the count is
+        -1; every list must fit list_cap).  "refit" / "model" ask for those outputs whatever the step was begun with."""
         S = self.S
         tr = np.zeros((S, 6), np.float64); ok = np.zeros(S, np.int32); ninl = np.zeros(S, np.int32); counts = np.zeros(S, np.int32)
         out = np.zeros((S, int(list_cap)), P_MATCH_DTYPE) if want_lists else None
-        rc = _lib().vh_group_post_finish_device(self._h, int(age), _ptr(tr) if estimator else None, _ptr(ok) if estimator else None,
-                                                _ptr(ninl) if estimator else None, _ptr(out), int(list_cap) if want_lists else 0, _ptr(counts))
+        args = (self._h, int(age), _ptr(tr) if estimator else None, _ptr(ok) if estimator else None,
+                _ptr(ninl) if estimator else None, _ptr(out), int(list_cap) if want_lists else 0, _ptr(counts))
+        if dense is None:
+            name = "vh_group_post_finish_device"
+            rc = _lib().vh_group_post_finish_device(*args)
+        else:
+            name = "vh_group_post_finish_device_dense"
+            dense = (dense,) if isinstance(dense, str) else tuple(dense)
+            assert dense and set(dense) <= {"counts", "lists", "refit", "model"}, dense
+            steps = getattr(self, "_dense_steps", [])
+            mode, mono = steps[-1 - int(age)] if int(age) < len(steps) else (0, False)
+            cap = int(list_cap)
+            extra = {"voted_counts": np.zeros(S, np.int32), "inlier_counts": np.zeros(S, np.int32)}
+            if mode >= 2 or "refit" in dense:
+                extra.update(tr_refit=np.zeros((S, 6), np.float64), ok_refit=np.zeros(S, np.int32), n_updates=np.zeros(S, np.int32))
+            if mono or "model" in dense:
+                extra["model"] = np.zeros(S, MONO_MODEL_DTYPE)
+            if "lists" in dense:
+                extra.update(voted_pm=np.zeros((S, cap), P_MATCH_DTYPE), flags=np.zeros((S, cap), np.uint8),
+                             inlier_pm=np.zeros((S, cap), P_MATCH_DTYPE), src_pos=np.zeros((S, cap), np.int32))
+            d = PostDense(**{k: v.ctypes.data for k, v in extra.items()})
+            rc = _lib().vh_group_post_finish_device_dense(*(args[:6] + (cap if (want_lists or "lists" in dense) else 0, args[7], C.byref(d))))
         if strict or rc in (VH_ERR_INVALID_ARG, VH_ERR_STATE, VH_ERR_HIP, VH_ERR_NO_DEVICE):
-            _check(rc, "vh_group_post_finish_device")
+            _check(rc, name)
         lists = [out[s, :max(int(counts[s]), 0)].copy() for s in range(S)] if want_lists else None
-        return {"tr": tr, "ok": ok.astype(bool), "n_inliers": ninl, "lists": lists, "counts": counts, "rc": rc}
+        res = {"tr": tr, "ok": ok.astype(bool), "n_inliers": ninl, "lists": lists, "counts": counts, "rc": rc}
+        if dense is not None:
+            nv, ni = np.maximum(extra["voted_counts"], 0), np.maximum(extra["inlier_counts"], 0)
+            if "ok_refit" in extra:
+                extra["ok_refit"] = extra["ok_refit"].astype(bool)
+            if "lists" in dense:
+                extra["voted"] = [extra["voted_pm"][s, :nv[s]].copy() for s in range(S)]
+                extra["flags"] = [extra["flags"][s, :nv[s]].copy() for s in range(S)]
+                extra["inliers"] = [extra["inlier_pm"][s, :ni[s]].copy() for s in range(S)]
+                extra["src_pos"] = [extra["src_pos"][s, :ni[s]].copy() for s in range(S)]
+                del extra["voted_pm"], extra["inlier_pm"]
+            res.update(extra)
+        return res
 
     def estimateMotionMono(self, mono: "MonoParams", rand8, model: bool = False):
         """VisualOdometryMono::estimateMotion (reference src/viso_mono.cpp:41-160) on every stream's device-resident

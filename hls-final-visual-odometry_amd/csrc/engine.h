@@ -262,6 +262,25 @@ struct InlierTest {
   bool args_ok() const { return params_ok() && (is_mono ? model != nullptr : tr != nullptr); }
 };
 
+inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+// The arrays of one classification inside one device block: flags | records | positions | tile counts | counts | ok | tr
+struct InlierLayout {
+  size_t o_out, o_src, o_tiles, o_ninl, o_ok, o_tr, bytes;
+  InlierLayout(size_t lists, size_t slots, size_t tiles) {
+    o_out = up256(slots);
+    o_src = o_out + up256(sizeof(vh_p_match) * slots);
+    o_tiles = o_src + up256(sizeof(int32_t) * slots);
+    o_ninl = o_tiles + up256(sizeof(int32_t) * lists * tiles);
+    o_ok = o_ninl + up256(sizeof(int32_t) * lists);
+    o_tr = o_ok + up256(sizeof(int32_t) * lists);
+    bytes = o_tr + up256(sizeof(double) * 6 * lists);
+  }
+};
+
+// the launch grid is lists x tiles workgroups of 256 threads
+inline bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
+
 // Motion inliers of the handle's lists (vh_group_motion_inliers; engine_inlier.hip): one arena
 // block, allocated by the first call, cut into the arrays below.  Nothing here exists on a handle that never calls it.
 struct InlierState {
@@ -290,6 +309,32 @@ struct RefitState {
   int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
 };
 
+// The dense stages of a batch (vh_group_post_device_dense; engine_post.hip): one block beside the
+// batch's own, cut into the arrays of one classification over the batch's P lists of `cap` slots (InlierLayout: its tr /
+// ok arrays hold the refit's results) and, behind them, the gate's arrays, the refit's update counts and the mono models;
+// and the page-locked mirror of what comes down with the batch's results.  Nothing here exists while the mode is 0.
+struct VoteDense {
+  DeviceBlock block;
+  size_t bytes = 0;
+  int32_t lists = 0, cap = 0, tiles = 0;  // what the block was cut for
+  bool with_model = false;
+  uint8_t *d_flags = nullptr;
+  vh_p_match *d_out = nullptr;
+  int32_t *d_src = nullptr, *d_tiles = nullptr, *d_ninl = nullptr;
+  int32_t *d_ok_refit = nullptr; double *d_tr_refit = nullptr;  // modes 2, 3
+  int32_t *d_cnt = nullptr, *d_ok = nullptr, *d_voted = nullptr, *d_nupd = nullptr;  // the gate's counts / ok / markers; updates
+  vh_mono_model *d_model = nullptr;
+  HostBlock<int32_t> h_int;   // [4][lists]: voted | inliers | ok_refit | n_updates
+  HostBlock<double> h_tr;     // [lists][6]
+  HostBlock<vh_mono_model> h_model;
+  int32_t h_lists = 0; bool h_with_model = false;
+  // bytes of the block for `lists` lists of `cap` slots
+  static size_t bytes_for(size_t lists, size_t cap, bool model) {
+    const size_t tiles = (cap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
+    return InlierLayout(lists, lists * cap, tiles).bytes + 4 * up256(sizeof(int32_t) * lists) + (model ? up256(sizeof(vh_mono_model) * lists) : 0);
+  }
+};
+
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
 struct VoteBatch {
   VoteBuffers vb;
@@ -310,6 +355,8 @@ struct VoteBatch {
   HostBlock<double> h_tr; HostBlock<int32_t> h_ok, h_cnt; HostBlock<VhVoteMeta> h_meta; HostBlock<vh_p_match> h_out;
   int32_t h_lists = 0, h_out_cap = 0;
   bool want_lists = false;
+  int32_t dense_mode = 0;  // vh_group_post_device_dense, as it was when the batch was started
+  VoteDense dn;
   VoteBatch() = default;
   VoteBatch(VoteBatch &&) = default;
   ~VoteBatch() { if (launched && ev_done) (void)hipEventSynchronize(ev_done); }  // (before the members free what the kernels use)
@@ -420,6 +467,7 @@ struct Group {
   // 0.4-0.5 s from launch to results whatever its size (profiles/r04_vote_trace.txt): the rate is the number of steps in
   // flight over that latency, and a wave of 64 lists costs the chip 1/14 of what 64 single-list waves cost.
   int32_t vote_steps = 64, vote_batches = 3, vote_lanes = 16;
+  int32_t vote_dense = 0;     // vh_group_post_device_dense: 0 off, 1 classify, 2 + refit, 3 + classify again
   int64_t post_dev_seq = 0;   // steps begun
   int32_t vote_cur = 0;       // batch receiving steps
   std::vector<VoteStep> vstep;  // ring over the steps begun, indexed by sequence number
@@ -548,11 +596,15 @@ struct Group {
                       double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts, double *host_ms);
   void vote_release() { vbatch.clear(); vstep.clear(); post_dev_seq = 0; vote_cur = 0; }
   int32_t post_device_config(int32_t steps_per_batch, int32_t batches, int32_t lanes);
+  int32_t post_device_dense(int32_t mode);
+  int32_t vote_dense_alloc(VoteBatch &b, int32_t lists, bool model);
+  int32_t vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs);
   int32_t bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid = nullptr) const;
   int32_t vote_launch(VoteBatch &b, int32_t index);
   int32_t post_begin_device(int32_t cap_ps, int32_t max_features, float bw, float bh, const vh_ego_params *e, const int32_t *rand3,
                             const vh_mono_params *mono, const int32_t *rand8, int32_t want_lists);
-  int32_t post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts);
+  int32_t post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
+                             const vh_post_dense *d = nullptr);
 };
 
 // times the HIP work queued on `st` during its lifetime under `name` (only while the group profiles)
@@ -580,6 +632,9 @@ struct LinkedLists {
 };
 int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index, const vh_p_match *carry_pm,
                           const vh_track *carry_trk, int32_t carry_count, int64_t carry_serial, bool has_carry, LinkedLists &out);
+// engine_inlier.hip
+// The flag pass of either test, then the scan and the scatter, on `st`; g: the handle whose profile takes the scopes (nullable)
+void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group *g);
 // engine_post.hip
 // Matcher::bucketFeatures (matcher.cpp:140-187) on the records pm[0, n): the selected records are written to
 // out (at most out_cap of them) in the reference's order; returns how many the reference would keep.

@@ -225,7 +225,7 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
   int64_t b = (int64_t)gq->device_bytes;
   if (gq->sparse) b += vh_group_device_bytes((const vh_group *)gq->sparse.get());  // the sparse sets of multi-stage matching
   b += (int64_t)gq->ms_vb.bytes;                                             // and the voted sparse lists of its device mode
-  for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes;
+  for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes + (int64_t)vb.dn.bytes;  // (dn: the dense stages' block)
   b += gq->rh.bytes;                                                         // the ring and the gather buffers of reconstruction
   return b;
 }
@@ -677,6 +677,15 @@ int32_t vh_group_post_finish_device(vh_group *g, int32_t age, double *tr, int32_
                                     int32_t *counts) {
   Group *gq = (Group *)g; ENTER(gq);
   return gq->post_finish_device(age, tr, ok, n_inliers, bucketed, cap_per_stream, counts);
+}
+int32_t vh_group_post_device_dense(vh_group *g, int32_t mode) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->post_device_dense(mode);
+}
+int32_t vh_group_post_finish_device_dense(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
+                                          int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->post_finish_device(age, tr, ok, n_inliers, bucketed, cap_per_stream, counts, d);
 }
 
 // ---- monocular egomotion -----------------------------------------

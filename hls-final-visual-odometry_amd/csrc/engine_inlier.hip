@@ -7,28 +7,9 @@
 
 namespace vh_engine {
 
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
-// The arrays of one classification inside one device block: flags | records | positions | tile counts | counts | ok | tr
-struct InlierLayout {
-  size_t o_out, o_src, o_tiles, o_ninl, o_ok, o_tr, bytes;
-  InlierLayout(size_t lists, size_t slots, size_t tiles) {
-    o_out = up256(slots);
-    o_src = o_out + up256(sizeof(vh_p_match) * slots);
-    o_tiles = o_src + up256(sizeof(int32_t) * slots);
-    o_ninl = o_tiles + up256(sizeof(int32_t) * lists * tiles);
-    o_ok = o_ninl + up256(sizeof(int32_t) * lists);
-    o_tr = o_ok + up256(sizeof(int32_t) * lists);
-    bytes = o_tr + up256(sizeof(double) * 6 * lists);
-  }
-};
-
-// the launch grid is lists x tiles workgroups of 256 threads
-static bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
-
 // The flag pass of either test, then the scan and the scatter both share.  g: the handle whose profile takes the
 // scopes (none for the stateless entries).
-static void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group *g) {
+void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group *g) {
   std::optional<Scope> sc;
   if (g) sc.emplace(g, t.is_mono ? "inlier_flag_mono" : "inlier_flag", st);
   if (t.is_mono) {

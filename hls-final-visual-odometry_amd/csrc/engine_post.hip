@@ -391,6 +391,90 @@ int32_t Group::post_device_config(int32_t steps_per_batch, int32_t batches, int3
   return VH_OK;
 }
 
+// The dense stages of the batches (include/viso_hip.h: vh_group_post_device_dense).  A change of mode changes what a batch
+// holds, so the ring is released and the next begin call sizes it again -- against the free memory, with the new mode's blocks.
+int32_t Group::post_device_dense(int32_t mode) {
+  if (mode < 0 || mode > 3) return VH_ERR_INVALID_ARG;
+  for (auto &b : vbatch) if (b.busy) return VH_ERR_STATE;
+  if (mode == vote_dense) return VH_OK;
+  vote_release();
+  vote_dense = mode;
+  return VH_OK;
+}
+
+// The dense block of batch b for `lists` lists of the batch's record slots: allocated (or grown) before the batch's first
+// launch; a refusal leaves the batch without one.
+int32_t Group::vote_dense_alloc(VoteBatch &b, int32_t lists, bool model) {
+  VoteDense &q = b.dn;
+  const int32_t cap = b.vb.v.cap;
+  if (q.block.p && q.lists >= lists && q.cap == cap && (q.with_model || !model)) return VH_OK;
+  q.block = DeviceBlock(); q.bytes = 0; q.lists = 0;
+  if (alloc_refused()) return VH_ERR_HIP;
+  const size_t L = (size_t)lists, tiles = ((size_t)cap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
+  const InlierLayout lay(L, L * (size_t)cap, tiles);
+  const size_t per_list = up256(sizeof(int32_t) * L), total = VoteDense::bytes_for(L, (size_t)cap, model);
+  VH_HIP(q.block.alloc(total));
+  uint8_t *d = q.block.as<uint8_t>();
+  q.d_flags = d; q.d_out = (vh_p_match *)(d + lay.o_out); q.d_src = (int32_t *)(d + lay.o_src); q.d_tiles = (int32_t *)(d + lay.o_tiles);
+  q.d_ninl = (int32_t *)(d + lay.o_ninl); q.d_ok_refit = (int32_t *)(d + lay.o_ok); q.d_tr_refit = (double *)(d + lay.o_tr);
+  q.d_cnt = (int32_t *)(d + lay.bytes); q.d_ok = (int32_t *)(d + lay.bytes + per_list); q.d_voted = (int32_t *)(d + lay.bytes + 2 * per_list);
+  q.d_nupd = (int32_t *)(d + lay.bytes + 3 * per_list);
+  q.d_model = model ? (vh_mono_model *)(d + lay.bytes + 4 * per_list) : nullptr;
+  q.bytes = total; q.lists = lists; q.cap = cap; q.tiles = (int32_t)tiles; q.with_model = model;
+  if (q.h_lists < lists || (model && !q.h_with_model)) {
+    q.h_lists = 0;
+    VH_HIP(q.h_int.alloc(4 * L, hipHostMallocDefault));
+    VH_HIP(q.h_tr.alloc(6 * L, hipHostMallocDefault));
+    if (model) VH_HIP(q.h_model.alloc(L, hipHostMallocDefault));
+    q.h_lists = lists; q.h_with_model = model;
+  }
+  return VH_OK;
+}
+
+// The dense stages of batch b, queued on its vote stream behind the estimator: gate -> flag -> scan + compact -> (mode >= 2)
+// refit -> (mode 3) the classification again, the refit's tr / ok in the place of the estimator's -> the small downloads.
+// The kernels are the stateless entries' (launch_inliers, vh_launch_refit) over the batch's fixed-stride slots.
+int32_t Group::vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs) {
+  VoteDense &q = b.dn;
+  {
+    Scope sc(this, "post_dense_gate", vs);
+    vh_launch_vote_gate(v, b.d_ok, q.d_cnt, q.d_ok, q.d_voted, vs);
+  }
+  VhInlierArgs a{};
+  a.pm = v.pm; a.pm_stride = v.cap; a.counts = q.d_cnt; a.count_cap = v.cap;
+  a.n_lists = v.P; a.tiles_per_list = q.tiles;
+  a.tr = b.has_mono ? nullptr : b.d_tr; a.model = b.has_mono ? q.d_model : nullptr; a.ok = q.d_ok; a.out_stride = v.cap;
+  a.flags = q.d_flags; a.tile_cnt = q.d_tiles; a.n_inl = q.d_ninl; a.out = q.d_out; a.src_pos = q.d_src;
+  const InlierTest t = b.has_mono ? InlierTest::monocular(&b.mono, nullptr) : InlierTest::stereo(&b.ego, nullptr);
+  launch_inliers(t, a, vs, this);
+  VH_HIP(hipGetLastError());
+  const size_t P = (size_t)v.P, L = (size_t)q.h_lists;
+  if (b.dense_mode >= 2) {
+    VhRefitArgs r{};
+    r.e = b.ego;
+    r.pm = q.d_out; r.pm_stride = v.cap; r.counts = q.d_ninl; r.count_cap = v.cap; r.n_lists = v.P;
+    r.tr_in = b.d_tr; r.ok_in = q.d_ok;
+    r.tr_out = q.d_tr_refit; r.ok_out = q.d_ok_refit; r.n_updates = q.d_nupd;
+    {
+      Scope sc(this, "motion_refit", vs);
+      vh_launch_refit(r, vs);
+    }
+    VH_HIP(hipGetLastError());
+    if (b.dense_mode == 3) {  // (a pointer switch: the refit's results stay where they are)
+      a.tr = q.d_tr_refit; a.ok = q.d_ok_refit;
+      launch_inliers(t, a, vs, this);
+      VH_HIP(hipGetLastError());
+    }
+    VH_HIP(hipMemcpyAsync(q.h_int + 2 * L, q.d_ok_refit, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(q.h_int + 3 * L, q.d_nupd, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(q.h_tr, q.d_tr_refit, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, vs));
+  }
+  VH_HIP(hipMemcpyAsync(q.h_int, q.d_voted, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+  VH_HIP(hipMemcpyAsync(q.h_int + L, q.d_ninl, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+  if (b.has_mono) VH_HIP(hipMemcpyAsync(q.h_model, q.d_model, sizeof(vh_mono_model) * P, hipMemcpyDeviceToHost, vs));
+  return VH_OK;
+}
+
 // bucket grid of Matcher::bucketFeatures on this group's images: floor(u_max / bw) + 1 columns, floor(v_max / bh) + 1 rows (matcher.cpp:150-151)
 int32_t Group::bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid) const {
   if (max_features < 1 || !(bw >= 1) || !(bh >= 1)) return VH_ERR_INVALID_ARG;
@@ -410,8 +494,10 @@ int32_t Group::vote_launch(VoteBatch &b, int32_t index) {
   vh_launch_vote(v, vote_lanes, b.max_features, b.bw, b.bh, b.vb.lfsr, b.vb.lfsr_n, b.vb.out, b.vb.out_cap, b.vb.out_count, nullptr, vs);
   VH_HIP(hipGetLastError());
   if (b.has_ego) vh_launch_ego(b.ego, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
-  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, nullptr, vs);
+  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0,
+                                       b.dense_mode ? b.dn.d_model : nullptr, vs);
   VH_HIP(hipGetLastError());
+  if (b.dense_mode) { const int32_t rc = vote_dense_launch(b, v, vs); if (rc) return rc; }
   if (b.has_ego || b.has_mono) {
     VH_HIP(hipMemcpyAsync(b.h_tr, b.d_tr, sizeof(double) * 6 * (size_t)v.P, hipMemcpyDeviceToHost, vs));
     VH_HIP(hipMemcpyAsync(b.h_ok, b.d_ok, sizeof(int32_t) * 2 * (size_t)v.P, hipMemcpyDeviceToHost, vs));
@@ -431,6 +517,8 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   if (cap_ps < 1 || (e && mono)) return VH_ERR_INVALID_ARG;
   if (e && (!rand3 || e->ransac_iters < 1)) return VH_ERR_INVALID_ARG;
   if (mono && (!rand8 || mono->ransac_iters < 1 || (int64_t)S * vote_steps * mono->ransac_iters > (int64_t)1 << 31)) return VH_ERR_INVALID_ARG;
+  if (vote_dense >= 1 && !e && !mono) return VH_ERR_INVALID_ARG;  // the dense stages classify under the batch's motion
+  if (vote_dense >= 2 && mono) return VH_ERR_INVALID_ARG;         // (the reference has no mono refit)
   if ((int64_t)S * vote_steps > 65535) return VH_ERR_UNSUPPORTED;  // (the tally and the monocular kernels put the list on grid.y: fewer steps per batch)
   if (!allocated || last_method < 0) return VH_ERR_STATE;
   if (e && last_method != VH_METHOD_QUAD) return VH_ERR_STATE;        // the stereo estimator needs both cameras of both frames
@@ -450,7 +538,8 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
       const int32_t P = steps * S;
       const size_t post = (e ? sizeof(double) * 4 * (size_t)P * (size_t)need : 0) + (mono ? (size_t)vh_mono_scratch_bytes(P, (int32_t)need, mono->ransac_iters) : 0) +
                           sizeof(double) * 6 * (size_t)P + sizeof(int32_t) * 2 * (size_t)P +
-                          sizeof(int32_t) * (size_t)steps * (e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0));
+                          sizeof(int32_t) * (size_t)steps * (e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0)) +
+                          (vote_dense ? VoteDense::bytes_for((size_t)P, (size_t)std::max(cap_ps, 4), mono != nullptr) : 0);
       return (double)vote_batches * (double)(VhVoteBuffers::bytes_for(P, cap_ps, (int32_t)need, (int32_t)grid) + post);
     };
     int32_t steps = vote_steps;
@@ -475,7 +564,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   const auto same = [&](const VoteBatch &q) {
     return q.method == last_method && q.max_features == max_features && q.bw == bw && q.bh == bh && q.has_ego == (e != nullptr) &&
            q.has_mono == (mono != nullptr) && (!e || memcmp(&q.ego, e, sizeof(*e)) == 0) && (!mono || memcmp(&q.mono, mono, sizeof(*mono)) == 0) &&
-           q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0);
+           q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0) && q.dense_mode == vote_dense;
   };
   if (b->steps > 0 && (b->launched || b->steps >= vote_steps || !same(*b))) {  // the batch is closed (full, flushed, or configured differently): next one
     if ((rc = vote_launch(*b, vote_cur))) return rc;
@@ -493,6 +582,8 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
     }
     b->steps = 0; b->launched = false; b->busy = false; b->handed = 0;
     const int32_t P = vote_steps * S;
+    // (the classification's launch grid: lists x tiles of the slots the batch will have)
+    if (vote_dense && !inlier_grid_ok(P, (std::max(b->vb.v.cap, cap_ps) + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
     if (b->vb.v.cap < cap_ps || b->vb.out_cap < need || b->vb.v.P < P || b->vb.v.nb_max < grid) {
       if (b->vb.block) {  // a batch grows (longer lists than the ring was sized for): only if the difference fits
         size_t free_b = 0, total_b = 0;
@@ -538,6 +629,9 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
     if (e) b->ego = *e;
     if (mono) b->mono = *mono;
     b->want_lists = want_lists != 0;
+    b->dense_mode = 0;  // (until its block exists: a refused allocation leaves a batch that launches nothing of it)
+    if (vote_dense && (rc = vote_dense_alloc(*b, P, mono != nullptr))) return rc;
+    b->dense_mode = vote_dense;
   }
   // the step's lists leave the matcher's buffer behind the emission that wrote them; the next emission waits for that (ev_down)
   VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
@@ -560,12 +654,21 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   return VH_OK;
 }
 
-int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts) {
-  if (age < 0 || (out && out_cap < 1)) return VH_ERR_INVALID_ARG;
+// (d, nullable: the dense stages' outputs, include/viso_hip.h: vh_post_dense)
+int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
+                                  const vh_post_dense *d) {
+  const bool d_records = d && (d->voted_pm || d->flags || d->inlier_pm || d->src_pos);
+  if (age < 0 || ((out || d_records) && out_cap < 1)) return VH_ERR_INVALID_ARG;
   if (vstep.empty() || post_dev_seq - 1 - age < 0 || age >= (int64_t)vstep.size()) return VH_ERR_STATE;
   VoteStep &st = vstep[(size_t)((post_dev_seq - 1 - age) % (int64_t)vstep.size())];
   if (!st.open) return VH_ERR_STATE;
   VoteBatch &b = vbatch[(size_t)st.batch];
+  if (d) {  // an output the step's mode did not produce: refused before anything happens to the step
+    const bool any = d->voted_counts || d->inlier_counts || d->tr_refit || d->ok_refit || d->n_updates || d->model || d_records;
+    if (any && b.dense_mode < 1) return VH_ERR_STATE;
+    if ((d->tr_refit || d->ok_refit || d->n_updates) && b.dense_mode < 2) return VH_ERR_STATE;
+    if (d->model && !b.has_mono) return VH_ERR_STATE;
+  }
   int32_t rc = vote_launch(b, st.batch);  // (a batch that is not full yet is closed and launched now)
   if (rc) return rc;
   VH_HIP(hipEventSynchronize(b.ev_done));
@@ -598,6 +701,36 @@ int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t 
       const int32_t k = b.h_cnt[p0 + s];
       if (k > out_cap) { ret = VH_ERR_CAPACITY; if (out_counts) out_counts[s] = -1; continue; }
       memcpy(out + (size_t)s * out_cap, b.h_out + (p0 + s) * (size_t)b.vb.out_cap, sizeof(vh_p_match) * (size_t)k);
+    }
+  }
+  if (!d || b.dense_mode < 1) return ret;
+  // The dense stages' outputs.  The small ones came down with the batch; the records of this step's lists are copied out
+  // of the batch's buffers now (they stay as they are until the ring comes round to the batch).
+  const VoteDense &q = b.dn;
+  const size_t L = (size_t)q.h_lists, cap = (size_t)b.vb.v.cap;
+  for (int32_t s = 0; s < S; s++) {
+    const size_t p = p0 + (size_t)s;
+    const int32_t voted = q.h_int[p];  // (-1: the gate's mark of a refused list)
+    const bool bad = voted < 0;
+    int32_t n_in = bad ? -1 : q.h_int[L + p], n_voted = voted;
+    if (!bad && (((d->voted_pm || d->flags) && voted > out_cap) || ((d->inlier_pm || d->src_pos) && n_in > out_cap))) {
+      ret = VH_ERR_CAPACITY;
+      n_in = n_voted = -1;
+    }
+    if (d->voted_counts) d->voted_counts[s] = n_voted;
+    if (d->inlier_counts) d->inlier_counts[s] = n_in;
+    const bool refit = b.dense_mode >= 2 && !bad;
+    if (d->ok_refit) d->ok_refit[s] = refit ? q.h_int[2 * L + p] : 0;
+    if (d->n_updates) d->n_updates[s] = refit ? q.h_int[3 * L + p] : 0;
+    if (d->tr_refit) for (int k = 0; k < 6; k++) d->tr_refit[6 * (size_t)s + k] = refit ? q.h_tr[6 * p + k] : 0.0;
+    if (d->model) { if (bad) memset(d->model + s, 0, sizeof(vh_mono_model)); else d->model[s] = q.h_model[p]; }
+    if (n_voted > 0) {
+      if (d->voted_pm) VH_HIP(hipMemcpy(d->voted_pm + (size_t)s * out_cap, b.vb.v.pm + p * cap, sizeof(vh_p_match) * (size_t)n_voted, hipMemcpyDeviceToHost));
+      if (d->flags) VH_HIP(hipMemcpy(d->flags + (size_t)s * out_cap, q.d_flags + p * cap, (size_t)n_voted, hipMemcpyDeviceToHost));
+    }
+    if (n_in > 0) {
+      if (d->inlier_pm) VH_HIP(hipMemcpy(d->inlier_pm + (size_t)s * out_cap, q.d_out + p * cap, sizeof(vh_p_match) * (size_t)n_in, hipMemcpyDeviceToHost));
+      if (d->src_pos) VH_HIP(hipMemcpy(d->src_pos + (size_t)s * out_cap, q.d_src + p * cap, sizeof(int32_t) * (size_t)n_in, hipMemcpyDeviceToHost));
     }
   }
   return ret;

@@ -414,7 +414,29 @@ __global__ __launch_bounds__(64) void vote_select_kernel(VhVote vt, int32_t max_
   }
 }
 
+// ---- vote_gate ---------------------------------------------------------------------------------------
+// The door between a voted batch and the stateless list kernels behind it (inliers, refit: VhInlierArgs / VhRefitArgs
+// read plain counts[P] and ok[P]), one lane per list: a list the vote kept (OK, SKIP) passes with meta.kept records and
+// the estimator's ok; a refused one (TRUNCATED, UNSUPPORTED, STACK) takes part in nothing -- no records, ok = 0 -- and is
+// marked -1 in the array the host reads.
+__global__ __launch_bounds__(256) void vote_gate_kernel(const VhVoteMeta *meta, int32_t P, int32_t cap, const int32_t *est_ok, int32_t *counts,
+                                                        int32_t *ok, int32_t *voted) {
+  const int32_t p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int32_t status = meta[p].status, kept = meta[p].kept;
+  const bool pass = status == VH_VOTE_OK || status == VH_VOTE_SKIP;
+  const int32_t n = pass ? (kept < 0 ? 0 : (kept > cap ? cap : kept)) : 0;
+  counts[p] = n;
+  ok[p] = pass && est_ok[p] ? 1 : 0;
+  voted[p] = pass ? n : -1;
+}
+
 }  // namespace
+
+void vh_launch_vote_gate(const VhVote &vt, const int32_t *est_ok, int32_t *counts, int32_t *ok, int32_t *voted, hipStream_t st) {
+  if (vt.P < 1) return;
+  hipLaunchKernelGGL(vote_gate_kernel, dim3((vt.P + 255) / 256), dim3(256), 0, st, vt.meta, vt.P, vt.cap, est_ok, counts, ok, voted);
+}
 
 // test hook (include/viso_hip.h): flip-stack slots the sweep uses, so that the refusal path can be driven with ordinary lists
 static int32_t g_vote_pend_cap = VH_VOTE_PEND;

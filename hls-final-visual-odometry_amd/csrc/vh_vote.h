@@ -57,6 +57,9 @@ void vh_launch_vote_prep(const VhVote &vt, int32_t p0, int32_t S, const vh_p_mat
 // sweep_ev: optional pair of events recorded around the sweep kernel
 void vh_launch_vote(const VhVote &vt, int32_t lanes, int32_t max_features, float bw, float bh, const uint32_t *lfsr, int32_t lfsr_n, vh_p_match *out,
                     int32_t out_cap, int32_t *out_count, hipEvent_t *sweep_ev, hipStream_t st);
+// behind vh_launch_vote and an estimator (est_ok[P]): counts[P] = the voted list's records, ok[P] = est_ok, both 0 for a
+// list the vote refused; voted[P] = counts, -1 for a refused list (the dense stages of the device post chain)
+void vh_launch_vote_gate(const VhVote &vt, const int32_t *est_ok, int32_t *counts, int32_t *ok, int32_t *voted, hipStream_t st);
 
 // Matcher::rand_number (matcher.cpp:113-124): LFSR, taps {32,22,2,1}, evaluated by the reference in double
 // arithmetic; its int(floor(number/2^0)) term is an out-of-range double->int conversion for number >= 2^31,

@@ -671,7 +671,8 @@ typedef struct vh_mono_model {
  * output, counted by vh_group_device_bytes (beside what vh_group_estimate_motion_mono allocates; the plain entry never
  * allocates it).
  * The pipelined post chains (vh_group_post_finish_mono, vh_group_post_begin_device / _finish_device) have no model
- * output: take the bucketed lists they return through vh_estimate_motion_mono_model. */
+ * output: take the bucketed lists they return through vh_estimate_motion_mono_model -- or set a dense mode
+ * (vh_group_post_device_dense) and take it from vh_group_post_finish_device_dense. */
 int32_t vh_estimate_motion_mono_model(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,
                                       const int32_t *offsets, const int32_t *rand8, double *tr, int32_t *ok,
                                       int32_t *n_inliers, int32_t *inliers, vh_mono_model *model);
@@ -743,6 +744,66 @@ int32_t vh_group_post_begin_device(vh_group *g, int32_t cap_per_stream, int32_t 
                                    int32_t want_lists);
 int32_t vh_group_post_finish_device(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
                                     int32_t cap_per_stream, int32_t *counts);
+
+/* ---- dense inliers and the motion refit as stages of the device post chain ----
+ * vh_group_motion_inliers(_mono) and vh_group_refit_motion work on the lists of the handle's last match call; in the
+ * device post chain a step's lists leave the matcher's buffer at once and its motion arrives steps_per_batch * batches
+ * steps later.  With a dense mode set, the batch itself classifies the VOTED list of every stream (what vote_select
+ * leaves compacted in the batch: the list removeOutliers returns, before bucketFeatures) under the motion its
+ * estimator found, behind the estimator on the batch's own stream: no host round trip, no upload.
+ *   vh_group_post_device_dense   mode 0: off (the default: every call allocates, launches and returns what it did
+ *                         without this entry); 1: classify every voted list under the batch's motion -- tr / ok of
+ *                         the stereo estimator (getInlier, as vh_motion_inliers), or the model / ok of the monocular
+ *                         one (as vh_motion_inliers_mono; the estimator's vh_mono_model becomes an output of the
+ *                         batch); 2: mode 1, then the refit of vh_refit_motion on the compacted inliers from the
+ *                         batch's tr / ok; 3: mode 2, then the classification again under tr_refit / ok_refit (as
+ *                         reclassify = 1 of vh_group_refit_motion).  VH_ERR_INVALID_ARG outside 0..3; VH_ERR_STATE
+ *                         while steps are in flight; a change of mode releases the ring (as
+ *                         vh_group_post_device_config), and the next begin call sizes it again.
+ *                         With mode >= 1 vh_group_post_begin_device returns VH_ERR_INVALID_ARG when no estimator is
+ *                         given and, with mode >= 2, when the estimator is the monocular one (the reference has no
+ *                         mono refit); VH_ERR_UNSUPPORTED when steps_per_batch * S lists of cap_per_stream records
+ *                         exceed the classification's launch grid (2^24 tiles of 1 024 records).  The mode is part
+ *                         of a batch's configuration.
+ *                         Device memory: per batch 53 bytes per record slot (flag, compacted record, position),
+ *                         4 bytes per tile of 1 024 slots and about 100 bytes per list (+ 128 per list for the mono
+ *                         model), in a block beside the batch's own; it is part of the ring the first begin call
+ *                         sizes against 80 % of the free memory, counted by vh_group_device_bytes, allocated before
+ *                         the batch's first launch (a refusal is VH_ERR_HIP, nothing has moved, the begin call can
+ *                         be repeated) and released with the ring.
+ *                         Profile scopes (on the batch's stream): "inlier_flag" / "inlier_flag_mono",
+ *                         "inlier_compact", "motion_refit", "post_dense_gate".
+ *   vh_group_post_finish_device_dense   vh_group_post_finish_device with one more argument; d = NULL, or a struct of
+ *                         NULLs, is that call.  tr, ok, n_inliers, bucketed, counts and the return value are those
+ *                         of vh_group_post_finish_device in every mode, bit for bit.
+ * vh_post_dense: nullable output pointers, each for this step's S streams.  Ten pointers in the order below: 80 bytes,
+ * member k at offset 8 k. */
+typedef struct vh_post_dense {
+  /* with the batch's results (a few bytes per list) */
+  int32_t *voted_counts;    /* [S] records of the voted list; mode >= 1 */
+  int32_t *inlier_counts;   /* [S] inliers (mode 3: of the second classification); mode >= 1 */
+  double *tr_refit;         /* [S][6]; mode >= 2; zero where ok_refit = 0 */
+  int32_t *ok_refit;        /* [S]; mode >= 2; 0: ok = 0, fewer than six inliers, or the refit failed */
+  int32_t *n_updates;       /* [S]; mode >= 2 */
+  vh_mono_model *model;     /* [S]; mode >= 1 with the monocular estimator */
+  /* per record: copied for this step's lists out of the batch's buffers when the call is made (they stay valid until
+   * the ring comes round to the batch); [S][cap_per_stream], list s at s * cap_per_stream; mode >= 1 */
+  vh_p_match *voted_pm;     /* the voted lists */
+  uint8_t *flags;           /* one byte per voted record (mode 3: of the second classification) */
+  vh_p_match *inlier_pm;    /* the inliers in list order */
+  int32_t *src_pos;        /* the position of each inlier in its voted list */
+} vh_post_dense;
+/* VH_ERR_STATE when d asks for an output the step's mode did not produce (checked first: the step stays open and
+ * can be finished again); VH_ERR_INVALID_ARG for a per-record output with cap_per_stream < 1.
+ * A voted list (voted_pm, flags) or an inlier list (inlier_pm, src_pos) longer than cap_per_stream: that stream's
+ * voted_counts and inlier_counts are -1, nothing of it is copied, the other streams are delivered and the call
+ * returns VH_ERR_CAPACITY.  A stream whose list the vote refused takes part in nothing: voted_counts = inlier_counts
+ * = -1, ok_refit = 0, tr_refit = 0, n_updates = 0, a zeroed model, and the call returns the refusal's code as
+ * vh_group_post_finish_device does.  A list with ok = 0 has no inliers (its tr / model is not read), and fewer than
+ * six inliers give ok_refit = 0: the stateless contracts.  Sequence handles as vh_group_post_begin_device. */
+int32_t vh_group_post_device_dense(vh_group *g, int32_t mode);
+int32_t vh_group_post_finish_device_dense(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
+                                          int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d);
 
 /* vh_group_post_finish with the MONOCULAR estimator as its last stage: what VisualOdometryMono::process runs
  * after the matching (src/viso_mono.cpp:34-37: bucketFeatures, then estimateMotion on the bucketed list; the
