@@ -82,6 +82,7 @@ ABI_SYMBOLS = (
     "vh_motion_inliers_mono", "vh_group_motion_inliers_mono", "vh_match_inliers_mono",
     "vh_refit_motion", "vh_group_refit_motion", "vh_match_refit_motion",
     "vh_group_post_device_dense", "vh_group_post_finish_device_dense",
+    "vh_gain", "vh_group_set_gain", "vh_set_gain", "vh_group_gain", "vh_match_gain", "vh_group_gain_indices", "vh_match_gain_indices",
 )
 
 
@@ -306,6 +307,10 @@ def _lib():
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
+            "vh_gain": [i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp],
+            "vh_group_set_gain": [vp, i32], "vh_set_gain": [vp, i32],
+            "vh_group_gain": [vp, vp, vp], "vh_match_gain": [vp, vp, vp],
+            "vh_group_gain_indices": [vp, vp, vp, vp, vp], "vh_match_gain_indices": [vp, vp, i32, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -499,6 +504,22 @@ class Matcher:
         _check(_lib().vh_match_refit_motion(self._h, C.byref(ego), 1 if reclassify else 0, _ptr(tr), C.byref(ok), C.byref(nupd), C.byref(n)),
                "vh_match_refit_motion")
         return tr, bool(ok.value), nupd.value, n.value
+
+    def setGain(self, on: bool = True):
+        """Keep the pushed left images on the device for getGain (vh_set_gain): before the first pushBack."""
+        _check(_lib().vh_set_gain(self._h, 1 if on else 0), "vh_set_gain")
+
+    def getGain(self, indices=None):
+        """Matcher::getGain (reference src/matcher.h:148): the gain between the previous and the current left image over
+        the positions `indices` of getMatches(), or over the inliers of the last motionInliers(Mono) when None
+        (vh_match_gain_indices / vh_match_gain) -> (gain np.float32, num)."""
+        g = C.c_float(0); n = C.c_int32(0)
+        if indices is None:
+            _check(_lib().vh_match_gain(self._h, C.byref(g), C.byref(n)), "vh_match_gain")
+        else:
+            idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+            _check(_lib().vh_match_gain_indices(self._h, _ptr(idx) if len(idx) else None, len(idx), C.byref(g), C.byref(n)), "vh_match_gain_indices")
+        return np.float32(g.value), n.value
 
     def getInlierMatches(self):
         """-> (the inlier records in list order, their positions in getMatches()) of the last motionInliers(Mono)."""
@@ -743,6 +764,27 @@ class StreamGroup:
         counts = np.zeros(self.S, np.int32)
         _check(_lib().vh_group_motion_inliers_mono(self._h, C.byref(mono), _ptr(model), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers_mono")
         return counts
+
+    def setGain(self, on: bool = True):
+        """Keep the pushed left images of every stream (sequence handle: frame) on the device for gain()
+        (vh_group_set_gain): before the first push."""
+        _check(_lib().vh_group_set_gain(self._h, 1 if on else 0), "vh_group_set_gain")
+
+    def gain(self, indices=None):
+        """Matcher::getGain (reference src/matcher.h:148) for every stream (sequence handle: row): over the inlier
+        positions of the current classification (indices None, vh_group_gain) or over `indices`, one array of positions
+        into getMatches(s) per stream (vh_group_gain_indices) -> (gain float32 [S], num int32 [S])."""
+        gain = np.zeros(self.S, np.float32); num = np.zeros(self.S, np.int32)
+        if indices is None:
+            _check(_lib().vh_group_gain(self._h, _ptr(gain), _ptr(num)), "vh_group_gain")
+            return gain, num
+        lists = [np.ascontiguousarray(q, np.int32).reshape(-1) for q in indices]
+        assert len(lists) == self.S
+        off = np.zeros(self.S + 1, np.int32)
+        off[1:] = np.cumsum([len(q) for q in lists])
+        idx = np.concatenate(lists) if off[-1] else np.zeros(1, np.int32)
+        _check(_lib().vh_group_gain_indices(self._h, _ptr(idx), _ptr(off), _ptr(gain), _ptr(num)), "vh_group_gain_indices")
+        return gain, num
 
     def getInlierFlags(self, stream: int) -> np.ndarray:
         """One byte per record of the stream's list: 1 = inlier of the last motionInliers (vh_group_get_inlier_flags)."""
@@ -1135,6 +1177,26 @@ def motion_inliers(ego: EgoParams, match_lists, tr, ok, device: int = 0):
     sl = [slice(int(offsets[s]), int(offsets[s]) + int(ninl[s])) for s in range(n)]
     return ([flags[offsets[s]:offsets[s + 1]].copy() for s in range(n)], ninl[:n],
             [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
+
+
+def gain(match_lists, index_lists, I_prev, I_cur, dims, device: int = 0):
+    """Matcher::getGain (reference src/matcher.h:148) for n lists in one call (vh_gain): `match_lists` (p_match arrays),
+    `index_lists` (int32 positions into each), I_prev / I_cur: uint8 [n, H, bpl] (or [H, bpl] for one list), the previous
+    and current left images at full resolution, dims = (W, H, bpl) -> (gain float32 [n], num int32 [n])."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    idxs = [np.ascontiguousarray(q, np.int32).reshape(-1) for q in index_lists]
+    n = len(lists)
+    assert len(idxs) == n
+    W, H, bpl = (int(d) for d in dims)
+    Ip = np.ascontiguousarray(I_prev, np.uint8).reshape(n, H, bpl); Ic = np.ascontiguousarray(I_cur, np.uint8).reshape(n, H, bpl)
+    offsets = np.zeros(n + 1, np.int32); ioff = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists]); ioff[1:] = np.cumsum([len(q) for q in idxs])
+    pm = np.concatenate(lists) if offsets[-1] else np.zeros(1, P_MATCH_DTYPE)
+    idx = np.concatenate(idxs) if ioff[-1] else np.zeros(1, np.int32)
+    out = np.zeros(max(n, 1), np.float32); num = np.zeros(max(n, 1), np.int32)
+    _check(_lib().vh_gain(device, n, _dims(dims), _ptr(Ip), _ptr(Ic), H * bpl, _ptr(pm), _ptr(offsets), _ptr(idx), _ptr(ioff), _ptr(out),
+                          _ptr(num)), "vh_gain")
+    return out[:n], num[:n]
 
 
 def refit_motion(ego: EgoParams, match_lists, tr, ok, device: int = 0):

@@ -5,6 +5,7 @@
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
+//   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
 #ifndef VH_ENGINE_H
 #define VH_ENGINE_H
 #include "vh_dev.h"
@@ -297,6 +298,7 @@ struct InlierState {
   int32_t *d_host_cnt = nullptr;
   int32_t tiles = 0;
   bool mono = false;                      // the classification is a mono one
+  bool from_host = false;                 // it read d_host_pm / d_host_cnt (a list was replaced on the host), not the emission's lists
   bool valid = false, truncated = false;  // a classification exists (of the lists of match call `seq`) / of a truncated list
   int64_t seq = 0;
   std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
@@ -307,6 +309,22 @@ struct InlierState {
 struct RefitState {
   double *d_tr = nullptr;                      // [S][6]
   int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
+};
+
+// The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
+// arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
+// first call that needs it.  Nothing here exists while the switch is off.
+struct GainState {
+  uint8_t *d_planes = nullptr;  // [VH_RING][S][H][pitch]: plane (ring slot, row) = left set id >> 1
+  int64_t plane = 0;            // bytes per plane: pitch * H
+  int32_t pitch = 0;            // W rounded up to 16
+  float *d_gain = nullptr;      // [S], and behind it int32 num [S]
+  float *d_ratio = nullptr;     // [S][mcap] the ratios over the classification's positions
+  int32_t *d_idx = nullptr;     // the caller's index lists: idx [idx_cap] | ratio [idx_cap] | offsets [S + 1]; grows
+  int64_t idx_cap = 0;
+  size_t idx_bytes = 0;
+  vh_p_match *d_host_pm = nullptr;  // [S][mcap] and counts [S]: the lists as the getters return them, once one was replaced on the host
+  int32_t *d_host_cnt = nullptr;
 };
 
 // The dense stages of a batch (vh_group_post_device_dense; engine_post.hip): one block beside the
@@ -487,6 +505,8 @@ struct Group {
   ReconHistory rh;
   InlierState inl;
   RefitState rft;
+  bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
+  GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
   // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
   // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
@@ -576,6 +596,10 @@ struct Group {
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
   int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
   int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);
+
+  // ---- engine_gain.hip ----
+  int32_t gain_copy(const VhImages &im);
+  int32_t gain_lists(const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num);
 
   // ---- engine_post.hip ----
   int32_t get_sparse_device(int32_t s, vh_p_match *out, int32_t capo, int32_t *n);

@@ -58,7 +58,7 @@ void Group::release() {
   vote_release();
   rh.release_device();
   allocs.clear(); device_bytes = 0;
-  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {};
+  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {}; gn = {};
   allocated = false;
 }
 
@@ -206,6 +206,11 @@ int32_t Group::allocate(const int32_t d[3]) {
     for (int k = 0; k < 2; k++)
       if ((rc = dmalloc(&mt.d_ref2[k], 2 * (size_t)S * cap, false))) return rc;
   }
+  if (gain_on) {  // the left images of the ring (a sequence handle's empty sets hold no image)
+    gn.pitch = round_up(dims[0], 16);
+    gn.plane = (int64_t)gn.pitch * dims[1];
+    if ((rc = dmalloc(&gn.d_planes, VH_RING * (size_t)S * gn.plane, false))) return rc;
+  }
   allocated = true;
   pair_cur = 0; pair_prev = 1; frames = 0; mt.epoch = 0; last_method = -1; failed = false;
   seq_n = seq_n_prev = 0; seq_first = seq_total = 0; trk_reset();
@@ -325,6 +330,7 @@ int32_t Group::push_device_queued(const void *dI1, const void *dI2, int64_t stri
     uint64_t *rec = det.d_rec + (size_t)s0 * ncam * std::max(g.nblocks, 1);
     // the refinement's planes come from the pushed full-resolution images, inside the window they are borrowed for
     if (p.refinement > 0) { Scope sc(this, "refine_planes", stream); vh_launch_refine_planes(im, rf, stream); }
+    if (gain_on && (rc = gain_copy(im))) return rc;  // (likewise: the full-resolution left images, before `im` turns to the half ones)
     int32_t *chunks = det.d_chunk_count + (size_t)s0 * ncam * g.nchunks;
     if (p.half_resolution) {
       const int64_t isz = (int64_t)g.bplm * g.Hm;

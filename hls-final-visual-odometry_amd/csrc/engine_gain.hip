@@ -1,0 +1,225 @@
+// engine_gain.hip -- the camera gain between the previous and the current left image over the lists of a handle or
+// caller-owned lists (kernels_gain.hip): the ring's image planes, the handle entries over the
+// inlier positions of the current classification or over the caller's index lists, the stateless entry, and their
+// part of the ABI.
+#include "engine.h"
+
+namespace vh_engine {
+
+// a sub-batch's full-resolution left images into the planes of the slot being written, on the detect stream
+int32_t Group::gain_copy(const VhImages &im) {
+  Scope sc(this, "gain_copy", stream);
+  uint8_t *dst = gn.d_planes + (int64_t)(vh_set_id(S, im.pair_cur, im.s0, 0) >> 1) * gn.plane;
+  vh_launch_gain_copy(im.base[0], im.stride, g.bpl, g.W, g.H, im.S, dst, gn.plane, gn.pitch, stream);
+  VH_HIP(hipGetLastError());
+  return VH_OK;
+}
+
+// idx_offsets null: over the inlier positions of the current classification, which are on the device already; otherwise
+// over idx[idx_offsets[s] .. idx_offsets[s + 1]) for list s, positions into the lists the getters return.
+int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num) {
+  if (!gain || !num) return VH_ERR_INVALID_ARG;
+  const bool by_inliers = !idx_offsets;
+  // (a push ends the pair the lists belong to: last_method; stereo lists hold no previous frame)
+  if (!gain_on || !allocated || failed || (last_method != VH_METHOD_FLOW && last_method != VH_METHOD_QUAD)) return VH_ERR_STATE;
+  if (by_inliers && !inliers_current()) return VH_ERR_STATE;
+  int64_t total = 0, kmax = mcap;
+  if (!by_inliers) {
+    if (idx_offsets[0] < 0) return VH_ERR_INVALID_ARG;
+    kmax = 0;
+    for (int32_t s = 0; s < S; s++) {
+      if (idx_offsets[s + 1] < idx_offsets[s]) return VH_ERR_INVALID_ARG;
+      kmax = std::max<int64_t>(kmax, idx_offsets[s + 1] - idx_offsets[s]);
+    }
+    total = (int64_t)idx_offsets[S] - idx_offsets[0];
+    if (total > 0 && !idx) return VH_ERR_INVALID_ARG;
+  }
+  const int64_t tiles = (kmax + VH_GAIN_TILE - 1) / VH_GAIN_TILE;
+  if (!inlier_grid_ok(S, tiles)) return VH_ERR_UNSUPPORTED;
+  for (int32_t s = 0; s < S; s++) { gain[s] = 1.0f; num[s] = 0; }
+  if (!by_inliers && total == 0) return VH_OK;
+  int32_t rc = VH_OK;
+  if (!gn.d_gain && (rc = dmalloc(&gn.d_gain, 2 * (size_t)S, false))) return rc;
+  if (by_inliers && !gn.d_ratio && (rc = dmalloc(&gn.d_ratio, (size_t)S * mcap, false))) return rc;
+  if (!by_inliers && gn.idx_cap < total) {  // idx | ratio | offsets; grows (the work on the old block has completed: every call waits)
+    const int64_t want = total + total / 4;
+    const size_t b_idx = up256(sizeof(int32_t) * (size_t)want), bytes = 2 * b_idx + sizeof(int32_t) * ((size_t)S + 1);
+    uint8_t *d = nullptr;
+    if ((rc = dmalloc(&d, bytes, false))) return rc;
+    if (gn.d_idx) { dfree(gn.d_idx); device_bytes -= (int64_t)gn.idx_bytes; }
+    gn.d_idx = (int32_t *)d; gn.idx_cap = want; gn.idx_bytes = bytes;
+  }
+  hipStream_t ps = post_stream;
+  VhGainArgs a{};
+  a.pm = (const vh_p_match *)mt.d_matches; a.pm_stride = mcap; a.counts = mt.d_match_count; a.count_cap = mcap;
+  std::vector<int32_t> host_cnt, off;
+  if (by_inliers) {
+    if (inl.from_host) { a.pm = inl.d_host_pm; a.counts = inl.d_host_cnt; }  // the lists the classification read
+    a.idx = inl.d_src; a.idx_stride = mcap; a.idx_counts = inl.d_ninl; a.idx_cap = mcap;
+    a.ok = inl.d_ok;
+    a.ratio = gn.d_ratio;
+  } else {
+    bool replaced = false;  // the getters serve a host-side list for some stream: the positions are positions in that list
+    for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
+    if (replaced && !gn.d_host_pm) {
+      uint8_t *d = nullptr;
+      const size_t b_pm = up256(sizeof(vh_p_match) * (size_t)S * mcap);
+      if ((rc = dmalloc(&d, b_pm + sizeof(int32_t) * (size_t)S, false))) return rc;
+      gn.d_host_pm = (vh_p_match *)d; gn.d_host_cnt = (int32_t *)(d + b_pm);
+    }
+    if (replaced) {  // (a replaced list is a subset of the device list it came from: it fits the slot)
+      host_cnt.assign((size_t)S, 0);
+      VH_HIP(hipMemcpyAsync(gn.d_host_cnt, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, ps));
+      for (int32_t s = 0; s < S; s++) {
+        vh_p_match *dst = gn.d_host_pm + (size_t)s * mcap;
+        if (!host_filtered[s]) {
+          VH_HIP(hipMemcpyAsync(dst, a.pm + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)mcap, hipMemcpyDeviceToDevice, ps));
+          continue;
+        }
+        host_cnt[s] = (int32_t)std::min<size_t>(host_matches[s].size(), (size_t)mcap);
+        if (host_cnt[s]) VH_HIP(hipMemcpyAsync(dst, host_matches[s].data(), sizeof(vh_p_match) * (size_t)host_cnt[s], hipMemcpyHostToDevice, ps));
+        VH_HIP(hipMemcpyAsync(gn.d_host_cnt + s, &host_cnt[s], sizeof(int32_t), hipMemcpyHostToDevice, ps));
+      }
+      a.pm = gn.d_host_pm; a.counts = gn.d_host_cnt;
+    }
+    const size_t b_idx = up256(sizeof(int32_t) * (size_t)gn.idx_cap);
+    int32_t *d_off = (int32_t *)((uint8_t *)gn.d_idx + 2 * b_idx);
+    off.resize((size_t)S + 1);
+    for (int32_t s = 0; s <= S; s++) off[s] = idx_offsets[s] - idx_offsets[0];
+    VH_HIP(hipMemcpyAsync(gn.d_idx, idx + idx_offsets[0], sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, ps));
+    VH_HIP(hipMemcpyAsync(d_off, off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, ps));
+    a.idx = gn.d_idx; a.idx_offsets = d_off;
+    a.ratio = (float *)((uint8_t *)gn.d_idx + b_idx);
+  }
+  a.n_lists = S; a.tiles_per_list = (int32_t)tiles;
+  a.planes_prev = a.planes_cur = gn.d_planes; a.plane = gn.plane; a.pitch = gn.pitch; a.W = dims[0]; a.H = dims[1];
+  a.by_set = 1; a.m = role_args();
+  a.gain = gn.d_gain; a.num = (int32_t *)(gn.d_gain + S);
+  a.check = sets.check;
+  // on the post stream, behind the emission of the lists and the classification
+  { Scope sc(this, "gain_ratio", ps); vh_launch_gain_ratio(a, ps); }
+  { Scope sc(this, "gain_sum", ps); vh_launch_gain_sum(a, ps); }
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipMemcpyAsync(gain, a.gain, sizeof(float) * (size_t)S, hipMemcpyDeviceToHost, ps));
+  VH_HIP(hipMemcpyAsync(num, a.num, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, ps));
+  VH_HIP(hipStreamSynchronize(ps));
+  return check_violation();
+}
+
+}  // namespace vh_engine
+
+using namespace vh_engine;
+
+#define ENTER(gq)                                   \
+  if (!(gq)) return VH_ERR_INVALID_ARG;             \
+  { hipError_t e_ = hipSetDevice((gq)->device);     \
+    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
+
+// The stateless gain: validation, one device block (records | offsets | index entries | their offsets | ratios | gain,
+// num | check words | the image planes, repacked to the pitch of a handle's), two launches, one download.
+static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dims, const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride,
+                              const vh_p_match *pm, const int32_t *offsets, const int32_t *idx, const int32_t *idx_offsets, float *gain,
+                              int32_t *num) {
+  if (n_sets < 0) return VH_ERR_INVALID_ARG;
+  if (n_sets == 0) return VH_OK;
+  if (!dims || !offsets || !idx_offsets || !gain || !num || offsets[0] < 0 || idx_offsets[0] < 0) return VH_ERR_INVALID_ARG;
+  if (dims[0] <= 0 || dims[1] <= 0 || dims[2] < dims[0] || image_stride < 0) return VH_ERR_INVALID_ARG;
+  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  int64_t nmax = 0, kmax = 0;
+  for (int32_t s = 0; s < n_sets; s++) {
+    if (offsets[s + 1] < offsets[s] || idx_offsets[s + 1] < idx_offsets[s]) return VH_ERR_INVALID_ARG;
+    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
+    kmax = std::max<int64_t>(kmax, idx_offsets[s + 1] - idx_offsets[s]);
+  }
+  const int64_t end = offsets[n_sets], total = end - offsets[0], k_end = idx_offsets[n_sets], k_total = k_end - idx_offsets[0];
+  if ((total > 0 && !pm) || (k_total > 0 && (!idx || !I_prev || !I_cur))) return VH_ERR_INVALID_ARG;
+  for (int32_t s = 0; s < n_sets; s++) { gain[s] = 1.0f; num[s] = 0; }
+  if (k_total == 0) return VH_OK;  // nothing to do: nothing is launched
+  const int64_t tiles = (kmax + VH_GAIN_TILE - 1) / VH_GAIN_TILE;
+  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, tiles)) return VH_ERR_UNSUPPORTED;  // (a list longer than any handle holds)
+  const int32_t rc = select_device(device);
+  if (rc) return rc;
+  const size_t lists = (size_t)n_sets;
+  const int32_t pitch = round_up(dims[0], 16);
+  const size_t plane = (size_t)pitch * dims[1];
+  const size_t o_off = up256(sizeof(vh_p_match) * (size_t)end), o_idx = o_off + up256(sizeof(int32_t) * (lists + 1));
+  const size_t o_ioff = o_idx + up256(sizeof(int32_t) * (size_t)k_end), o_ratio = o_ioff + up256(sizeof(int32_t) * (lists + 1));
+  const size_t o_gain = o_ratio + up256(sizeof(float) * (size_t)k_end), o_num = o_gain + up256(sizeof(float) * lists);
+  const size_t o_check = o_num + up256(sizeof(int32_t) * lists), o_prev = o_check + 256, o_cur = o_prev + up256(plane * lists);
+  DeviceBlock blk;
+  VH_HIP(blk.alloc(o_cur + plane * lists));
+  uint8_t *d = blk.as<uint8_t>();
+  const size_t first = (size_t)offsets[0], k_first = (size_t)idx_offsets[0];
+  if (total > 0) VH_HIP(hipMemcpy(d + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_idx + sizeof(int32_t) * k_first, idx + k_first, sizeof(int32_t) * (size_t)k_total, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(d + o_ioff, idx_offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
+  VH_HIP(hipMemset(d + o_check, 0, 256));
+  VH_HIP(hipMemset(d + o_prev, 0, o_cur + plane * lists - o_prev));  // (the planes' padding columns: read, never summed)
+  for (size_t s = 0; s < lists; s++) {
+    VH_HIP(hipMemcpy2D(d + o_prev + s * plane, (size_t)pitch, I_prev + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
+    VH_HIP(hipMemcpy2D(d + o_cur + s * plane, (size_t)pitch, I_cur + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
+  }
+  VhGainArgs a{};
+  a.pm = (const vh_p_match *)d; a.offsets = (const int32_t *)(d + o_off);
+  a.idx = (const int32_t *)(d + o_idx); a.idx_offsets = (const int32_t *)(d + o_ioff);
+  a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
+  a.planes_prev = d + o_prev; a.planes_cur = d + o_cur; a.plane = (int64_t)plane; a.pitch = pitch; a.W = dims[0]; a.H = dims[1];
+  a.ratio = (float *)(d + o_ratio); a.gain = (float *)(d + o_gain); a.num = (int32_t *)(d + o_num);
+  a.check = (uint32_t *)(d + o_check);
+  vh_launch_gain_ratio(a, nullptr);
+  vh_launch_gain_sum(a, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
+#ifdef VH_CHECK
+  {
+    uint32_t c[4] = {0, 0, 0, 0};
+    VH_HIP(hipMemcpy(c, a.check, sizeof(c), hipMemcpyDeviceToHost));
+    if (c[0]) {
+      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
+      fflush(stderr);
+      abort();
+    }
+  }
+#endif
+  VH_HIP(hipMemcpy(gain, a.gain, sizeof(float) * lists, hipMemcpyDeviceToHost));
+  VH_HIP(hipMemcpy(num, a.num, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  return VH_OK;
+}
+
+extern "C" {
+
+int32_t vh_group_set_gain(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: the planes belong to every frame of the ring
+  gq->gain_on = on != 0;
+  return VH_OK;
+}
+int32_t vh_set_gain(vh_matcher *m, int32_t on) { return vh_group_set_gain((vh_group *)m, on); }
+int32_t vh_gain(int32_t device, int32_t n_sets, const int32_t dims[3], const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride_bytes,
+                const vh_p_match *pm, const int32_t *offsets, const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num) {
+  return gain_stateless(device, n_sets, dims, I_prev, I_cur, image_stride_bytes, pm, offsets, idx, idx_offsets, gain, num);
+}
+int32_t vh_group_gain(vh_group *g, float *gain, int32_t *num) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->gain_lists(nullptr, nullptr, gain, num);
+}
+int32_t vh_match_gain(vh_matcher *m, float *gain, int32_t *num) {
+  Group *gq = (Group *)m; ENTER(gq);
+  if (gq->S != 1) return VH_ERR_INVALID_ARG;
+  return gq->gain_lists(nullptr, nullptr, gain, num);
+}
+int32_t vh_group_gain_indices(vh_group *g, const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num) {
+  Group *gq = (Group *)g; ENTER(gq);
+  if (!idx_offsets) return VH_ERR_INVALID_ARG;
+  return gq->gain_lists(idx, idx_offsets, gain, num);
+}
+int32_t vh_match_gain_indices(vh_matcher *m, const int32_t *idx, int32_t k, float *gain, int32_t *num) {
+  Group *gq = (Group *)m; ENTER(gq);
+  if (gq->S != 1 || k < 0) return VH_ERR_INVALID_ARG;
+  const int32_t off[2] = {0, k};
+  return gq->gain_lists(idx, off, gain, num);
+}
+
+}  // extern "C"

@@ -117,7 +117,8 @@ struct VhSets {
 //   codes: 1 rows_tile query position, 2 rows_tile candidate position, 3 row re-search candidate
 //          position, 4 bin_sort row slot, 5 emit_features stage slot, 6 bin_sort staged bin length,
 //          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position,
-//          10 recon_store predecessor position of a continued mark, 11 recon_gather position followed through the ring
+//          10 recon_store predecessor position of a continued mark, 11 recon_gather position followed through the ring,
+//          12 gain_ratio byte offset of a dword inside its image plane, 13 gain_ratio list position of an index entry
 #ifdef VH_CHECK
 #define VH_CHECK_RANGE(s_, code_, x_, lo_, hi_)                                          \
   do {                                                                                   \
@@ -437,6 +438,40 @@ struct VhRefitArgs {
   int32_t *n_updates;       // [n_lists] updateParameters calls made: 0 (not started), 1 .. 102
 };
 void vh_launch_refit(const VhRefitArgs &a, hipStream_t st);
+
+// The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
+// as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
+// entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.
+// The images are u8 planes of `pitch` bytes per row (a multiple of 4, the base 4-byte aligned), `plane` bytes apart.
+#define VH_GAIN_TILE 256  // index entries per workgroup of gain_ratio
+struct VhGainArgs {
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  const int32_t *idx;
+  int64_t idx_stride;
+  const int32_t *idx_offsets, *idx_counts;
+  int32_t idx_cap;
+  const int32_t *ok;        // null, or [n_lists]; 0: the list reads as one without index entries
+  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest index list / VH_GAIN_TILE)
+  const uint8_t *planes_prev, *planes_cur;
+  int64_t plane;
+  int32_t pitch, W, H;
+  // by_set = 0: list l reads plane l of planes_prev / planes_cur.  1 (a handle): the plane of its previous / current left
+  // set under m (vh_row_set(m, l, 0 / 2) >> 1: the planes are indexed by ring slot and row); a sequence row outside
+  // [seq_lo, rows) reads as a list without index entries
+  int32_t by_set;
+  VhMatchArgs m;
+  float *ratio;
+  float *gain;              // [n_lists]
+  int32_t *num;             // [n_lists]
+  uint32_t *check;          // VH_CHECK builds: {violations, code, value, bound}
+};
+void vh_launch_gain_copy(const uint8_t *src, int64_t stride, int32_t bpl, int32_t W, int32_t H, int32_t n_images, uint8_t *dst, int64_t plane,
+                         int32_t pitch, hipStream_t st);
+void vh_launch_gain_ratio(const VhGainArgs &a, hipStream_t st);
+void vh_launch_gain_sum(const VhGainArgs &a, hipStream_t st);  // behind gain_ratio on the same stream
 
 struct vh_mono_params;
 int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters);

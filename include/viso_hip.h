@@ -594,6 +594,57 @@ int32_t vh_group_refit_motion(vh_group *g, const vh_ego_params *e, int32_t recla
 int32_t vh_match_refit_motion(vh_matcher *m, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
                               int32_t *n_updates, int32_t *count);
 
+/* ---- the camera gain over motion inliers (csrc/kernels_gain.hip) -----------------------------------------
+ * Matcher::getGain (reference src/matcher.h:145-148, src/viso.h:104: "given a vector of inliers computes gain factor
+ * between the current and the previous frame"; the reference keeps the body commented out and its helper
+ * Matcher::mean, src/matcher.cpp:347-354, compiled -- the loop is stock libviso2's, parity unpinned; the helper is
+ * pinned by tests/golden/gain_reference.npz).  For one list pm[0, n), index entries idx[0, k) and the previous / current
+ * LEFT images at full resolution (dims = {W, H, bpl}; also under half_resolution: match coordinates are full-resolution):
+ *   gain = 0; num = 0
+ *   for every entry i = idx[j], in order:  skipped if i < 0 or i >= n, or if one of u1p, v1p, u1c, v1c is not finite or
+ *       has a magnitude >= 2^24;
+ *     (up, vp) = the truncated (u1p, v1p); u_min = min(max(up - 3, 0), W - 1), u_max = min(max(up + 3, 0), W - 1), v alike
+ *     mean_prev = Matcher::mean(I_prev, window), mean_curr likewise around (u1c, v1c) in I_cur
+ *     if (mean_prev > 10) { gain += mean_curr / mean_prev; num++; }
+ *   gain = num > 0 ? gain / num : 1
+ * Single precision throughout; the sum runs in the order of idx, and that order is part of the result: gain and num are
+ * bit-identical to the sequential evaluation (the numpy restatement under tests/).  Two rules are tighter than stock, which reads
+ * outside its arguments there: windows are clamped to W - 1 / H - 1 (stock: W / H, one column or row past the image; the
+ * matcher's own coordinates lie 7 px inside, where the rules agree), and stock tests only i < n and no coordinate.
+ *
+ * Stateless (replaces src/matcher.h:148 for n_sets lists in one call): all pointers are host pointers; list s is
+ * pm[offsets[s] .. offsets[s+1]) with the index entries idx[idx_offsets[s] .. idx_offsets[s+1]) and its own image pair at
+ * I_prev / I_cur + s * image_stride_bytes -> gain[n_sets], num[n_sets] (1, 0 for a list without a counted entry).
+ * n_sets == 0 or no index entries at all: VH_OK, nothing is launched and no device is needed.  VH_ERR_UNSUPPORTED: an
+ * image beyond 16384 x 16384, a list of 2^24 or more records, or a launch grid beyond the device's. */
+int32_t vh_gain(int32_t device, int32_t n_sets, const int32_t dims[3], const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride_bytes,
+                const vh_p_match *pm, const int32_t *offsets, const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num);
+/* The images of a handle (the state behind src/matcher.h:148; the reference's Matcher keeps no images either): with
+ * the switch on, every push also copies the pushed full-resolution left image of every row into a u8 plane of the ring
+ * (pitch: W rounded up to 16; VH_RING x streams planes, allocated with the ring at the first push and counted by
+ * vh_group_device_bytes; profile scope "gain_copy", on the detect stream, per sub-batch).  Before the first push only:
+ * VH_ERR_STATE afterwards.  Plain groups, sequence handles and lone matchers.  Off (the default): nothing is allocated,
+ * launched or changed. */
+int32_t vh_group_set_gain(vh_group *g, int32_t on);
+int32_t vh_set_gain(vh_matcher *m, int32_t on);
+/* getGain (src/matcher.h:148) on the lists of the handle's last FLOW or QUAD match call -- exactly those
+ * vh_group_get_matches returns -- over the inlier positions of its current classification (vh_group_motion_inliers,
+ * _mono, or the reclassification of vh_group_refit_motion): lists and positions are on the device already, nothing is
+ * uploaded -> gain[S], num[S]; the call waits once, for that download.  gain = 1, num = 0 for a stream classified with
+ * ok = 0, an empty list, a sequence row without a pair and a list without a counted entry.  VH_ERR_STATE with the switch
+ * off, before a classification of the current lists, after the next push or match, and on stereo lists (they hold no
+ * previous frame).  The first call adds S * (max_matches + 2) floats, counted by vh_group_device_bytes; a refused
+ * allocation is VH_ERR_HIP before any launch and leaves the handle as it was.  Profile scopes: "gain_ratio", "gain_sum". */
+int32_t vh_group_gain(vh_group *g, float *gain, int32_t *num);
+int32_t vh_match_gain(vh_matcher *m, float *gain, int32_t *num);
+/* The same (src/matcher.h:148) over the caller's index lists, which are uploaded: stream s takes
+ * idx[idx_offsets[s] .. idx_offsets[s+1]), positions into the list vh_group_get_matches returns for it (also where that
+ * list was replaced on the host by vh_remove_outliers / vh_bucket_features: the lists then go up as well).  The form for
+ * bucketed or voted index sets and the one Matcher::getGain of viso_hip_matcher.hpp uses.  VH_ERR_STATE with the switch
+ * off, before a match call, after the next push, and on stereo lists. */
+int32_t vh_group_gain_indices(vh_group *g, const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num);
+int32_t vh_match_gain_indices(vh_matcher *m, const int32_t *idx, int32_t k, float *gain, int32_t *num);
+
 /* ---- the steps after matching, pipelined ------------------------------------------------------------- */
 /* What the reference's loop runs between Matcher::matching and the pose -- removeOutliers (the tail of
  * matchFeatures, src/matcher.cpp:108), bucketFeatures (src/viso_stereo.cpp:41-43 -> src/matcher.cpp:140-187)
@@ -998,7 +1049,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place;
  *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
- *  "motion_refit" per vh_group_refit_motion)
+ *  "motion_refit" per vh_group_refit_motion;
+ *  with vh_group_set_gain "gain_copy" per sub-batch of a push, and "gain_ratio", "gain_sum" per vh_group_gain(_indices))
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
 int32_t vh_group_profile_read(vh_group *g, const char *name, double *ms, int64_t *launches);

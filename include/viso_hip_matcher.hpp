@@ -91,7 +91,7 @@ class Matcher {
   };
 
   // constructor (src/matcher.cpp:32-41); `device` selects the GPU of this stream
-  explicit Matcher(parameters param, int32_t device = 0) : outlier_removal(true), param(param), handle(0), device(device) {
+  explicit Matcher(parameters param, int32_t device = 0) : outlier_removal(true), param(param), handle(0), device(device), gain_images(false) {
     static_assert(sizeof(parameters) == sizeof(vh_params), "parameters must mirror vh_params");
     static_assert(sizeof(p_match) == sizeof(vh_p_match) && sizeof(p_match) == 48, "p_match must be 48 bytes");
     vh_params p;
@@ -249,6 +249,29 @@ class Matcher {
     if (param.half_resolution) { I_du_full = duf; I_dv_full = dvf; }
   }
 
+  // Not in the reference (its `parameters` must not grow): keep the pushed left images on the GPU so that getGain has
+  // something to read (vh_set_gain).  Off by default; before the first pushBack, returns false (and says why) otherwise.
+  bool setGainImages(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_gain(handle, on ? 1 : 0);
+    if (rc != VH_OK) report("setGainImages", rc);
+    else gain_images = on;
+    return rc == VH_OK;
+  }
+
+  // src/matcher.h:145-148 (commented out there; stock libviso2's signature): the gain factor between the current and the
+  // previous left image over the matches `inliers` of getMatches() (vh_match_gain_indices).  1 without setGainImages(true),
+  // with fewer than two pushes, without a flow or quad match, or with empty arguments -- as stock returns when it holds no images.
+  float getGain(std::vector<int32_t> inliers) {
+    if (!handle || !gain_images || inliers.empty()) return 1;
+    float gain = 1;
+    int32_t num = 0;
+    const int32_t rc = vh_match_gain_indices(handle, inliers.data(), (int32_t)inliers.size(), &gain, &num);
+    if (rc == VH_ERR_STATE) return 1;
+    if (rc != VH_OK) { report("getGain", rc); return 1; }
+    return gain;
+  }
+
   // The ring buffer's packed feature records {u,v,0,class,d1..d8}
   // (max2p/max2c of the reference, src/matcher.h:252); which = VH_SET_*.
   std::vector<int32_t> getFeatures(int32_t which) {
@@ -277,6 +300,7 @@ class Matcher {
   parameters param;
   vh_matcher *handle;
   int32_t device;
+  bool gain_images;
 };
 
 #endif  // VISO_HIP_MATCHER_HPP
