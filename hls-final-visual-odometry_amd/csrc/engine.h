@@ -3,6 +3,7 @@
 //   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
+//   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -12,6 +13,7 @@
 #include "../../include/viso_hip.h"
 #include "vh_vote.h"
 #include "vh_recon.h"
+#include "engine_lists.h"
 
 #include <algorithm>
 #include <chrono>
@@ -47,6 +49,12 @@ extern thread_local std::string t_last_error;  // (defined in engine.hip)
       return VH_ERR_HIP;                                                                      \
     }                                                                                         \
   } while (0)
+
+// every extern "C" entry on a handle begins with it
+#define ENTER(gq)                                   \
+  if (!(gq)) return VH_ERR_INVALID_ARG;             \
+  { hipError_t e_ = hipSetDevice((gq)->device);     \
+    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
 
 inline int32_t round_up(int32_t x, int32_t m) { return (x + m - 1) / m * m; }
 
@@ -263,42 +271,25 @@ struct InlierTest {
   bool args_ok() const { return params_ok() && (is_mono ? model != nullptr : tr != nullptr); }
 };
 
-inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
-// The arrays of one classification inside one device block: flags | records | positions | tile counts | counts | ok | tr
-struct InlierLayout {
-  size_t o_out, o_src, o_tiles, o_ninl, o_ok, o_tr, bytes;
-  InlierLayout(size_t lists, size_t slots, size_t tiles) {
-    o_out = up256(slots);
-    o_src = o_out + up256(sizeof(vh_p_match) * slots);
-    o_tiles = o_src + up256(sizeof(int32_t) * slots);
-    o_ninl = o_tiles + up256(sizeof(int32_t) * lists * tiles);
-    o_ok = o_ninl + up256(sizeof(int32_t) * lists);
-    o_tr = o_ok + up256(sizeof(int32_t) * lists);
-    bytes = o_tr + up256(sizeof(double) * 6 * lists);
-  }
-};
-
 // the launch grid is lists x tiles workgroups of 256 threads
 inline bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
 
+// The lists as the getters return them once a list was replaced on the host (vh_remove_outliers, vh_bucket_features), staged
+// on the device by Group::stage_host_lists: one arena block, allocated by the first need.
+struct HostLists {
+  vh_p_match *d_pm = nullptr;   // [S][mcap]
+  int32_t *d_cnt = nullptr;     // [S]
+  std::vector<int32_t> h_cnt;   // the replaced lists' counts, alive until the uploads have run
+};
+
 // Motion inliers of the handle's lists (vh_group_motion_inliers; engine_inlier.hip): one arena
 // block, allocated by the first call, cut into the arrays below.  Nothing here exists on a handle that never calls it.
-struct InlierState {
-  uint8_t *d_flags = nullptr;     // [S][mcap]
-  vh_p_match *d_out = nullptr;    // [S][mcap] the inlier records of each list, in list order
-  int32_t *d_src = nullptr;       // [S][mcap] their positions in the list
-  int32_t *d_tiles = nullptr;     // [S][tiles]
-  int32_t *d_ninl = nullptr, *d_ok = nullptr;  // [S]
-  double *d_tr = nullptr;         // [S][6]
+struct InlierState : InlierArrays {      // [S][mcap], [S][tiles], [S], [S][6]
   vh_mono_model *d_model = nullptr;  // [S] a block of its own, allocated by the first mono classification
-  // a second block, allocated only once a list was replaced on the host (vh_remove_outliers, vh_bucket_features): the
-  // lists as the getters return them, [S][mcap] and their counts [S]
-  vh_p_match *d_host_pm = nullptr;
-  int32_t *d_host_cnt = nullptr;
+  HostLists host;                    // its own copy: it must outlive a vh_group_gain_indices that stages other lists
   int32_t tiles = 0;
   bool mono = false;                      // the classification is a mono one
-  bool from_host = false;                 // it read d_host_pm / d_host_cnt (a list was replaced on the host), not the emission's lists
+  bool from_host = false;                 // it read `host` (a list was replaced on the host), not the emission's lists
   bool valid = false, truncated = false;  // a classification exists (of the lists of match call `seq`) / of a truncated list
   int64_t seq = 0;
   std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
@@ -321,14 +312,15 @@ struct GainState {
   float *d_gain = nullptr;      // [S], and behind it int32 num [S]
   float *d_ratio = nullptr;     // [S][mcap] the ratios over the classification's positions
   int32_t *d_idx = nullptr;     // the caller's index lists: idx [idx_cap] | ratio [idx_cap] | offsets [S + 1]; grows
+  float *d_idx_ratio = nullptr;
+  int32_t *d_idx_off = nullptr;
   int64_t idx_cap = 0;
   size_t idx_bytes = 0;
-  vh_p_match *d_host_pm = nullptr;  // [S][mcap] and counts [S]: the lists as the getters return them, once one was replaced on the host
-  int32_t *d_host_cnt = nullptr;
+  HostLists host;               // what the index lists are positions in, once a list was replaced on the host
 };
 
 // The dense stages of a batch (vh_group_post_device_dense; engine_post.hip): one block beside the
-// batch's own, cut into the arrays of one classification over the batch's P lists of `cap` slots (InlierLayout: its tr /
+// batch's own, cut into the arrays of one classification over the batch's P lists of `cap` slots (InlierArrays: its tr /
 // ok arrays hold the refit's results) and, behind them, the gate's arrays, the refit's update counts and the mono models;
 // and the page-locked mirror of what comes down with the batch's results.  Nothing here exists while the mode is 0.
 struct VoteDense {
@@ -346,11 +338,17 @@ struct VoteDense {
   HostBlock<double> h_tr;     // [lists][6]
   HostBlock<vh_mono_model> h_model;
   int32_t h_lists = 0; bool h_with_model = false;
-  // bytes of the block for `lists` lists of `cap` slots
-  static size_t bytes_for(size_t lists, size_t cap, bool model) {
-    const size_t tiles = (cap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
-    return InlierLayout(lists, lists * cap, tiles).bytes + 4 * up256(sizeof(int32_t) * lists) + (model ? up256(sizeof(vh_mono_model) * lists) : 0);
+  // the pointers into a block at `base` for `lists` lists of `cap` slots (null: none, the size only) -> its bytes
+  size_t carve(void *base, size_t lists, size_t cap, bool model) {
+    InlierArrays ia;
+    Carver c = ia.carve(base, lists, lists * cap, (cap + VH_INLIER_TILE - 1) / VH_INLIER_TILE);
+    d_flags = ia.d_flags; d_out = ia.d_out; d_src = ia.d_src; d_tiles = ia.d_tiles; d_ninl = ia.d_ninl;
+    d_ok_refit = ia.d_ok; d_tr_refit = ia.d_tr;
+    d_cnt = c.ptr<int32_t>(lists); d_ok = c.ptr<int32_t>(lists); d_voted = c.ptr<int32_t>(lists); d_nupd = c.ptr<int32_t>(lists);
+    d_model = model ? c.ptr<vh_mono_model>(lists) : nullptr;
+    return c.bytes();
   }
+  static size_t bytes_for(size_t lists, size_t cap, bool model) { return VoteDense().carve(nullptr, lists, cap, model); }
 };
 
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
@@ -521,6 +519,7 @@ struct Group {
   VhMatchArgs role_args() const;
   int32_t sync_all();
   int32_t check_violation();
+  int32_t stage_host_lists(HostLists &h, hipStream_t st, bool &replaced, const vh_p_match *&pm, const int32_t *&counts);
   void release();
   bool alloc_refused();
   template <class T> int32_t dmalloc(T **out, size_t count, bool zero) {
@@ -644,6 +643,10 @@ struct Scope {
 
 // engine.hip
 int32_t check_params(const vh_params *p);
+// -DVH_CHECK builds: aborts when the kernels recorded an index violation in d_check (nullable); the work must have completed
+int32_t report_violation(const uint32_t *d_check);
+// list l of n: counts[l] records from pm + l * stride to dst + l * cap, blocking
+int32_t upload_strided_lists(vh_p_match *dst, int64_t cap, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n);
 int32_t select_device(int32_t device);
 int32_t group_new(const vh_params *p, int32_t device, int32_t S, int32_t mf, int32_t mm, Group **out);
 // engine_api.hip

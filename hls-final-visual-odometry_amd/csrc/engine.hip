@@ -40,16 +40,61 @@ int32_t Group::sync_all() {
 int32_t Group::check_violation() {
 #ifdef VH_CHECK
   if (allocated && sets.check) {
-    uint32_t c[4] = {0, 0, 0, 0};
     VH_HIP(hipDeviceSynchronize());
-    VH_HIP(hipMemcpy(c, sets.check, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[0]) {
-      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
-      fflush(stderr);
-      abort();
-    }
+    return report_violation(sets.check);
   }
 #endif
+  return VH_OK;
+}
+
+int32_t report_violation(const uint32_t *d_check) {
+#ifdef VH_CHECK
+  uint32_t c[4] = {0, 0, 0, 0};
+  if (d_check) VH_HIP(hipMemcpy(c, d_check, sizeof(c), hipMemcpyDeviceToHost));
+  if (c[0]) {
+    fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
+    fflush(stderr);
+    abort();
+  }
+#endif
+  return VH_OK;
+}
+
+int32_t upload_strided_lists(vh_p_match *dst, int64_t cap, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n) {
+  for (int32_t l = 0; l < n; l++)
+    if (counts[l]) VH_HIP(hipMemcpy(dst + (size_t)l * cap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  return VH_OK;
+}
+
+// The lists a classification or a gain reads, on `st` behind the emission: the emission's own, or -- once the getters serve
+// a host-side list for some stream -- all of them staged in `h`: the untouched streams' device lists and the replaced ones
+// (each a subset of the device list it came from: it fits the slot).
+int32_t Group::stage_host_lists(HostLists &h, hipStream_t st, bool &replaced, const vh_p_match *&pm, const int32_t *&counts) {
+  pm = (const vh_p_match *)mt.d_matches; counts = mt.d_match_count;
+  replaced = false;
+  for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
+  if (!replaced) return VH_OK;
+  if (!h.d_pm) {  // one block: a refused allocation leaves nothing behind
+    Carver c;
+    const size_t o_pm = c.take<vh_p_match>((size_t)S * mcap), o_cnt = c.take<int32_t>((size_t)S);
+    uint8_t *d = nullptr;
+    const int32_t rc = dmalloc(&d, c.tight(), false);
+    if (rc) return rc;
+    h.d_pm = (vh_p_match *)(d + o_pm); h.d_cnt = (int32_t *)(d + o_cnt);
+  }
+  h.h_cnt.assign((size_t)S, 0);
+  VH_HIP(hipMemcpyAsync(h.d_cnt, counts, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, st));
+  for (int32_t s = 0; s < S; s++) {
+    vh_p_match *dst = h.d_pm + (size_t)s * mcap;
+    if (!host_filtered[s]) {
+      VH_HIP(hipMemcpyAsync(dst, pm + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)mcap, hipMemcpyDeviceToDevice, st));
+      continue;
+    }
+    h.h_cnt[s] = (int32_t)std::min<size_t>(host_matches[s].size(), (size_t)mcap);
+    if (h.h_cnt[s]) VH_HIP(hipMemcpyAsync(dst, host_matches[s].data(), sizeof(vh_p_match) * (size_t)h.h_cnt[s], hipMemcpyHostToDevice, st));
+    VH_HIP(hipMemcpyAsync(h.d_cnt + s, &h.h_cnt[s], sizeof(int32_t), hipMemcpyHostToDevice, st));
+  }
+  pm = h.d_pm; counts = h.d_cnt;
   return VH_OK;
 }
 
@@ -124,12 +169,11 @@ int32_t Group::ensure(const int32_t d[3]) {
 }
 
 int32_t Group::allocate(const int32_t d[3]) {
-  if (d[0] <= 0 || d[1] <= 0 || d[2] < d[0]) return VH_ERR_INVALID_ARG;
-  if (d[0] > 16384 || d[1] > 16384) return VH_ERR_UNSUPPORTED;
+  int32_t rc = check_dims(d, true);
+  if (rc) return rc;
   // emit_features addresses its patch rows with 24 x 24 -> 32-bit byte offsets from the image base
   if (d[2] >= (1 << 24) || (int64_t)d[2] * d[1] > (1ll << 28)) return VH_ERR_UNSUPPORTED;
-  int32_t rc = setup_geometry(d);
-  if (rc != VH_OK) return rc;
+  if ((rc = setup_geometry(d))) return rc;
   dims[0] = d[0]; dims[1] = d[1]; dims[2] = d[2];
   int64_t c = req_features > 0 ? req_features : std::max<int64_t>(4 * (int64_t)g.nblocks, 64);
   if (c > (1 << VH_MASK_IDX_BITS) - 1) c = (1 << VH_MASK_IDX_BITS) - 1;  // feature indices are packed into VH_MASK_IDX_BITS bits (flow pixel mask)

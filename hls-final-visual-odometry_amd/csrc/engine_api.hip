@@ -6,11 +6,6 @@
 
 namespace vh_engine {
 
-#define ENTER(gq)                                   \
-  if (!(gq)) return VH_ERR_INVALID_ARG;             \
-  { hipError_t e_ = hipSetDevice((gq)->device);     \
-    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
-
 struct Temp {  // transient one-stream group for the stateless entry points
   Group *gq = nullptr;
   ~Temp() { if (gq) { (void)gq->sync_all(); delete gq; } }
@@ -23,6 +18,24 @@ int32_t temp_new(const vh_params *p, int32_t device, int32_t mf, int32_t mm, Tem
   vh_params q = *p;
   q.refinement = 0;
   return group_new(&q, device, 1, mf, mm, &t.gq);
+}
+// The set-up of the entries that search caller-supplied features: a transient group sized for the longest set (with
+// room for as many matches, or none), allocated for dims with a line at least as long as the width, the sets loaded in order.
+struct FeatureLoad { int32_t role; const int32_t *m; int32_t n; };
+static int32_t temp_with_features(const vh_params *p, int32_t device, const int32_t dims[3], bool matches, std::initializer_list<FeatureLoad> sets, Temp &t) {
+  int32_t rc, nmax = 64;
+  for (const FeatureLoad &f : sets) nmax = std::max(nmax, f.n);
+  if ((rc = temp_new(p, device, nmax, matches ? nmax : 1, t))) return rc;
+  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
+  if ((rc = t.gq->ensure(d))) return rc;
+  for (const FeatureLoad &f : sets)
+    if ((rc = t.gq->load_features(f.role, f.m, f.n))) return rc;
+  return VH_OK;
+}
+
+// host_threads < 1: one worker per hardware thread
+static int32_t default_threads(int32_t host_threads) {
+  return host_threads < 1 ? (int32_t)std::max(1u, std::thread::hardware_concurrency()) : host_threads;
 }
 
 // Device work buffer of the stateless estimators: one per device, grow-only, kept between calls (an allocation and its
@@ -67,33 +80,28 @@ template <class Bytes, class Launch>
 static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac_iters, int32_t draws, bool unsupported, const vh_p_match *pm,
                                   const int32_t *offsets, const int32_t *rnd, double *tr, int32_t *ok, int32_t *n_inliers, int32_t *inliers,
                                   Bytes scratch_bytes, Launch launch, void *extra = nullptr, size_t extra_bytes = 0) {
-  if (n_sets < 1 || !offsets || !rnd || !tr || !ok || !n_inliers || ransac_iters < 1) return VH_ERR_INVALID_ARG;
-  if (offsets[0] < 0) return VH_ERR_INVALID_ARG;
-  int64_t nmax = 0;
-  for (int32_t s = 0; s < n_sets; s++) {
-    if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
-    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
-  }
-  const int64_t total = offsets[n_sets], cap = std::max<int64_t>(nmax, 1);
+  ListSpan sp;
+  if (n_sets < 1 || !rnd || !tr || !ok || !n_inliers || ransac_iters < 1 || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
+  const int64_t total = sp.end, cap = std::max<int64_t>(sp.longest, 1);  // (the records go up from record 0)
   if (total > 0 && !pm) return VH_ERR_INVALID_ARG;
   if (unsupported) return VH_ERR_UNSUPPORTED;
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  const size_t b_pm = sizeof(vh_p_match) * (size_t)std::max<int64_t>(total, 1), b_off = sizeof(int32_t) * ((size_t)n_sets + 1);
-  const size_t b_r = sizeof(int32_t) * (size_t)n_sets * ransac_iters * draws, b_ok = sizeof(int32_t) * 2 * (size_t)n_sets, b_inl = sizeof(int32_t) * (size_t)std::max<int64_t>(total, 1);
-  const size_t b_tr = sizeof(double) * 6 * (size_t)n_sets, b_scr = scratch_bytes(cap);
-  auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-  const size_t o_off = up(b_pm), o_r = o_off + up(b_off), o_ok = o_r + up(b_r), o_inl = o_ok + up(b_ok), o_tr = o_inl + up(b_inl), o_scr = o_tr + up(b_tr);
+  const size_t lists = (size_t)n_sets, slots = (size_t)std::max<int64_t>(total, 1);
+  const size_t b_off = sizeof(int32_t) * (lists + 1), b_r = sizeof(int32_t) * lists * ransac_iters * draws, b_tr = sizeof(double) * 6 * lists;
+  Carver c;
+  const size_t o_pm = c.take<vh_p_match>(slots), o_off = c.take<int32_t>(lists + 1), o_r = c.take<int32_t>(lists * ransac_iters * draws);
+  const size_t o_ok = c.take<int32_t>(2 * lists), o_inl = c.take<int32_t>(slots), o_tr = c.take<double>(6 * lists);
+  const size_t o_scr = c.take<uint8_t>(scratch_bytes(cap)), o_extra = extra ? c.take<uint8_t>(extra_bytes) : 0;
   EgoWorkLease lease;
-  const size_t o_extra = o_scr + up(b_scr);
-  VH_HIP(lease.take(device, extra ? o_extra + extra_bytes : o_scr + b_scr));
+  VH_HIP(lease.take(device, c.tight()));
   uint8_t *d = lease.d;
   hipError_t er = hipSuccess;
-  if (total) er = hipMemcpy(d, pm, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice);
+  if (total) er = hipMemcpy(d + o_pm, pm, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice);
   if (er == hipSuccess) er = hipMemcpy(d + o_off, offsets, b_off, hipMemcpyHostToDevice);
   if (er == hipSuccess) er = hipMemcpy(d + o_r, rnd, b_r, hipMemcpyHostToDevice);
   if (er == hipSuccess) {
-    launch((const vh_p_match *)d, (const int32_t *)(d + o_off), (const int32_t *)(d + o_r), d + o_scr, cap, (double *)(d + o_tr), (int32_t *)(d + o_ok),
+    launch((const vh_p_match *)(d + o_pm), (const int32_t *)(d + o_off), (const int32_t *)(d + o_r), d + o_scr, cap, (double *)(d + o_tr), (int32_t *)(d + o_ok),
            (int32_t *)(d + o_inl), extra ? d + o_extra : nullptr);
     er = hipGetLastError();  // (a rejected launch is not reported by the synchronisation)
     if (er == hipSuccess) er = hipDeviceSynchronize();
@@ -110,8 +118,7 @@ static int32_t estimate_stateless(int32_t device, int32_t n_sets, int32_t ransac
 // (arguments validated and the device selected by the caller)
 int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index, const vh_p_match *carry_pm,
                           const vh_track *carry_trk, int32_t ccnt, int64_t carry_serial, bool has_carry, LinkedLists &out) {
-  int32_t cmax = 0;
-  for (int32_t l = 0; l < n_lists; l++) cmax = std::max(cmax, counts[l]);
+  const int32_t cmax = n_lists > 0 ? *std::max_element(counts, counts + n_lists) : 0;
   const int32_t lcap = std::max(std::max(cmax, ccnt), 1), slots = n_lists + 1, cslot = n_lists;
   std::vector<DeviceBlock> &blocks = out.blocks;
   const auto alloc = [&](void **ptr, size_t bytes) { blocks.emplace_back(); const hipError_t e = blocks.back().alloc(bytes); *ptr = blocks.back().p; return e; };
@@ -130,8 +137,8 @@ int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride,
   std::vector<int32_t> hc(counts, counts + n_lists);
   hc.push_back(ccnt);
   VH_HIP(hipMemcpy(d_cnt, hc.data(), sizeof(int32_t) * (size_t)slots, hipMemcpyHostToDevice));
-  for (int32_t l = 0; l < n_lists; l++)
-    if (counts[l]) VH_HIP(hipMemcpy(d_pm + (size_t)l * lcap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  int32_t rc = upload_strided_lists(d_pm, lcap, pm, stride, counts, n_lists);
+  if (rc) return rc;
   VhTrackArgs t{};
   t.pm = d_pm; t.pm_stride = lcap; t.counts = d_cnt; t.count_cap = lcap; t.n_index = n_index;
   t.tab_c = d_tc; t.tab_p = d_tp; t.trk = d_trk; t.trk_stride = lcap; t.slot_count = d_scnt; t.check = d_check;
@@ -152,19 +159,42 @@ int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride,
   vh_launch_track_rank(t, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-#ifdef VH_CHECK
-  {
-    uint32_t c[4] = {0, 0, 0, 0};
-    VH_HIP(hipMemcpy(c, d_check, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[0]) {
-      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
-      fflush(stderr);
-      abort();
-    }
-  }
-#endif
+  if ((rc = report_violation(d_check))) return rc;
   out.d_pm = d_pm; out.d_trk = d_trk; out.d_cnt = d_cnt; out.d_check = d_check; out.lcap = lcap; out.serial0 = t.serial0;
   return VH_OK;
+}
+
+// one search of m1's features among m2's; launch(gq, a) queues it on the transient group's stream, its result in mt.d_best
+template <class Launch>
+static int32_t match_all(const vh_params *p, int32_t device, const int32_t dims[3], const int32_t *m1, int32_t n1, const int32_t *m2, int32_t n2,
+                         int32_t flow, int32_t *best, Launch launch) {
+  if (!p || !dims || (n1 > 0 && !best)) return VH_ERR_INVALID_ARG;
+  Temp t;
+  int32_t rc;
+  if ((rc = temp_with_features(p, device, dims, false, {{VH_SET_1C, m1, n1}, {VH_SET_1P, m2, n2}}, t))) return rc;
+  Group *gq = t.gq;
+  VhMatchArgs a = gq->match_args(VH_METHOD_FLOW);
+  a.npass = 1; a.pass[0] = {VH_SET_1C, VH_SET_1P, flow ? 1 : 0, 0};
+  launch(gq, a);
+  VH_HIP(hipGetLastError());
+  if (n1) VH_HIP(hipMemcpyAsync(best, gq->mt.d_best, sizeof(int32_t) * (size_t)n1, hipMemcpyDeviceToHost, gq->stream));
+  VH_HIP(hipStreamSynchronize(gq->stream));
+  return VH_OK;
+}
+
+// Matcher::matching on caller-supplied features; ranges (nullable): with use_prior = true inside them (kernels_ranged.hip)
+static int32_t match_stateless(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, const int32_t *m1p, int32_t n1p,
+                               const int32_t *m2p, int32_t n2p, const int32_t *m1c, int32_t n1c, const int32_t *m2c, int32_t n2c,
+                               const float *ranges, vh_p_match *out, int32_t cap, int32_t *n) {
+  if (!p || !dims || !n) return VH_ERR_INVALID_ARG;
+  if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
+  Temp t;
+  int32_t rc;
+  if ((rc = temp_with_features(p, device, dims, true, {{VH_SET_1P, m1p, n1p}, {VH_SET_2P, m2p, n2p}, {VH_SET_1C, m1c, n1c}, {VH_SET_2C, m2c, n2c}}, t))) return rc;
+  Group *gq = t.gq;
+  if (ranges && (rc = gq->load_ranges(ranges))) return rc;
+  if ((rc = gq->match(method, nullptr, ranges != nullptr))) return rc;
+  return gq->get_matches(0, out, cap, n);
 }
 
 }  // namespace vh_engine
@@ -317,10 +347,9 @@ int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32
 }
 int32_t vh_prior_statistics(const vh_params *p, const int32_t dims[3], int32_t method, const vh_p_match *pm, int32_t n, float *ranges) {
   if (!p || !dims || !ranges || n < 0 || (n > 0 && !pm) || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
-  const int32_t rc = check_params(p);
+  int32_t rc = check_params(p);
   if (rc) return rc;
-  if (dims[0] <= 0 || dims[1] <= 0) return VH_ERR_INVALID_ARG;
-  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  if ((rc = check_dims(dims, false))) return rc;
   return prior_statistics(*p, dims, method, pm, n, ranges);
 }
 // The statistics of n_lists lists at once on the device (kernels_stats.hip), list l = pm[l * stride .. + counts[l]):
@@ -331,14 +360,10 @@ int32_t vh_prior_statistics_device(const vh_params *p, int32_t device, const int
   if (!p || !dims || !ranges || !counts || n_lists < 1 || stride < 0 || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
   int32_t rc = check_params(p);
   if (rc) return rc;
-  if (dims[0] <= 0 || dims[1] <= 0) return VH_ERR_INVALID_ARG;
-  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
-  int32_t cap = 1;
-  for (int32_t l = 0; l < n_lists; l++) {
-    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
-    if (counts[l] > 0 && !pm) return VH_ERR_INVALID_ARG;
-    cap = std::max(cap, counts[l]);
-  }
+  if ((rc = check_dims(dims, false))) return rc;
+  int32_t cap = 0;
+  if (check_counts(counts, n_lists, stride, cap) || (cap > 0 && !pm)) return VH_ERR_INVALID_ARG;
+  cap = std::max(cap, 1);
   if ((rc = select_device(device))) return rc;
   const float bs = (float)p->match_binsize;
   VhStatsArgs sa{};
@@ -350,8 +375,7 @@ int32_t vh_prior_statistics_device(const vh_params *p, int32_t device, const int
   VH_HIP(b_cnt.alloc(sizeof(int32_t) * 2 * (size_t)n_lists));  // counts, then the error flags
   VH_HIP(b_out.alloc(sizeof(float) * per * (size_t)n_lists));
   struct { vh_p_match *src; int32_t *cnt; float *out; } gd{b_src.as<vh_p_match>(), b_cnt.as<int32_t>(), b_out.as<float>()};
-  for (int32_t l = 0; l < n_lists; l++)
-    if (counts[l]) VH_HIP(hipMemcpy(gd.src + (size_t)l * cap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  if ((rc = upload_strided_lists(gd.src, cap, pm, stride, counts, n_lists))) return rc;
   VH_HIP(hipMemcpy(gd.cnt, counts, sizeof(int32_t) * (size_t)n_lists, hipMemcpyHostToDevice));
   VH_HIP(hipMemset(gd.cnt + n_lists, 0, sizeof(int32_t) * (size_t)n_lists));
   sa.pm = gd.src; sa.pm_stride = cap; sa.counts = gd.cnt; sa.status = nullptr; sa.count_stride = 1; sa.count_cap = cap;
@@ -409,12 +433,8 @@ void vh_track_carry_free(vh_track_carry *c) { delete c; }
 int32_t vh_link_tracks(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t n_index,
                        const vh_track_carry *carry_in, vh_track_carry **carry_out, vh_track *out) {
   if (carry_out) *carry_out = nullptr;
-  if (n_lists < 1 || !counts || stride < 0 || n_index < 1) return VH_ERR_INVALID_ARG;
   int32_t cmax = 0;
-  for (int32_t l = 0; l < n_lists; l++) {
-    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
-    cmax = std::max(cmax, counts[l]);
-  }
+  if (n_lists < 1 || stride < 0 || n_index < 1 || check_counts(counts, n_lists, stride, cmax)) return VH_ERR_INVALID_ARG;
   if (cmax > 0 && (!pm || !out)) return VH_ERR_INVALID_ARG;
   if (cmax > (int32_t)VH_TRACK_POS_MASK || (int64_t)n_lists + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;  // (positions share a table entry with the epoch; rows are a grid dimension)
   const int32_t rc = select_device(device);
@@ -579,8 +599,7 @@ int32_t vh_remove_outliers(vh_matcher *m) {
 }
 int32_t vh_group_remove_outliers(vh_group *g, int32_t host_threads) {
   Group *gq = (Group *)g; ENTER(gq);
-  if (host_threads < 1) host_threads = (int32_t)std::max(1u, std::thread::hardware_concurrency());
-  return gq->remove_outliers(0, gq->S, host_threads);
+  return gq->remove_outliers(0, gq->S, default_threads(host_threads));
 }
 int32_t vh_get_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n) {
   Group *gq = (Group *)m; ENTER(gq);
@@ -653,15 +672,13 @@ int32_t vh_group_post_finish(vh_group *g, int32_t age, int32_t max_features, flo
                              const vh_ego_params *e, const int32_t *rand3, double *tr, int32_t *ok, int32_t *n_inliers,
                              vh_p_match *bucketed, int32_t cap_per_stream, int32_t *counts, double *host_ms) {
   Group *gq = (Group *)g; ENTER(gq);
-  if (host_threads < 1) host_threads = (int32_t)std::max(1u, std::thread::hardware_concurrency());
-  return gq->post_finish(age, max_features, bucket_width, bucket_height, host_threads, e, rand3, nullptr, nullptr, tr, ok, n_inliers, bucketed, cap_per_stream, counts, host_ms);
+  return gq->post_finish(age, max_features, bucket_width, bucket_height, default_threads(host_threads), e, rand3, nullptr, nullptr, tr, ok, n_inliers, bucketed, cap_per_stream, counts, host_ms);
 }
 int32_t vh_group_post_finish_mono(vh_group *g, int32_t age, int32_t max_features, float bucket_width, float bucket_height, int32_t host_threads,
                                   const vh_mono_params *e, const int32_t *rand8, double *tr, int32_t *ok, int32_t *n_inliers,
                                   vh_p_match *bucketed, int32_t cap_per_stream, int32_t *counts, double *host_ms) {
   Group *gq = (Group *)g; ENTER(gq);
-  if (host_threads < 1) host_threads = (int32_t)std::max(1u, std::thread::hardware_concurrency());
-  return gq->post_finish(age, max_features, bucket_width, bucket_height, host_threads, nullptr, nullptr, e, rand8, tr, ok, n_inliers, bucketed, cap_per_stream, counts, host_ms);
+  return gq->post_finish(age, max_features, bucket_width, bucket_height, default_threads(host_threads), nullptr, nullptr, e, rand8, tr, ok, n_inliers, bucketed, cap_per_stream, counts, host_ms);
 }
 
 int32_t vh_group_post_device_config(vh_group *g, int32_t steps_per_batch, int32_t batches, int32_t lanes_per_wave) {
@@ -737,21 +754,17 @@ int32_t vh_filters(int32_t device, const uint8_t *I, int32_t bpl, int32_t H, uin
   int32_t rc = select_device(device);
   if (rc) return rc;
   const size_t n = (size_t)bpl * H;
-  uint8_t *d = nullptr;
-  VH_HIP(hipMalloc((void **)&d, n * 7));
-  uint8_t *dI = d, *ddu = d + n, *ddv = d + 2 * n;
+  DeviceBlock blk;
+  VH_HIP(blk.alloc(n * 7));
+  uint8_t *d = blk.as<uint8_t>(), *dI = d, *ddu = d + n, *ddv = d + 2 * n;
   int16_t *df1 = (int16_t *)(d + 3 * n), *df2 = (int16_t *)(d + 5 * n);
-  hipError_t e = hipMemcpy(dI, I, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    vh_launch_planes(dI, bpl, H, ddu, ddv, df1, df2, nullptr);
-    e = hipDeviceSynchronize();
-  }
-  if (e == hipSuccess && du) e = hipMemcpy(du, ddu, n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && dv) e = hipMemcpy(dv, ddv, n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && f1) e = hipMemcpy(f1, df1, 2 * n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && f2) e = hipMemcpy(f2, df2, 2 * n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) { t_last_error = hipGetErrorString(e); return VH_ERR_HIP; }
+  VH_HIP(hipMemcpy(dI, I, n, hipMemcpyHostToDevice));
+  vh_launch_planes(dI, bpl, H, ddu, ddv, df1, df2, nullptr);
+  VH_HIP(hipDeviceSynchronize());
+  if (du) VH_HIP(hipMemcpy(du, ddu, n, hipMemcpyDeviceToHost));
+  if (dv) VH_HIP(hipMemcpy(dv, ddv, n, hipMemcpyDeviceToHost));
+  if (f1) VH_HIP(hipMemcpy(f1, df1, 2 * n, hipMemcpyDeviceToHost));
+  if (f2) VH_HIP(hipMemcpy(f2, df2, 2 * n, hipMemcpyDeviceToHost));
   return VH_OK;
 }
 
@@ -773,15 +786,14 @@ int32_t vh_compute_features(const vh_params *p, int32_t device, const uint8_t *I
     if (du || dv) {  // I_du / I_dv at matching resolution (matcher.cpp:596-600, :606-612)
       const VhGeom &g = t.gq->g;
       const size_t np = (size_t)g.bplm * g.Hm;
-      uint8_t *d = nullptr;
-      VH_HIP(hipMalloc((void **)&d, 2 * np));
+      DeviceBlock blk;
+      VH_HIP(blk.alloc(2 * np));
+      uint8_t *d = blk.as<uint8_t>();
       const uint8_t *src = p->half_resolution ? t.gq->det.d_half : t.gq->stg.d_stage[0];
       vh_launch_planes(src, g.bplm, g.Hm, d, d + np, nullptr, nullptr, t.gq->stream);
-      hipError_t e = hipStreamSynchronize(t.gq->stream);
-      if (e == hipSuccess && du) e = hipMemcpy(du, d, np, hipMemcpyDeviceToHost);
-      if (e == hipSuccess && dv) e = hipMemcpy(dv, d + np, np, hipMemcpyDeviceToHost);
-      (void)hipFree(d);
-      if (e != hipSuccess) { t_last_error = hipGetErrorString(e); return VH_ERR_HIP; }
+      VH_HIP(hipStreamSynchronize(t.gq->stream));
+      if (du) VH_HIP(hipMemcpy(du, d, np, hipMemcpyDeviceToHost));
+      if (dv) VH_HIP(hipMemcpy(dv, d + np, np, hipMemcpyDeviceToHost));
     }
   }
   if (p->multi_stage) {  // sparse set (matcher.cpp:621-628)
@@ -805,10 +817,7 @@ int32_t vh_create_index(const vh_params *p, int32_t device, const int32_t dims[3
   if (!p || !dims || !bin_start || (n > 0 && !list)) return VH_ERR_INVALID_ARG;
   Temp t;
   int32_t rc;
-  if ((rc = temp_new(p, device, std::max(n, 64), 1, t))) return rc;
-  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
-  if ((rc = t.gq->ensure(d))) return rc;
-  if ((rc = t.gq->load_features(VH_SET_1C, m, n))) return rc;
+  if ((rc = temp_with_features(p, device, dims, false, {{VH_SET_1C, m, n}}, t))) return rc;
   Group *gq = t.gq;
   int32_t *d_bs = nullptr, *d_list = nullptr;
   if ((rc = gq->dmalloc(&d_bs, (size_t)gq->sets.nbins + 1, false))) return rc;
@@ -822,84 +831,25 @@ int32_t vh_create_index(const vh_params *p, int32_t device, const int32_t dims[3
 
 int32_t vh_match_all(const vh_params *p, int32_t device, const int32_t dims[3], const int32_t *m1, int32_t n1,
                      const int32_t *m2, int32_t n2, int32_t flow, int32_t *best) {
-  if (!p || !dims || (n1 > 0 && !best)) return VH_ERR_INVALID_ARG;
-  Temp t;
-  int32_t rc;
-  if ((rc = temp_new(p, device, std::max(std::max(n1, n2), 64), 1, t))) return rc;
-  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
-  Group *gq = t.gq;
-  if ((rc = gq->ensure(d))) return rc;
-  if ((rc = gq->load_features(VH_SET_1C, m1, n1))) return rc;
-  if ((rc = gq->load_features(VH_SET_1P, m2, n2))) return rc;
-  VhMatchArgs a = gq->match_args(VH_METHOD_FLOW);
-  a.npass = 1; a.pass[0] = {VH_SET_1C, VH_SET_1P, flow ? 1 : 0, 0};
-  vh_launch_match(gq->sets, a, gq->mt.d_best, gq->mt.d_redo, gq->force_mode == 0 ? 0 : 1, 0, 0, gq->stream);
-  VH_HIP(hipGetLastError());
-  if (n1) VH_HIP(hipMemcpyAsync(best, gq->mt.d_best, sizeof(int32_t) * (size_t)n1, hipMemcpyDeviceToHost, gq->stream));
-  VH_HIP(hipStreamSynchronize(gq->stream));
-  return VH_OK;
+  return match_all(p, device, dims, m1, n1, m2, n2, flow, best, [](Group *gq, const VhMatchArgs &a) {
+    vh_launch_match(gq->sets, a, gq->mt.d_best, gq->mt.d_redo, gq->force_mode == 0 ? 0 : 1, 0, 0, gq->stream); });
 }
-
 int32_t vh_match_all_prior(const vh_params *p, int32_t device, const int32_t dims[3], const int32_t *m1, int32_t n1,
                            const int32_t *m2, int32_t n2, int32_t flow, double u_, double v_, int32_t *best) {
-  if (!p || !dims || (n1 > 0 && !best)) return VH_ERR_INVALID_ARG;
-  Temp t;
-  int32_t rc;
-  if ((rc = temp_new(p, device, std::max(std::max(n1, n2), 64), 1, t))) return rc;
-  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
-  Group *gq = t.gq;
-  if ((rc = gq->ensure(d))) return rc;
-  if ((rc = gq->load_features(VH_SET_1C, m1, n1))) return rc;
-  if ((rc = gq->load_features(VH_SET_1P, m2, n2))) return rc;
-  VhMatchArgs a = gq->match_args(VH_METHOD_FLOW);
-  a.npass = 1; a.pass[0] = {VH_SET_1C, VH_SET_1P, flow ? 1 : 0, 0};
-  vh_launch_match_prior(gq->sets, a, u_, v_, gq->mt.d_best, gq->stream);
-  VH_HIP(hipGetLastError());
-  if (n1) VH_HIP(hipMemcpyAsync(best, gq->mt.d_best, sizeof(int32_t) * (size_t)n1, hipMemcpyDeviceToHost, gq->stream));
-  VH_HIP(hipStreamSynchronize(gq->stream));
-  return VH_OK;
+  return match_all(p, device, dims, m1, n1, m2, n2, flow, best, [&](Group *gq, const VhMatchArgs &a) {
+    vh_launch_match_prior(gq->sets, a, u_, v_, gq->mt.d_best, gq->stream); });
 }
 
 int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, const int32_t *m1p,
                  int32_t n1p, const int32_t *m2p, int32_t n2p, const int32_t *m1c, int32_t n1c,
                  const int32_t *m2c, int32_t n2c, vh_p_match *out, int32_t cap, int32_t *n) {
-  if (!p || !dims || !n) return VH_ERR_INVALID_ARG;
-  if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
-  Temp t;
-  int32_t rc;
-  const int32_t nmax = std::max(std::max(n1p, n2p), std::max(n1c, n2c));
-  if ((rc = temp_new(p, device, std::max(nmax, 64), std::max(nmax, 64), t))) return rc;
-  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
-  Group *gq = t.gq;
-  if ((rc = gq->ensure(d))) return rc;
-  if ((rc = gq->load_features(VH_SET_1P, m1p, n1p))) return rc;
-  if ((rc = gq->load_features(VH_SET_2P, m2p, n2p))) return rc;
-  if ((rc = gq->load_features(VH_SET_1C, m1c, n1c))) return rc;
-  if ((rc = gq->load_features(VH_SET_2C, m2c, n2c))) return rc;
-  if ((rc = gq->match(method))) return rc;
-  return gq->get_matches(0, out, cap, n);
+  return match_stateless(p, device, dims, method, m1p, n1p, m2p, n2p, m1c, n1c, m2c, n2c, nullptr, out, cap, n);
 }
-
-// Matcher::matching with use_prior = true on caller-supplied features and ranges (kernels_ranged.hip)
 int32_t vh_match_ranged(const vh_params *p, int32_t device, const int32_t dims[3], int32_t method, const int32_t *m1p,
                         int32_t n1p, const int32_t *m2p, int32_t n2p, const int32_t *m1c, int32_t n1c,
                         const int32_t *m2c, int32_t n2c, const float *ranges, vh_p_match *out, int32_t cap, int32_t *n) {
-  if (!p || !dims || !n || !ranges) return VH_ERR_INVALID_ARG;
-  if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
-  Temp t;
-  int32_t rc;
-  const int32_t nmax = std::max(std::max(n1p, n2p), std::max(n1c, n2c));
-  if ((rc = temp_new(p, device, std::max(nmax, 64), std::max(nmax, 64), t))) return rc;
-  const int32_t d[3] = {dims[0], dims[1], std::max(dims[2], dims[0])};
-  Group *gq = t.gq;
-  if ((rc = gq->ensure(d))) return rc;
-  if ((rc = gq->load_features(VH_SET_1P, m1p, n1p))) return rc;
-  if ((rc = gq->load_features(VH_SET_2P, m2p, n2p))) return rc;
-  if ((rc = gq->load_features(VH_SET_1C, m1c, n1c))) return rc;
-  if ((rc = gq->load_features(VH_SET_2C, m2c, n2c))) return rc;
-  if ((rc = gq->load_ranges(ranges))) return rc;
-  if ((rc = gq->match(method, nullptr, true))) return rc;
-  return gq->get_matches(0, out, cap, n);
+  if (!ranges) return VH_ERR_INVALID_ARG;
+  return match_stateless(p, device, dims, method, m1p, n1p, m2p, n2p, m1c, n1c, m2c, n2c, ranges, out, cap, n);
 }
 
 // Matcher::refinement on caller-owned records (kernels_refine.hip: the hops of the stateful path, same device code)
@@ -908,8 +858,7 @@ int32_t vh_refine_matches(const vh_params *p, int32_t device, int32_t method, co
   if (!p || !dims || !n_out || n < 0 || (n > 0 && !pm) || method < 0 || method > 2) return VH_ERR_INVALID_ARG;
   int32_t rc = check_params(p);
   if (rc) return rc;
-  if (dims[0] <= 0 || dims[1] <= 0 || dims[2] < dims[0]) return VH_ERR_INVALID_ARG;
-  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
+  if ((rc = check_dims(dims, true))) return rc;
   const uint8_t *img[4] = {I1p, I2p, I1c, I2c};
   const bool need[4] = {method != VH_METHOD_STEREO, method == VH_METHOD_QUAD, true, method != VH_METHOD_FLOW};
   for (int k = 0; k < 4; k++) if (need[k] && !img[k]) return VH_ERR_INVALID_ARG;
@@ -922,32 +871,36 @@ int32_t vh_refine_matches(const vh_params *p, int32_t device, int32_t method, co
   rf.pitch = round_up(dims[0], 16);
   rf.plane = (int64_t)rf.pitch * dims[1];
   rf.mode = p->refinement == 2 ? 2 : 1;
-  const size_t isz = (size_t)dims[2] * dims[1], ialloc = (isz + 255) / 256 * 256;
-  const size_t bytes = 4 * ialloc + 8 * (size_t)rf.plane + sizeof(vh_p_match) * (size_t)n + sizeof(int32_t) * (size_t)n;
-  uint8_t *d = nullptr;
-  VH_HIP(hipMalloc((void **)&d, bytes));
-  rf.du = d + 4 * ialloc; rf.dv = rf.du + 4 * rf.plane;
-  vh_p_match *dpm = (vh_p_match *)(rf.dv + 4 * rf.plane);
-  int32_t *dkeep = (int32_t *)(dpm + n);
-  hipError_t e = hipSuccess;
-  for (int k = 0; k < 4 && e == hipSuccess; k++) {
+  const size_t isz = (size_t)dims[2] * dims[1];
+  Carver c;  // the four images | du | dv (four planes each) | the records | their keep flags
+  size_t o_img[4];
+  for (int k = 0; k < 4; k++) o_img[k] = c.take<uint8_t>(isz);
+  const size_t o_du = c.take<uint8_t>(4 * (size_t)rf.plane), o_dv = c.take<uint8_t>(4 * (size_t)rf.plane);
+  const size_t o_pm = c.take<vh_p_match>((size_t)n), o_keep = c.take<int32_t>((size_t)n);
+  DeviceBlock blk;
+  VH_HIP(blk.alloc(c.bytes()));
+  uint8_t *d = blk.as<uint8_t>();
+  rf.du = d + o_du; rf.dv = d + o_dv;
+  vh_p_match *dpm = (vh_p_match *)(d + o_pm);
+  int32_t *dkeep = (int32_t *)(d + o_keep);
+  for (int k = 0; k < 4; k++) {
     if (!need[k]) continue;
-    e = hipMemcpy(d + k * ialloc, img[k], isz, hipMemcpyHostToDevice);
+    VH_HIP(hipMemcpy(d + o_img[k], img[k], isz, hipMemcpyHostToDevice));
     VhImages im{};
-    im.base[0] = d + k * ialloc; im.stride = (int64_t)isz; im.ncam = 1; im.S = 1; im.S_total = 1;
+    im.base[0] = d + o_img[k]; im.stride = (int64_t)isz; im.ncam = 1; im.S = 1; im.S_total = 1;
     VhRefine rk = rf;  // planes of role k: set 0 of this launch
     rk.du += k * rf.plane; rk.dv += k * rf.plane;
-    if (e == hipSuccess) { vh_launch_refine_planes(im, rk, nullptr); e = hipGetLastError(); }
+    vh_launch_refine_planes(im, rk, nullptr);
+    VH_HIP(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipMemcpy(dpm, pm, sizeof(vh_p_match) * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) { vh_launch_refine_records(rf, method, dpm, n, dkeep, nullptr); e = hipGetLastError(); }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
+  VH_HIP(hipMemcpy(dpm, pm, sizeof(vh_p_match) * (size_t)n, hipMemcpyHostToDevice));
+  vh_launch_refine_records(rf, method, dpm, n, dkeep, nullptr);
+  VH_HIP(hipGetLastError());
+  VH_HIP(hipDeviceSynchronize());
   std::vector<vh_p_match> out((size_t)n);
   std::vector<int32_t> keep((size_t)n);
-  if (e == hipSuccess) e = hipMemcpy(out.data(), dpm, sizeof(vh_p_match) * (size_t)n, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(keep.data(), dkeep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) { t_last_error = hipGetErrorString(e); return VH_ERR_HIP; }
+  VH_HIP(hipMemcpy(out.data(), dpm, sizeof(vh_p_match) * (size_t)n, hipMemcpyDeviceToHost));
+  VH_HIP(hipMemcpy(keep.data(), dkeep, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
   int32_t k = 0;
   for (int32_t i = 0; i < n; i++) if (keep[i]) pm[k++] = out[i];
   *n_out = k;
@@ -963,12 +916,9 @@ int32_t vh_remove_outliers_device(int32_t device, int32_t n_lists, const vh_p_ma
                                   int32_t *n_triangles, float *sweep_ms) {
   if (n_lists < 1 || !counts || !out_counts || out_cap < 0 || (out_cap > 0 && !out) || stride < 0) return VH_ERR_INVALID_ARG;
   if (max_features >= 1 && (!(bw >= 1) || !(bh >= 1))) return VH_ERR_INVALID_ARG;
-  int32_t cap = 4;
-  for (int32_t l = 0; l < n_lists; l++) {
-    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
-    cap = std::max(cap, counts[l]);
-  }
-  if (cap > 1 && !pm) return VH_ERR_INVALID_ARG;
+  int32_t cap = 0;
+  if (check_counts(counts, n_lists, stride, cap) || !pm) return VH_ERR_INVALID_ARG;
+  cap = std::max(cap, 4);
   if (cap > VH_VOTE_LIST_MAX) return VH_ERR_UNSUPPORTED;  // (16-bit hull links; the sweep's angular hash has VH_VOTE_HASH_MAX slots in LDS)
   const int32_t rc = select_device(device);
   if (rc) return rc;
@@ -993,8 +943,8 @@ int32_t vh_remove_outliers_device(int32_t device, int32_t n_lists, const vh_p_ma
   VH_HIP(b_src.alloc(sizeof(vh_p_match) * (size_t)n_lists * cap));
   VH_HIP(b_cnt.alloc(sizeof(int32_t) * (size_t)n_lists));
   vh_p_match *src = b_src.as<vh_p_match>();
-  for (int32_t l = 0; l < n_lists; l++)
-    if (counts[l]) VH_HIP(hipMemcpy(src + (size_t)l * cap, pm + (size_t)l * stride, sizeof(vh_p_match) * (size_t)counts[l], hipMemcpyHostToDevice));
+  const int32_t ru = upload_strided_lists(src, cap, pm, stride, counts, n_lists);
+  if (ru) return ru;
   VH_HIP(hipMemcpy(b_cnt.p, counts, sizeof(int32_t) * (size_t)n_lists, hipMemcpyHostToDevice));
   VH_HIP(ev0.create(hipEventDefault)); VH_HIP(ev1.create(hipEventDefault));
   hipEvent_t ev[2] = {ev0, ev1};

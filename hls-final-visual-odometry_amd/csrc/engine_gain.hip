@@ -24,14 +24,10 @@ int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float 
   if (!gain_on || !allocated || failed || (last_method != VH_METHOD_FLOW && last_method != VH_METHOD_QUAD)) return VH_ERR_STATE;
   if (by_inliers && !inliers_current()) return VH_ERR_STATE;
   int64_t total = 0, kmax = mcap;
+  ListSpan sp;
   if (!by_inliers) {
-    if (idx_offsets[0] < 0) return VH_ERR_INVALID_ARG;
-    kmax = 0;
-    for (int32_t s = 0; s < S; s++) {
-      if (idx_offsets[s + 1] < idx_offsets[s]) return VH_ERR_INVALID_ARG;
-      kmax = std::max<int64_t>(kmax, idx_offsets[s + 1] - idx_offsets[s]);
-    }
-    total = (int64_t)idx_offsets[S] - idx_offsets[0];
+    if (check_offsets(idx_offsets, S, sp)) return VH_ERR_INVALID_ARG;
+    kmax = sp.longest; total = sp.total;
     if (total > 0 && !idx) return VH_ERR_INVALID_ARG;
   }
   const int64_t tiles = (kmax + VH_GAIN_TILE - 1) / VH_GAIN_TILE;
@@ -43,53 +39,32 @@ int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float 
   if (by_inliers && !gn.d_ratio && (rc = dmalloc(&gn.d_ratio, (size_t)S * mcap, false))) return rc;
   if (!by_inliers && gn.idx_cap < total) {  // idx | ratio | offsets; grows (the work on the old block has completed: every call waits)
     const int64_t want = total + total / 4;
-    const size_t b_idx = up256(sizeof(int32_t) * (size_t)want), bytes = 2 * b_idx + sizeof(int32_t) * ((size_t)S + 1);
+    Carver c;
+    const size_t o_idx = c.take<int32_t>((size_t)want), o_ratio = c.take<float>((size_t)want), o_off = c.take<int32_t>((size_t)S + 1);
     uint8_t *d = nullptr;
-    if ((rc = dmalloc(&d, bytes, false))) return rc;
+    if ((rc = dmalloc(&d, c.tight(), false))) return rc;
     if (gn.d_idx) { dfree(gn.d_idx); device_bytes -= (int64_t)gn.idx_bytes; }
-    gn.d_idx = (int32_t *)d; gn.idx_cap = want; gn.idx_bytes = bytes;
+    gn.d_idx = (int32_t *)(d + o_idx); gn.d_idx_ratio = (float *)(d + o_ratio); gn.d_idx_off = (int32_t *)(d + o_off);
+    gn.idx_cap = want; gn.idx_bytes = c.tight();
   }
   hipStream_t ps = post_stream;
   VhGainArgs a{};
   a.pm = (const vh_p_match *)mt.d_matches; a.pm_stride = mcap; a.counts = mt.d_match_count; a.count_cap = mcap;
-  std::vector<int32_t> host_cnt, off;
+  std::vector<int32_t> off;
   if (by_inliers) {
-    if (inl.from_host) { a.pm = inl.d_host_pm; a.counts = inl.d_host_cnt; }  // the lists the classification read
+    if (inl.from_host) { a.pm = inl.host.d_pm; a.counts = inl.host.d_cnt; }  // the lists the classification read
     a.idx = inl.d_src; a.idx_stride = mcap; a.idx_counts = inl.d_ninl; a.idx_cap = mcap;
     a.ok = inl.d_ok;
     a.ratio = gn.d_ratio;
   } else {
     bool replaced = false;  // the getters serve a host-side list for some stream: the positions are positions in that list
-    for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
-    if (replaced && !gn.d_host_pm) {
-      uint8_t *d = nullptr;
-      const size_t b_pm = up256(sizeof(vh_p_match) * (size_t)S * mcap);
-      if ((rc = dmalloc(&d, b_pm + sizeof(int32_t) * (size_t)S, false))) return rc;
-      gn.d_host_pm = (vh_p_match *)d; gn.d_host_cnt = (int32_t *)(d + b_pm);
-    }
-    if (replaced) {  // (a replaced list is a subset of the device list it came from: it fits the slot)
-      host_cnt.assign((size_t)S, 0);
-      VH_HIP(hipMemcpyAsync(gn.d_host_cnt, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, ps));
-      for (int32_t s = 0; s < S; s++) {
-        vh_p_match *dst = gn.d_host_pm + (size_t)s * mcap;
-        if (!host_filtered[s]) {
-          VH_HIP(hipMemcpyAsync(dst, a.pm + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)mcap, hipMemcpyDeviceToDevice, ps));
-          continue;
-        }
-        host_cnt[s] = (int32_t)std::min<size_t>(host_matches[s].size(), (size_t)mcap);
-        if (host_cnt[s]) VH_HIP(hipMemcpyAsync(dst, host_matches[s].data(), sizeof(vh_p_match) * (size_t)host_cnt[s], hipMemcpyHostToDevice, ps));
-        VH_HIP(hipMemcpyAsync(gn.d_host_cnt + s, &host_cnt[s], sizeof(int32_t), hipMemcpyHostToDevice, ps));
-      }
-      a.pm = gn.d_host_pm; a.counts = gn.d_host_cnt;
-    }
-    const size_t b_idx = up256(sizeof(int32_t) * (size_t)gn.idx_cap);
-    int32_t *d_off = (int32_t *)((uint8_t *)gn.d_idx + 2 * b_idx);
+    if ((rc = stage_host_lists(gn.host, ps, replaced, a.pm, a.counts))) return rc;
     off.resize((size_t)S + 1);
     for (int32_t s = 0; s <= S; s++) off[s] = idx_offsets[s] - idx_offsets[0];
-    VH_HIP(hipMemcpyAsync(gn.d_idx, idx + idx_offsets[0], sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, ps));
-    VH_HIP(hipMemcpyAsync(d_off, off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, ps));
-    a.idx = gn.d_idx; a.idx_offsets = d_off;
-    a.ratio = (float *)((uint8_t *)gn.d_idx + b_idx);
+    VH_HIP(hipMemcpyAsync(gn.d_idx, idx + sp.first, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, ps));
+    VH_HIP(hipMemcpyAsync(gn.d_idx_off, off.data(), sizeof(int32_t) * ((size_t)S + 1), hipMemcpyHostToDevice, ps));
+    a.idx = gn.d_idx; a.idx_offsets = gn.d_idx_off;
+    a.ratio = gn.d_idx_ratio;
   }
   a.n_lists = S; a.tiles_per_list = (int32_t)tiles;
   a.planes_prev = a.planes_cur = gn.d_planes; a.plane = gn.plane; a.pitch = gn.pitch; a.W = dims[0]; a.H = dims[1];
@@ -110,11 +85,6 @@ int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float 
 
 using namespace vh_engine;
 
-#define ENTER(gq)                                   \
-  if (!(gq)) return VH_ERR_INVALID_ARG;             \
-  { hipError_t e_ = hipSetDevice((gq)->device);     \
-    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
-
 // The stateless gain: validation, one device block (records | offsets | index entries | their offsets | ratios | gain,
 // num | check words | the image planes, repacked to the pitch of a handle's), two launches, one download.
 static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dims, const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride,
@@ -122,16 +92,13 @@ static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dim
                               int32_t *num) {
   if (n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
-  if (!dims || !offsets || !idx_offsets || !gain || !num || offsets[0] < 0 || idx_offsets[0] < 0) return VH_ERR_INVALID_ARG;
-  if (dims[0] <= 0 || dims[1] <= 0 || dims[2] < dims[0] || image_stride < 0) return VH_ERR_INVALID_ARG;
-  if (dims[0] > 16384 || dims[1] > 16384) return VH_ERR_UNSUPPORTED;
-  int64_t nmax = 0, kmax = 0;
-  for (int32_t s = 0; s < n_sets; s++) {
-    if (offsets[s + 1] < offsets[s] || idx_offsets[s + 1] < idx_offsets[s]) return VH_ERR_INVALID_ARG;
-    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
-    kmax = std::max<int64_t>(kmax, idx_offsets[s + 1] - idx_offsets[s]);
-  }
-  const int64_t end = offsets[n_sets], total = end - offsets[0], k_end = idx_offsets[n_sets], k_total = k_end - idx_offsets[0];
+  ListSpan rec, pos;
+  // (the first offsets are judged before dims, the order of the others after them: the entry's precedence of refusals)
+  if (!gain || !num || image_stride < 0 || check_offsets(offsets, 0, rec) || check_offsets(idx_offsets, 0, pos)) return VH_ERR_INVALID_ARG;
+  const int32_t rd = check_dims(dims, true);
+  if (rd) return rd;
+  if (check_offsets(offsets, n_sets, rec) || check_offsets(idx_offsets, n_sets, pos)) return VH_ERR_INVALID_ARG;
+  const int64_t nmax = rec.longest, kmax = pos.longest, end = rec.end, total = rec.total, k_end = pos.end, k_total = pos.total;
   if ((total > 0 && !pm) || (k_total > 0 && (!idx || !I_prev || !I_cur))) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) { gain[s] = 1.0f; num[s] = 0; }
   if (k_total == 0) return VH_OK;  // nothing to do: nothing is launched
@@ -142,26 +109,27 @@ static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dim
   const size_t lists = (size_t)n_sets;
   const int32_t pitch = round_up(dims[0], 16);
   const size_t plane = (size_t)pitch * dims[1];
-  const size_t o_off = up256(sizeof(vh_p_match) * (size_t)end), o_idx = o_off + up256(sizeof(int32_t) * (lists + 1));
-  const size_t o_ioff = o_idx + up256(sizeof(int32_t) * (size_t)k_end), o_ratio = o_ioff + up256(sizeof(int32_t) * (lists + 1));
-  const size_t o_gain = o_ratio + up256(sizeof(float) * (size_t)k_end), o_num = o_gain + up256(sizeof(float) * lists);
-  const size_t o_check = o_num + up256(sizeof(int32_t) * lists), o_prev = o_check + 256, o_cur = o_prev + up256(plane * lists);
+  Carver c;
+  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
+  const size_t o_idx = c.take<int32_t>((size_t)k_end), o_ioff = c.take<int32_t>(lists + 1), o_ratio = c.take<float>((size_t)k_end);
+  const size_t o_gain = c.take<float>(lists), o_num = c.take<int32_t>(lists), o_check = c.take<uint32_t>(64);
+  const size_t o_prev = c.take<uint8_t>(plane * lists), o_cur = c.take<uint8_t>(plane * lists);
   DeviceBlock blk;
-  VH_HIP(blk.alloc(o_cur + plane * lists));
+  VH_HIP(blk.alloc(c.bytes()));
   uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)offsets[0], k_first = (size_t)idx_offsets[0];
-  if (total > 0) VH_HIP(hipMemcpy(d + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
+  const size_t first = (size_t)rec.first, k_first = (size_t)pos.first;
+  if (total > 0) VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_idx + sizeof(int32_t) * k_first, idx + k_first, sizeof(int32_t) * (size_t)k_total, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_ioff, idx_offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
   VH_HIP(hipMemset(d + o_check, 0, 256));
-  VH_HIP(hipMemset(d + o_prev, 0, o_cur + plane * lists - o_prev));  // (the planes' padding columns: read, never summed)
+  VH_HIP(hipMemset(d + o_prev, 0, c.bytes() - o_prev));  // (the planes' padding columns: read, never summed)
   for (size_t s = 0; s < lists; s++) {
     VH_HIP(hipMemcpy2D(d + o_prev + s * plane, (size_t)pitch, I_prev + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
     VH_HIP(hipMemcpy2D(d + o_cur + s * plane, (size_t)pitch, I_cur + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
   }
   VhGainArgs a{};
-  a.pm = (const vh_p_match *)d; a.offsets = (const int32_t *)(d + o_off);
+  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
   a.idx = (const int32_t *)(d + o_idx); a.idx_offsets = (const int32_t *)(d + o_ioff);
   a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
   a.planes_prev = d + o_prev; a.planes_cur = d + o_cur; a.plane = (int64_t)plane; a.pitch = pitch; a.W = dims[0]; a.H = dims[1];
@@ -171,17 +139,7 @@ static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dim
   vh_launch_gain_sum(a, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-#ifdef VH_CHECK
-  {
-    uint32_t c[4] = {0, 0, 0, 0};
-    VH_HIP(hipMemcpy(c, a.check, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[0]) {
-      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
-      fflush(stderr);
-      abort();
-    }
-  }
-#endif
+  { const int32_t rv = report_violation(a.check); if (rv) return rv; }
   VH_HIP(hipMemcpy(gain, a.gain, sizeof(float) * lists, hipMemcpyDeviceToHost));
   VH_HIP(hipMemcpy(num, a.num, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
   return VH_OK;

@@ -28,62 +28,37 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
   if (!(t.on_device ? t.params_ok() && !t.is_mono : t.args_ok() && ok) || !counts) return VH_ERR_INVALID_ARG;
   // the stereo test reads the right camera's columns; the mono test the left camera's flow, which flow and quad lists carry
   if (!allocated || !(last_method == VH_METHOD_QUAD || (t.is_mono && last_method == VH_METHOD_FLOW))) return VH_ERR_STATE;
-  bool replaced = false;  // the getters serve a host-side list for some stream: that list is classified, from a device copy
-  for (int32_t s = 0; s < S; s++) replaced = replaced || host_filtered[s] != 0;
   const int32_t tiles = (mcap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
   if (!inlier_grid_ok(S, tiles)) return VH_ERR_UNSUPPORTED;
   inl.valid = false;
-  const InlierLayout lay((size_t)S, (size_t)S * mcap, (size_t)tiles);
+  const size_t bytes = InlierArrays().carve(nullptr, (size_t)S, (size_t)S * mcap, (size_t)tiles).bytes();
   const bool first = !inl.d_flags;
   if (first) {  // one block: a refused allocation leaves nothing behind
     uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, lay.bytes, false);
+    const int32_t rc = dmalloc(&d, bytes, false);
     if (rc) return rc;
-    inl.d_flags = d; inl.d_out = (vh_p_match *)(d + lay.o_out); inl.d_src = (int32_t *)(d + lay.o_src);
-    inl.d_tiles = (int32_t *)(d + lay.o_tiles); inl.d_ninl = (int32_t *)(d + lay.o_ninl); inl.d_ok = (int32_t *)(d + lay.o_ok);
-    inl.d_tr = (double *)(d + lay.o_tr);
+    inl.carve(d, (size_t)S, (size_t)S * mcap, (size_t)tiles);
     inl.tiles = tiles;
   }
   if (t.is_mono && !inl.d_model) {  // the models of the mono test: a block of their own, so that the stereo path allocates what it always did
     const int32_t rc = dmalloc(&inl.d_model, (size_t)S, false);
     if (rc) {
       if (first) {  // (nothing has used the main block yet, and no other block of `inl` exists) -- the refused call leaves the handle as it found it
-        dfree(inl.d_flags); device_bytes -= (int64_t)lay.bytes;
+        dfree(inl.d_flags); device_bytes -= (int64_t)bytes;
         inl = InlierState();
       }
       return rc;
     }
   }
-  if (replaced && !inl.d_host_pm) {
-    uint8_t *d = nullptr;
-    const size_t b_pm = up256(sizeof(vh_p_match) * (size_t)S * mcap);
-    const int32_t rc = dmalloc(&d, b_pm + sizeof(int32_t) * (size_t)S, false);
-    if (rc) return rc;
-    inl.d_host_pm = (vh_p_match *)d; inl.d_host_cnt = (int32_t *)(d + b_pm);
-  }
+  // on the post stream, behind the emission of the lists: the lists the getters serve
+  const vh_p_match *d_lists = nullptr;
+  const int32_t *d_counts = nullptr;
+  bool replaced = false;
+  { const int32_t rc = stage_host_lists(inl.host, post_stream, replaced, d_lists, d_counts); if (rc) return rc; }
   inl.n_list.assign((size_t)S, 0); inl.n_inl.assign((size_t)S, 0);
-  // on the post stream, behind the emission of the lists
   if (t.is_mono) VH_HIP(hipMemcpyAsync(inl.d_model, t.model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyHostToDevice, post_stream));
   else if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
   if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
-  const vh_p_match *d_lists = (const vh_p_match *)mt.d_matches;
-  const int32_t *d_counts = mt.d_match_count;
-  std::vector<int32_t> host_cnt;
-  if (replaced) {  // a replaced list is a subset of the device list it came from: it fits the slot
-    host_cnt.assign((size_t)S, 0);
-    VH_HIP(hipMemcpyAsync(inl.d_host_cnt, mt.d_match_count, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
-    for (int32_t s = 0; s < S; s++) {
-      vh_p_match *dst = inl.d_host_pm + (size_t)s * mcap;
-      if (!host_filtered[s]) {
-        VH_HIP(hipMemcpyAsync(dst, d_lists + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)mcap, hipMemcpyDeviceToDevice, post_stream));
-        continue;
-      }
-      host_cnt[s] = (int32_t)std::min<size_t>(host_matches[s].size(), (size_t)mcap);
-      if (host_cnt[s]) VH_HIP(hipMemcpyAsync(dst, host_matches[s].data(), sizeof(vh_p_match) * (size_t)host_cnt[s], hipMemcpyHostToDevice, post_stream));
-      VH_HIP(hipMemcpyAsync(inl.d_host_cnt + s, &host_cnt[s], sizeof(int32_t), hipMemcpyHostToDevice, post_stream));
-    }
-    d_lists = inl.d_host_pm; d_counts = inl.d_host_cnt;
-  }
   VhInlierArgs a{};
   a.pm = d_lists; a.pm_stride = mcap; a.counts = d_counts; a.count_cap = mcap;
   a.n_lists = S; a.tiles_per_list = inl.tiles;
@@ -112,12 +87,13 @@ int32_t Group::refit_motion(const vh_ego_params *e, int32_t reclassify, double *
   if (!e || !tr_out || !ok_out || !n_updates || !counts) return VH_ERR_INVALID_ARG;
   // (a push ends the pair the lists belong to: last_method)
   if (!inliers_current() || inl.mono || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
-  const size_t o_ok = up256(sizeof(double) * 6 * (size_t)S), o_nupd = o_ok + up256(sizeof(int32_t) * (size_t)S);
   if (!rft.d_tr) {  // one block: a refused allocation leaves nothing behind
+    Carver c;
+    const size_t o_tr = c.take<double>(6 * (size_t)S), o_ok = c.take<int32_t>((size_t)S), o_nupd = c.take<int32_t>((size_t)S);
     uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, o_nupd + up256(sizeof(int32_t) * (size_t)S), false);
+    const int32_t rc = dmalloc(&d, c.bytes(), false);
     if (rc) return rc;
-    rft.d_tr = (double *)d; rft.d_ok = (int32_t *)(d + o_ok); rft.d_nupd = (int32_t *)(d + o_nupd);
+    rft.d_tr = (double *)(d + o_tr); rft.d_ok = (int32_t *)(d + o_ok); rft.d_nupd = (int32_t *)(d + o_nupd);
   }
   VhRefitArgs a{};
   a.e = *e;
@@ -195,24 +171,15 @@ int32_t Group::get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t
 
 using namespace vh_engine;
 
-#define ENTER(gq)                                   \
-  if (!(gq)) return VH_ERR_INVALID_ARG;             \
-  { hipError_t e_ = hipSetDevice((gq)->device);     \
-    if (e_ != hipSuccess) { t_last_error = hipGetErrorString(e_); return VH_ERR_HIP; } }
-
 // The stateless classification under either test: validation, one device block, the uploads, the flag launch of the
 // test, the scan and the scatter, the downloads.
 static int32_t inliers_stateless(const InlierTest &t, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
                                  const int32_t *ok, uint8_t *flags, int32_t *n_inliers, vh_p_match *inlier_pm, int32_t *src_pos) {
   if (!t.params_ok() || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
-  if (!offsets || !t.args_ok() || !ok || !n_inliers || offsets[0] < 0) return VH_ERR_INVALID_ARG;
-  int64_t nmax = 0;
-  for (int32_t s = 0; s < n_sets; s++) {
-    if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
-    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
-  }
-  const int64_t end = offsets[n_sets], total = end - offsets[0];
+  ListSpan sp;
+  if (!t.args_ok() || !ok || !n_inliers || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
+  const int64_t nmax = sp.longest, end = sp.end, total = sp.total;
   if (total > 0 && (!pm || !flags)) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) n_inliers[s] = 0;
   if (total == 0) return VH_OK;
@@ -220,27 +187,28 @@ static int32_t inliers_stateless(const InlierTest &t, int32_t device, int32_t n_
   if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, tiles)) return VH_ERR_UNSUPPORTED;  // (a list longer than any handle holds)
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  // one block: the arrays of InlierLayout, addressed by the same offsets | the records up to offsets[n_sets] | offsets | (mono) the models
-  const InlierLayout lay((size_t)n_sets, (size_t)end, (size_t)tiles);
-  const size_t o_pm = up256(lay.bytes), o_off = o_pm + up256(sizeof(vh_p_match) * (size_t)end);
-  const size_t o_model = o_off + up256(sizeof(int32_t) * ((size_t)n_sets + 1));
+  // one block: the arrays of a classification | the records up to offsets[n_sets] | offsets | (mono) the models
+  InlierArrays ia;
+  Carver c = ia.carve(nullptr, (size_t)n_sets, (size_t)end, (size_t)tiles);
+  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>((size_t)n_sets + 1);
+  const size_t o_model = c.take<vh_mono_model>(t.is_mono ? (size_t)n_sets : 0);
   DeviceBlock blk;
-  VH_HIP(blk.alloc(t.is_mono ? o_model + sizeof(vh_mono_model) * (size_t)n_sets : o_off + sizeof(int32_t) * ((size_t)n_sets + 1)));
+  VH_HIP(blk.alloc(c.bytes()));
   uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)offsets[0];
+  ia.carve(d, (size_t)n_sets, (size_t)end, (size_t)tiles);
+  const size_t first = (size_t)sp.first;
   VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
   if (t.is_mono) VH_HIP(hipMemcpy(d + o_model, t.model, sizeof(vh_mono_model) * (size_t)n_sets, hipMemcpyHostToDevice));
-  else VH_HIP(hipMemcpy(d + lay.o_tr, t.tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + lay.o_ok, ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyHostToDevice));
+  else VH_HIP(hipMemcpy(ia.d_tr, t.tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
+  VH_HIP(hipMemcpy(ia.d_ok, ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyHostToDevice));
   VhInlierArgs a{};
   a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
   a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
-  a.tr = t.is_mono ? nullptr : (const double *)(d + lay.o_tr);  // (each flag kernel reads its own of the two)
+  a.tr = t.is_mono ? nullptr : ia.d_tr;  // (each flag kernel reads its own of the two)
   a.model = t.is_mono ? (const vh_mono_model *)(d + o_model) : nullptr;
-  a.ok = (const int32_t *)(d + lay.o_ok);
-  a.flags = d; a.out = (vh_p_match *)(d + lay.o_out); a.src_pos = (int32_t *)(d + lay.o_src);
-  a.tile_cnt = (int32_t *)(d + lay.o_tiles); a.n_inl = (int32_t *)(d + lay.o_ninl);
+  a.ok = ia.d_ok;
+  a.flags = ia.d_flags; a.out = ia.d_out; a.src_pos = ia.d_src; a.tile_cnt = ia.d_tiles; a.n_inl = ia.d_ninl;
   launch_inliers(t, a, nullptr, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
@@ -262,13 +230,9 @@ static int32_t refit_stateless(const vh_ego_params *e, int32_t device, int32_t n
                                const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates) {
   if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
-  if (!offsets || !tr_in || !ok_in || !tr_out || !ok_out || !n_updates || offsets[0] < 0) return VH_ERR_INVALID_ARG;
-  int64_t nmax = 0;
-  for (int32_t s = 0; s < n_sets; s++) {
-    if (offsets[s + 1] < offsets[s]) return VH_ERR_INVALID_ARG;
-    nmax = std::max<int64_t>(nmax, offsets[s + 1] - offsets[s]);
-  }
-  const int64_t end = offsets[n_sets], total = end - offsets[0];
+  ListSpan sp;
+  if (!tr_in || !ok_in || !tr_out || !ok_out || !n_updates || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
+  const int64_t nmax = sp.longest, end = sp.end, total = sp.total;
   if (total > 0 && !pm) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) {
     ok_out[s] = 0; n_updates[s] = 0;
@@ -279,20 +243,21 @@ static int32_t refit_stateless(const vh_ego_params *e, int32_t device, int32_t n
   const int32_t rc = select_device(device);
   if (rc) return rc;
   const size_t lists = (size_t)n_sets;
-  const size_t o_off = up256(sizeof(vh_p_match) * (size_t)end), o_tr = o_off + up256(sizeof(int32_t) * (lists + 1));
-  const size_t o_ok = o_tr + up256(sizeof(double) * 6 * lists), o_tr2 = o_ok + up256(sizeof(int32_t) * lists);
-  const size_t o_ok2 = o_tr2 + up256(sizeof(double) * 6 * lists), o_nupd = o_ok2 + up256(sizeof(int32_t) * lists);
+  Carver c;
+  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
+  const size_t o_tr = c.take<double>(6 * lists), o_ok = c.take<int32_t>(lists);
+  const size_t o_tr2 = c.take<double>(6 * lists), o_ok2 = c.take<int32_t>(lists), o_nupd = c.take<int32_t>(lists);
   DeviceBlock blk;
-  VH_HIP(blk.alloc(o_nupd + sizeof(int32_t) * lists));
+  VH_HIP(blk.alloc(c.bytes()));
   uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)offsets[0];
-  VH_HIP(hipMemcpy(d + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
+  const size_t first = (size_t)sp.first;
+  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_tr, tr_in, sizeof(double) * 6 * lists, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(d + o_ok, ok_in, sizeof(int32_t) * lists, hipMemcpyHostToDevice));
   VhRefitArgs a{};
   a.e = *e;
-  a.pm = (const vh_p_match *)d; a.offsets = (const int32_t *)(d + o_off); a.n_lists = n_sets;
+  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off); a.n_lists = n_sets;
   a.tr_in = (const double *)(d + o_tr); a.ok_in = (const int32_t *)(d + o_ok);
   a.tr_out = (double *)(d + o_tr2); a.ok_out = (int32_t *)(d + o_ok2); a.n_updates = (int32_t *)(d + o_nupd);
   vh_launch_refit(a, nullptr);

@@ -411,15 +411,9 @@ int32_t Group::vote_dense_alloc(VoteBatch &b, int32_t lists, bool model) {
   q.block = DeviceBlock(); q.bytes = 0; q.lists = 0;
   if (alloc_refused()) return VH_ERR_HIP;
   const size_t L = (size_t)lists, tiles = ((size_t)cap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
-  const InlierLayout lay(L, L * (size_t)cap, tiles);
-  const size_t per_list = up256(sizeof(int32_t) * L), total = VoteDense::bytes_for(L, (size_t)cap, model);
+  const size_t total = VoteDense::bytes_for(L, (size_t)cap, model);
   VH_HIP(q.block.alloc(total));
-  uint8_t *d = q.block.as<uint8_t>();
-  q.d_flags = d; q.d_out = (vh_p_match *)(d + lay.o_out); q.d_src = (int32_t *)(d + lay.o_src); q.d_tiles = (int32_t *)(d + lay.o_tiles);
-  q.d_ninl = (int32_t *)(d + lay.o_ninl); q.d_ok_refit = (int32_t *)(d + lay.o_ok); q.d_tr_refit = (double *)(d + lay.o_tr);
-  q.d_cnt = (int32_t *)(d + lay.bytes); q.d_ok = (int32_t *)(d + lay.bytes + per_list); q.d_voted = (int32_t *)(d + lay.bytes + 2 * per_list);
-  q.d_nupd = (int32_t *)(d + lay.bytes + 3 * per_list);
-  q.d_model = model ? (vh_mono_model *)(d + lay.bytes + 4 * per_list) : nullptr;
+  q.carve(q.block.p, L, (size_t)cap, model);
   q.bytes = total; q.lists = lists; q.cap = cap; q.tiles = (int32_t)tiles; q.with_model = model;
   if (q.h_lists < lists || (model && !q.h_with_model)) {
     q.h_lists = 0;

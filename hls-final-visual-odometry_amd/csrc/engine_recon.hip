@@ -204,17 +204,7 @@ int32_t recon_run(ReconHistory &h, Group *gq, hipStream_t st, VhReconGatherArgs 
     VH_HIP(hipMemcpyAsync(met.data(), h.g_met.b.p, sizeof(double) * 2 * (size_t)ns, hipMemcpyDeviceToHost, st));
   }
   VH_HIP(hipStreamSynchronize(st));
-#ifdef VH_CHECK
-  if (a.check) {
-    uint32_t c[4] = {0, 0, 0, 0};
-    VH_HIP(hipMemcpy(c, a.check, sizeof(c), hipMemcpyDeviceToHost));
-    if (c[0]) {
-      fprintf(stderr, "VH_CHECK: %u index violations; first: code %u, value %d, bound %d (codes: vh_dev.h)\n", c[0], c[1], (int)c[2], (int)c[3]);
-      fflush(stderr);
-      abort();
-    }
-  }
-#endif
+  if ((rc = report_violation(a.check))) return rc;
   std::vector<int32_t> order((size_t)nt);
   std::iota(order.begin(), order.end(), 0);
   std::sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
@@ -421,9 +411,7 @@ int32_t vh_sequence_set_reconstruction(vh_group *g, const vh_recon_params *r, in
 }
 
 int32_t vh_sequence_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, int32_t *n_accepted) {
-  Group *gq = (Group *)g;
-  if (!gq) return VH_ERR_INVALID_ARG;
-  if (hipSetDevice(gq->device) != hipSuccess) { t_last_error = "hipSetDevice"; return VH_ERR_HIP; }
+  Group *gq = (Group *)g; ENTER(gq);
   if (!gq->seq) { if (n_tracks) *n_tracks = 0; if (n_accepted) *n_accepted = 0; return n_tracks && n_accepted ? VH_ERR_STATE : VH_ERR_INVALID_ARG; }
   return gq->reconstruct(Tr, n_tracks, n_accepted);
 }
@@ -452,7 +440,7 @@ int32_t vh_group_reconstruct(vh_group *g, const double *Tr, int32_t *n_tracks, i
   Group *gq = (Group *)g;
   if (!gq) return VH_ERR_INVALID_ARG;
   if (gq->seq) return VH_ERR_UNSUPPORTED;
-  if (hipSetDevice(gq->device) != hipSuccess) { t_last_error = "hipSetDevice"; return VH_ERR_HIP; }
+  ENTER(gq);
   return gq->reconstruct(Tr, n_tracks, n_accepted);
 }
 
@@ -483,12 +471,8 @@ int32_t vh_reconstruct_lists(const vh_recon_params *r, int32_t device, int32_t n
   if (!r || !n || n_lists < 0 || cap < 0 || (cap > 0 && !out)) return VH_ERR_INVALID_ARG;
   *n = 0;
   if (n_lists == 0) return VH_OK;
-  if (!counts || !Tr || stride < 0 || n_index < 1) return VH_ERR_INVALID_ARG;
   int32_t cmax = 0;
-  for (int32_t l = 0; l < n_lists; l++) {
-    if (counts[l] < 0 || counts[l] > stride) return VH_ERR_INVALID_ARG;
-    cmax = std::max(cmax, counts[l]);
-  }
+  if (!Tr || stride < 0 || n_index < 1 || check_counts(counts, n_lists, stride, cmax)) return VH_ERR_INVALID_ARG;
   if (cmax > 0 && !pm) return VH_ERR_INVALID_ARG;
   if (cmax > (int32_t)VH_TRACK_POS_MASK || (int64_t)n_lists + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;  // (as vh_link_tracks)
   int32_t rc = select_device(device);
@@ -519,14 +503,11 @@ int32_t vh_group_debug_reconstruct_lists(const vh_recon_params *r, int32_t devic
   if (total + 1 > (1 << 16)) return VH_ERR_UNSUPPORTED;
   std::vector<int32_t> cnt((size_t)total, 0);
   std::vector<vh_p_match> rows;
-  int64_t cmax = 0;
-  for (int64_t k = 0; k < (int64_t)n_streams * n_lists; k++) {
-    if (counts[k] < 0 || counts[k] > stride) return VH_ERR_INVALID_ARG;
-    cmax = std::max<int64_t>(cmax, counts[k]);
-  }
+  int32_t cmax = 0;
+  if (check_counts(counts, (int64_t)n_streams * n_lists, stride, cmax)) return VH_ERR_INVALID_ARG;
   if (cmax > 0 && !pm) return VH_ERR_INVALID_ARG;
-  if (cmax > (int64_t)VH_TRACK_POS_MASK) return VH_ERR_UNSUPPORTED;
-  const int64_t rs = std::max<int64_t>(cmax, 1);
+  if (cmax > (int32_t)VH_TRACK_POS_MASK) return VH_ERR_UNSUPPORTED;
+  const int64_t rs = std::max(cmax, 1);
   rows.resize((size_t)(total * rs));
   for (int32_t s = 0; s < n_streams; s++)
     for (int32_t l = 0; l < n_lists; l++) {

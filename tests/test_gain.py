@@ -435,6 +435,45 @@ def test_gpu_indices_form_and_lone_matcher(pkg, ob, gpu):
 
 
 @pytest.mark.gpu
+def test_gpu_one_stream_replaced_on_the_host(pkg, ob, gpu):
+    """The matcher form of removeOutliers on a group handle replaces stream 0's list alone: the classification, the gain over
+    it and the gain over index lists read a staged copy in which stream 0 is the shorter host-side list and streams 1 and 2
+    are still their device lists.  Each equals the stateless entry on the lists vh_group_get_matches_all returns, exactly."""
+    fr, dims = frames_of(pkg), dims_of(pkg)
+    g = pkg.StreamGroup(S, pkg.Params.default())
+    g.setGain(True)
+    e = pkg.EgoParams.default(ransac_iters=50, inlier_threshold=2.5, **CAL)
+    push(g, fr, 0, dims)
+    push(g, fr, 1, dims)
+    Ip, Ic = lefts(fr, 0), lefts(fr, 1)
+    g.matchFeatures(QUAD)
+    device_lists = [g.getMatches(s) for s in range(S)]
+    assert pkg._lib().vh_remove_outliers(g._h) == pkg.VH_OK
+    rows, n_rows = g.getMatchesAll()
+    lists = [rows[s, :n_rows[s]].copy() for s in range(S)]
+    print("device", [len(pm) for pm in device_lists], "served", list(n_rows))
+    # the premise: streams 1 and 2 still serve their device lists, stream 0 a shorter one (the test is void otherwise)
+    assert 0 < len(lists[0]) < len(device_lists[0]) and len(lists[2]) > 0
+    assert [lists[s].tobytes() for s in (1, 2)] == [device_lists[s].tobytes() for s in (1, 2)]
+    tr, ok = np.array([TR] * S), np.ones(S, np.int32)
+    counts = g.motionInliers(e, tr, ok)
+    want_flags, want_n, want_pm, want_pos = pkg.motion_inliers(e, lists, tr, ok)
+    print("inliers", counts, want_n)
+    assert np.array_equal(counts, want_n) and counts[0] > 50 and counts[2] > 0
+    for s in range(S):
+        got_pm, got_pos = g.getInlierMatches(s)
+        assert g.getInlierFlags(s).tobytes() == want_flags[s].tobytes(), s
+        assert got_pm.tobytes() == want_pm[s].tobytes() and np.array_equal(got_pos, want_pos[s]), s
+    same_as_stateless(pkg, g.gain(), lists, want_pos, Ip, Ic, dims, "inliers, stream 0 replaced")
+    idx = [np.array([0, len(pm) - 1, len(pm) // 2, len(pm), -1, 0], np.int32) for pm in lists]   # a few positions per stream
+    got = g.gain(idx)
+    same_as_stateless(pkg, got, lists, idx, Ip, Ic, dims, "indices, stream 0 replaced")
+    assert got[1][0] > 0 and got[1][1] == 0 and got[1][2] > 0
+    same_as_stateless(pkg, g.gain(), lists, want_pos, Ip, Ic, dims, "inliers again: the classification's copy is its own")
+    g.close()
+
+
+@pytest.mark.gpu
 def test_gpu_state_rules_and_failed_allocation(pkg, ob, gpu):
     fr, dims = frames_of(pkg), dims_of(pkg)
     state = pkg.VH_ERR_STATE
