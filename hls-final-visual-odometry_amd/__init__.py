@@ -1269,10 +1269,11 @@ def remove_outliers(pm) -> np.ndarray:
 
 
 def remove_outliers_device(lists, lanes_per_wave: int = 1, max_features: int = 0, bucket_width: float = 50.0, bucket_height: float = 50.0,
-                           device: int = 0, out_cap: int = 0, strict: bool = True):
+                           device: int = 0, out_cap: int = 0, strict: bool = True, with_counts: bool = False):
     """removeOutliers (and bucketFeatures when max_features >= 1) of several match lists at once on the GPU
     (vh_remove_outliers_device) -> (lists, triangles per list, sweep kernel ms).  strict=False: an error code does not
-    raise; the healthy lists are returned (a refused list comes back empty) with the code as a fourth element."""
+    raise; the healthy lists are returned (a refused list comes back empty) with the code as a fourth element.
+    with_counts: out_counts as the call left them (the length a list that did not fit out_cap needs) as a last element."""
     lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in lists]
     n = len(lists)
     stride = max([len(m) for m in lists] + [1])
@@ -1286,10 +1287,11 @@ def remove_outliers_device(lists, lanes_per_wave: int = 1, max_features: int = 0
     rc = _lib().vh_remove_outliers_device(device, n, _ptr(pm), stride, _ptr(counts), int(lanes_per_wave), int(max_features),
                                           C.c_float(bucket_width), C.c_float(bucket_height), _ptr(out), out_cap, _ptr(oc), _ptr(ntri),
                                           C.byref(ms))
+    tail = (oc.copy(),) if with_counts else ()
     if strict:
         _check(rc, "vh_remove_outliers_device")
-        return [out[l, :oc[l]].copy() for l in range(n)], ntri, ms.value
-    return [out[l, :min(int(oc[l]), out_cap)].copy() for l in range(n)], ntri, ms.value, rc
+        return ([out[l, :oc[l]].copy() for l in range(n)], ntri, ms.value) + tail
+    return ([out[l, :oc[l]].copy() if oc[l] <= out_cap else out[l, :0].copy() for l in range(n)], ntri, ms.value, rc) + tail
 
 
 class TrackCarry:

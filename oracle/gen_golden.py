@@ -9,7 +9,8 @@ and stores inputs' parameters plus the reference's outputs.  The fixtures are
 data only (feature records, bin lists, match records, hashes); the images are
 re-generated from (W,H,dx,dy,blur,gain,seed) at test time.
 
-    python oracle/gen_golden.py            # rewrites tests/golden/
+    python oracle/gen_golden.py               # rewrites tests/golden/
+    python oracle/gen_golden.py bucket_edges  # rewrites tests/golden/bucket_edges.npz alone
 """
 from __future__ import annotations
 
@@ -59,11 +60,45 @@ def run_case(ref, ob, synth, W, H, blur, gain, seed, pan, over):
                          bin_start=bs, bin_list=lst, fwd=fwd)
 
 
+def save_npz_reproducible(path, arrays):
+    """np.savez_compressed without the clock: entries in name order, the zip format's earliest date."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue())
+
+
+def bucket_edges(pkg, ob, ref):
+    """bucketFeatures at the edges of its grid (oracle/bucket_edges.py states the cases and asserts, before the
+    reference is called, that each stays inside its buckets[126][256] and POINT_L): inputs and recorded outputs."""
+    from oracle import bucket_edges as be
+    p = ob.Params.default()
+    z = {}
+    for name, pm, calls in be.families(0, pkg.P_MATCH_DTYPE):
+        z[name + "__in"] = pm
+        z[name + "__calls"] = np.array(calls, np.float64)
+        for k, (mf, bw, bh) in enumerate(calls):
+            assert be.within_reference_bounds(pm, bw, bh), (name, mf, bw, bh)
+            z[f"{name}__out{k}"] = ref.bucket_features(p, pm, mf, bw, bh)
+            cols, rows, _, lens = be.shape(pm, bw, bh)
+            print(f"bucket_edges {name} ({mf},{bw},{bh}): grid {cols}x{rows}, fullest {lens.max()}, empty {(lens == 0).sum()}: "
+                  f"{len(pm)} -> {len(z[f'{name}__out{k}'])}")
+    save_npz_reproducible(os.path.join(GOLDEN, "bucket_edges.npz"), z)
+
+
 def main():
     pkg = entry.load_package()
     ob = entry.load_oracle()
     ob.build(ref=True)
     ref = ob.Reference()
+    if sys.argv[1:] == ["bucket_edges"]:
+        return bucket_edges(pkg, ob, ref)
     o = ob.Oracle()
     synth = pkg.synth
     os.makedirs(GOLDEN, exist_ok=True)
@@ -149,6 +184,8 @@ def main():
     ol["kitti__fnv_out"] = np.uint64(o.fnv(out))
     print(f"removeOutliers(kitti): {len(pm)} -> {len(out)} fnv={int(ol['kitti__fnv_out']):016x}")
     np.savez_compressed(os.path.join(GOLDEN, "outliers.npz"), **ol)
+
+    bucket_edges(pkg, ob, ref)
 
 
 if __name__ == "__main__":

@@ -88,6 +88,45 @@ def test_bucket_features_golden(pkg, ob, oracle):
         assert out.tobytes() == g[key].tobytes(), key
 
 
+def _bucket_edge_fixture():
+    z = np.load(os.path.join(GOLDEN, "bucket_edges.npz"))
+    names = sorted(k[:-len("__in")] for k in z.files if k.endswith("__in"))
+    return z, names
+
+
+def test_bucket_features_edge_fixtures(oracle):
+    """bucketFeatures at the edges of its grid, inside the reference's buckets[126][256] (oracle/bucket_edges.py,
+    recorded by oracle/gen_golden.py): sizes that are no integers or exceed the field, coordinates on bucket edges and
+    between pixels, grids of 1, 63, 64, 65 and 126 buckets with empty ones, max_features around the fullest bucket's
+    length.  The oracle reproduces every recorded output byte for byte."""
+    from oracle import bucket_edges as be
+    z, names = _bucket_edge_fixture()
+    assert len(names) >= 11
+    grids, tops = set(), set()
+    for name in names:
+        pm = z[name + "__in"]
+        for k, (mf, bw, bh) in enumerate(z[name + "__calls"]):
+            assert be.within_reference_bounds(pm, bw, bh), (name, k)
+            cols, rows, _, lens = be.shape(pm, bw, bh)
+            grids.add(cols * rows)
+            tops.add(int(mf) - int(lens.max()))
+            out = oracle.bucket_features(pm, int(mf), float(bw), float(bh))
+            assert out.tobytes() == z[f"{name}__out{k}"].tobytes(), (name, int(mf), bw, bh)
+            assert len(out) == int(np.minimum(lens, int(mf)).sum())
+    assert {1, 63, 64, 65, 126} <= grids and {-1, 0, 1} <= tops  # (what the fixture claims to hold)
+
+
+def test_bucket_features_vs_reference_fresh_inputs(pkg, ob, oracle, reference):
+    """The same families from seeds no fixture holds, put to the reference itself (its answers: the `reference` fixture)."""
+    from oracle import bucket_edges as be
+    p = ob.Params.default()
+    for seed in (1, 2):
+        for name, pm, calls in be.families(seed, pkg.P_MATCH_DTYPE):
+            for mf, bw, bh in calls:
+                assert be.within_reference_bounds(pm, bw, bh), (seed, name)
+                assert oracle.bucket_features(pm, mf, bw, bh).tobytes() == reference.bucket_features(p, pm, mf, bw, bh).tobytes(), (seed, name, mf, bw, bh)
+
+
 def test_oracle_vs_reference_fresh_inputs(pkg, ob, oracle, reference):
     """Compare with the reference on inputs no per-case fixture holds (its answers: the `reference` fixture)."""
     rng = np.random.default_rng(7)
