@@ -626,6 +626,41 @@ detect_nms_fast_kernel(VhImages im, VhGeom g, uint64_t *__restrict__ rec, int32_
 // sample-point offsets of the 16 (du,dv) pairs, byte order of matcher.cpp:482-513
 __constant__ int8_t c_desc_dx[16] = {-3, -3, -1, -1, +3, +3, +1, +1, -1, -1, +1, +1, -5, -5, +5, +5};
 __constant__ int8_t c_desc_dy[16] = {-1, +1, -1, +1, -1, +1, -1, +1, -5, +5, -5, +5, -3, +3, -3, +3};
+// Signed byte weights of the 5 taps of a window row, laid over the two aligned dwords {lo, hi} that hold them, for
+// each byte alignment a = (dx + 5) & 3 of the window in its patch row (v_dot4_i32_i8 operands; the patch bytes are made
+// signed by ^ 0x80, which changes no sum because the weights of either Sobel kernel add up to 0 over the window).
+// Per alignment: du rows with column weight 1 / 4 / 6 (taps 1 2 0 -2 -1), then dv rows with column weight
+// +1 / +2 / -2 / -1 (taps 1 4 6 4 1); {lo, hi} each, padded to 16 dwords.
+struct DescWeights { uint32_t w[4][16]; };
+constexpr uint64_t desc_taps(int m, int t0, int t1, int t2, int t3, int t4, int a) {
+  return ((uint64_t)(uint8_t)(int8_t)(m * t0) | ((uint64_t)(uint8_t)(int8_t)(m * t1) << 8) | ((uint64_t)(uint8_t)(int8_t)(m * t2) << 16) |
+          ((uint64_t)(uint8_t)(int8_t)(m * t3) << 24) | ((uint64_t)(uint8_t)(int8_t)(m * t4) << 32)) << (8 * a);
+}
+constexpr DescWeights make_desc_weights() {
+  DescWeights d{};
+  const int du_m[3] = {1, 4, 6}, dv_m[4] = {1, 2, -2, -1};
+  for (int a = 0; a < 4; a++) {
+    for (int i = 0; i < 3; i++) {
+      const uint64_t t = desc_taps(du_m[i], 1, 2, 0, -2, -1, a);
+      d.w[a][2 * i] = (uint32_t)t; d.w[a][2 * i + 1] = (uint32_t)(t >> 32);
+    }
+    for (int i = 0; i < 4; i++) {
+      const uint64_t t = desc_taps(dv_m[i], 1, 4, 6, 4, 1, a);
+      d.w[a][6 + 2 * i] = (uint32_t)t; d.w[a][6 + 2 * i + 1] = (uint32_t)(t >> 32);
+    }
+  }
+  return d;
+}
+__constant__ DescWeights c_desc_w = make_desc_weights();
+
+#ifdef VH_EXP_EMIT_STOP  // timing-only builds (EXTRA=-DVH_EXP_EMIT_STOP=k): emit_features stops after phase k (1 prefix,
+// 2 ordered compaction, 3 bin slots + row ranks + staging), so that the SQ_INSTS_VALU differences between the builds
+// split the kernel's instructions by phase.  No descriptors are written.  (The runtime condition keeps the phases
+// before the stop from being optimised away.)
+#define VH_EMIT_STOP(k) if (VH_EXP_EMIT_STOP == (k) && g.nbx > 0) return
+#else
+#define VH_EMIT_STOP(k) do { } while (0)
+#endif
 
 
 #ifndef VH_EMIT_NF
@@ -674,8 +709,9 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
   const int32_t incl = vh_wave_scan(mine);
   if ((tid & 63) == 63) { sWave[tid >> 6] = incl; sWaveP[tid >> 6] = part; }
   __syncthreads();
-  const int32_t base = sWaveP[0] + sWaveP[1] + sWaveP[2] + sWaveP[3];
+  const int32_t base = __builtin_amdgcn_readfirstlane(sWaveP[0] + sWaveP[1] + sWaveP[2] + sWaveP[3]);  // (workgroup-uniform: a scalar)
   VH_ETICK(0);
+  VH_EMIT_STOP(1);
   int32_t woff = 0;
   for (int32_t w = 0; w < (tid >> 6); w++) woff += sWave[w];
   const int32_t total = sWave[0] + sWave[1] + sWave[2] + sWave[3];
@@ -706,6 +742,7 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
   __syncthreads();
   if (chunk == g.nchunks - 1 && tid == 0) count[set] = base + total;
   VH_ETICK(1);
+  VH_EMIT_STOP(2);
   // (phase B's lane roles, here because its first patch loads are requested now, ahead of phase A2)
   const int32_t grp = tid >> 4, k = tid & 15;
   const int32_t dx = c_desc_dx[k], dy = c_desc_dy[k];
@@ -714,26 +751,38 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
   // The patch rows of trip i+1 are in flight while trip i is handed round, computed and stored
   // (one 16-byte load per lane and feature: 8 registers for the double buffer).
   typedef uint32_t u32x4a1 __attribute__((ext_vector_type(4), aligned(1)));
-  struct Coords { int32_t fs[NF], us[NF], vs[NF], cs[NF]; bool lives[NF]; };
+  // 32-bit byte offsets from the (wave-uniform) image base: images are <= 2^28 bytes, rows < 2^14, strides
+  // < 2^24.  Byte-granular: no alignment of the image or its stride is assumed.  u+8 <= W-1 for every feature.
+  // Only the list entry depends on the feature; what depends on the lane alone (row prk of the patch, its first
+  // byte at u-7) is one loop-invariant term of the offset (sums are mod 2^32, the offset itself is >= 0).
+  const uint32_t lane_off = (uint32_t)(prk * g.bplm - 7);
+  const int32_t last = total - 1;
+  struct Coords { int32_t fs[NF]; uint32_t es[NF]; };  // list index and entry; a slot past the list holds the last entry and stores nothing
   auto fetch = [&](int32_t f0, Coords &q, u32x4a1 (&prow)[NF]) {
 #pragma unroll
     for (int32_t h = 0; h < NF; h++) {
       q.fs[h] = f0 + 16 * h + grp;
-      q.lives[h] = q.fs[h] < total;
-      const uint32_t e = sList[q.lives[h] ? q.fs[h] : 0];  // dead lanes recompute feature 0 and drop the result
-      q.us[h] = e & 0x3FFF; q.vs[h] = (e >> 14) & 0x3FFF; q.cs[h] = e >> 28;
-      // 32-bit byte offsets from the (wave-uniform) image base: images are <= 2^28 bytes, rows < 2^14, strides
-      // < 2^24.  Byte-granular: no alignment of the image or its stride is assumed.  u+8 <= W-1 for every feature.
+      const uint32_t e = sList[min(q.fs[h], last)];
+      q.es[h] = e;
+      const uint32_t u = e & 0x3FFF, v = (e >> 14) & 0x3FFF;
 #ifdef VH_EXP_NOPATCH  // timing-only build: the descriptor's instructions without its patch gathers (descriptors are wrong)
-      prow[h] = u32x4a1{(uint32_t)q.us[h], (uint32_t)q.vs[h], 0u, 0u};
+      prow[h] = u32x4a1{u, v, 0u, 0u};
 #else
-      prow[h] = *(const u32x4a1 *)(I + (__umul24((uint32_t)(q.vs[h] + prk), (uint32_t)g.bplm) + (uint32_t)(q.us[h] - 7)));
+      prow[h] = *(const u32x4a1 *)(I + (__umul24(v, (uint32_t)g.bplm) + u + lane_off));
 #endif
     }
   };
   Coords qa, qb;
   u32x4a1 pa[NF], pb[NF];
   if (total > 0) fetch(0, qa, pa);
+  // the lane's weight dwords (requested here, used in phase B)
+  uint32_t wt[14];
+  {
+    const uint4 *wp = (const uint4 *)c_desc_w.w[(dx + 5) & 3];
+    const uint4 w0 = wp[0], w1 = wp[1], w2 = wp[2], w3 = wp[3];
+    wt[0] = w0.x; wt[1] = w0.y; wt[2] = w0.z; wt[3] = w0.w; wt[4] = w1.x; wt[5] = w1.y; wt[6] = w1.z; wt[7] = w1.w;
+    wt[8] = w2.x; wt[9] = w2.y; wt[10] = w2.z; wt[11] = w2.w; wt[12] = w3.x; wt[13] = w3.y;
+  }
 
   // phase A2: bin histogram + per-bin staging + row histogram, one lane per
   // feature.  Kept out of the descriptor loop below: a returning atomic inside
@@ -784,11 +833,14 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
     __syncthreads();
   }
   VH_ETICK(2);
+  const int32_t sh = g.scale - 1;  // scale is 1 or 2
+  uint32_t *__restrict__ fuv = s.f_uv + (int64_t)set * cap;
   for (int32_t f = tid; f < total; f += 256) {
     const int32_t fi = base + f;
     if (fi >= cap) break;
     const uint32_t e = sList[f];
     const int32_t vv = (int32_t)((e >> 14) & 0x3FFF) * g.scale, c = e >> 28;
+    fuv[fi] = ((e & 0x3FFF) << sh) | ((((e >> 14) & 0x3FFF) << sh) << 16);  // (here, one lane per feature, not in phase B's 16)
     const int32_t b = f == tid ? b0 : bin_of_entry(e);
     const int32_t rowrel = rows_in_lds ? sRow[c * ROWS_LDS + (vv - v_first)] + (int32_t)sLoc[f] : atomicAdd(&rowh[c * s.H + vv], 1);
     const int32_t slot = f == tid ? slot0 : atomicAdd(&s.hist[(int64_t)set * s.nbins + b], 1);
@@ -799,6 +851,7 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
   }
 
   VH_ETICK(3);
+  VH_EMIT_STOP(3);
   // phase B: 16 lanes per feature, lane k = sample point k; NF features per lane and loop trip.
   // The 16 windows of a feature (5x5 bytes each) all lie in the 15x15 patch around it.  Fetched
   // window by window (5 loads per lane) a wave-wide load touches ~8 cache lines per feature, 40
@@ -808,29 +861,29 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
   // feature, plus the rows that straddle a line -- and handed round through LDS, from where every
   // lane takes its five row segments at offsets that depend on the lane alone.  A lane group
   // lives inside one wave and a wave's LDS instructions execute in order: no barrier is needed.
-  const int32_t sh = g.scale - 1;  // scale is 1 or 2
-  int32_t *__restrict__ out = feat + (int64_t)set * cap * 12;
-  uint32_t *__restrict__ fuv = s.f_uv + (int64_t)set * cap;
-  // lane L<4 writes the header word, lane 4+j the descriptor dword j = pair[2j] | pair[2j+1]<<16
-  const int32_t gbase = (tid & 63) & ~15, j = (k >= 4) ? (k - 4) : 0;
-  // (branch-free word select: the lane's role is loop-invariant; word 2, val, is zeroed on packing, matcher.cpp:667)
-  const uint32_t m_u = k == 0 ? ~0u : 0u, m_v = k == 1 ? ~0u : 0u, m_c = k == 3 ? ~0u : 0u, m_d = k >= 4 ? ~0u : 0u;
+  // The 12 words of a record are stored by lanes 0..11 of its group: lanes 0..3 the header (u, v, val = 0 -- zeroed
+  // on packing, matcher.cpp:667 -- and class), each as one bit field of the list entry (offset, width and scale shift
+  // depend on the lane alone); lane 4+j the descriptor dword j = pair[2j] | pair[2j+1]<<16, which it reads back from
+  // LDS after every lane has written its 16-bit pair there (into the feature's patch slot, dead once the windows are
+  // in registers; same wave, LDS in order: no barrier, as for the patches).
+  // Stores go to a wave-uniform base plus a 32-bit byte offset; lanes 12..15, slots past the list and records past
+  // the capacity store nothing: one compare against the lane's own limit.
+  char *__restrict__ outb = (char *)(feat + (int64_t)set * cap * 12) + (int64_t)base * 48;
+  const int32_t lim = k < 12 ? min(total, cap - base) : 0;
+  const uint32_t hdr_off = k == 0 ? 0u : (k == 1 ? 14u : 28u), hdr_bits = k < 2 ? 14u : (k == 3 ? 4u : 0u), hdr_sh = k < 2 ? (uint32_t)sh : 0u;
+  const bool is_hdr = k < 4;
+  const int32_t j = is_hdr ? 0 : k - 4;
   static_assert(16 * NF * 16 * 16 <= (int)sizeof(sLoc), "the patches reuse sLoc");
   __syncthreads();  // sLoc is dead from here on
   uint32_t *sPatch = (uint32_t *)sLoc + grp * (NF * 64);  // [feature of the trip][16 rows: 15 + lane 15's spare][4 dwords] of this lane group
+  typedef uint16_t u16alias __attribute__((may_alias));
   const int32_t rd0 = (dy + 5) * 4 + ((dx + 5) >> 2);         // first dword of the lane's window in a patch
-  const uint32_t psel = 0x03020100u + (uint32_t)((dx + 5) & 3) * 0x01010101u;  // v_perm selector of its first four bytes there
   auto process = [&](const Coords &q, const u32x4a1 (&prow)[NF]) {
-    const int32_t *fs = q.fs, *us = q.us, *vs = q.vs, *cs = q.cs;
-    const bool *lives = q.lives;
     uint32_t lo[NF][5], hi[NF][5];
-    uint32_t sel[NF];
-#pragma unroll
-    for (int32_t h = 0; h < NF; h++) sel[h] = psel;
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int32_t h = 0; h < NF; h++)
-      *(uint4 *)(sPatch + (h * 16 + k) * 4) = make_uint4(prow[h].x, prow[h].y, prow[h].z, prow[h].w);
+    for (int32_t h = 0; h < NF; h++)  // (bytes - 128: signed operands for v_dot4_i32_i8)
+      *(uint4 *)(sPatch + (h * 16 + k) * 4) = make_uint4(prow[h].x ^ 0x80808080u, prow[h].y ^ 0x80808080u, prow[h].z ^ 0x80808080u, prow[h].w ^ 0x80808080u);
 #pragma unroll
     for (int32_t h = 0; h < NF; h++)
 #pragma unroll
@@ -841,39 +894,31 @@ emit_features_kernel(VhImages im, VhGeom g, const uint64_t *__restrict__ rec,
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int32_t h = 0; h < NF; h++) {
-      const int32_t u = us[h], v = vs[h];
       // 5x5 Sobel pair at (u+dx, v+dy): du = smooth_y (x) deriv_x, dv = deriv_y (x) smooth_x
       // (filter.cpp:288-318 column pass, :132-171 / :79-127 row passes)
-      // With w = bytes x0..x0+3 and w' = bytes x0+1..x0+4 of a row, its sums are byte dot products
-      // (v_dot4_u32_u8, accumulating): a+2b-2d-e = w.(1,2,0,0) - w'.(0,0,2,1) and
-      // a+4b+6c+4d+e = w.(1,4,6,0) + w'.(0,0,4,1); the column weights (1,4,6,4,1) resp.
-      // (1,2,0,-2,-1) are folded into the byte weights, positive and negative parts apart.
-      uint32_t du_p = 0, du_n = 0, dv_p = 0, dv_n = 0;
+      // The 5 bytes of a window row lie in the aligned dwords {lo, hi}; a row's sum is two signed byte dot products
+      // (v_dot4_i32_i8, accumulating) with the lane's weight dwords (c_desc_w): the taps (1,2,0,-2,-1) resp.
+      // (1,4,6,4,1) times the column weight (1,4,6,4,1) resp. (1,2,0,-2,-1) of the row, 0 on the bytes outside the window.
+      // (the sums start at 128 << 7: the +128 that follows the >> 7, for free)
+      int32_t a_du = 128 << 7, a_dv = 128 << 7;
 #pragma unroll
       for (int32_t r = 0; r < 5; r++) {
-        const uint32_t w = __builtin_amdgcn_perm(hi[h][r], lo[h][r], sel[h]);
-        const uint32_t w1 = __builtin_amdgcn_perm(hi[h][r], lo[h][r], sel[h] + 0x01010101u);
-        const uint32_t sw = (r == 0 || r == 4) ? 1u : (r == 2 ? 6u : 4u);
-        du_p = __builtin_amdgcn_udot4(w, sw * 0x00000201u, du_p, false);
-        du_n = __builtin_amdgcn_udot4(w1, sw * 0x01020000u, du_n, false);
+        const int32_t wu = (r == 0 || r == 4) ? 0 : (r == 2 ? 4 : 2);
+        a_du = __builtin_amdgcn_sdot4((int32_t)lo[h][r], (int32_t)wt[wu], a_du, false);
+        a_du = __builtin_amdgcn_sdot4((int32_t)hi[h][r], (int32_t)wt[wu + 1], a_du, false);
         if (r != 2) {
-          const uint32_t dw = (r == 0 || r == 4) ? 1u : 2u;
-          uint32_t &acc = r < 2 ? dv_p : dv_n;
-          acc = __builtin_amdgcn_udot4(w, dw * 0x00060401u, acc, false);
-          acc = __builtin_amdgcn_udot4(w1, dw * 0x01040000u, acc, false);
+          const int32_t wv = 6 + 2 * (r < 2 ? r : r - 1);
+          a_dv = __builtin_amdgcn_sdot4((int32_t)lo[h][r], (int32_t)wt[wv], a_dv, false);
+          a_dv = __builtin_amdgcn_sdot4((int32_t)hi[h][r], (int32_t)wt[wv + 1], a_dv, false);
         }
       }
-      const int32_t a_du = (int32_t)(du_p - du_n), a_dv = (int32_t)(dv_p - dv_n);
       // arithmetic >>7, +128, unsigned saturation (filter.cpp:114-115,124 / :159-160,168)
-      const uint32_t du = (uint32_t)min(255, max(0, (a_du >> 7) + 128));
-      const uint32_t dv = (uint32_t)min(255, max(0, (a_dv >> 7) + 128));
-      const uint32_t pair = du | (dv << 8);
-      const uint32_t plo = __shfl(pair, gbase + 2 * j), phi = __shfl(pair, gbase + 2 * j + 1);
-      const uint32_t word = (((uint32_t)u << sh) & m_u) | (((uint32_t)v << sh) & m_v) | ((uint32_t)cs[h] & m_c) | ((plo | (phi << 16)) & m_d);
-      const int32_t fi = base + fs[h];
-      const bool okf = lives[h] && fi < cap;
-      if (okf && k < 12) out[(int64_t)fi * 12 + k] = (int32_t)word;
-      if (okf && k == 12) fuv[fi] = (uint32_t)(u << sh) | ((uint32_t)(v << sh) << 16);
+      const uint32_t du = (uint32_t)min(255, max(0, a_du >> 7));
+      const uint32_t dv = (uint32_t)min(255, max(0, a_dv >> 7));
+      ((u16alias *)(sPatch + h * 64))[k] = (uint16_t)(du | (dv << 8));
+      const uint32_t hdr = __builtin_amdgcn_ubfe(q.es[h], hdr_off, hdr_bits) << hdr_sh;
+      const uint32_t desc = sPatch[h * 64 + j];
+      if (q.fs[h] < lim) *(uint32_t *)(outb + (__umul24((uint32_t)q.fs[h], 48u) + 4u * (uint32_t)k)) = is_hdr ? hdr : desc;
     }
   };
   // two register sets, taken in turns: a copy from "next" to "current" would have to wait for the loads
