@@ -83,6 +83,7 @@ ABI_SYMBOLS = (
     "vh_refit_motion", "vh_group_refit_motion", "vh_match_refit_motion",
     "vh_group_post_device_dense", "vh_group_post_finish_device_dense",
     "vh_gain", "vh_group_set_gain", "vh_set_gain", "vh_group_gain", "vh_match_gain", "vh_group_gain_indices", "vh_match_gain_indices",
+    "vh_sequence_set_multi_stage", "vh_set_multi_stage_prior", "vh_group_set_multi_stage_prior",
 )
 
 
@@ -311,6 +312,7 @@ def _lib():
             "vh_group_set_gain": [vp, i32], "vh_set_gain": [vp, i32],
             "vh_group_gain": [vp, vp, vp], "vh_match_gain": [vp, vp, vp],
             "vh_group_gain_indices": [vp, vp, vp, vp, vp], "vh_match_gain_indices": [vp, vp, i32, vp, vp],
+            "vh_sequence_set_multi_stage": [vp, i32], "vh_set_multi_stage_prior": [vp, i32], "vh_group_set_multi_stage_prior": [vp, i32],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -453,6 +455,11 @@ class Matcher:
         """The vote and the statistics between the two passes on the GPU (vh_set_multi_stage_device): matchFeatures only
         queues work.  After setMultiStageMatching(True), before the first pushBack."""
         _check(_lib().vh_set_multi_stage_device(self._h, 1 if on else 0), "vh_set_multi_stage_device")
+
+    def setMultiStagePrior(self, on: bool = True):
+        """matchFeatures(2, Tr_delta) hands the motion estimate to both passes of multi-stage matching
+        (vh_set_multi_stage_prior): after setMultiStageMatching(True), before the first pushBack."""
+        _check(_lib().vh_set_multi_stage_prior(self._h, 1 if on else 0), "vh_set_multi_stage_prior")
 
     def getSparseMatches(self) -> np.ndarray:
         """The sparse list of pass 1 after the vote (multi-stage matching on)."""
@@ -628,6 +635,11 @@ class StreamGroup:
         """The vote and the statistics between the two passes on the GPU for every stream
         (vh_group_set_multi_stage_device): after setMultiStageMatching(True), before the first pushBack."""
         _check(_lib().vh_group_set_multi_stage_device(self._h, 1 if on else 0), "vh_group_set_multi_stage_device")
+
+    def setMultiStagePrior(self, on: bool = True):
+        """matchFeaturesPrior hands the motion estimates to both passes of multi-stage matching
+        (vh_group_set_multi_stage_prior): after multi-stage matching was switched on, before the first pushBack."""
+        _check(_lib().vh_group_set_multi_stage_prior(self._h, 1 if on else 0), "vh_group_set_multi_stage_prior")
 
     def getSparseMatches(self, stream: int) -> np.ndarray:
         """The sparse list of pass 1 after the vote (multi-stage matching on)."""
@@ -1053,6 +1065,23 @@ class SequenceGroup(StreamGroup):
         tr = np.ascontiguousarray(Tr_delta, dtype=np.float64).reshape(-1, 16)
         assert tr.shape[0] == n, (tr.shape, n)
         _check(_lib().vh_group_match_features_prior(self._h, int(method), _ptr(tr)), "vh_group_match_features_prior")
+
+    def setMultiStage(self, mode: int):
+        """Two-pass matching of stock libviso2 on every row (vh_sequence_set_multi_stage): 0 off, 1 with the vote and the
+        statistics on the host, 2 with both on the device.  Before the first pushBack, with param.multi_stage = 1;
+        getSparseMatches(row) then returns the voted sparse list of a row."""
+        _check(_lib().vh_sequence_set_multi_stage(self._h, int(mode)), "vh_sequence_set_multi_stage")
+        self._ms_mode = int(mode)
+
+    def setMultiStageMatching(self, on: bool = True):
+        """setMultiStage(1) / setMultiStage(0) (the group's own entry refuses a sequence handle)."""
+        self.setMultiStage(1 if on else 0)
+
+    def setMultiStageDevice(self, on: bool = True):
+        """setMultiStage(2), or back to setMultiStage(1): after setMultiStageMatching(True), as on a group."""
+        if not getattr(self, "_ms_mode", 0):
+            raise VisoHipError(VH_ERR_STATE, "vh_sequence_set_multi_stage")
+        self.setMultiStage(2 if on else 1)
 
     def setReconstruction(self, recon: "ReconParams | None", history_frames: int = 0):
         """3-d points from the tracks that end, gathered on the device (vh_sequence_set_reconstruction): before the first

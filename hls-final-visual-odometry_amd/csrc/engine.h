@@ -434,6 +434,8 @@ struct Group {
   // vh_group_set_multi_stage_device: the vote and the statistics between the passes run on the device, behind pass 1 on the
   // sparse group's post stream (multi_stage_ranges_device); ms_vb holds the S voted sparse lists
   bool ms_device = false;
+  // vh_group_set_multi_stage_prior: a match call with a motion estimate hands it to both passes (quad only); off: refused
+  bool ms_prior = false;
   static constexpr int32_t kMsVoteLanes = 16;  // lists per wave of the sweep
 
   bool allocated = false;
@@ -508,7 +510,9 @@ struct Group {
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
   // whose detector runs at the sparse NMS distance (matcher.cpp:621-628) -- its dense set IS the sparse set -- on this
   // group's detect stream, behind every push.  A match runs pass 1 on it, votes and takes the statistics on the host,
-  // and searches this group's sets inside rg.d_ranges (kernels_ranged.hip).
+  // and searches this group's sets inside rg.d_ranges (kernels_ranged.hip).  On a sequence handle (vh_sequence_set_multi_stage)
+  // the sparse group is a sequence group too: it takes the same chunks, rotates its ring with this one's and resolves the
+  // rows' sets through the same vh_row_set, so a frame's sparse set is detected once and serves both of its pairs.
   std::unique_ptr<Group> sparse;
 
   // ---- engine.hip ----
@@ -559,9 +563,10 @@ struct Group {
   int32_t match_recover();
   size_t n_ranges() const { return (size_t)S * sets.ubn * sets.vbn * 16; }
   int32_t ensure_ranges(bool staging = true);
-  int32_t multi_stage_ranges(int32_t method);
+  int32_t multi_stage_ranges(int32_t method, const double *tr16);
   int32_t ensure_ms_vote();
-  int32_t multi_stage_ranges_device(int32_t method);
+  int32_t multi_stage_ranges_device(int32_t method, const double *tr16);
+  int32_t stage_prior(const double *tr16, int32_t buf, int32_t rows, hipStream_t ms);
   int32_t load_ranges(const float *ranges);
   int32_t match(int32_t method, const double *tr16 = nullptr, bool ranged = false);
   int32_t match_call(int32_t method, const double *tr16, bool ranged);

@@ -306,13 +306,8 @@ int32_t vh_sequence_position(const vh_group *g, int64_t *first_frame, int32_t *n
   *n_frames = gq->seq_n;
   return VH_OK;
 }
-int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on) {
-  Group *gq = (Group *)g;
-  if (!gq) return VH_ERR_INVALID_ARG;
-  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: the sparse sets belong to every frame of the ring
-  if (on && !gq->p.multi_stage) return VH_ERR_INVALID_ARG;
-  if (gq->seq) return VH_ERR_UNSUPPORTED;
-  if (!on) { gq->sparse.reset(); gq->ms_device = false; return VH_OK; }
+// the sparse group of multi-stage matching: the same rows (a sequence handle's: a sequence group), the sparse NMS distance
+static int32_t make_sparse(Group *gq) {
   if (gq->sparse) return VH_OK;
   vh_params q = gq->p;
   q.nms_n = gq->p.nms_n * 4;  // matcher.cpp:621-623
@@ -322,9 +317,42 @@ int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on) {
   const int32_t rc = group_new(&q, gq->device, gq->S, 0, 0, &sp);
   if (rc) return rc;
   sp->stream = gq->stream;  // (its own detect stream stays idle, or carries its searches in a small group)
+  sp->seq = gq->seq;
   gq->sparse.reset(sp);
   return VH_OK;
 }
+static void drop_sparse(Group *gq) { gq->sparse.reset(); gq->ms_device = gq->ms_prior = false; }
+int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: the sparse sets belong to every frame of the ring
+  if (on && !gq->p.multi_stage) return VH_ERR_INVALID_ARG;
+  if (gq->seq) return VH_ERR_UNSUPPORTED;  // (vh_sequence_set_multi_stage)
+  if (!on) { drop_sparse(gq); return VH_OK; }
+  return make_sparse(gq);
+}
+int32_t vh_sequence_set_multi_stage(vh_group *g, int32_t mode) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (!gq->seq) return VH_ERR_UNSUPPORTED;  // a group or a lone matcher keeps its own entries
+  if (mode < 0 || mode > 2) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;
+  if (mode && !gq->p.multi_stage) return VH_ERR_INVALID_ARG;
+  if (!mode) { drop_sparse(gq); return VH_OK; }
+  const int32_t rc = make_sparse(gq);
+  if (rc) return rc;
+  gq->ms_device = mode == 2;
+  return VH_OK;
+}
+int32_t vh_group_set_multi_stage_prior(vh_group *g, int32_t on) {
+  Group *gq = (Group *)g;
+  if (!gq) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;      // before the first push only, like the mode it belongs to
+  if (on && !gq->sparse) return VH_ERR_STATE;  // multi-stage matching first
+  gq->ms_prior = on != 0;
+  return VH_OK;
+}
+int32_t vh_set_multi_stage_prior(vh_matcher *m, int32_t on) { return vh_group_set_multi_stage_prior((vh_group *)m, on); }
 int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on) { return vh_group_set_multi_stage_matching((vh_group *)m, on); }
 int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n) {
   Group *gq = (Group *)g; ENTER(gq);

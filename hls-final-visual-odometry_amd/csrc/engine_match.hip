@@ -70,13 +70,15 @@ int32_t Group::ensure_ranges(bool staging) {
 
 // Pass 1 of multi-stage matching and the statistics: the method's matching on the sparse sets, the vote on the host
 // (flow and quad lists), one range table per stream into rg.h_ranges, queued for the match stream.
-int32_t Group::multi_stage_ranges(int32_t method) {
-  int32_t rc = sparse->match(method);
+int32_t Group::multi_stage_ranges(int32_t method, const double *tr16) {
+  int32_t rc = sparse->match(method, tr16);
   if (rc) return rc;
   auto t0 = std::chrono::steady_clock::now();
-  for (int32_t s = 0; s < S; s++) if ((rc = sparse->fetch_matches(s))) return rc;
+  // a sequence handle: the rows of the chunk only -- the others hold no pair, their sparse lists are empty and their ranges +-R
+  const int32_t rows = seq ? seq_n : S;
+  for (int32_t s = 0; s < rows; s++) if ((rc = sparse->fetch_matches(s))) return rc;
   const int32_t threads = (int32_t)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if ((rc = sparse->remove_outliers(0, S, threads))) return rc;
+  if ((rc = sparse->remove_outliers(0, rows, threads))) return rc;
   prof_host("sparse_vote_host", t0);
   // (the table the previous match's pass 2 read has gone up: the copy below is the next thing on the match stream)
   VH_HIP(hipStreamSynchronize(match_stream));
@@ -85,7 +87,7 @@ int32_t Group::multi_stage_ranges(int32_t method) {
   std::vector<float> fr(per);
   for (int32_t s = 0; s < S; s++) {
     const std::vector<vh_p_match> &pm = sparse->host_matches[s];
-    if ((rc = prior_statistics(p, dims, method, pm.data(), (int32_t)pm.size(), fr.data()))) return rc;
+    if ((rc = prior_statistics(p, dims, method, pm.data(), s < rows ? (int32_t)pm.size() : 0, fr.data()))) return rc;
     for (size_t k = 0; k < per; k++) rg.h_ranges[s * per + k] = range_bound(fr[k], (k & 1) == 0);
   }
   prof_host("statistics_host", t0);
@@ -107,8 +109,8 @@ int32_t Group::ensure_ms_vote() {
   return VH_OK;
 }
 
-int32_t Group::multi_stage_ranges_device(int32_t method) {
-  int32_t rc = sparse->match(method);
+int32_t Group::multi_stage_ranges_device(int32_t method, const double *tr16) {
+  int32_t rc = sparse->match(method, tr16);
   if (rc) return rc;
   hipStream_t vs = sparse->post_stream;
   {
@@ -157,9 +159,10 @@ int32_t Group::match(int32_t method, const double *tr16, bool ranged) {
 int32_t Group::match_call(int32_t method, const double *tr16, bool ranged) {
   if (method < 0 || method > 2) return VH_ERR_INVALID_ARG;
   if (!allocated || failed) return VH_ERR_STATE;
-  if (sparse && tr16) return VH_ERR_UNSUPPORTED;  // the motion prior does not combine with multi-stage matching
+  if (sparse && tr16 && !ms_prior) return VH_ERR_UNSUPPORTED;  // the motion prior combines with multi-stage matching by its own switch only
   if (tr16 && method != VH_METHOD_QUAD) tr16 = nullptr;  // (stock libviso2 uses the prediction in the quad circle only)
   if (tr16 && !(p.f > 0 && p.base > 0)) return VH_ERR_STATE;  // setIntrinsics first
+  if (sparse && tr16) { sparse->p.f = p.f; sparse->p.cu = p.cu; sparse->p.cv = p.cv; sparse->p.base = p.base; }  // (pass 1 predicts with the same camera)
   if (match_dirty) { const int32_t rr = match_recover(); if (rr) return rr; }
   if (tr16 && !pri.d_prior_tr) { const int32_t rt = dmalloc(&pri.d_prior_tr, 16 * (size_t)S, false); if (rt) return rt; }
   if (tr16 && !pri.h_prior_tr) VH_HIP(pri.h_prior_tr.alloc(2 * 16 * (size_t)S, hipHostMallocDefault));
@@ -173,11 +176,11 @@ int32_t Group::match_call(int32_t method, const double *tr16, bool ranged) {
     int32_t rr = ensure_ranges(false);
     if (rr) return rr;
     if ((rr = ensure_ms_vote())) return rr;
-    if ((rr = multi_stage_ranges_device(method))) { match_dirty = true; return rr; }
+    if ((rr = multi_stage_ranges_device(method, tr16))) { match_dirty = true; return rr; }
   } else if (sparse) {
     int32_t rr = ensure_ranges();
     if (rr) return rr;
-    if ((rr = multi_stage_ranges(method))) return rr;
+    if ((rr = multi_stage_ranges(method, tr16))) return rr;
   }
   const int32_t rc = match_queued(method, tr16, (sparse || ranged) ? rg.d_ranges : nullptr);
   if (rc) { match_dirty = true; trk_cur_valid = false; }
@@ -203,7 +206,16 @@ int32_t Group::match_queued(int32_t method, const double *tr16, const int32_t *r
     // stream also waits for the previous step's post-processing -- and the mask's epoch advances on the match stream.
     if (ev_post_valid[buf ^ 1]) VH_HIP(hipStreamWaitEvent(ms, ev_post[buf ^ 1], 0));
     if (method == VH_METHOD_FLOW) { const int32_t re = mask_epoch(ms); if (re) return re; }
-    { Scope sc(this, "ranged", ms); vh_launch_ranged_circle(sets, a, method, ranges, mt.d_chain2[buf], mt.d_mask, mt.epoch, mt.d_mchunk2[buf], ms); }
+    if (tr16) {  // (quad: pass 2 hands the estimate to its second hop, as pass 1 did on the sparse sets)
+      const int32_t rp = stage_prior(tr16, buf, a.rows, ms);
+      if (rp) return rp;
+      const VhPriorArgs pa{pri.d_prior_tr, p.f, p.cu, p.cv, p.base};
+      Scope sc(this, "ranged", ms);
+      vh_launch_ranged_circle_prior(sets, a, ranges, pa, mt.d_chain2[buf], mt.d_mchunk2[buf], ms);
+    } else {
+      Scope sc(this, "ranged", ms);
+      vh_launch_ranged_circle(sets, a, method, ranges, mt.d_chain2[buf], mt.d_mask, mt.epoch, mt.d_mchunk2[buf], ms);
+    }
     VH_HIP(hipGetLastError());
     VH_HIP(hipEventRecord(ev_tables[buf], ms));
     return match_post(method, a, buf, true, false);
@@ -224,15 +236,22 @@ int32_t Group::match_queued(int32_t method, const double *tr16, const int32_t *r
   { Scope sc(this, "match", ms); vh_launch_match(sets, a, mt.d_best2[buf], mt.d_redo + (size_t)buf * S, spec ? 1 : 0, gx_hint, units * 1280, ms); }
   VH_HIP(hipGetLastError());
   if (tr16) {  // hop 2 of the circle, per driving feature, behind the 1p -> 2p table of the launch above
-    double *ht = pri.h_prior_tr + (size_t)buf * 16 * S;
-    VH_HIP(hipEventSynchronize(ev_tables[buf]));  // (recorded behind the copy that last read this slot, two matches ago; at once if never recorded)
-    memcpy(ht, tr16, sizeof(double) * 16 * (size_t)a.rows);  // (a sequence chunk: one per frame pair)
-    VH_HIP(hipMemcpyAsync(pri.d_prior_tr, ht, sizeof(double) * 16 * (size_t)a.rows, hipMemcpyHostToDevice, ms));
+    const int32_t rp = stage_prior(tr16, buf, a.rows, ms);
+    if (rp) return rp;
     { Scope sc(this, "quad_prior", ms); vh_launch_quad_prior(sets, a, pri.d_prior_tr, p.f, p.cu, p.cv, p.base, mt.d_best2[buf], ms); }
     VH_HIP(hipGetLastError());
   }
   VH_HIP(hipEventRecord(ev_tables[buf], ms));
   return match_post(method, a, buf, false, spec);
+}
+
+// the caller's motion estimates, one per row, to pri.d_prior_tr on `ms` through the page-locked slot of table buffer buf
+int32_t Group::stage_prior(const double *tr16, int32_t buf, int32_t rows, hipStream_t ms) {
+  double *ht = pri.h_prior_tr + (size_t)buf * 16 * S;
+  VH_HIP(hipEventSynchronize(ev_tables[buf]));  // (recorded behind the copy that last read this slot, two matches ago; at once if never recorded)
+  memcpy(ht, tr16, sizeof(double) * 16 * (size_t)rows);  // (a sequence chunk: one per frame pair)
+  VH_HIP(hipMemcpyAsync(pri.d_prior_tr, ht, sizeof(double) * 16 * (size_t)rows, hipMemcpyHostToDevice, ms));
+  return VH_OK;
 }
 
 // The flow method's pixel mask holds (epoch, feature index) per pixel: a new epoch per match call, the mask cleared on

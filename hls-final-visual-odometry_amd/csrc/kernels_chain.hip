@@ -13,6 +13,7 @@
 // The rules around the hops (circle below) are the same, and both kernels write the same things: index tuple,
 // coordinate tuple, pixel-mask bid, survivors per emission chunk.  flow_keep, refine and emit_matches follow either.
 #include "vh_findmatch.h"
+#include "vh_prior.h"
 #include "vh_wave.h"
 #include <algorithm>
 
@@ -136,11 +137,53 @@ __device__ __forceinline__ int32_t find_ranged(const VhSets &s, int32_t qset, in
   return key == ~0ull ? 0 : s.s_idx[(int64_t)cset * cap + (uint32_t)key];
 }
 
+// The same findMatch with the motion prior's distance term (vh_prior.h; src/matcher.cpp:257-264) for the prediction
+// (u_, v_): the cost is a double, so the key trick does not apply.  Every lane keeps the first strict minimum below
+// 10000000 (:222) of the candidates it visits, in ascending position; the group reduces lexicographically on (cost,
+// position), which is the first strict minimum of the reference's visiting order in any arrival order.  A cost that is
+// not below 10000000 (an infinite prediction) or does not compare (NaN) is never accepted: min_ind = 0 (:221).
+__device__ __forceinline__ int32_t find_ranged_prior(const VhSets &s, int32_t qset, int32_t iq, int32_t cset, const int4 rg, int32_t g, double u_,
+                                                     double v_) {
+  const int64_t cap = s.cap;
+  const int32_t *__restrict__ q = s.feat + ((int64_t)qset * cap + iq) * 12;
+  const int32_t u1 = q[0], v1 = q[1], c = q[3];
+  const uint4 a0 = *(const uint4 *)(q + 4), a1 = *(const uint4 *)(q + 8);
+  const VhWindow w = {u1 + rg.x, u1 + rg.y, v1 + rg.z, v1 + rg.w};  // (the hop is a flow stage)
+  const VhBins b = bins_of_interest(s, w);
+  const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
+  const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * cap;
+  const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * cap * 8);
+  double min_cost = 10000000;
+  int32_t min_pos = INT32_MAX;
+  if (b.vb0 <= b.vb1) {
+    for (int32_t ub = b.ub0; ub <= b.ub1; ub++) {
+      const int32_t row = (c * s.ubn + ub) * s.vbn;
+      const int32_t p1 = cbs[row + b.vb1 + 1];
+      for (int32_t p = cbs[row + b.vb0] + g; p < p1; p += VH_RANGED_G) {
+        const uint32_t uv2 = cuv[p];
+        if (outside_window(uv2, w)) continue;
+        const double cost = vh_prior_cost(sad32(a0, a1, cdesc[2 * (int64_t)p], cdesc[2 * (int64_t)p + 1], 0), uv2, u_, v_);
+        if (cost < min_cost) { min_cost = cost; min_pos = p; }
+      }
+    }
+  }
+#pragma unroll
+  for (int32_t d = VH_RANGED_G / 2; d >= 1; d >>= 1) {
+    const double oc = __longlong_as_double((long long)vh_shfl_xor_u64((uint64_t)__double_as_longlong(min_cost), d));
+    const int32_t op = __shfl_xor(min_pos, d);
+    if (oc < min_cost || (oc == min_cost && op < min_pos)) { min_cost = oc; min_pos = op; }
+  }
+  return min_pos == INT32_MAX ? 0 : s.s_idx[(int64_t)cset * cap + min_pos];
+}
+
 // The hops are searches inside the ranges of the driver's statistics bin; lane g == 0 of a driver's group writes.
 // ranges: [row][ubn * vbn][4 stages]{u_min, u_max, v_min, v_max} int32
-__global__ void __launch_bounds__(256) ranged_circle_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restrict__ ranges,
-                                                            int4 *__restrict__ chain, uint32_t *__restrict__ mask, uint32_t epoch,
-                                                            int32_t *__restrict__ mchunk, int32_t nchm) {
+// PRIOR (quad only): stage 1, previous right -> current right, carries the distance term for the driver's prediction
+// under pa.tr[row]; its accept window stays query + range[stage 1], the other three stages keep the integer key.
+template <bool PRIOR>
+__device__ __forceinline__ void ranged_circle(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *__restrict__ ranges,
+                                              int4 *__restrict__ chain, uint32_t *__restrict__ mask, uint32_t epoch,
+                                              int32_t *__restrict__ mchunk, int32_t nchm, const VhPriorArgs &pa) {
   const int32_t stream = blockIdx.y;
   const CircleSets cs = circle_sets(s, a, stream);
   const int4 *__restrict__ rrow = ranges + (int64_t)stream * (s.ubn * s.vbn) * 4;
@@ -155,10 +198,25 @@ __global__ void __launch_bounds__(256) ranged_circle_kernel(VhSets s, VhMatchArg
     // (the 64 / G drivers of a wave lie in one emission chunk of 256 drivers)
     circle(s, cs, method, stream, i, g == 0,
            [&](int32_t stage, int32_t qrole, int32_t iq, int32_t crole, bool flow) __attribute__((always_inline)) {
+             if (PRIOR && stage == 1) {
+               const int32_t u2p = s.feat[((int64_t)cs.set[qrole] * s.cap + iq) * 12];  // the query of this hop: previous right feature i2p
+               const VhPrediction pr = vh_prior_predict(pa.tr + 16 * (int64_t)stream, pa.f, pa.cu, pa.cv, pa.base, (int32_t)(uvi & 0xFFFFu),
+                                                        (int32_t)(uvi >> 16), u2p);
+               return find_ranged_prior(s, cs.set[qrole], iq, cs.set[crole], rg[stage], g, pr.u, pr.v);
+             }
              return find_ranged(s, cs.set[qrole], iq, cs.set[crole], rg[stage], flow, a.disp_tol, g);
            },
            chain + 2 * (int64_t)stream * s.cap, mask, epoch, mchunk + stream * nchm);
   }
+}
+__global__ void __launch_bounds__(256) ranged_circle_kernel(VhSets s, VhMatchArgs a, int32_t method, const int4 *__restrict__ ranges,
+                                                            int4 *__restrict__ chain, uint32_t *__restrict__ mask, uint32_t epoch,
+                                                            int32_t *__restrict__ mchunk, int32_t nchm) {
+  ranged_circle<false>(s, a, method, ranges, chain, mask, epoch, mchunk, nchm, VhPriorArgs{});
+}
+__global__ void __launch_bounds__(256) ranged_circle_prior_kernel(VhSets s, VhMatchArgs a, const int4 *__restrict__ ranges, int4 *__restrict__ chain,
+                                                                  int32_t *__restrict__ mchunk, int32_t nchm, VhPriorArgs pa) {
+  ranged_circle<true>(s, a, 2, ranges, chain, nullptr, 0u, mchunk, nchm, pa);
 }
 
 // ------------------------------------------------------------------ flow_keep
@@ -313,4 +371,11 @@ void vh_launch_ranged_circle(const VhSets &s, const VhMatchArgs &a, int32_t meth
   const int32_t per_wg = 256 / VH_RANGED_G;
   dim3 grid(std::min(std::max((s.cap + per_wg - 1) / per_wg, 1), 2048), a.rows);
   hipLaunchKernelGGL(ranged_circle_kernel, grid, dim3(256), 0, st, s, a, method, (const int4 *)ranges, chain, mask, epoch, mchunk, nchm);
+}
+void vh_launch_ranged_circle_prior(const VhSets &s, const VhMatchArgs &a, const int32_t *ranges, const VhPriorArgs &pa, int4 *chain, int32_t *mchunk,
+                                   hipStream_t st) {
+  const int32_t nchm = (s.cap + 255) / 256;
+  const int32_t per_wg = 256 / VH_RANGED_G;
+  dim3 grid(std::min(std::max((s.cap + per_wg - 1) / per_wg, 1), 2048), a.rows);
+  hipLaunchKernelGGL(ranged_circle_prior_kernel, grid, dim3(256), 0, st, s, a, (const int4 *)ranges, chain, mchunk, nchm, pa);
 }

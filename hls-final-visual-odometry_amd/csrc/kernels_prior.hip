@@ -10,7 +10,7 @@
 // reference's order (u-bin, v-bin, list position = ascending bin-order position) with the literal accept test and a
 // double-precision compare.  Built with -ffp-contract=off: du * du + dv * dv rounds twice, as on the reference's x86 build.
 #include "vh_findmatch.h"
-#include <math.h>
+#include "vh_prior.h"
 
 namespace {
 
@@ -36,11 +36,7 @@ __device__ __forceinline__ int32_t find_match_prior(const VhSets &s, int32_t qse
     for (int32_t p = cbs[row + b.vb0]; p < cbs[row + b.vb1 + 1]; p++) {
       const uint32_t uv2 = cuv[p];
       if (outside_window(uv2, w)) continue;
-      double cost = (double)sad32(a0, a1, cdesc[2 * (int64_t)p], cdesc[2 * (int64_t)p + 1], 0);
-      if (u_ >= 0 && v_ >= 0) {
-        const double du = (double)(int32_t)(uv2 & 0xFFFFu) - u_, dv = (double)(int32_t)(uv2 >> 16) - v_;
-        cost += 4 * sqrt(du * du + dv * dv);
-      }
+      const double cost = vh_prior_cost(sad32(a0, a1, cdesc[2 * (int64_t)p], cdesc[2 * (int64_t)p + 1], 0), uv2, u_, v_);
       if (cost < min_cost) { min_cost = cost; min_pos = p; }
     }
   }
@@ -72,16 +68,9 @@ __global__ void __launch_bounds__(128) quad_prior_kernel(VhSets s, VhMatchArgs a
     const uint32_t uv1 = s.f_uv[(int64_t)set1p * cap + i];
     const int32_t u2p = s.feat[((int64_t)set2p * cap + i2p) * 12];  // the query of this hop: previous right feature i2p
     const int32_t u1p = (int32_t)(uv1 & 0xFFFFu), v1p = (int32_t)(uv1 >> 16);
-    // the prediction [upstream-recollection]
-    double d = (double)u1p - (double)u2p;
-    if (d < 1.0) d = 1.0;
-    const double x1p = ((double)u1p - cu) * base / d, y1p = ((double)v1p - cv) * base / d, z1p = f * base / d;
-    const double x2c = t[0] * x1p + t[1] * y1p + t[2] * z1p + t[3] - base;
-    const double y2c = t[4] * x1p + t[5] * y1p + t[6] * z1p + t[7];
-    const double z2c = t[8] * x1p + t[9] * y1p + t[10] * z1p + t[11];
-    const double u_ = f * x2c / z2c + cu, v_ = f * y2c / z2c + cv;
+    const VhPrediction pr = vh_prior_predict(t, f, cu, cv, base, u1p, v1p, u2p);
     // flow search window; table slot 1 is indexed by the DRIVING feature here (kernels_chain.hip: chain_kernel, a.prior)
-    T[1 * cap + i] = find_match_prior(s, set2p, i2p, set2c, a.radius, a.radius, u_, v_);
+    T[1 * cap + i] = find_match_prior(s, set2p, i2p, set2c, a.radius, a.radius, pr.u, pr.v);
   }
 }
 

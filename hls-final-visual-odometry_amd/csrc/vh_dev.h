@@ -244,6 +244,14 @@ void vh_launch_flow_keep(const VhSets &s, const VhMatchArgs &a, int4 *chain, con
 // first kernel writes (flow: vh_launch_flow_keep follows)
 void vh_launch_ranged_circle(const VhSets &s, const VhMatchArgs &a, int32_t method, const int32_t *ranges, int4 *chain, uint32_t *mask,
                              uint32_t epoch, int32_t *mchunk, hipStream_t st);
+// The motion prior of quad matching: tr [rows][16] row-major 4x4 per row of the launch, and the intrinsics of vh_set_intrinsics
+struct VhPriorArgs {
+  const double *tr;
+  double f, cu, cv, base;
+};
+// the quad circle of pass 2 with the prior's distance term on its second hop (vh_prior.h); writes what vh_launch_ranged_circle writes
+void vh_launch_ranged_circle_prior(const VhSets &s, const VhMatchArgs &a, const int32_t *ranges, const VhPriorArgs &pa, int4 *chain, int32_t *mchunk,
+                                   hipStream_t st);
 // ref: refined coordinates of the step (vh_launch_refine), or null: the chain's own
 void vh_launch_emit_matches(const VhSets &s, const VhMatchArgs &a, int32_t method, const int4 *chain,
                             void *matches, int32_t mcap, int32_t *match_count, int32_t *overflow,

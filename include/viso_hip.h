@@ -260,8 +260,9 @@ int32_t vh_match(const vh_params *p, int32_t device, const int32_t dims[3], int3
  * see it.  Off (the default), nothing is allocated or launched and p.multi_stage keeps its only other meaning
  * (vh_compute_features hands out the sparse set).
  * Before the first push only (VH_ERR_STATE afterwards); on = 1 needs p.multi_stage = 1 (VH_ERR_INVALID_ARG);
- * a sequence handle (vh_sequence_create) does not support the mode: VH_ERR_UNSUPPORTED.  The motion prior does not
- * combine with it: vh_match_features / vh_group_match_features_prior with Tr_delta16 != NULL return VH_ERR_UNSUPPORTED.
+ * a sequence handle (vh_sequence_create) has its own entry, vh_sequence_set_multi_stage, and answers these two with
+ * VH_ERR_UNSUPPORTED.  The motion prior combines with the mode through vh_(group_)set_multi_stage_prior only: without
+ * it vh_match_features / vh_group_match_features_prior with Tr_delta16 != NULL return VH_ERR_UNSUPPORTED.
  * The vote between the passes runs on the host: a match call waits for pass 1 (DESIGN.md section 6 has the cost),
  * unless vh_set_multi_stage_device moves it to the device. */
 int32_t vh_set_multi_stage_matching(vh_matcher *m, int32_t on);
@@ -271,7 +272,8 @@ int32_t vh_group_set_multi_stage_matching(vh_group *g, int32_t on);
  * pass 2 behind them.  A match call then only queues work, like every other match call of the library: no wait, no
  * transfer of lists, no host threads.  Lists and ranges equal the host form's (off, the default: that form, unchanged).
  * Before the first push only (VH_ERR_STATE afterwards); on = 1 needs multi-stage matching switched on already
- * (VH_ERR_STATE); a sequence handle: VH_ERR_UNSUPPORTED.  Switching multi-stage matching off clears it.
+ * (VH_ERR_STATE); a sequence handle: VH_ERR_UNSUPPORTED (vh_sequence_set_multi_stage, mode 2).  Switching multi-stage
+ * matching off clears it.
  * A sparse list the device vote refuses (truncated, above 65 535 records, more pending flips than its stack holds) gets
  * +-match_radius in every bin, for which pass 2 is single-stage matching: the match call returns VH_OK, and
  * vh_(group_)get_sparse_matches returns the refusal's code for that stream (VH_ERR_CAPACITY / VH_ERR_UNSUPPORTED) with
@@ -283,6 +285,33 @@ int32_t vh_group_set_multi_stage_device(vh_group *g, int32_t on);
  * In device mode the list comes from the vote buffer, and the call waits for the vote. */
 int32_t vh_get_sparse_matches(vh_matcher *m, vh_p_match *out, int32_t cap, int32_t *n);
 int32_t vh_group_get_sparse_matches(vh_group *g, int32_t stream, vh_p_match *out, int32_t cap, int32_t *n);
+/* Multi-stage matching on a sequence handle (vh_sequence_create).  mode 0: off; 1: the vote and the statistics between
+ * the passes on the host (as vh_group_set_multi_stage_matching); 2: both on the device (as vh_group_set_multi_stage_device
+ * on top of it).  Row r of a chunk pushed at position F holds the pair F + r - 1 -> F + r, and its list is the list of a
+ * lone matcher with vh_set_multi_stage_matching on that was pushed frame F + r - 1, then frame F + r, byte for byte, for
+ * every method.  The sparse sets live in a sequence handle of their own that takes the same chunks: row 0 links to the
+ * last row of the previous chunk in the sparse pass as in the dense one (a chunk that was pushed and never matched
+ * included), and a frame's sparse set is detected once.  Rows that hold no pair (row 0 of the first chunk, rows >=
+ * n_frames) have an empty sparse list, ranges of +-match_radius and an empty list.  Every reader of the lists sees the
+ * list of pass 2, as on a group; vh_group_get_sparse_matches(g, row, ...) returns the voted pass-1 list of the row (mode
+ * 2: the refusal's code with *n = 0 for a list the device vote refused, whose row was matched over the full window).
+ * vh_group_device_bytes counts the sparse handle's arrays and, in mode 2, the vote buffer of max_frames lists.
+ * Before the first push only (VH_ERR_STATE afterwards); mode outside 0..2: VH_ERR_INVALID_ARG; mode > 0 needs
+ * p.multi_stage = 1 (VH_ERR_INVALID_ARG); a group or a lone matcher: VH_ERR_UNSUPPORTED (they keep their own entries). */
+int32_t vh_sequence_set_multi_stage(vh_group *g, int32_t mode);
+/* The motion prior together with multi-stage matching [upstream-recollection: stock matchFeatures hands Tr_delta to both
+ * passes].  On, vh_match_features(m, 2, Tr), vh_group_match_features_prior and its sequence form (one Tr per row) are
+ * honoured for the quad method: pass 1 is the prior's quad matching on the sparse sets, and pass 2 adds the term to the
+ * second hop of the circle (previous right -> current right) -- the accept window stays query + range[bin of the
+ * driver][stage 1], the cost becomes SAD + 4 * sqrt(du * du + dv * dv) in double around the prediction of the DRIVING
+ * feature (csrc/vh_prior.h), added only when both of its coordinates are >= 0, first strict minimum below 10000000 in the
+ * reference's visiting order, min_ind = 0 when nothing is accepted (src/matcher.cpp:221-264).  Flow and stereo ignore the
+ * estimate, as single-stage matching does.  VH_ERR_STATE from the match call without intrinsics (f, base > 0).
+ * Off (the default): such a call returns VH_ERR_UNSUPPORTED, as before.  Lone matchers, groups and sequence handles;
+ * before the first push only and after multi-stage matching was switched on (VH_ERR_STATE otherwise); switching
+ * multi-stage matching off clears it. */
+int32_t vh_set_multi_stage_prior(vh_matcher *m, int32_t on);
+int32_t vh_group_set_multi_stage_prior(vh_group *g, int32_t on);
 /* computePriorStatistics on caller-owned records (host function, needs no device): ranges[nb][4][4] float, nb = ubn * vbn
  * statistics bins of matching's grid for dims (src/matcher.cpp:282-283), bin = v_bin * ubn + u_bin, then stage 0..3, then
  * u_min, u_max, v_min, v_max relative to the query of the stage.  Each match contributes its displacement per stage

@@ -129,6 +129,15 @@ class Matcher {
     return rc == VH_OK;
   }
 
+  // The motion prior together with multi-stage matching (vh_set_multi_stage_prior): a Tr_delta handed to the library's
+  // quad matching then goes to both passes.  After setMultiStageMatching(true), before the first pushBack.
+  bool setMultiStagePrior(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_multi_stage_prior(handle, on ? 1 : 0);
+    if (rc != VH_OK) report("setMultiStagePrior", rc);
+    return rc == VH_OK;
+  }
+
   // Feature tracks (vh_set_track_linking): every matchFeatures also links its list to the list of the previous pair on
   // the GPU.  Off by default; before the first pushBack, returns false (and says why) otherwise.  The tracks describe
   // the list as matching left it, before removeOutliers: read them with outlier_removal = false, or link the voted
