@@ -25,6 +25,7 @@ from . import synth  # noqa: F401  (synthetic KITTI-shaped frames)
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VISO_HIP_LIB") or os.path.join(HERE, "libviso_hip.so")  # override: experiment builds
 CHECK_LIB_PATH = os.path.join(HERE, "libviso_hip_check.so")  # the -DVH_CHECK build (tests only)
+NOSNAKE_LIB_PATH = os.path.join(HERE, "libviso_hip_nosnake.so")  # the -DVH_SNAKE=0 build: flow tiles over the plain bin order (tests only)
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.normpath(os.path.join(HERE, "..", "include"))
 
@@ -211,11 +212,13 @@ class VisoHipError(RuntimeError):
 
 def build(verbose: bool = False) -> str:
     """Compile every HIP source for gfx950 into libviso_hip.so (in-tree), and the -DVH_CHECK
-    variant libviso_hip_check.so (index invariants verified on the device, csrc/vh_dev.h) that
-    tests/ run a part of the suite on."""
+    variant libviso_hip_check.so (index invariants verified on the device, csrc/vh_dev.h) and the
+    -DVH_SNAKE=0 variant libviso_hip_nosnake.so that tests/ run a part of the suite on."""
     cmd = ["make", "-C", CSRC, "-j4"] + ([] if verbose else ["-s"])
     subprocess.check_call(cmd)
     subprocess.check_call(cmd + ["VARIANT=check"])
+    # (only the two units that read the switch are compiled again; the other objects are the shipped build's)
+    subprocess.check_call(cmd + ["VARIANT=nosnake", "EXTRA=-DVH_SNAKE=0", "ONLY=kernels_bin kernels_match"])
     return LIB_PATH
 
 

@@ -214,6 +214,7 @@ int32_t Group::allocate(const int32_t d[3]) {
   if ((rc = dmalloc(&sets.r_pos, ns * cap, false))) return rc;
   if ((rc = dmalloc(&sets.tiles, ns * sets.max_tiles, false))) return rc;
   if ((rc = dmalloc(&sets.tile_cnt, ns, true))) return rc;
+  if ((rc = dmalloc(&sets.snake_pos, ns * cap, false))) return rc;
   if ((rc = dmalloc(&sets.check, 4, true))) return rc;
   if ((rc = dmalloc(&det.d_rec, 2 * (size_t)S * std::max(g.nblocks, 1), false))) return rc;
   if ((rc = dmalloc(&det.d_chunk_count, 2 * (size_t)S * g.nchunks, true))) return rc;

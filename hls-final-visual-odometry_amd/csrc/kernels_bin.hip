@@ -112,7 +112,8 @@ __device__ __forceinline__ int32_t scan_exclusive(int32_t n, int32_t *sWave, Loa
 // at column ends instead leave ~10 % of the lanes idle; tiles over plain bin order make every crossing tile span the
 // whole image height (tools/tile_model3.py: evaluated / in-window pairs 1.40 / 1.38 / 1.32 at KITTI size).
 // A tile record is {first snake index, end, class, column of the first index}; a snake index k inside column
-// [A, B) of the bin order is the position k (even column) or A + B - 1 - k (odd column): kernels_match.hip.
+// [A, B) of the bin order is the position k (even column) or A + B - 1 - k (odd column); the searches read that mapping
+// from snake_pos, which bin_sort writes (one word per feature, beside the records it moves).
 // One lane per (class, column) writes the tiles that start inside its column.
 __device__ __forceinline__ void make_tiles(const VhSets &s, const int32_t *__restrict__ bs, int32_t set) {
   const int32_t span = s.ubn * s.vbn;
@@ -194,6 +195,7 @@ __global__ void __launch_bounds__(256) bin_sort_kernel(VhSets s, int32_t set0, i
   const int32_t *__restrict__ rs = s.row_start + (int64_t)set * (nrow + 1);
   int32_t *__restrict__ rcur = s.row_cursor + (int64_t)set * nrow;
   int32_t *__restrict__ rpos = s.r_pos + (int64_t)set * s.cap;
+  int32_t *__restrict__ snake = s.snake_pos + (int64_t)set * s.cap;
   for (int32_t e0 = 0; e0 < L; e0 += 16) {
     const int32_t e = e0 + gl;
     int32_t mine = 0x7FFFFFFF, rowrel = 0;
@@ -214,6 +216,12 @@ __global__ void __launch_bounds__(256) bin_sort_kernel(VhSets s, int32_t set0, i
     }
     if (e < L) {
       const int32_t p = p0 + rank;
+      {  // snake index of position p (make_tiles): p itself in an even (class, u-bin) column [A, B), A + B - 1 - p in an odd one
+        const int32_t colidx = (int32_t)h.w * s.ubn + min((int32_t)__umulhi((uint32_t)h.x, s.inv_binsize), s.ubn - 1);
+        int32_t k = p;
+        if (VH_SNAKE && (colidx & 1) != (((int32_t)h.w * s.ubn) & 1)) k = bs[colidx * s.vbn] + bs[(colidx + 1) * s.vbn] - 1 - p;
+        snake[k] = p;
+      }
       sidx[p] = mine;
       suv[p] = (uint32_t)h.x | ((uint32_t)h.y << 16);
       sdesc[2 * (int64_t)p] = d0;

@@ -54,9 +54,6 @@ extern "C" int32_t vh_debug_flow_stats(unsigned long long *out, int32_t reset) {
 #ifndef VH_MATCH_WAVES
 #define VH_MATCH_WAVES 7
 #endif
-#ifndef VH_SNAKE
-#define VH_SNAKE 1  // 0 (experiments): query tiles over the plain bin order
-#endif
 
 namespace {
 
@@ -492,57 +489,39 @@ __device__ __forceinline__ void finish_tile(const VhSets &s, const VhMatchArgs &
 // original at a larger position, so their keys are larger than the original's
 // key and never change a minimum.  That lets every range of the chunk be rounded
 // outward to whole trips of 2*P candidates without any tail code.
-template <int Q, int P, int KM, bool SPEC>
-__device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a, int32_t pass, int32_t stream,
-                                          int32_t qset, int32_t cset, int32_t q0, int32_t q1, int32_t c, int32_t col0,
-                                          int32_t pbase, int32_t pcnt, uint4 *wD, uint32_t *wU, TileOut<Q> &out) {
+// The part of a flow tile that does not depend on the key encoding: the queries and the region the wave walks.
+struct FlowRegion {
+  int32_t UB0, UB1, VB0, VB1;                 // bins of interest of the union window
+  int32_t ULO_MAX, UHI_MIN, VA0, VA1;         // (tested loop) what lies inside EVERY query's window
+};
+template <int Q, int P, bool SPEC>
+__device__ __forceinline__ FlowRegion flow_queries(const VhSets &s, const VhMatchArgs &a, int32_t rv, int32_t qset, int32_t q0, int32_t q1,
+                                                   int32_t c, TileOut<Q> &out) {
   constexpr int L = 64 / P;
   static_assert(L == 8 || L == 16, "every 16-lane row must hold the whole tile (row-wise window reduction)");
-  constexpr int TRIP = 2 * P;  // candidates per trip: two steps, joined by one v_min3_u32 per query
-  const int32_t lane = threadIdx.x & 63, ph = lane / L, l = lane % L;
+  const int32_t l = (threadIdx.x & 63) % L;
   const uint32_t *__restrict__ quv = s.s_uv + (int64_t)qset * s.cap;
   const uint4 *__restrict__ qdesc = (const uint4 *)(s.s_desc + (int64_t)qset * s.cap * 8);
-  const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
-  const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
-  const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
-  const int32_t rv = a.pass[pass].flow ? a.radius : a.disp_tol;
-
   bool (&valid)[Q] = out.valid;  // the lane's queries live in the tile's result
   uint4 (&a0)[Q] = out.a0, (&a1)[Q] = out.a1;
   uint32_t (&uv1)[Q] = out.uv1;
-  int32_t v_lo[Q];
-  us2 lo2[Q];
-  typedef typename KeyT<KM>::type key_t;
-  const key_t KNONE = (key_t)~(key_t)0;
-  key_t best_key[Q];
   int32_t umin = 0x7FFFFFFF, umax = -1, vmin = 0x7FFFFFFF, vmax = -1;
-  // [q0, q1) are SNAKE indices (kernels_bin.hip: make_tiles): inside the column [A, B) of the query set's bin order
-  // the index k is the position k (even column) or A + B - 1 - k (odd column).  Column starts from col0 on, one per lane.
+  // [q0, q1) are SNAKE indices; bin_sort resolved them to positions of the query set's bin order once for the set
+  // (snake_pos): one gather per query slot.  Without the snake (VH_SNAKE=0) an index is its position.
   int32_t (&qp)[Q] = out.qpos;
+  const int32_t *__restrict__ qsnake = s.snake_pos + (int64_t)qset * s.cap;
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
     const int32_t q = q0 + L * qi + l;
     valid[qi] = q < q1;
     qp[qi] = valid[qi] ? q : q0;
-  }
-  {
-    const int32_t *__restrict__ qbs = s.bin_start + (int64_t)qset * (s.nbins + 1);
-    int32_t colb = col0, j = 0;
-    int32_t csv = ld_off(qbs, (uint32_t)((c * s.ubn + min(colb + lane, s.ubn)) * s.vbn) * 4u);
-    int32_t A = __builtin_amdgcn_readlane(csv, 0);
-    int32_t k[Q];
-#pragma unroll
-    for (int32_t qi = 0; qi < Q; qi++) k[qi] = qp[qi];
-    for (;;) {
-      const int32_t B = __builtin_amdgcn_readlane(csv, j + 1);
-      if (VH_SNAKE && ((colb + j) & 1)) {
-#pragma unroll
-        for (int32_t qi = 0; qi < Q; qi++) if (k[qi] >= A && k[qi] < B) qp[qi] = A + B - 1 - k[qi];
-      }
-      if (B >= q1 || colb + j + 1 >= s.ubn) break;  // (wave-uniform)
-      A = B;
-      if (++j == 63) { colb += 63; j = 0; csv = ld_off(qbs, (uint32_t)((c * s.ubn + min(colb + lane, s.ubn)) * s.vbn) * 4u); }
+    if (VH_SNAKE) qp[qi] = ld_off(qsnake, (uint32_t)qp[qi] * 4u);
+#ifdef VH_CHECK
+    {  // the gathered position lies among the positions of the tile's class in the query set's bin order
+      const int32_t *qbs = s.bin_start + (int64_t)qset * (s.nbins + 1);
+      VH_CHECK_RANGE(s, 14, qp[qi], qbs[c * s.ubn * s.vbn], qbs[(c + 1) * s.ubn * s.vbn]);
     }
+#endif
   }
 #pragma unroll
   for (int32_t qi = 0; qi < Q; qi++) {
@@ -550,10 +529,6 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     uv1[qi] = ld_off(quv, (uint32_t)ql * 4u);
     a0[qi] = ld_off(qdesc, (uint32_t)ql * 32u); a1[qi] = ld_off(qdesc, (uint32_t)ql * 32u + 16u);
     const int32_t u1 = uv1[qi] & 0xFFFF, v1 = uv1[qi] >> 16;
-    // search window (matcher.cpp:231-234; stereo: v narrowed to +-disp_tolerance), packed as vh_findmatch.h says
-    v_lo[qi] = v1 - rv;
-    lo2[qi] = window_lo2(uv1[qi], a.radius, rv);
-    best_key[qi] = KNONE;
     // (lanes past q1 repeat query q0: it is valid, so the extrema are unchanged)
     umin = min(umin, u1); umax = max(umax, u1); vmin = min(vmin, v1); vmax = max(vmax, v1);
   }
@@ -565,15 +540,42 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   // bins of interest of the union window: the bin of a coordinate is monotone, so the union's bins follow from the
   // extreme queries
   const VhBins ub = bins_of_interest(s, VhWindow{umin - a.radius, umax + a.radius, vmin - rv, vmax + rv});
-  const int32_t UB0 = ub.ub0, UB1 = ub.ub1, VB0 = ub.vb0, VB1 = ub.vb1;
-  const us2 span2 = window_span2(a.radius, rv);
+  FlowRegion r;
+  r.UB0 = ub.ub0; r.UB1 = ub.ub1; r.VB0 = ub.vb0; r.VB1 = ub.vb1;
   // (tested loop) columns whose pixel range [ub*bs, ub*bs+bs-1] is inside EVERY query's u
   // window, and v-bins [VA0, VA1] whose pixel rows lie inside EVERY query's v window: in
   // an interior column their candidates need no accept test at all
-  const int32_t ULO_MAX = umax - a.radius, UHI_MIN = umin + a.radius;
+  r.ULO_MAX = umax - a.radius; r.UHI_MIN = umin + a.radius;
   const int32_t VLO_MAX = vmax - rv, VHI_MIN = vmin + rv;
-  const int32_t VA0 = SPEC ? 0 : max(VB0, (max(VLO_MAX, 0) + s.binsize - 1) / s.binsize);
-  const int32_t VA1 = SPEC ? 0 : min(VB1, (VHI_MIN + 1) / s.binsize - 1);
+  r.VA0 = SPEC ? 0 : max(r.VB0, (max(VLO_MAX, 0) + s.binsize - 1) / s.binsize);
+  r.VA1 = SPEC ? 0 : min(r.VB1, (VHI_MIN + 1) / s.binsize - 1);
+  VH_STAT(0, 1); VH_STAT(5, q1 - q0); VH_STAT(6, r.UB1 - r.UB0 + 1);
+  return r;
+}
+
+template <int Q, int P, int KM, bool SPEC>
+__device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a, int32_t rv, int32_t cset, int32_t c, const FlowRegion &r,
+                                          int32_t pbase, uint4 *wD, uint32_t *wU, TileOut<Q> &out) {
+  constexpr int L = 64 / P;
+  constexpr int TRIP = 2 * P;  // candidates per trip: two steps, joined by one v_min3_u32 per query
+  const int32_t ph = (threadIdx.x & 63) / L;
+  const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
+  const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
+  const int32_t *__restrict__ cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
+  const uint4 (&a0)[Q] = out.a0, (&a1)[Q] = out.a1;
+  typedef typename KeyT<KM>::type key_t;
+  const key_t KNONE = (key_t)~(key_t)0;
+  key_t best_key[Q];
+  int32_t v_lo[Q];
+  us2 lo2[Q];
+#pragma unroll
+  for (int32_t qi = 0; qi < Q; qi++) {
+    // search window (matcher.cpp:231-234; stereo: v narrowed to +-disp_tolerance), packed as vh_findmatch.h says
+    v_lo[qi] = (int32_t)(out.uv1[qi] >> 16) - rv;
+    lo2[qi] = window_lo2(out.uv1[qi], a.radius, rv);
+    best_key[qi] = KNONE;
+  }
+  const us2 span2 = window_span2(a.radius, rv);
 
   // best = min over candidates of the key (sad_key): SAD, then bin-order position.
   // TEST: 2 = full (u,v) window test, 1 = v only, 0 = none
@@ -588,8 +590,7 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     const key_t key = sad_key<KM>(a0[qi], a1[qi], b0, b1, seed);
     return (TEST != 0 && out) ? KNONE : key;
   };
-  VH_STAT(0, 1); VH_STAT(5, q1 - q0); VH_STAT(6, UB1 - UB0 + 1);
-  walk_region_lds<!SPEC>(s, cbs, cuv, cdesc, c, UB0, UB1, VB0, VB1, ULO_MAX, UHI_MIN, VA0, VA1, wD, wU,
+  walk_region_lds<!SPEC>(s, cbs, cuv, cdesc, c, r.UB0, r.UB1, r.VB0, r.VB1, r.ULO_MAX, r.UHI_MIN, r.VA0, r.VA1, wD, wU,
     [&](int32_t pc, int32_t p1, int32_t pa0, int32_t pa1, const uint4 *cD, const uint32_t *cU) {
       VH_STAT(1, 1);
       const int32_t mcnt = min(64, p1 - pc);
@@ -641,19 +642,19 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
 }
 
 // What surrounds a tile of either kind of pass: the class's span of candidate positions, the key encoding it needs
-// (resolved once: tile(key mode constant, pbase, pcnt, out) is flow_tile or rows_tile), and the end of the tile.
+// (resolved once: tile(key mode constant, pbase, pcnt) is flow_tile or rows_tile, filling `out`), and the end of the tile.
 template <bool SPEC, bool FLOW, class Tile>
 __device__ __forceinline__ void search_tile(const VhSets &s, const VhMatchArgs &a, int32_t pass, int32_t stream, int32_t qset, int32_t cset,
-                                            int32_t c, int32_t *__restrict__ best, int32_t *__restrict__ redo_count, Tile tile) {
+                                            int32_t c, int32_t *__restrict__ best, int32_t *__restrict__ redo_count,
+                                            TileOut<VH_FLOW_Q> &out, Tile tile) {
   // candidates of class c occupy the contiguous positions [pbase, pend) of the bin order
   const int32_t *cbs = s.bin_start + (int64_t)cset * (s.nbins + 1);
   const int32_t pbase = ld_uniform_i32(cbs + c * s.ubn * s.vbn);
   const int32_t pend = ld_uniform_i32(cbs + (c + 1) * s.ubn * s.vbn);
   const int32_t km = key_mode_of(pend - pbase, a.wide_keys);
-  TileOut<VH_FLOW_Q> out;
-  if (km == KEY_HI16) tile(std::integral_constant<int, KEY_HI16>{}, pbase, pend - pbase, out);
-  else if (km == KEY_W19) tile(std::integral_constant<int, KEY_W19>{}, pbase, pend - pbase, out);
-  else tile(std::integral_constant<int, KEY_64>{}, pbase, pend - pbase, out);
+  if (km == KEY_HI16) tile(std::integral_constant<int, KEY_HI16>{}, pbase, pend - pbase);
+  else if (km == KEY_W19) tile(std::integral_constant<int, KEY_W19>{}, pbase, pend - pbase);
+  else tile(std::integral_constant<int, KEY_64>{}, pbase, pend - pbase);
   finish_tile<VH_FLOW_Q, VH_FLOW_P, SPEC, FLOW>(s, a, pass, stream, qset, cset, c, pbase, pend - pbase, out, best, redo_count);
 }
 
@@ -666,10 +667,14 @@ __device__ __forceinline__ void flow_pass(const VhSets &s, const VhMatchArgs &a,
     typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
     const i32x4 t = ld_uniform((const i32x4 *)(s.tiles + (int64_t)qset * s.max_tiles + tile));
     const int32_t q0 = __builtin_amdgcn_readfirstlane(t.x), q1 = __builtin_amdgcn_readfirstlane(t.y);
-    const int32_t c = __builtin_amdgcn_readfirstlane(t.z), col0 = __builtin_amdgcn_readfirstlane(t.w);
-    search_tile<SPEC, true>(s, a, pass, stream, qset, cset, c, best, redo_count,
-      [&](auto km, int32_t pbase, int32_t pcnt, TileOut<VH_FLOW_Q> &out) __attribute__((always_inline)) {
-        flow_tile<VH_FLOW_Q, VH_FLOW_P, decltype(km)::value, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, col0, pbase, pcnt, wD, wU, out);
+    const int32_t c = __builtin_amdgcn_readfirstlane(t.z);
+    // the queries and the region are loaded once, ahead of the key encoding's three copies of the walk
+    TileOut<VH_FLOW_Q> out;
+    const int32_t rv = a.pass[pass].flow ? a.radius : a.disp_tol;
+    const FlowRegion r = flow_queries<VH_FLOW_Q, VH_FLOW_P, SPEC>(s, a, rv, qset, q0, q1, c, out);
+    search_tile<SPEC, true>(s, a, pass, stream, qset, cset, c, best, redo_count, out,
+      [&](auto km, int32_t pbase, int32_t) __attribute__((always_inline)) {
+        flow_tile<VH_FLOW_Q, VH_FLOW_P, decltype(km)::value, SPEC>(s, a, rv, cset, c, r, pbase, wD, wU, out);
       });
   }
 }
@@ -794,8 +799,9 @@ __device__ __forceinline__ void rows_pass(const VhSets &s, const VhMatchArgs &a,
       if (c < 0) t -= nt;
     }
     if (c < 0) break;  // past the last tile (uniform)
-    search_tile<SPEC, false>(s, a, pass, stream, qset, cset, c, best, redo_count,
-      [&](auto km, int32_t pbase, int32_t pcnt, TileOut<VH_FLOW_Q> &out) __attribute__((always_inline)) {
+    TileOut<VH_FLOW_Q> out;
+    search_tile<SPEC, false>(s, a, pass, stream, qset, cset, c, best, redo_count, out,
+      [&](auto km, int32_t pbase, int32_t pcnt) __attribute__((always_inline)) {
         rows_tile<VH_FLOW_Q, VH_FLOW_P, decltype(km)::value, SPEC>(s, a, pass, stream, qset, cset, q0, q1, c, pbase, pcnt, wD, wU, wV, out);
       });
   }

@@ -49,6 +49,9 @@
 #define VH_FLOW_P 4
 #endif
 #define VH_TILE_Q (64 * VH_FLOW_Q / VH_FLOW_P)  // queries per flow-search tile
+#ifndef VH_SNAKE
+#define VH_SNAKE 1  // 0 (experiments): query tiles over the plain bin order (kernels_bin.hip: make_tiles, kernels_match.hip: flow_queries)
+#endif
 #define VH_NO_CODE 0xFFFFu
 // Wave priority of the detection chain's kernels (detect_nms, emit_features, bin_scan, bin_sort): their instructions
 // issue ahead of the searches' on a shared SIMD.  The chain is the step's critical path (4 sub-batches x 4 dependent
@@ -100,8 +103,10 @@ struct VhSets {
   int32_t *row_hist;   // [set][4*H]
   int32_t *row_cursor; // [set][4*H]
   int32_t *r_pos;      // [set][cap] bin-order position of the feature at each row-order position
-  int4 *tiles;       // [set][max_tiles] {first snake index, end, class, column of the first} (kernels_bin.hip: make_tiles)
+  int4 *tiles;       // [set][max_tiles] {first snake index, end, class, column of the first} (kernels_bin.hip: make_tiles; the column is
+                     // not read by the searches any more: it stays so that a record is one 16-byte store and one scalar load, and for debugging)
   int32_t *tile_cnt; // [set]
+  int32_t *snake_pos; // [set][cap] bin-order position of the query with snake index k (bin_sort writes it; read by flow_queries only)
   int32_t cap, nbins, ubn, vbn, binsize, max_tiles;
   uint32_t inv_binsize;  // ceil(2^32 / binsize): x / binsize == __umulhi(x, inv_binsize) for 0 <= x < 2^18
   int32_t W, H;      // dims_c of the matcher (full resolution)
@@ -118,7 +123,8 @@ struct VhSets {
 //          position, 4 bin_sort row slot, 5 emit_features stage slot, 6 bin_sort staged bin length,
 //          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position,
 //          10 recon_store predecessor position of a continued mark, 11 recon_gather position followed through the ring,
-//          12 gain_ratio byte offset of a dword inside its image plane, 13 gain_ratio list position of an index entry
+//          12 gain_ratio byte offset of a dword inside its image plane, 13 gain_ratio list position of an index entry,
+//          14 flow_queries query position gathered through snake_pos
 #ifdef VH_CHECK
 #define VH_CHECK_RANGE(s_, code_, x_, lo_, hi_)                                          \
   do {                                                                                   \
