@@ -51,6 +51,8 @@ VH_OK = 0
 VH_ERR_INVALID_ARG, VH_ERR_NO_DEVICE, VH_ERR_HIP, VH_ERR_CAPACITY, VH_ERR_UNSUPPORTED, VH_ERR_STATE = -1, -2, -3, -4, -5, -6
 SET_1P, SET_2P, SET_1C, SET_2C = 0, 1, 2, 3
 METHOD_FLOW, METHOD_STEREO, METHOD_QUAD = 0, 1, 2
+#: rule of the outlier vote (vh_vote_rule): the reference's flow vote under its literal 5 / stock libviso2's per-method rule
+VOTE_REFERENCE, VOTE_STOCK = 0, 1
 
 #: every symbol include/viso_hip.h declares (checked by the CPU test-suite)
 ABI_SYMBOLS = (
@@ -85,6 +87,7 @@ ABI_SYMBOLS = (
     "vh_group_post_device_dense", "vh_group_post_finish_device_dense",
     "vh_gain", "vh_group_set_gain", "vh_set_gain", "vh_group_gain", "vh_match_gain", "vh_group_gain_indices", "vh_match_gain_indices",
     "vh_sequence_set_multi_stage", "vh_set_multi_stage_prior", "vh_group_set_multi_stage_prior",
+    "vh_remove_outliers_pm_rule", "vh_remove_outliers_device_rule", "vh_set_vote_rule", "vh_group_set_vote_rule",
 )
 
 
@@ -106,6 +109,28 @@ class Params(C.Structure):
                 raise AttributeError(k)
             setattr(p, k, v)
         return p
+
+
+class VoteRule(C.Structure):
+    """vh_vote_rule (include/viso_hip.h): the rule of the outlier vote, 16 bytes."""
+    _fields_ = [("rule", C.c_int32), ("method", C.c_int32), ("flow_tolerance", C.c_float), ("disp_tolerance", C.c_float)]
+
+    @classmethod
+    def stock(cls, method: int, flow_tolerance: float = 5.0, disp_tolerance: float = 5.0):
+        return cls(VOTE_STOCK, int(method), float(flow_tolerance), float(disp_tolerance))
+
+    @classmethod
+    def reference(cls):
+        return cls(VOTE_REFERENCE, 0, 0.0, 0.0)
+
+
+def _rule(rule):
+    """None, a VoteRule or (rule, method, flow_tolerance, disp_tolerance) -> the pointer argument"""
+    if rule is None:
+        return None
+    if not isinstance(rule, VoteRule):
+        rule = VoteRule(*rule)
+    return C.byref(rule)
 
 
 class EgoParams(C.Structure):
@@ -287,6 +312,8 @@ def _lib():
             "vh_prior_statistics_device": [vp, i32, vp, i32, i32, vp, i64, vp, vp],
             "vh_match_ranged": [vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, i32, vp],
             "vh_set_track_linking": [vp, i32], "vh_group_set_track_linking": [vp, i32],
+            "vh_remove_outliers_pm_rule": [vp, i32, vp, vp], "vh_set_vote_rule": [vp, i32], "vh_group_set_vote_rule": [vp, i32],
+            "vh_remove_outliers_device_rule": [i32, i32, vp, i64, vp, i32, i32, f32, f32, vp, i32, vp, vp, vp, vp],
             "vh_get_tracks": [vp, vp, i32, vp], "vh_group_get_tracks": [vp, i32, vp, i32, vp],
             "vh_group_get_tracks_all": [vp, vp, i32, vp], "vh_group_tracks_device": [vp, vp, vp],
             "vh_link_tracks": [i32, i32, vp, i64, vp, i32, vp, vp, vp],
@@ -479,6 +506,11 @@ class Matcher:
         with link_tracks()."""
         _check(_lib().vh_set_track_linking(self._h, 1 if on else 0), "vh_set_track_linking")
 
+    def setVoteRule(self, rule: int = VOTE_STOCK):
+        """The rule of every outlier vote of this handle (vh_set_vote_rule), before the first push: VOTE_REFERENCE or
+        VOTE_STOCK -- the per-method rule under this handle's outlier_flow_tolerance / outlier_disp_tolerance."""
+        _check(_lib().vh_set_vote_rule(self._h, int(rule)), "vh_set_vote_rule")
+
     def getTracks(self) -> np.ndarray:
         """One TRACK record per record of the last matchFeatures' list (vh_get_tracks)."""
         n = C.c_int32(0)
@@ -658,6 +690,11 @@ class StreamGroup:
         """Link every stream's (row's) match lists to their predecessors on the GPU (vh_group_set_track_linking): before
         the first pushBack; also on a SequenceGroup."""
         _check(_lib().vh_group_set_track_linking(self._h, 1 if on else 0), "vh_group_set_track_linking")
+
+    def setVoteRule(self, rule: int = VOTE_STOCK):
+        """The rule of every outlier vote of this handle (vh_group_set_vote_rule), before the first push: VOTE_REFERENCE or
+        VOTE_STOCK -- the per-method rule under this handle's outlier_flow_tolerance / outlier_disp_tolerance."""
+        _check(_lib().vh_group_set_vote_rule(self._h, int(rule)), "vh_group_set_vote_rule")
 
     def getTracks(self, stream: int) -> np.ndarray:
         """One TRACK record per record of the stream's (row's) list of the last matchFeatures (vh_group_get_tracks)."""
@@ -1292,18 +1329,22 @@ def motion_inliers_mono(mono: MonoParams, match_lists, model, ok, device: int = 
             [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
 
 
-def remove_outliers(pm) -> np.ndarray:
-    """removeOutliers (reference src/remove_outliers.cpp:4-94) on p_match records; host only."""
+def remove_outliers(pm, rule=None) -> np.ndarray:
+    """removeOutliers (reference src/remove_outliers.cpp:4-94) on p_match records; host only.  rule: None (the reference's
+    vote) or a VoteRule (VoteRule.stock(method, flow_tolerance, disp_tolerance): stock libviso2's per-method rule)."""
     pm = np.ascontiguousarray(pm, dtype=P_MATCH_DTYPE).copy()
     n = C.c_int32(0)
-    _check(_lib().vh_remove_outliers_pm(_ptr(pm), len(pm), C.byref(n)), "vh_remove_outliers_pm")
+    if rule is None:
+        _check(_lib().vh_remove_outliers_pm(_ptr(pm), len(pm), C.byref(n)), "vh_remove_outliers_pm")
+    else:
+        _check(_lib().vh_remove_outliers_pm_rule(_ptr(pm), len(pm), _rule(rule), C.byref(n)), "vh_remove_outliers_pm_rule")
     return pm[:n.value].copy()
 
 
 def remove_outliers_device(lists, lanes_per_wave: int = 1, max_features: int = 0, bucket_width: float = 50.0, bucket_height: float = 50.0,
-                           device: int = 0, out_cap: int = 0, strict: bool = True, with_counts: bool = False):
+                           device: int = 0, out_cap: int = 0, strict: bool = True, with_counts: bool = False, rule=None):
     """removeOutliers (and bucketFeatures when max_features >= 1) of several match lists at once on the GPU
-    (vh_remove_outliers_device) -> (lists, triangles per list, sweep kernel ms).  strict=False: an error code does not
+    (vh_remove_outliers_device) -> (lists, triangles per list, sweep kernel ms).  rule: as remove_outliers.  strict=False: an error code does not
     raise; the healthy lists are returned (a refused list comes back empty) with the code as a fourth element.
     with_counts: out_counts as the call left them (the length a list that did not fit out_cap needs) as a last element."""
     lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in lists]
@@ -1316,9 +1357,9 @@ def remove_outliers_device(lists, lanes_per_wave: int = 1, max_features: int = 0
     out_cap = int(out_cap) if out_cap else stride
     out = np.zeros((n, out_cap), P_MATCH_DTYPE)
     oc = np.zeros(n, np.int32); ntri = np.zeros(n, np.int32); ms = C.c_float(0.0)
-    rc = _lib().vh_remove_outliers_device(device, n, _ptr(pm), stride, _ptr(counts), int(lanes_per_wave), int(max_features),
-                                          C.c_float(bucket_width), C.c_float(bucket_height), _ptr(out), out_cap, _ptr(oc), _ptr(ntri),
-                                          C.byref(ms))
+    args = (device, n, _ptr(pm), stride, _ptr(counts), int(lanes_per_wave), int(max_features), C.c_float(bucket_width), C.c_float(bucket_height),
+            _ptr(out), out_cap, _ptr(oc), _ptr(ntri), C.byref(ms))
+    rc = _lib().vh_remove_outliers_device(*args) if rule is None else _lib().vh_remove_outliers_device_rule(*args, _rule(rule))
     tail = (oc.copy(),) if with_counts else ()
     if strict:
         _check(rc, "vh_remove_outliers_device")

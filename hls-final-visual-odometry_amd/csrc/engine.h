@@ -360,6 +360,7 @@ struct VoteBatch {
   int32_t handed = 0;
   Event ev_prep, ev_done;
   int32_t method = -1, max_features = 0; float bw = 0, bh = 0;
+  int32_t rule = VH_VOTE_REFERENCE;  // the group's vote rule as it was when the batch was started
   bool has_ego = false, has_mono = false;
   vh_ego_params ego{}; vh_mono_params mono{};
   int32_t *d_rand = nullptr; size_t rand_per_step = 0;
@@ -488,6 +489,11 @@ struct Group {
   int32_t vote_dense = 0;     // vh_group_post_device_dense: 0 off, 1 classify, 2 + refit, 3 + classify again
   int64_t post_dev_seq = 0;   // steps begun
   int32_t vote_cur = 0;       // batch receiving steps
+  // vh_group_set_vote_rule: VH_VOTE_REFERENCE (the reference's flow vote under its literal 5; stereo lists are not voted)
+  // or VH_VOTE_STOCK (the per-method rule under this handle's two tolerances; every list is voted)
+  int32_t vote_rule = VH_VOTE_REFERENCE;
+  bool votes_on(int32_t method) const { return method != VH_METHOD_STEREO || vote_rule == VH_VOTE_STOCK; }
+  vh_vote_rule rule_for(int32_t method) const { return vh_vote_rule{vote_rule, method, (float)p.outlier_flow_tolerance, (float)p.outlier_disp_tolerance}; }
   std::vector<VoteStep> vstep;  // ring over the steps begun, indexed by sequence number
 
   std::vector<DeviceBlock> allocs;  // the arena: every dmalloc'ed block, counted in device_bytes
@@ -629,6 +635,9 @@ struct Group {
   int32_t vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs);
   int32_t bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid = nullptr) const;
   int32_t vote_launch(VoteBatch &b, int32_t index);
+  // vh_launch_vote on lists of `method` under this handle's rule; with profiling on, the tally is timed under a scope of
+  // its own (vote_tally: the reference test; vote_tally_flow / _disp / _quad: the stock rule's)
+  void vote_run(const VhVote &v, int32_t method, int32_t lanes, int32_t max_features, float bw, float bh, const VhVoteBuffers &vb, hipStream_t st);
   int32_t post_begin_device(int32_t cap_ps, int32_t max_features, float bw, float bh, const vh_ego_params *e, const int32_t *rand3,
                             const vh_mono_params *mono, const int32_t *rand8, int32_t want_lists);
   int32_t post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts,

@@ -428,6 +428,15 @@ int32_t vh_group_set_track_linking(vh_group *g, int32_t on) {
   return VH_OK;
 }
 int32_t vh_set_track_linking(vh_matcher *m, int32_t on) { return vh_group_set_track_linking((vh_group *)m, on); }
+// ---- the rule of the outlier vote ----------------------------------------------
+int32_t vh_group_set_vote_rule(vh_group *g, int32_t rule) {
+  Group *gq = (Group *)g;
+  if (!gq || (rule != VH_VOTE_REFERENCE && rule != VH_VOTE_STOCK)) return VH_ERR_INVALID_ARG;
+  if (gq->allocated) return VH_ERR_STATE;  // before the first push only: no step in flight is voted under two rules
+  gq->vote_rule = rule;
+  return VH_OK;
+}
+int32_t vh_set_vote_rule(vh_matcher *m, int32_t rule) { return vh_group_set_vote_rule((vh_group *)m, rule); }
 int32_t vh_group_get_tracks(vh_group *g, int32_t stream, vh_track *out, int32_t cap, int32_t *n) {
   Group *gq = (Group *)g; ENTER(gq);
   return gq->get_tracks(stream, out, cap, n);
@@ -942,6 +951,14 @@ int32_t vh_refine_matches(const vh_params *p, int32_t device, int32_t method, co
 int32_t vh_remove_outliers_device(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t lanes_per_wave,
                                   int32_t max_features, float bw, float bh, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
                                   int32_t *n_triangles, float *sweep_ms) {
+  return vh_remove_outliers_device_rule(device, n_lists, pm, stride, counts, lanes_per_wave, max_features, bw, bh, out, out_cap, out_counts, n_triangles,
+                                        sweep_ms, nullptr);
+}
+// rule: NULL or VH_VOTE_REFERENCE -- the reference's vote; VH_VOTE_STOCK -- the per-method rule (include/viso_hip.h: vh_vote_rule)
+int32_t vh_remove_outliers_device_rule(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t lanes_per_wave,
+                                       int32_t max_features, float bw, float bh, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
+                                       int32_t *n_triangles, float *sweep_ms, const vh_vote_rule *rule) {
+  if (rule && rule->rule != VH_VOTE_REFERENCE && (rule->rule != VH_VOTE_STOCK || rule->method < 0 || rule->method > 2)) return VH_ERR_INVALID_ARG;
   if (n_lists < 1 || !counts || !out_counts || out_cap < 0 || (out_cap > 0 && !out) || stride < 0) return VH_ERR_INVALID_ARG;
   if (max_features >= 1 && (!(bw >= 1) || !(bh >= 1))) return VH_ERR_INVALID_ARG;
   int32_t cap = 0;
@@ -977,7 +994,7 @@ int32_t vh_remove_outliers_device(int32_t device, int32_t n_lists, const vh_p_ma
   VH_HIP(ev0.create(hipEventDefault)); VH_HIP(ev1.create(hipEventDefault));
   hipEvent_t ev[2] = {ev0, ev1};
   vh_launch_vote_prep(vb.v, 0, n_lists, src, cap, b_cnt.as<int32_t>(), cap, nullptr, 1, nullptr);
-  vh_launch_vote(vb.v, lanes_per_wave, max_features, bw, bh, vb.lfsr, vb.lfsr_n, vb.out, vb.out_cap, vb.out_count, ev, nullptr);
+  vh_launch_vote(vb.v, VhVoteRule::of(rule), lanes_per_wave, max_features, bw, bh, vb.lfsr, vb.lfsr_n, vb.out, vb.out_cap, vb.out_count, ev, nullptr, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
   if (sweep_ms) VH_HIP(hipEventElapsedTime(sweep_ms, ev0, ev1));

@@ -71,6 +71,7 @@ int32_t Group::ensure_ranges(bool staging) {
 // Pass 1 of multi-stage matching and the statistics: the method's matching on the sparse sets, the vote on the host
 // (flow and quad lists), one range table per stream into rg.h_ranges, queued for the match stream.
 int32_t Group::multi_stage_ranges(int32_t method, const double *tr16) {
+  sparse->vote_rule = vote_rule;  // (pass 1 is voted under this handle's rule, with the sparse list's method)
   int32_t rc = sparse->match(method, tr16);
   if (rc) return rc;
   auto t0 = std::chrono::steady_clock::now();
@@ -110,14 +111,15 @@ int32_t Group::ensure_ms_vote() {
 }
 
 int32_t Group::multi_stage_ranges_device(int32_t method, const double *tr16) {
+  sparse->vote_rule = vote_rule;
   int32_t rc = sparse->match(method, tr16);
   if (rc) return rc;
   hipStream_t vs = sparse->post_stream;
   {
     Scope sc(this, "sparse_vote", vs);
     vh_launch_vote_prep(ms_vb.v, 0, S, (const vh_p_match *)sparse->mt.d_matches, sparse->mcap, sparse->mt.d_match_count, sparse->mcap, sparse->mt.d_overflow,
-                        method != VH_METHOD_STEREO ? 1 : 0, vs);
-    vh_launch_vote(ms_vb.v, kMsVoteLanes, 0, 0.0f, 0.0f, ms_vb.lfsr, ms_vb.lfsr_n, ms_vb.out, ms_vb.out_cap, ms_vb.out_count, nullptr, vs);
+                        votes_on(method) ? 1 : 0, vs);
+    vote_run(ms_vb.v, method, kMsVoteLanes, 0, 0.0f, 0.0f, ms_vb, vs);
   }
   VH_HIP(hipGetLastError());
   VH_HIP(hipStreamWaitEvent(vs, ev_tables[(match_seq + 1) & 1], 0));  // (never recorded: no wait)

@@ -173,10 +173,12 @@ int32_t Group::fetch_matches(int32_t s) {
 
 // removeOutliers (remove_outliers.cpp:4-94) on streams [0, S): host work, one
 // stream per task, `threads` workers.  Stereo records carry no previous-frame
-// position (u1p = -1), so the flow vote only applies to flow and quad matches.
+// position (u1p = -1), so the reference's flow vote only applies to flow and quad
+// matches; under the stock rule (vh_group_set_vote_rule) a stereo list is voted on its disparities.
 int32_t Group::remove_outliers(int32_t s_lo, int32_t s_hi, int32_t threads) {
   if (!allocated || last_method < 0) return VH_ERR_STATE;
-  if (last_method == VH_METHOD_STEREO) return VH_OK;
+  if (!votes_on(last_method)) return VH_OK;
+  const vh_vote_rule rule = rule_for(last_method);
   for (int32_t s = s_lo; s < s_hi; s++) {
     const int32_t rc = fetch_matches(s);
     if (rc) return rc;
@@ -185,7 +187,7 @@ int32_t Group::remove_outliers(int32_t s_lo, int32_t s_hi, int32_t threads) {
   for_each_stream(s_lo, s_hi, threads, [&](int32_t s) {
     std::vector<vh_p_match> &pm = host_matches[s];
     int32_t kept = 0;
-    if (vh_remove_outliers_pm(pm.data(), (int32_t)pm.size(), &kept) != VH_OK) { failed = 1; return; }
+    if (vh_remove_outliers_pm_rule(pm.data(), (int32_t)pm.size(), &rule, &kept) != VH_OK) { failed = 1; return; }
     pm.resize((size_t)kept);
   });
   return failed ? VH_ERR_INVALID_ARG : VH_OK;
@@ -329,12 +331,13 @@ int32_t Group::post_finish(int32_t age, int32_t max_features, float bw, float bh
   }
   const auto t0 = std::chrono::steady_clock::now();
   std::atomic<int32_t> failed(0);
-  const bool vote = sl.method != VH_METHOD_STEREO;  // stereo records carry no previous-frame position (as remove_outliers())
+  const bool vote = votes_on(sl.method);  // stereo records carry no previous-frame position (as remove_outliers())
+  const vh_vote_rule rule = rule_for(sl.method);
   for_each_stream(0, S, threads, [&](int32_t s) {
     thread_local std::vector<int32_t> scratch;
     vh_p_match *pm = sl.h_pm + (size_t)s * sl.cap_ps;
     int32_t n = sl.h_cnt[s];
-    if (vote && vh_remove_outliers_pm(pm, n, &n) != VH_OK) { failed = 1; return; }
+    if (vote && vh_remove_outliers_pm_rule(pm, n, &rule, &n) != VH_OK) { failed = 1; return; }
     post.h_bcnt[s] = bucket_records(pm, n, max_features, bw, bh, post.h_bucket + (size_t)s * post.bcap, post.bcap, scratch);
   });
   if (host_ms) *host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -479,13 +482,25 @@ int32_t Group::bucket_need(int32_t max_features, float bw, float bh, int64_t *ne
   return VH_OK;
 }
 
+void Group::vote_run(const VhVote &v, int32_t method, int32_t lanes, int32_t max_features, float bw, float bh, const VhVoteBuffers &vb, hipStream_t st) {
+  const vh_vote_rule r = rule_for(method);
+  const VhVoteRule rule = VhVoteRule::of(&r);
+  Event e0, e1;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  const bool timed = prof && e0.create(hipEventDefault) == hipSuccess && e1.create(hipEventDefault) == hipSuccess;
+  if (timed) { ev[0] = e0; ev[1] = e1; }
+  vh_launch_vote(v, rule, lanes, max_features, bw, bh, vb.lfsr, vb.lfsr_n, vb.out, vb.out_cap, vb.out_count, nullptr, timed ? ev : nullptr, st);
+  static const char *const names[4] = {"vote_tally", "vote_tally_flow", "vote_tally_disp", "vote_tally_quad"};
+  if (timed) prof_entries[names[rule.test]].pending.emplace_back(std::move(e0), std::move(e1));
+}
+
 int32_t Group::vote_launch(VoteBatch &b, int32_t index) {
   if (b.launched || b.steps == 0) return VH_OK;
   hipStream_t vs = vote_stream[index % kVoteStreams];
   VhVote v = b.vb.v;
   v.P = b.steps * S;
   VH_HIP(hipStreamWaitEvent(vs, b.ev_prep, 0));
-  vh_launch_vote(v, vote_lanes, b.max_features, b.bw, b.bh, b.vb.lfsr, b.vb.lfsr_n, b.vb.out, b.vb.out_cap, b.vb.out_count, nullptr, vs);
+  vote_run(v, b.method, vote_lanes, b.max_features, b.bw, b.bh, b.vb, vs);
   VH_HIP(hipGetLastError());
   if (b.has_ego) vh_launch_ego(b.ego, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
   else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0,
@@ -556,7 +571,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   VoteBatch *b = &vbatch[(size_t)vote_cur];
   const size_t rand_per_step = e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0);
   const auto same = [&](const VoteBatch &q) {
-    return q.method == last_method && q.max_features == max_features && q.bw == bw && q.bh == bh && q.has_ego == (e != nullptr) &&
+    return q.method == last_method && q.rule == vote_rule && q.max_features == max_features && q.bw == bw && q.bh == bh && q.has_ego == (e != nullptr) &&
            q.has_mono == (mono != nullptr) && (!e || memcmp(&q.ego, e, sizeof(*e)) == 0) && (!mono || memcmp(&q.mono, mono, sizeof(*mono)) == 0) &&
            q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0) && q.dense_mode == vote_dense;
   };
@@ -619,7 +634,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
       VH_HIP(b->h_out.alloc((size_t)P * ocap, hipHostMallocDefault));
       b->h_out_cap = ocap;
     }
-    b->method = last_method; b->max_features = max_features; b->bw = bw; b->bh = bh; b->has_ego = e != nullptr; b->has_mono = mono != nullptr;
+    b->method = last_method; b->rule = vote_rule; b->max_features = max_features; b->bw = bw; b->bh = bh; b->has_ego = e != nullptr; b->has_mono = mono != nullptr;
     if (e) b->ego = *e;
     if (mono) b->mono = *mono;
     b->want_lists = want_lists != 0;
@@ -629,7 +644,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   }
   // the step's lists leave the matcher's buffer behind the emission that wrote them; the next emission waits for that (ev_down)
   VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
-  vh_launch_vote_prep(b->vb.v, b->steps * S, S, (const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, mt.d_overflow, last_method != VH_METHOD_STEREO ? 1 : 0, down_stream);
+  vh_launch_vote_prep(b->vb.v, b->steps * S, S, (const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, mt.d_overflow, votes_on(last_method) ? 1 : 0, down_stream);
   VH_HIP(hipGetLastError());
   if (rand_per_step) {
     // through the batch's page-locked slot of this step: an asynchronous copy from the caller's pageable array would

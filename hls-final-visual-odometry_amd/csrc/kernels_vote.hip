@@ -249,27 +249,45 @@ __global__ __launch_bounds__(64) void vote_sweep_kernel(VhVote vt, int32_t lanes
 
 // ---- vote_tally --------------------------------------------------------------------------------------
 // remove_outliers.cpp:36-80: every triangle votes for each of its corners once per agreeing neighbour
-__device__ __forceinline__ void tally_triangle(const VhVote &vt, int32_t p, int32_t t, int32_t &a, int32_t &b, int32_t &c, int32_t &va, int32_t &vb, int32_t &vc) {
+// TEST (vh_vote.h): which terms an edge is tested on.  A corner loads the fields its test reads and no others: the flow
+// test the two float2 (u1p, v1p) and (u1c, v1c), the disparity test u1c and u2c, the quad test the two float2 and u2c.
+template <int32_t TEST>
+__device__ __forceinline__ void tally_triangle(const VhVote &vt, const VhVoteTol &tol, int32_t p, int32_t t, int32_t &a, int32_t &b, int32_t &c, int32_t &va,
+                                               int32_t &vb, int32_t &vc) {
   const vh_sh::Half *T = vote_half(vt, p) + (int64_t)t * 3;
   const int32_t *order = vt.order + (int64_t)p * vt.cap;
   a = order[T[0].p]; b = order[T[1].p]; c = order[T[2].p];  // corner ranks -> matches
-  // flow vectors (u1c - u1p, v1c - v1p), remove_outliers.cpp:40-47, from the records themselves
   const vh_p_match *pm = vt.pm + (int64_t)p * vt.cap;
-  const auto flow_of = [pm](int32_t i) {
-    const float2 prev = *(const float2 *)&pm[i].u1p, cur = *(const float2 *)&pm[i].u1c;
-    return make_float2(cur.x - prev.x, cur.y - prev.y);
-  };
-  const float2 fa = flow_of(a), fb = flow_of(b), fc = flow_of(c);
-  const float tol = 5;  // hard-coded in the reference (:34), not parameters::outlier_flow_tolerance
-  const int32_t ab = fabsf(fa.x - fb.x) + fabsf(fa.y - fb.y) < tol ? 1 : 0;
-  const int32_t bc = fabsf(fb.x - fc.x) + fabsf(fb.y - fc.y) < tol ? 1 : 0;
-  const int32_t ac = fabsf(fa.x - fc.x) + fabsf(fa.y - fc.y) < tol ? 1 : 0;
+  int32_t ab = 1, bc = 1, ac = 1;
+  if constexpr (TEST == VH_TALLY_DISP) {  // disparities u1c - u2c
+    const auto disp_of = [pm](int32_t i) { return pm[i].u1c - pm[i].u2c; };
+    const float da = disp_of(a), db = disp_of(b), dc = disp_of(c);
+    ab = fabsf(da - db) < tol.disp ? 1 : 0;
+    bc = fabsf(db - dc) < tol.disp ? 1 : 0;
+    ac = fabsf(da - dc) < tol.disp ? 1 : 0;
+  } else {
+    // flow vectors (u1c - u1p, v1c - v1p), remove_outliers.cpp:40-47, from the records themselves; z: the disparity (quad test)
+    const auto flow_of = [pm](int32_t i) {
+      const float2 prev = *(const float2 *)&pm[i].u1p, cur = *(const float2 *)&pm[i].u1c;
+      return make_float3(cur.x - prev.x, cur.y - prev.y, TEST == VH_TALLY_QUAD ? cur.x - pm[i].u2c : 0.0f);
+    };
+    const float3 fa = flow_of(a), fb = flow_of(b), fc = flow_of(c);
+    const float ftol = TEST == VH_TALLY_REFERENCE ? 5.0f : tol.flow;  // hard-coded in the reference (:34), not parameters::outlier_flow_tolerance
+    ab = fabsf(fa.x - fb.x) + fabsf(fa.y - fb.y) < ftol ? 1 : 0;
+    bc = fabsf(fb.x - fc.x) + fabsf(fb.y - fc.y) < ftol ? 1 : 0;
+    ac = fabsf(fa.x - fc.x) + fabsf(fa.y - fc.y) < ftol ? 1 : 0;
+    if constexpr (TEST == VH_TALLY_QUAD) {
+      ab &= fabsf(fa.z - fb.z) < tol.disp ? 1 : 0;
+      bc &= fabsf(fb.z - fc.z) < tol.disp ? 1 : 0;
+      ac &= fabsf(fa.z - fc.z) < tol.disp ? 1 : 0;
+    }
+  }
   va = ab + ac; vb = ab + bc; vc = bc + ac;
 }
 
 // lists of up to 16 384 records: one workgroup per list, the counters in LDS (54 k votes per KITTI list: as global
 // atomics they were the whole kernel), written out once
-__global__ __launch_bounds__(1024) void vote_tally_kernel(VhVote vt) {
+template <int32_t TEST> __global__ __launch_bounds__(1024) void vote_tally_kernel(VhVote vt, VhVoteTol tol) {
   extern __shared__ int32_t sv[];
   const int32_t p = blockIdx.x;
   const VhVoteMeta &m = vt.meta[p];
@@ -279,7 +297,7 @@ __global__ __launch_bounds__(1024) void vote_tally_kernel(VhVote vt) {
   __syncthreads();
   for (int32_t t = threadIdx.x; t < ntri; t += 1024) {
     int32_t a, b, c, va, vb, vc;
-    tally_triangle(vt, p, t, a, b, c, va, vb, vc);
+    tally_triangle<TEST>(vt, tol, p, t, a, b, c, va, vb, vc);
     if (va) atomicAdd(&sv[a], va);
     if (vb) atomicAdd(&sv[b], vb);
     if (vc) atomicAdd(&sv[c], vc);
@@ -290,14 +308,14 @@ __global__ __launch_bounds__(1024) void vote_tally_kernel(VhVote vt) {
 }
 
 // longer lists: a thread per triangle, global counters (zeroed by vote_prep)
-__global__ __launch_bounds__(256) void vote_tally_global_kernel(VhVote vt) {
+template <int32_t TEST> __global__ __launch_bounds__(256) void vote_tally_global_kernel(VhVote vt, VhVoteTol tol) {
   const int32_t p = blockIdx.y;
   const VhVoteMeta &m = vt.meta[p];
   if (m.status != VH_VOTE_OK) return;
   const int32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= m.ntri) return;
   int32_t a, b, c, va, vb, vc;
-  tally_triangle(vt, p, t, a, b, c, va, vb, vc);
+  tally_triangle<TEST>(vt, tol, p, t, a, b, c, va, vb, vc);
   int32_t *votes = vt.votes + (int64_t)p * vt.cap;
   if (va) atomicAdd(&votes[a], va);
   if (vb) atomicAdd(&votes[b], vb);
@@ -453,8 +471,21 @@ void vh_launch_vote_prep(const VhVote &vt, int32_t p0, int32_t S, const vh_p_mat
   hipLaunchKernelGGL(vote_prep_kernel, dim3((width + 255) / 256, S), dim3(256), 0, st, vt, p0, src, src_stride, src_count, src_cap, src_overflow, vote);
 }
 
-void vh_launch_vote(const VhVote &vt, int32_t lanes, int32_t max_features, float bw, float bh, const uint32_t *lfsr, int32_t lfsr_n, vh_p_match *out,
-                    int32_t out_cap, int32_t *out_count, hipEvent_t *sweep_ev, hipStream_t st) {
+VhVoteRule VhVoteRule::of(const vh_vote_rule *r) {
+  VhVoteRule v;
+  if (!r || r->rule != VH_VOTE_STOCK) return v;
+  v.test = r->method == VH_METHOD_FLOW ? VH_TALLY_FLOW : (r->method == VH_METHOD_STEREO ? VH_TALLY_DISP : VH_TALLY_QUAD);
+  v.tol = VhVoteTol{r->flow_tolerance, r->disp_tolerance};
+  return v;
+}
+
+template <int32_t TEST> static void launch_tally(const VhVote &vt, const VhVoteTol &tol, hipStream_t st) {
+  if (vt.cap <= 16384) hipLaunchKernelGGL(vote_tally_kernel<TEST>, dim3(vt.P), dim3(1024), sizeof(int32_t) * (size_t)vt.cap, st, vt, tol);
+  else hipLaunchKernelGGL(vote_tally_global_kernel<TEST>, dim3((2 * vt.cap + 255) / 256, vt.P), dim3(256), 0, st, vt, tol);
+}
+
+void vh_launch_vote(const VhVote &vt, const VhVoteRule &rule, int32_t lanes, int32_t max_features, float bw, float bh, const uint32_t *lfsr, int32_t lfsr_n,
+                    vh_p_match *out, int32_t out_cap, int32_t *out_count, hipEvent_t *sweep_ev, hipEvent_t *tally_ev, hipStream_t st) {
   if (vt.P < 1) return;
   lanes = lanes < 1 ? 1 : (lanes > 64 ? 64 : lanes);
   {  // the lanes' hashes and flip stacks share 64 KB of LDS: fewer lists per wave for very long lists
@@ -466,7 +497,13 @@ void vh_launch_vote(const VhVote &vt, int32_t lanes, int32_t max_features, float
   static const int32_t prio = [] { const char *e = getenv("VH_VOTE_PRIO"); return e ? atoi(e) : 3; }();
   hipLaunchKernelGGL(vote_sweep_kernel, dim3((vt.P + lanes - 1) / lanes), dim3(64), sizeof(int32_t) * (size_t)lanes * (vt.hsize + VH_VOTE_PEND), st, vt, lanes, prio, g_vote_pend_cap);
   if (sweep_ev) (void)hipEventRecord(sweep_ev[1], st);
-  if (vt.cap <= 16384) hipLaunchKernelGGL(vote_tally_kernel, dim3(vt.P), dim3(1024), sizeof(int32_t) * (size_t)vt.cap, st, vt);
-  else hipLaunchKernelGGL(vote_tally_global_kernel, dim3((2 * vt.cap + 255) / 256, vt.P), dim3(256), 0, st, vt);
+  if (tally_ev) (void)hipEventRecord(tally_ev[0], st);
+  switch (rule.test) {
+    case VH_TALLY_FLOW: launch_tally<VH_TALLY_FLOW>(vt, rule.tol, st); break;
+    case VH_TALLY_DISP: launch_tally<VH_TALLY_DISP>(vt, rule.tol, st); break;
+    case VH_TALLY_QUAD: launch_tally<VH_TALLY_QUAD>(vt, rule.tol, st); break;
+    default: launch_tally<VH_TALLY_REFERENCE>(vt, rule.tol, st); break;
+  }
+  if (tally_ev) (void)hipEventRecord(tally_ev[1], st);
   hipLaunchKernelGGL(vote_select_kernel, dim3(vt.P), dim3(64), 0, st, vt, max_features, bw, bh, lfsr, lfsr_n, out, out_cap, out_count);
 }

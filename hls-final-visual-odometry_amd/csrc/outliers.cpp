@@ -141,8 +141,14 @@ int32_t triangulate(Scratch &w, int32_t n) {
 
 }  // namespace
 
-extern "C" int32_t vh_remove_outliers_pm(vh_p_match *pm, int32_t n, int32_t *n_out) {
+static_assert(sizeof(vh_vote_rule) == 16, "vh_vote_rule is 16 bytes");
+
+// rule == NULL or VH_VOTE_REFERENCE: the reference's vote (flow under the literal 5); VH_VOTE_STOCK: stock libviso2's
+// per-method rule as include/viso_hip.h states it
+extern "C" int32_t vh_remove_outliers_pm_rule(vh_p_match *pm, int32_t n, const vh_vote_rule *rule, int32_t *n_out) {
   if (!n_out || n < 0 || (n > 0 && !pm)) return VH_ERR_INVALID_ARG;
+  const bool stock = rule && rule->rule != VH_VOTE_REFERENCE;
+  if (stock && (rule->rule != VH_VOTE_STOCK || rule->method < 0 || rule->method > 2)) return VH_ERR_INVALID_ARG;
   *n_out = n;
   if (n <= 3) return VH_OK;  // remove_outliers.cpp:6-7
   thread_local Scratch scratch;
@@ -152,15 +158,25 @@ extern "C" int32_t vh_remove_outliers_pm(vh_p_match *pm, int32_t n, int32_t *n_o
   const vh_sh::Half *half = scratch.half.data();
   std::vector<int32_t> &votes = scratch.votes;
   votes.assign(static_cast<size_t>(n), 0);
-  const float tol = 5;  // hard-coded in the reference (:34), not parameters::outlier_flow_tolerance
-  const auto flow_agrees = [pm, tol](int32_t a, int32_t b) {
-    const float au = pm[a].u1c - pm[a].u1p, av = pm[a].v1c - pm[a].v1p;
-    const float bu = pm[b].u1c - pm[b].u1p, bv = pm[b].v1c - pm[b].v1p;
-    return std::fabs(au - bu) + std::fabs(av - bv) < tol ? 1 : 0;
+  // the reference: flow alone under a hard-coded 5 (:34), not parameters::outlier_flow_tolerance; stock: flow for
+  // method 0, disparity for method 1, both for method 2, each under its tolerance
+  const bool flow = !stock || rule->method != VH_METHOD_STEREO, disp = stock && rule->method != VH_METHOD_FLOW;
+  const float flow_tol = stock ? rule->flow_tolerance : 5, disp_tol = stock ? rule->disp_tolerance : 0;
+  const auto agree = [pm, flow, disp, flow_tol, disp_tol](int32_t a, int32_t b) {
+    if (disp) {
+      const float da = pm[a].u1c - pm[a].u2c, db = pm[b].u1c - pm[b].u2c;
+      if (!(std::fabs(da - db) < disp_tol)) return 0;
+    }
+    if (flow) {
+      const float au = pm[a].u1c - pm[a].u1p, av = pm[a].v1c - pm[a].v1p;
+      const float bu = pm[b].u1c - pm[b].u1p, bv = pm[b].v1c - pm[b].v1p;
+      if (!(std::fabs(au - bu) + std::fabs(av - bv) < flow_tol)) return 0;
+    }
+    return 1;
   };
   for (int32_t t = 0; t < ntri; t++) {
     const int32_t a = half[3 * t].p, b = half[3 * t + 1].p, c = half[3 * t + 2].p;
-    const int32_t ab = flow_agrees(a, b), bc = flow_agrees(b, c), ac = flow_agrees(a, c);
+    const int32_t ab = agree(a, b), bc = agree(b, c), ac = agree(a, c);
     votes[a] += ab + ac;
     votes[b] += ab + bc;
     votes[c] += bc + ac;
@@ -171,3 +187,5 @@ extern "C" int32_t vh_remove_outliers_pm(vh_p_match *pm, int32_t n, int32_t *n_o
   *n_out = kept;
   return VH_OK;
 }
+
+extern "C" int32_t vh_remove_outliers_pm(vh_p_match *pm, int32_t n, int32_t *n_out) { return vh_remove_outliers_pm_rule(pm, n, nullptr, n_out); }

@@ -8,6 +8,7 @@
 #include "sweep_hull.h"
 
 struct vh_p_match;
+struct vh_vote_rule;
 
 #define VH_VOTE_PEND 30   // flip-stack slots per list beyond the one in a register, in LDS (the reference has 13 in all)
 #define VH_VOTE_HASH_MAX 256  // angular-hash slots per list, in LDS: lists of up to 65 536 records
@@ -15,7 +16,7 @@ struct vh_p_match;
 
 // status of a list
 #define VH_VOTE_OK 0           // to be voted on
-#define VH_VOTE_SKIP 1         // n <= 3 (remove_outliers.cpp:6-7) or a stereo list (no flow to vote on): kept as it is
+#define VH_VOTE_SKIP 1         // n <= 3 (remove_outliers.cpp:6-7) or a stereo list under the reference rule (no flow to vote on): kept as it is
 #define VH_VOTE_TRUNCATED 2    // the list did not fit (its slot, the matcher's capacities, or the output): VH_ERR_CAPACITY
 #define VH_VOTE_UNSUPPORTED 3  // NaN / infinite / negative coordinates, or a bucket grid beyond the scratch: VH_ERR_UNSUPPORTED
 #define VH_VOTE_STACK 4        // more than VH_VOTE_PEND + 1 flips pending: VH_ERR_UNSUPPORTED
@@ -50,13 +51,28 @@ __host__ __device__ inline vh_sh::Half *vote_half(const VhVote &vt, int64_t p) {
 __host__ __device__ inline uint2 *vote_sort_buf(const VhVote &vt, int64_t p) { return (uint2 *)vote_half(vt, p); }          // [2][cap]
 __host__ __device__ inline float2 *vote_pts(const VhVote &vt, int64_t p) { return (float2 *)vote_half(vt, p) + 2 * vt.cap; }  // [cap]
 
-// the lists of S streams (one step) enter the batch as its lists [p0, p0 + S); vote = 0: no vote (stereo lists)
+// The edge test of the tally (include/viso_hip.h: vh_vote_rule): the reference's flow term under its literal 5, or one of
+// the stock rule's three -- flow (method 0), disparity (method 1), both (method 2) -- under the tolerances.
+#define VH_TALLY_REFERENCE 0
+#define VH_TALLY_FLOW 1
+#define VH_TALLY_DISP 2
+#define VH_TALLY_QUAD 3
+struct VhVoteTol { float flow, disp; };  // travels by value beside VhVote (the reference test reads neither)
+struct VhVoteRule {
+  int32_t test = VH_TALLY_REFERENCE;
+  VhVoteTol tol{0.0f, 0.0f};
+  bool stock() const { return test != VH_TALLY_REFERENCE; }
+  // of a checked rule (rule and method in range) or of NULL
+  static VhVoteRule of(const vh_vote_rule *r);
+};
+
+// the lists of S streams (one step) enter the batch as its lists [p0, p0 + S); vote = 0: no vote (stereo lists under the reference rule)
 void vh_launch_vote_prep(const VhVote &vt, int32_t p0, int32_t S, const vh_p_match *src, int64_t src_stride, const int32_t *src_count, int32_t src_cap,
                          const int32_t *src_overflow, int32_t vote, hipStream_t st);
 // order -> sweep (`lanes` lists per wave) -> tally -> select (+ bucketing into out[P][out_cap] when max_features >= 1);
-// sweep_ev: optional pair of events recorded around the sweep kernel
-void vh_launch_vote(const VhVote &vt, int32_t lanes, int32_t max_features, float bw, float bh, const uint32_t *lfsr, int32_t lfsr_n, vh_p_match *out,
-                    int32_t out_cap, int32_t *out_count, hipEvent_t *sweep_ev, hipStream_t st);
+// sweep_ev / tally_ev: optional pairs of events recorded around the sweep kernel / the tally kernel; rule: the tally's edge test
+void vh_launch_vote(const VhVote &vt, const VhVoteRule &rule, int32_t lanes, int32_t max_features, float bw, float bh, const uint32_t *lfsr, int32_t lfsr_n, vh_p_match *out,
+                    int32_t out_cap, int32_t *out_count, hipEvent_t *sweep_ev, hipEvent_t *tally_ev, hipStream_t st);
 // behind vh_launch_vote and an estimator (est_ok[P]): counts[P] = the voted list's records, ok[P] = est_ok, both 0 for a
 // list the vote refused; voted[P] = counts, -1 for a refused list (the dense stages of the device post chain)
 void vh_launch_vote_gate(const VhVote &vt, const int32_t *est_ok, int32_t *counts, int32_t *ok, int32_t *voted, hipStream_t st);

@@ -46,8 +46,8 @@ typedef struct vh_params {
   int32_t match_binsize;          /* matching bin width/height */
   int32_t match_radius;           /* matching radius (du/dv in pixels) */
   int32_t match_disp_tolerance;   /* dv tolerance for stereo matches (pixels) */
-  int32_t outlier_disp_tolerance; /* accepted, unused by this path (as in the reference) */
-  int32_t outlier_flow_tolerance; /* accepted, unused by this path */
+  int32_t outlier_disp_tolerance; /* disparity tolerance of the outlier vote under VH_VOTE_STOCK (vh_set_vote_rule); not read under the default rule, as in the reference */
+  int32_t outlier_flow_tolerance; /* flow tolerance of the outlier vote under VH_VOTE_STOCK; not read under the default rule (the reference's literal 5) */
   int32_t multi_stage;            /* 1 = also extract the sparse feature set (max1) */
   int32_t half_resolution;        /* 1 = detect at half resolution, coordinates x2 */
   int32_t refinement;             /* 0 = none, 1 = pixel, 2 = sub-pixel relocation of the matches (stock libviso2;
@@ -155,7 +155,9 @@ int32_t vh_match_features(vh_matcher *m, int32_t method, const double *Tr_delta1
  * Delaunay-neighbour flow-consistency vote on the current matches, host side
  * (a sequential float triangulation whose result depends on its
  * visiting order -- see csrc/outliers.cpp).  Filters flow and quad matches;
- * stereo matches (no previous-frame position) are left as they are.
+ * stereo matches (no previous-frame position) are left as they are.  Under
+ * VH_VOTE_STOCK (vh_set_vote_rule, below) the vote uses the last match call's
+ * method and the handle's two tolerances, and stereo matches are voted too.
  * VH_ERR_STATE before the first vh_match_features. */
 int32_t vh_remove_outliers(vh_matcher *m);
 /* The same on caller-owned records, in place, order preserved; *n_out = count
@@ -176,6 +178,45 @@ int32_t vh_remove_outliers_pm(vh_p_match *pm, int32_t n, int32_t *n_out);
 int32_t vh_remove_outliers_device(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts,
                                   int32_t lanes_per_wave, int32_t max_features, float bucket_width, float bucket_height,
                                   vh_p_match *out, int32_t out_cap, int32_t *out_counts, int32_t *n_triangles, float *sweep_ms);
+
+/* ---- the rule of the vote ---------------------------------------------------
+ * VH_VOTE_REFERENCE (the default everywhere): the reference's cut-down vote (src/remove_outliers.cpp:34-90) -- the flow
+ * term under the literal 5, no method; method and the tolerances are not read, and on a handle a stereo list is not voted.
+ * VH_VOTE_STOCK: stock libviso2's Matcher::removeOutliers(p_matched, method) [upstream-recollection; absent from the
+ * reference tree, parity unpinned] as this project defines it, in single precision, for a list of method M:
+ *     fu(i) = u1c - u1p,  fv(i) = v1c - v1p,  d(i) = u1c - u2c
+ *     F(a,b) = fabsf(fu(a) - fu(b)) + fabsf(fv(a) - fv(b)) < flow_tolerance
+ *     D(a,b) = fabsf(d(a) - d(b)) < disp_tolerance
+ *     agree(a,b) = M == 0 ? F : M == 1 ? D : (D && F)
+ * Everything else is the vote as it is: n <= 3 returns the list, the points are (u1c, v1c) under the same triangulation
+ * (csrc/sweep_hull.h), a triangle gives each corner one vote per agreeing edge it lies on, a record survives with at
+ * least 4 votes, in list order.  The compares are strict: a NaN term disagrees, a tolerance <= 0 agrees with nothing
+ * (every record of a list longer than 3 is dropped).  STOCK with method 0 and flow_tolerance 5 is REFERENCE bit for bit.
+ * Any other rule, or a method outside 0..2 under VH_VOTE_STOCK, is VH_ERR_INVALID_ARG.  A NULL rule is VH_VOTE_REFERENCE. */
+#define VH_VOTE_REFERENCE 0
+#define VH_VOTE_STOCK 1
+typedef struct vh_vote_rule {
+  int32_t rule;          /* VH_VOTE_REFERENCE or VH_VOTE_STOCK */
+  int32_t method;        /* VH_METHOD_* of the list (STOCK only) */
+  float flow_tolerance;  /* STOCK only */
+  float disp_tolerance;  /* STOCK only */
+} vh_vote_rule;
+typedef char vh_vote_rule_is_16_bytes[sizeof(vh_vote_rule) == 16 ? 1 : -1]; /* (a static assertion that C99 and C++11 both take) */
+/* vh_remove_outliers_pm / vh_remove_outliers_device under a rule (the plain entries are these with rule = NULL); the
+ * refusals and the envelope of the device form are unchanged. */
+int32_t vh_remove_outliers_pm_rule(vh_p_match *pm, int32_t n, const vh_vote_rule *rule, int32_t *n_out);
+int32_t vh_remove_outliers_device_rule(int32_t device, int32_t n_lists, const vh_p_match *pm, int64_t stride, const int32_t *counts,
+                                       int32_t lanes_per_wave, int32_t max_features, float bucket_width, float bucket_height,
+                                       vh_p_match *out, int32_t out_cap, int32_t *out_counts, int32_t *n_triangles, float *sweep_ms,
+                                       const vh_vote_rule *rule);
+/* The rule of a handle (lone matcher, group or sequence handle): rule = VH_VOTE_REFERENCE or VH_VOTE_STOCK, before the
+ * first push only (VH_ERR_STATE afterwards).  Under VH_VOTE_STOCK every vote of the handle -- vh_remove_outliers,
+ * vh_group_remove_outliers, the host and device post chains, pass 1 of multi-stage matching in host and device mode and
+ * so what vh_(group_)get_sparse_matches returns -- uses the method of the list it votes (stereo lists are voted too) and
+ * the tolerances (float)outlier_flow_tolerance / (float)outlier_disp_tolerance of the vh_params given at creation.  With
+ * the default rule nothing is allocated, launched or decided differently; no rule needs more device memory. */
+int32_t vh_set_vote_rule(vh_matcher *m, int32_t rule);
+int32_t vh_group_set_vote_rule(vh_group *g, int32_t rule);
 
 /* Matcher::bucketFeatures (src/matcher.h:132, src/matcher.cpp:140-187):
  * host-side post-processing of the current matches, LFSR shuffle included. */

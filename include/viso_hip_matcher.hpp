@@ -138,6 +138,17 @@ class Matcher {
     return rc == VH_OK;
   }
 
+  // The rule of removeOutliers (vh_set_vote_rule).  Off (the default): the reference's vote -- flow under its literal 5,
+  // stereo lists left as they are.  On: stock libviso2's removeOutliers(p_matched, method) -- matchFeatures(method) votes
+  // with its method (flow, disparity, or both) under this matcher's outlier_flow_tolerance / outlier_disp_tolerance.
+  // Before the first pushBack; returns false (and says why) otherwise.  The reference's `parameters` has no such field.
+  bool setStockOutlierRule(bool on) {
+    if (!handle) return false;
+    const int32_t rc = vh_set_vote_rule(handle, on ? VH_VOTE_STOCK : VH_VOTE_REFERENCE);
+    if (rc != VH_OK) report("setStockOutlierRule", rc);
+    return rc == VH_OK;
+  }
+
   // Feature tracks (vh_set_track_linking): every matchFeatures also links its list to the list of the previous pair on
   // the GPU.  Off by default; before the first pushBack, returns false (and says why) otherwise.  The tracks describe
   // the list as matching left it, before removeOutliers: read them with outlier_removal = false, or link the voted
