@@ -88,6 +88,7 @@ ABI_SYMBOLS = (
     "vh_gain", "vh_group_set_gain", "vh_set_gain", "vh_group_gain", "vh_match_gain", "vh_group_gain_indices", "vh_match_gain_indices",
     "vh_sequence_set_multi_stage", "vh_set_multi_stage_prior", "vh_group_set_multi_stage_prior",
     "vh_remove_outliers_pm_rule", "vh_remove_outliers_device_rule", "vh_set_vote_rule", "vh_group_set_vote_rule",
+    "vh_motion_covariance", "vh_group_motion_covariance", "vh_match_motion_covariance",
 )
 
 
@@ -335,6 +336,8 @@ def _lib():
             "vh_motion_inliers_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_motion_inliers_mono": [vp, vp, vp, vp, vp], "vh_match_inliers_mono": [vp, vp, vp, i32, vp],
             "vh_refit_motion": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_motion_covariance": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp], "vh_match_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
@@ -546,6 +549,19 @@ class Matcher:
         _check(_lib().vh_match_refit_motion(self._h, C.byref(ego), 1 if reclassify else 0, _ptr(tr), C.byref(ok), C.byref(nupd), C.byref(n)),
                "vh_match_refit_motion")
         return tr, bool(ok.value), nupd.value, n.value
+
+    def motionCovariance(self, ego: "EgoParams", tr=None, ok: bool = True):
+        """The covariance of the stereo motion over ALL inliers of the last motionInliers / refitMotion(reclassify=True)
+        (vh_match_motion_covariance) -> (cov [6, 6], ssr, ok, count).  tr None: under the motion the list was classified
+        under, which is on the device; else under tr [6] / ok -- refitMotion's tr after reclassify=False."""
+        cov = np.zeros((6, 6), np.float64); ssr = C.c_double(0); oko = C.c_int32(0); n = C.c_int32(0)
+        okin = C.c_int32(1 if ok else 0)
+        if tr is not None:
+            tr = np.ascontiguousarray(tr, np.float64).reshape(6)
+        _check(_lib().vh_match_motion_covariance(self._h, C.byref(ego), _ptr(tr) if tr is not None else None,
+                                                 C.byref(okin) if tr is not None else None, _ptr(cov), C.byref(ssr), C.byref(oko),
+                                                 C.byref(n)), "vh_match_motion_covariance")
+        return cov, ssr.value, bool(oko.value), n.value
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images on the device for getGain (vh_set_gain): before the first pushBack."""
@@ -806,6 +822,22 @@ class StreamGroup:
         _check(_lib().vh_group_refit_motion(self._h, C.byref(ego), 1 if reclassify else 0, _ptr(tr), _ptr(ok), _ptr(nupd), _ptr(counts)),
                "vh_group_refit_motion")
         return tr, ok.astype(bool), nupd, counts
+
+    def motionCovariance(self, ego: "EgoParams", tr=None, ok=None):
+        """The covariance of every stream's stereo motion over its compacted inlier list (vh_group_motion_covariance)
+        -> (cov [S, 6, 6], ssr [S], ok [S], counts [S]).  tr None (then ok None): under the tr / ok the lists were
+        classified under -- after refitMotion(reclassify=True) the refined motions -- which are on the device; else under
+        tr [S, 6] / ok [S], e.g. refitMotion's results after reclassify=False.  One without the other: VH_ERR_INVALID_ARG."""
+        cov = np.zeros((self.S, 6, 6), np.float64); ssr = np.zeros(self.S, np.float64); oko = np.zeros(self.S, np.int32)
+        counts = np.zeros(self.S, np.int32)
+        if tr is not None:
+            tr = np.ascontiguousarray(tr, np.float64)
+            assert tr.shape == (self.S, 6)
+        if ok is not None:
+            ok = np.ascontiguousarray(ok).astype(np.int32).reshape(self.S)
+        _check(_lib().vh_group_motion_covariance(self._h, C.byref(ego), None if tr is None else _ptr(tr), None if ok is None else _ptr(ok),
+                                                 _ptr(cov), _ptr(ssr), _ptr(oko), _ptr(counts)), "vh_group_motion_covariance")
+        return cov, ssr, oko.astype(bool), counts
 
     def motionInliersMono(self, mono: "MonoParams", model, ok) -> np.ndarray:
         """VisualOdometryMono::getInlier (reference src/viso_mono.cpp:268-315) on every stream's whole device-resident flow
@@ -1282,6 +1314,22 @@ def refit_motion(ego: EgoParams, match_lists, tr, ok, device: int = 0):
     _check(_lib().vh_refit_motion(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(tr), _ptr(ok), _ptr(tr_out), _ptr(ok_out),
                                   _ptr(nupd)), "vh_refit_motion")
     return tr_out[:n], ok_out[:n].astype(bool), nupd[:n]
+
+
+def motion_covariance(ego: EgoParams, match_lists, tr, ok, device: int = 0):
+    """The 6x6 covariance sigma^2 (J^T J)^-1 of stereo motions over whole quad lists, every record active, at the motions
+    tr [n, 6] / ok [n] (vh_motion_covariance): J and the residuals as the reference's computeResidualsAndJacobian forms
+    them at tr, sigma^2 = ssr / (4 N - 6).  -> (cov [n, 6, 6], ssr [n], ok [n] bool)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    pm = np.concatenate(lists) if int(offsets[-1]) else np.zeros(0, P_MATCH_DTYPE)
+    tr = np.ascontiguousarray(tr, np.float64).reshape(n, 6); ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    cov = np.zeros((max(n, 1), 6, 6), np.float64); ssr = np.zeros(max(n, 1), np.float64); ok_out = np.zeros(max(n, 1), np.int32)
+    _check(_lib().vh_motion_covariance(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(tr), _ptr(ok), _ptr(cov), _ptr(ssr),
+                                       _ptr(ok_out)), "vh_motion_covariance")
+    return cov[:n], ssr[:n], ok_out[:n].astype(bool)
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):

@@ -4,6 +4,7 @@
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
 //   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays
+//   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -302,6 +303,16 @@ struct RefitState {
   int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
 };
 
+// The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
+// 4.15): one arena block, allocated by the first call -- the outputs, and the arrays a caller-given tr / ok go up into.
+struct CovState {
+  double *d_cov = nullptr;                     // [S][36]
+  double *d_ssr = nullptr;                     // [S]
+  int32_t *d_ok = nullptr;                     // [S] ok_out
+  double *d_tr = nullptr;                      // [S][6] the caller's motion (the classification's own stays in inl.d_tr)
+  int32_t *d_okin = nullptr;                   // [S]
+};
+
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
 // arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
 // first call that needs it.  Nothing here exists while the switch is off.
@@ -511,6 +522,7 @@ struct Group {
   ReconHistory rh;
   InlierState inl;
   RefitState rft;
+  CovState cv;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -606,6 +618,9 @@ struct Group {
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
   int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
   int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);
+
+  // ---- engine_cov.hip ----
+  int32_t motion_covariance(const vh_ego_params *e, const double *tr, const int32_t *ok, double *cov, double *ssr, int32_t *ok_out, int32_t *counts);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

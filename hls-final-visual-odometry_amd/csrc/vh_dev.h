@@ -453,6 +453,23 @@ struct VhRefitArgs {
 };
 void vh_launch_refit(const VhRefitArgs &a, hipStream_t st);
 
+// The covariance of a stereo motion over whole lists (kernels_cov.hip): one accumulation pass at
+// a fixed tr, sigma^2 (J^T J)^-1, one workgroup of VH_REFIT_THREADS lanes per list.  The lists are addressed as vh_list does.
+struct VhCovArgs {
+  vh_ego_params e;          // f, cu, cv, base, reweighting (ransac_iters and inlier_threshold are not read)
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists;
+  const double *tr;         // [n_lists][6]; not read where ok = 0 or the list has fewer than 6 records
+  const int32_t *ok;        // [n_lists]
+  double *cov;              // [n_lists][36] row-major, exactly symmetric; zero where ok_out = 0
+  double *ssr;              // [n_lists] the sum of the 4 N squared weighted residuals; zero where ok_out = 0
+  int32_t *ok_out;          // [n_lists]
+};
+void vh_launch_motion_cov(const VhCovArgs &a, hipStream_t st);
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

@@ -1,7 +1,8 @@
 // vh_ego.h -- the stereo reprojection model of VisualOdometryStereo, once: the rotation and its derivatives, the
 // prediction of one match, the inlier test of getInlier, and one match's rows of the normal equations with their 6x6
 // solve (updateParameters).  kernels_ego.hip (the estimator), kernels_inlier.hip (the classification of whole lists
-// under a given motion) and kernels_refit.hip (Gauss-Newton on whole lists) include it; all are built with
+// under a given motion), kernels_refit.hip (Gauss-Newton on whole lists) and kernels_cov.hip (the covariance of a motion
+// over whole lists) include it; all are built with
 // -ffp-contract=off, so every product and sum rounds on its own as on the reference's x86 build.
 #ifndef VH_EGO_H
 #define VH_EGO_H
@@ -79,7 +80,9 @@ VH_EGO_HD bool ego_is_inlier(const vh_ego_params &e, const EgoRot &R, const doub
 
 // Adds the four rows of one match to the normal equations: acc[0..20] = upper triangle of
 // J^T J (row-major, m <= n), acc[21..26] = J^T r; rows in the reference's order (u1, v1, u2, v2).
-VH_EGO_HD void ego_accumulate(const vh_ego_params &e, const EgoRot &R, const double tr[6], const EgoObs &o, double acc[27]) {
+// WITH_SSR (kernels_cov.hip): acc has 28 entries, acc[27] += the four squared weighted residuals, in that order.
+template <bool WITH_SSR = false>
+VH_EGO_HD void ego_accumulate(const vh_ego_params &e, const EgoRot &R, const double tr[6], const EgoObs &o, double *acc) {
   double p[4], X1c, Y1c, Z1c;
   ego_predict(e, R, tr, o, p, X1c, Y1c, Z1c);
   double weight = 1.0;
@@ -109,6 +112,7 @@ VH_EGO_HD void ego_accumulate(const vh_ego_params &e, const EgoRot &R, const dou
       for (int32_t n = m; n < 6; n++) acc[k++] += Jr[row][m] * Jr[row][n];
 #pragma unroll
     for (int32_t m = 0; m < 6; m++) acc[21 + m] += Jr[row][m] * res;
+    if (WITH_SSR) acc[27] += res * res;
   }
 }
 

@@ -78,3 +78,42 @@ template <int N> SVD_HD bool vh_gauss_jordan(double (&A)[N][N], double (&b)[N]) 
   }
   return true;
 }
+
+// The same elimination with NB right-hand sides, on arrays in addressable memory: A [N][N] and B [N][NB], row-major,
+// both changed in place; on success B holds the solutions (the inverse, for the unit matrix).  The pivot's row and
+// column index the arrays as they do in the original, so this is for memory where a data-dependent index is free -- the
+// LDS of kernels_cov.hip, the host -- and not for private arrays (see above).  A function of its own: the register
+// form above is untouched by it.  The pivot rule, irow / icol and the arithmetic on every element are those above, so a
+// column of B equals the single right-hand side solved alone, bit for bit.
+template <int N, int NB> SVD_HD bool vh_gauss_jordan_mem(double *__restrict__ A, double *__restrict__ B) {
+  static_assert(N <= 8, "ipiv packs a 4-bit count per column");
+  uint32_t ipiv = 0;  // nibble q: how often column q was chosen (ipiv[q] above; more than once only when every candidate of a step is NaN)
+  int32_t irow = 0, icol = 0;
+  for (int32_t i = 0; i < N; i++) {
+    double big = 0.0;
+    for (int32_t j = 0; j < N; j++)
+      for (int32_t k = 0; k < N; k++) {
+        const double v = fabs(A[N * j + k]);
+        if (((ipiv >> (4 * j)) & 15u) != 1u && ((ipiv >> (4 * k)) & 15u) == 0u && v >= big) { big = v; irow = j; icol = k; }
+      }
+    ipiv += 1u << (4 * icol);
+    if (irow != icol) {
+      for (int32_t l = 0; l < N; l++) { const double t = A[N * irow + l]; A[N * irow + l] = A[N * icol + l]; A[N * icol + l] = t; }
+      for (int32_t l = 0; l < NB; l++) { const double t = B[NB * irow + l]; B[NB * irow + l] = B[NB * icol + l]; B[NB * icol + l] = t; }
+    }
+    const double piv = A[N * icol + icol];
+    if (fabs(piv) < 1e-20) return false;
+    const double pivinv = 1.0 / piv;
+    A[N * icol + icol] = 1.0;
+    for (int32_t l = 0; l < N; l++) A[N * icol + l] *= pivinv;
+    for (int32_t l = 0; l < NB; l++) B[NB * icol + l] *= pivinv;
+    for (int32_t ll = 0; ll < N; ll++) {
+      if (ll == icol) continue;
+      const double dum = A[N * ll + icol];
+      A[N * ll + icol] = 0.0;
+      for (int32_t l = 0; l < N; l++) A[N * ll + l] -= A[N * icol + l] * dum;
+      for (int32_t l = 0; l < NB; l++) B[NB * ll + l] -= B[NB * icol + l] * dum;
+    }
+  }
+  return true;
+}

@@ -664,6 +664,46 @@ int32_t vh_group_refit_motion(vh_group *g, const vh_ego_params *e, int32_t recla
 int32_t vh_match_refit_motion(vh_matcher *m, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
                               int32_t *n_updates, int32_t *count);
 
+/* ---- the covariance of a stereo motion over whole lists (csrc/kernels_cov.hip) --------------------------
+ * How well a quad list of N records determines the motion tr[6] = (rx,ry,rz,tx,ty,tz): the 6x6 covariance of the least
+ * squares estimate, in the order of tr.  The reference and stock libviso2 have no counterpart; every term is theirs:
+ *   J (4N x 6), r (4N): the rows computeResidualsAndJacobian (src/viso_stereo.cpp:274-330) forms per record AT tr, every
+ *     record active, in the order u1c, v1c, u2c, v2c, both weighted by 1 / (|u1c - cu| / |cu| + 0.05) under `reweighting`;
+ *   A = J^T J;  ssr = sum r^2 (the 4N weighted squared residuals);  dof = 4N - 6;  sigma2 = ssr / dof;
+ *   cov = sigma2 * A^-1, A^-1 by Matrix::solve (src/matrix.cpp:417-504) on the six unit right-hand sides; the upper
+ *     triangle m <= n is computed and mirrored: cov is exactly symmetric, row-major.
+ * One pass at a fixed tr, no update: pass the motion the list was fitted to (vh_refit_motion's tr_out on its own list).
+ * Double precision; f, cu, cv, base, reweighting are read, inlier_threshold and ransac_iters are not.  Per list, never
+ * an error of the call:
+ *   ok_out = 0, cov = 0, ssr = 0 where ok == 0 (tr is then not read), where N < 6, where Matrix::solve refuses
+ *   (a pivot below 1e-20), and where ssr or an entry of cov is not finite (non-finite records propagate and end here);
+ *   ok_out = 1 otherwise.
+ * The sums run in parallel in an order that depends on N alone: cov agrees with a sequential evaluation to rounding, is
+ * the same from run to run, does not depend on the other lists of the call, and is the same bytes from the stateless
+ * and the handle forms on the same records and tr.
+ *
+ * Stateless: lists laid out as for vh_refit_motion, tr[n_sets][6], ok[n_sets] -> cov[n_sets][36], ssr[n_sets],
+ * ok_out[n_sets].  n_sets == 0 or no records at all: VH_OK (outputs zero), nothing is launched and no device is needed.
+ * Length limits as vh_motion_inliers. */
+int32_t vh_motion_covariance(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                             const double *tr, const int32_t *ok, double *cov, double *ssr, int32_t *ok_out);
+/* The same on the compacted inlier lists of the handle's current STEREO classification -> cov[S][36], ssr[S], ok_out[S]
+ * and counts[S] (the lists' lengths); the call is synchronous.
+ *   tr == NULL (then ok == NULL): under the tr / ok that classification was made under, which are on the device already
+ *   -- after vh_group_refit_motion(reclassify = 1) the refined motion and its inliers.  Nothing is uploaded.
+ *   tr != NULL (then ok != NULL; one without the other is VH_ERR_INVALID_ARG): tr[S][6], ok[S] go up, the caller's motion
+ *   on the same lists -- after reclassify = 0, where the refit's tr_out belongs to the lists it was fitted on.
+ * VH_ERR_STATE where vh_group_refit_motion returns it: before any classification of the current lists, after the next
+ * push or match, and when the current result is a mono classification.  Rows without a pair have ok_out = 0.  Plain
+ * groups, sequence handles and lone matchers.  The first call adds one block of 352 bytes per stream (288 + 8 + 4 and the
+ * 48 + 4 a caller's tr / ok go up into; each of the five arrays rounded up to 256 bytes), counted by vh_group_device_bytes; a handle that never calls it allocates and launches
+ * nothing.  A refused allocation is VH_ERR_HIP before any launch and leaves the handle as it was; the call may be
+ * repeated.  Profile scope: "motion_cov". */
+int32_t vh_group_motion_covariance(vh_group *g, const vh_ego_params *e, const double *tr, const int32_t *ok, double *cov, double *ssr,
+                                   int32_t *ok_out, int32_t *counts);
+int32_t vh_match_motion_covariance(vh_matcher *m, const vh_ego_params *e, const double *tr, const int32_t *ok, double *cov, double *ssr,
+                                   int32_t *ok_out, int32_t *count);
+
 /* ---- the camera gain over motion inliers (csrc/kernels_gain.hip) -----------------------------------------
  * Matcher::getGain (reference src/matcher.h:145-148, src/viso.h:104: "given a vector of inliers computes gain factor
  * between the current and the previous frame"; the reference keeps the body commented out and its helper
@@ -1119,7 +1159,7 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place;
  *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
- *  "motion_refit" per vh_group_refit_motion;
+ *  "motion_refit" per vh_group_refit_motion, "motion_cov" per vh_group_motion_covariance;
  *  with vh_group_set_gain "gain_copy" per sub-batch of a push, and "gain_ratio", "gain_sum" per vh_group_gain(_indices))
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
