@@ -89,6 +89,7 @@ ABI_SYMBOLS = (
     "vh_sequence_set_multi_stage", "vh_set_multi_stage_prior", "vh_group_set_multi_stage_prior",
     "vh_remove_outliers_pm_rule", "vh_remove_outliers_device_rule", "vh_set_vote_rule", "vh_group_set_vote_rule",
     "vh_motion_covariance", "vh_group_motion_covariance", "vh_match_motion_covariance",
+    "vh_refit_model_mono", "vh_group_refit_model_mono", "vh_match_refit_model_mono",
 )
 
 
@@ -338,6 +339,8 @@ def _lib():
             "vh_refit_motion": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
             "vh_motion_covariance": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp], "vh_match_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_refit_model_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
@@ -562,6 +565,16 @@ class Matcher:
                                                  C.byref(okin) if tr is not None else None, _ptr(cov), C.byref(ssr), C.byref(oko),
                                                  C.byref(n)), "vh_match_motion_covariance")
         return cov, ssr.value, bool(oko.value), n.value
+
+    def refitModelMono(self, mono: "MonoParams", reclassify: bool = False):
+        """fundamentalMatrix (reference src/viso_mono.cpp:235-266) on ALL inliers of the last motionInliersMono, in the frame
+        of the model it classified under (vh_match_refit_model_mono) -> (model [1] MONO_MODEL_DTYPE, ok, w [2] = the two
+        smallest singular values w[8], w[7] of the moment matrix, count); reclassify: the list is classified again under
+        the refined model, and count / getInlierMatches() are that classification's."""
+        model = np.zeros(1, MONO_MODEL_DTYPE); ok = C.c_int32(0); w = np.zeros(2, np.float64); n = C.c_int32(0)
+        _check(_lib().vh_match_refit_model_mono(self._h, C.byref(mono), 1 if reclassify else 0, _ptr(model), C.byref(ok), _ptr(w), C.byref(n)),
+               "vh_match_refit_model_mono")
+        return model, bool(ok.value), w, n.value
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images on the device for getGain (vh_set_gain): before the first pushBack."""
@@ -848,6 +861,18 @@ class StreamGroup:
         counts = np.zeros(self.S, np.int32)
         _check(_lib().vh_group_motion_inliers_mono(self._h, C.byref(mono), _ptr(model), _ptr(ok), _ptr(counts)), "vh_group_motion_inliers_mono")
         return counts
+
+    def refitModelMono(self, mono: "MonoParams", reclassify: bool = False):
+        """fundamentalMatrix (reference src/viso_mono.cpp:235-266) on every stream's compacted inlier list of the last
+        motionInliersMono, in the frame of the model / ok it classified under (vh_group_refit_model_mono) -> (model [S]
+        MONO_MODEL_DTYPE, ok [S], w [S, 2] = the two smallest singular values w[8], w[7] of the moment matrix, counts [S]);
+        reclassify: the lists are classified again under the refined models (queued behind the refit), and counts and the
+        getters are that classification's."""
+        model = np.zeros(self.S, MONO_MODEL_DTYPE); ok = np.zeros(self.S, np.int32); w = np.zeros((self.S, 2), np.float64)
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_refit_model_mono(self._h, C.byref(mono), 1 if reclassify else 0, _ptr(model), _ptr(ok), _ptr(w), _ptr(counts)),
+               "vh_group_refit_model_mono")
+        return model, ok.astype(bool), w, counts
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images of every stream (sequence handle: frame) on the device for gain()
@@ -1375,6 +1400,23 @@ def motion_inliers_mono(mono: MonoParams, match_lists, model, ok, device: int = 
     sl = [slice(int(offsets[s]), int(offsets[s]) + int(ninl[s])) for s in range(n)]
     return ([flags[offsets[s]:offsets[s + 1]].copy() for s in range(n)], ninl[:n],
             [out[q].copy() for q in sl], [pos[q].copy() for q in sl])
+
+
+def refit_model_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
+    """fundamentalMatrix (reference src/viso_mono.cpp:235-266) over whole flow or quad lists, every record active, in the
+    normalised frame of model [n] (MONO_MODEL_DTYPE) / ok [n] (vh_refit_model_mono): c, s copied, F refitted on all records.
+    -> (model [n], ok [n] bool, w [n, 2]: the two smallest singular values w[8], w[7] of the 9x9 moment matrix)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    pm = np.concatenate(lists) if int(offsets[-1]) else np.zeros(0, P_MATCH_DTYPE)
+    model = _models(model, n) if n else np.zeros(1, MONO_MODEL_DTYPE)
+    ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    model_out = np.zeros(max(n, 1), MONO_MODEL_DTYPE); ok_out = np.zeros(max(n, 1), np.int32); w = np.zeros((max(n, 1), 2), np.float64)
+    _check(_lib().vh_refit_model_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(model_out), _ptr(ok_out),
+                                      _ptr(w)), "vh_refit_model_mono")
+    return model_out[:n], ok_out[:n].astype(bool), w[:n]
 
 
 def remove_outliers(pm, rule=None) -> np.ndarray:

@@ -5,6 +5,7 @@
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
 //   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays
 //   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
+//   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -265,7 +266,7 @@ struct InlierTest {
   const vh_mono_params *mono = nullptr;
   const vh_mono_model *model = nullptr;
   bool is_mono = false;
-  bool on_device = false;  // stereo: tr and ok are what the handle's block holds already (Group::refit_motion); nothing goes up
+  bool on_device = false;  // tr (mono: model) and ok are what the handle's block holds already (Group::refit_motion, refit_model_mono); nothing goes up
   static InlierTest stereo(const vh_ego_params *e, const double *tr) { InlierTest t; t.ego = e; t.tr = tr; return t; }
   static InlierTest monocular(const vh_mono_params *e, const vh_mono_model *m) { InlierTest t; t.mono = e; t.model = m; t.is_mono = true; return t; }
   bool params_ok() const { return is_mono ? mono != nullptr : ego != nullptr; }
@@ -301,6 +302,14 @@ struct InlierState : InlierArrays {      // [S][mcap], [S][tiles], [S], [S][6]
 struct RefitState {
   double *d_tr = nullptr;                      // [S][6]
   int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
+};
+
+// The epipolar model refitted on the compacted inlier lists of a mono classification (vh_group_refit_model_mono;
+// engine_mono_refit.hip): one arena block, allocated by the first call -- the outputs are all of it.
+struct MonoRefitState {
+  vh_mono_model *d_model = nullptr;  // [S]
+  double *d_w = nullptr;             // [S][2]
+  int32_t *d_ok = nullptr;           // [S]
 };
 
 // The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
@@ -523,6 +532,7 @@ struct Group {
   InlierState inl;
   RefitState rft;
   CovState cv;
+  MonoRefitState mrf;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -621,6 +631,9 @@ struct Group {
 
   // ---- engine_cov.hip ----
   int32_t motion_covariance(const vh_ego_params *e, const double *tr, const int32_t *ok, double *cov, double *ssr, int32_t *ok_out, int32_t *counts);
+
+  // ---- engine_mono_refit.hip ----
+  int32_t refit_model_mono(const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out, int32_t *ok_out, double *w_out, int32_t *counts);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

@@ -25,7 +25,7 @@ void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group 
 }
 
 int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts) {
-  if (!(t.on_device ? t.params_ok() && !t.is_mono : t.args_ok() && ok) || !counts) return VH_ERR_INVALID_ARG;
+  if (!(t.on_device ? t.params_ok() : t.args_ok() && ok) || !counts) return VH_ERR_INVALID_ARG;
   // the stereo test reads the right camera's columns; the mono test the left camera's flow, which flow and quad lists carry
   if (!allocated || !(last_method == VH_METHOD_QUAD || (t.is_mono && last_method == VH_METHOD_FLOW))) return VH_ERR_STATE;
   const int32_t tiles = (mcap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
@@ -56,9 +56,11 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
   bool replaced = false;
   { const int32_t rc = stage_host_lists(inl.host, post_stream, replaced, d_lists, d_counts); if (rc) return rc; }
   inl.n_list.assign((size_t)S, 0); inl.n_inl.assign((size_t)S, 0);
-  if (t.is_mono) VH_HIP(hipMemcpyAsync(inl.d_model, t.model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyHostToDevice, post_stream));
-  else if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
-  if (!t.on_device) VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  if (!t.on_device) {  // (on_device: a refit put them there)
+    if (t.is_mono) VH_HIP(hipMemcpyAsync(inl.d_model, t.model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+    else VH_HIP(hipMemcpyAsync(inl.d_tr, t.tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
+    VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  }
   VhInlierArgs a{};
   a.pm = d_lists; a.pm_stride = mcap; a.counts = d_counts; a.count_cap = mcap;
   a.n_lists = S; a.tiles_per_list = inl.tiles;

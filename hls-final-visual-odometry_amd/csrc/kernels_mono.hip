@@ -37,6 +37,7 @@
 #include "svd_static.h"
 #include "vh_wave.h"
 #include "vh_mono.h"
+#include "vh_rank2.h"  // matmul, rank2_3x3
 
 namespace {
 
@@ -153,38 +154,9 @@ __device__ __forceinline__ void svd_sort_phase(int n, double *w, Save save, Move
   } while (inc > 1);
 }
 
-// C = A (ma x na) * B (na x nb): Matrix::operator* (src/matrix.cpp:263-277), sums from 0, k ascending
-__device__ void matmul(const double *A, int ma, int na, const double *B, int nb, double *C) {
-  for (int i = 0; i < ma; i++)
-    for (int j = 0; j < nb; j++) {
-      double c = 0.0;
-      for (int k = 0; k < na; k++) c += A[i * na + k] * B[k * nb + j];
-      C[i * nb + j] = c;
-    }
-}
 __device__ void transpose3(const double *A, double *T) {
   for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T[j * 3 + i] = A[i * 3 + j];
 }
-// Matrix::svd of a 3x3 followed by U * diag(W with W[2] = 0) * ~V (src/viso_mono.cpp:262-265, :91-94).
-// The factors live in registers (svd_static.h: every index static after unrolling).
-// (returns svd_static's zero-pivot flag, see fundamental8)
-__device__ __forceinline__ bool rank2_3x3(const double *M, double *out) {
-  double U[3][3], w[3], V[3][3], a[9], D[9], UD[9], Vt[9];
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) U[i][j] = M[i * 3 + j];
-  const bool zero_pivot = svd_static<3, 3>(U, w, V);
-#pragma unroll
-  for (int i = 0; i < 3; i++)
-#pragma unroll
-    for (int j = 0; j < 3; j++) { a[i * 3 + j] = U[i][j]; Vt[j * 3 + i] = V[i][j]; D[i * 3 + j] = 0.0; }
-  D[0] = w[0]; D[4] = w[1]; D[8] = 0.0;
-  matmul(a, 3, 3, D, 3, UD);
-  matmul(UD, 3, 3, Vt, 3, out);
-  return zero_pivot;
-}
-
 // Matrix::det of a 3x3 (src/matrix.cpp:400-415) over Matrix::lu (:514-572)
 __device__ double det3(const double *M) {
   double a[3][3], vv[3], big, dum, sum, temp, d = 1.0;
@@ -797,11 +769,7 @@ mono_final_a_kernel(vh_mono_params e, const vh_p_match *__restrict__ pm_base, in
   // F from all inliers: the nbest x 9 system (src/viso_mono.cpp:84, :242-256)
   double *Asys = nbest <= MONO_LDS_ROWS ? sA : L.A;
   for (int32_t i = tid; i < nbest; i += MONO_T) {
-    const float4 q = L.pn[L.idx[i]];
-    double *r = Asys + (int64_t)i * 9;
-    r[0] = (double)(q.z * q.x); r[1] = (double)(q.z * q.y); r[2] = (double)q.z;
-    r[3] = (double)(q.w * q.x); r[4] = (double)(q.w * q.y); r[5] = (double)q.w;
-    r[6] = (double)q.x; r[7] = (double)q.y; r[8] = 1.0;
+    mono_row9(L.pn[L.idx[i]], Asys + (int64_t)i * 9);
   }
   __syncthreads();
   double w9[9];

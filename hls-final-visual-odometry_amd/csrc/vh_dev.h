@@ -470,6 +470,23 @@ struct VhCovArgs {
 };
 void vh_launch_motion_cov(const VhCovArgs &a, hipStream_t st);
 
+// The epipolar model refitted on whole lists (kernels_mono_refit.hip): fundamentalMatrix over every
+// record of a list in the frame of the incoming model, one workgroup of VH_REFIT_THREADS lanes per list.  The lists are
+// addressed as vh_list does.
+struct VhMonoRefitArgs {
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists;
+  const vh_mono_model *model_in;  // [n_lists]; not read where ok_in = 0 or the list has fewer than 10 records
+  const int32_t *ok_in;           // [n_lists]
+  vh_mono_model *model_out;       // [n_lists]; c, s copied, F refitted, valid = 1; the zero record where ok_out = 0
+  int32_t *ok_out;                // [n_lists]
+  double *w_out;                  // [n_lists][2] the two smallest singular values of M: w[8], w[7]; zero where ok_out = 0
+};
+void vh_launch_mono_refit(const VhMonoRefitArgs &a, hipStream_t st);
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

@@ -869,6 +869,60 @@ int32_t vh_motion_inliers_mono(const vh_mono_params *e, int32_t device, int32_t 
 int32_t vh_group_motion_inliers_mono(vh_group *g, const vh_mono_params *e, const vh_mono_model *model, const int32_t *ok,
                                      int32_t *counts);
 int32_t vh_match_inliers_mono(vh_matcher *m, const vh_mono_params *e, const vh_mono_model *model, int32_t ok, int32_t *count);
+
+/* ---- the epipolar model refitted on whole lists (csrc/kernels_mono_refit.hip) ----------------------------
+ * The estimator's F comes from the inliers of its best hypothesis in a bucketed list (the refit of src/viso_mono.cpp:80,
+ * a few hundred rows).  This is the same fundamentalMatrix (:235-266) over EVERY record of any flow or quad list (pass
+ * an inlier list), in the normalised frame of the model the list was classified under.  The reference has no
+ * counterpart (its estimator stops at :80); every term is its own:
+ *   1. normalisation: the incoming model's.  c[4] and s[2] are copied to the output unchanged (bit for bit), not
+ *      recomputed over the list; a record is normalised as vh_motion_inliers_mono does -- (float)((double)u - c), then
+ *      (float)((double)q * s), one rounding to float per step;
+ *   2. rows: the nine entries of :244-252 as the estimator's own refit forms them -- u1c*u1p, u1c*v1p, u1c, v1c*u1p,
+ *      v1c*v1p, v1c, u1p, v1p, 1: float products of the normalised float fields, then widened to double;
+ *   3. moments: M = sum a a^T in double, the 45 sums of the upper triangle mirrored.  The sums run in parallel in an
+ *      order that depends on the list's length alone: the result agrees with a sequential evaluation to rounding, is the
+ *      same bytes from run to run, alone or among other lists, and from the stateless and the handle forms;
+ *   4. null direction: f = the right singular vector of M for its smallest singular value -- Matrix::svd
+ *      (src/matrix.cpp:579-802, restated) on the 9 x 9 M, the column of V its descending sort puts last (M is symmetric
+ *      positive semi-definite: the right singular vectors of the N x 9 system the reference decomposes).  Matrix::svd's
+ *      sign normalisation is not applied; instead f is negated when its dot product with model_in's F (nine terms,
+ *      row-major order, in double) is negative -- a zero or NaN product leaves it as it is -- so that the refined F is
+ *      comparable entry by entry with the F it refines.  w_out[.][0] = w[8] and w_out[.][1] = w[7], the two smallest
+ *      singular values of M (squares of the system's): w[8] / w[7] near 1 is a degenerate fit (pure rotation, a plane);
+ *   5. rank 2: the 3 x 3 step of :262-265 on f.
+ *   6. per list, never an error of the call: ok_out = 0, a zeroed model_out and w_out = 0 where ok_in == 0 (model_in is
+ *      then not read), where the list has fewer than 10 records (the reference's floor at :76), and where an entry of
+ *      F, w[8] or w[7] is not finite (non-finite records propagate and end here); otherwise ok_out = 1, valid = 1.0.
+ * Double precision; vh_mono_params is not read by the refit itself (inlier_threshold by the reclassification below).
+ *
+ * Stateless: lists laid out as for vh_motion_inliers_mono, model_in[n_sets], ok_in[n_sets] -> model_out[n_sets],
+ * ok_out[n_sets], w_out[n_sets][2].  n_sets == 0 or no records at all: VH_OK (outputs zero), nothing is launched and no
+ * device is needed.  Length limits as vh_motion_inliers. */
+int32_t vh_refit_model_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                            const vh_mono_model *model_in, const int32_t *ok_in, vh_mono_model *model_out, int32_t *ok_out,
+                            double *w_out /* [n_sets][2] */);
+/* The same on the compacted inlier lists of the handle's current MONO classification (vh_group_motion_inliers_mono /
+ * vh_match_inliers_mono), from the model / ok that classification was made under -- both are on the device already:
+ * nothing goes up, model_out[S], ok_out[S], w_out[S][2] and counts[S] come back; the call is synchronous.  VH_ERR_STATE
+ * before any classification of the current lists, after the next push or match, and when the current result is a
+ * stereo classification.  Rows without a pair have ok_out = 0.
+ *   reclassify == 0: the classification is untouched, counts are its counts.
+ *   reclassify != 0: the lists are classified again under model_out / ok_out with e->inlier_threshold, queued behind
+ *   the refit on the same stream (the host does not wait in between); the refined model becomes the model the
+ *   classification was made under, so a second call refits again with nothing uploaded; the getters and
+ *   vh_group_inliers_device then return the refined model's inliers and counts are theirs (VH_ERR_CAPACITY as
+ *   vh_group_motion_inliers).  Should that classification fail with another error, model_out / ok_out / w_out are still
+ *   delivered and the handle is left without a classification (VH_ERR_STATE from the getters) until
+ *   vh_group_motion_inliers_mono is called again.
+ * Plain groups, sequence handles and lone matchers.  The first call adds one block of 148 bytes per stream (128 + 16 +
+ * 4, each of its three arrays rounded up to 256 bytes), counted by vh_group_device_bytes; a handle that never calls it
+ * allocates and launches nothing.  A refused allocation is VH_ERR_HIP before any launch and leaves the handle as it
+ * was; the call may be repeated.  Profile scope: "mono_refit". */
+int32_t vh_group_refit_model_mono(vh_group *g, const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out,
+                                  int32_t *ok_out, double *w_out, int32_t *counts);
+int32_t vh_match_refit_model_mono(vh_matcher *m, const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out,
+                                  int32_t *ok_out, double *w_out, int32_t *count);
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
@@ -1159,7 +1213,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  detection and pass 1, and the host steps "sparse_vote_host", "statistics_host": wall-clock milliseconds;
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place;
  *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
- *  "motion_refit" per vh_group_refit_motion, "motion_cov" per vh_group_motion_covariance;
+ *  "motion_refit" per vh_group_refit_motion, "motion_cov" per vh_group_motion_covariance, "mono_refit" per
+ *  vh_group_refit_model_mono;
  *  with vh_group_set_gain "gain_copy" per sub-batch of a push, and "gain_ratio", "gain_sum" per vh_group_gain(_indices))
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
