@@ -90,6 +90,7 @@ ABI_SYMBOLS = (
     "vh_remove_outliers_pm_rule", "vh_remove_outliers_device_rule", "vh_set_vote_rule", "vh_group_set_vote_rule",
     "vh_motion_covariance", "vh_group_motion_covariance", "vh_match_motion_covariance",
     "vh_refit_model_mono", "vh_group_refit_model_mono", "vh_match_refit_model_mono",
+    "vh_pose_mono", "vh_group_pose_mono", "vh_match_pose_mono",
 )
 
 
@@ -172,6 +173,9 @@ class MonoModel(C.Structure):
 
 #: numpy layout of vh_mono_model, for arrays of models (one per list / stream)
 MONO_MODEL_DTYPE = np.dtype([("c", "<f8", (4,)), ("s", "<f8", (2,)), ("F", "<f8", (9,)), ("valid", "<f8")])
+# vh_mono_pose (152 bytes): what pose_mono / poseMono formed tr from
+MONO_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "<f8"), ("median", "<f8"), ("plane", "<f8"),
+                            ("chirality", "<i4", (4,)), ("candidate", "<i4"), ("n_front", "<i4"), ("reason", "<i4"), ("reserved_", "<i4")])
 
 
 def _models(model, n):
@@ -341,6 +345,8 @@ def _lib():
             "vh_group_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp], "vh_match_motion_covariance": [vp, vp, vp, vp, vp, vp, vp, vp],
             "vh_refit_model_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp],
+            "vh_pose_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_pose_mono": [vp, vp, vp, vp, vp, vp], "vh_match_pose_mono": [vp, vp, vp, vp, vp],
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
@@ -575,6 +581,15 @@ class Matcher:
         _check(_lib().vh_match_refit_model_mono(self._h, C.byref(mono), 1 if reclassify else 0, _ptr(model), C.byref(ok), _ptr(w), C.byref(n)),
                "vh_match_refit_model_mono")
         return model, bool(ok.value), w, n.value
+
+    def poseMono(self, mono: "MonoParams", pose: bool = False):
+        """The mono pose (reference src/viso_mono.cpp:83-158: E, R|t, chirality, the ground-plane scale) over ALL inliers of
+        the last motionInliersMono, under the model it classified under (vh_match_pose_mono) -> (tr [6], ok) and, with
+        pose=True, the MONO_POSE_DTYPE record [1] as a third value."""
+        tr = np.zeros(6, np.float64); ok = C.c_int32(0)
+        rec = np.zeros(1, MONO_POSE_DTYPE)
+        _check(_lib().vh_match_pose_mono(self._h, C.byref(mono), _ptr(tr), C.byref(ok), _ptr(rec) if pose else None), "vh_match_pose_mono")
+        return (tr, bool(ok.value), rec) if pose else (tr, bool(ok.value))
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images on the device for getGain (vh_set_gain): before the first pushBack."""
@@ -873,6 +888,16 @@ class StreamGroup:
         _check(_lib().vh_group_refit_model_mono(self._h, C.byref(mono), 1 if reclassify else 0, _ptr(model), _ptr(ok), _ptr(w), _ptr(counts)),
                "vh_group_refit_model_mono")
         return model, ok.astype(bool), w, counts
+
+    def poseMono(self, mono: "MonoParams", pose: bool = False):
+        """The mono pose (reference src/viso_mono.cpp:83-158: E, R|t, chirality, the ground-plane scale) over every stream's
+        compacted inlier list of the last motionInliersMono, under the model / ok it classified under -- after
+        refitModelMono(reclassify=True) the refined model with its inliers (vh_group_pose_mono) -> (tr [S, 6], ok [S],
+        counts [S]) and, with pose=True, the MONO_POSE_DTYPE records [S] as a fourth value."""
+        tr = np.zeros((self.S, 6), np.float64); ok = np.zeros(self.S, np.int32); counts = np.zeros(self.S, np.int32)
+        rec = np.zeros(self.S, MONO_POSE_DTYPE)
+        _check(_lib().vh_group_pose_mono(self._h, C.byref(mono), _ptr(tr), _ptr(ok), _ptr(rec) if pose else None, _ptr(counts)), "vh_group_pose_mono")
+        return (tr, ok.astype(bool), counts, rec) if pose else (tr, ok.astype(bool), counts)
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images of every stream (sequence handle: frame) on the device for gain()
@@ -1417,6 +1442,23 @@ def refit_model_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
     _check(_lib().vh_refit_model_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(model_out), _ptr(ok_out),
                                       _ptr(w)), "vh_refit_model_mono")
     return model_out[:n], ok_out[:n].astype(bool), w[:n]
+
+
+def pose_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
+    """The rest of VisualOdometryMono::estimateMotion after the refit (reference src/viso_mono.cpp:83-158) over whole flow or
+    quad lists under model [n] (MONO_MODEL_DTYPE) / ok [n] (vh_pose_mono): E, the four (R, t) candidates, the chirality count
+    of every record, the ground-plane vote over the points in front.  -> (tr [n, 6], ok [n] bool, pose [n] MONO_POSE_DTYPE)."""
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    pm = np.concatenate(lists) if int(offsets[-1]) else np.zeros(0, P_MATCH_DTYPE)
+    model = _models(model, n) if n else np.zeros(1, MONO_MODEL_DTYPE)
+    ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    tr = np.zeros((max(n, 1), 6), np.float64); ok_out = np.zeros(max(n, 1), np.int32); pose = np.zeros(max(n, 1), MONO_POSE_DTYPE)
+    _check(_lib().vh_pose_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(tr), _ptr(ok_out), _ptr(pose)),
+           "vh_pose_mono")
+    return tr[:n], ok_out[:n].astype(bool), pose[:n]
 
 
 def remove_outliers(pm, rule=None) -> np.ndarray:

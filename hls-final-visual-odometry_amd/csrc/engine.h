@@ -6,6 +6,7 @@
 //   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays
 //   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
+//   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -312,6 +313,16 @@ struct MonoRefitState {
   int32_t *d_ok = nullptr;           // [S]
 };
 
+// The mono pose over the compacted inlier lists of a mono classification (vh_group_pose_mono; engine_mono_pose.hip,
+// DESIGN.md section 4.17): one arena block, allocated by the first call.
+struct MonoPoseState {
+  double *d_dist = nullptr, *d_d = nullptr;  // [S][mcap] the points in front: L1 distance (later the vote's sum), ground-plane coordinate
+  double *d_hdr = nullptr;                   // [S][VH_MONO_POSE_HDR]
+  double *d_tr = nullptr;                    // [S][6]
+  vh_mono_pose *d_pose = nullptr;            // [S]
+  int32_t *d_ok = nullptr;                   // [S]
+};
+
 // The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
 // 4.15): one arena block, allocated by the first call -- the outputs, and the arrays a caller-given tr / ok go up into.
 struct CovState {
@@ -533,6 +544,7 @@ struct Group {
   RefitState rft;
   CovState cv;
   MonoRefitState mrf;
+  MonoPoseState mps;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -634,6 +646,9 @@ struct Group {
 
   // ---- engine_mono_refit.hip ----
   int32_t refit_model_mono(const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out, int32_t *ok_out, double *w_out, int32_t *counts);
+
+  // ---- engine_mono_pose.hip ----
+  int32_t pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

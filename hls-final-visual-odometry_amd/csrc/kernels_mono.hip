@@ -38,6 +38,7 @@
 #include "vh_wave.h"
 #include "vh_mono.h"
 #include "vh_rank2.h"  // matmul, rank2_3x3
+#include "vh_mono_pose.h"  // transpose3, det3
 
 namespace {
 
@@ -154,48 +155,7 @@ __device__ __forceinline__ void svd_sort_phase(int n, double *w, Save save, Move
   } while (inc > 1);
 }
 
-__device__ void transpose3(const double *A, double *T) {
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T[j * 3 + i] = A[i * 3 + j];
-}
-// Matrix::det of a 3x3 (src/matrix.cpp:400-415) over Matrix::lu (:514-572)
-__device__ double det3(const double *M) {
-  double a[3][3], vv[3], big, dum, sum, temp, d = 1.0;
-  int imax = 0;
-  bool ok = true;
-  for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) a[i][j] = M[i * 3 + j];
-  for (int i = 0; i < 3 && ok; i++) {
-    big = 0.0;
-    for (int j = 0; j < 3; j++) if ((temp = fabs(a[i][j])) > big) big = temp;
-    if (big == 0.0) { ok = false; break; }
-    vv[i] = 1.0 / big;
-  }
-  if (ok)
-    for (int j = 0; j < 3; j++) {
-      for (int i = 0; i < j; i++) {
-        sum = a[i][j];
-        for (int k = 0; k < i; k++) sum -= a[i][k] * a[k][j];
-        a[i][j] = sum;
-      }
-      big = 0.0;
-      for (int i = j; i < 3; i++) {
-        sum = a[i][j];
-        for (int k = 0; k < j; k++) sum -= a[i][k] * a[k][j];
-        a[i][j] = sum;
-        if ((dum = vv[i] * fabs(sum)) >= big) { big = dum; imax = i; }
-      }
-      if (j != imax) {
-        for (int k = 0; k < 3; k++) { dum = a[imax][k]; a[imax][k] = a[j][k]; a[j][k] = dum; }
-        d = -d;
-        vv[imax] = vv[j];
-      }
-      if (j != 2) {
-        dum = 1.0 / a[j][j];
-        for (int i = j + 1; i < 3; i++) a[i][j] *= dum;
-      }
-    }
-  for (int i = 0; i < 3; i++) d *= a[i][i];
-  return d;
-}
+// (transpose3, det3: vh_mono_pose.h)
 
 // -DVH_MONO_TIMING: workgroup 0 of mono_final adds the 100 MHz clock ticks of its phases to g_mono_t (tools/mono_phases.py)
 __device__ unsigned long long g_mono_t[16];

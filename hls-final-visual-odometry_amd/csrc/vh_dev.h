@@ -487,6 +487,35 @@ struct VhMonoRefitArgs {
 };
 void vh_launch_mono_refit(const VhMonoRefitArgs &a, hipStream_t st);
 
+// The pose tail of the mono estimator on whole lists (kernels_mono_pose.hip): E, the four (R, t)
+// candidates, the chirality count of every record, the points in front under the winner, their median distance, the
+// ground-plane vote, tr.  The lists are addressed as vh_list does; dist and d of list s begin at offsets[s]
+// (concatenated lists) or at s * slot_stride (fixed-stride slots).
+#define VH_MONO_POSE_TILE 512  // elements of a list staged in LDS per trip of the rank and vote kernels
+#define VH_MONO_POSE_HDR 96    // doubles per list: Ra[9] Rb[9] t0[3] | P1[12] | P2[4][12] | median | int32: counts[4], reason, winner, np
+struct VhMonoPoseArgs {
+  vh_mono_params e;         // f, cu, cv, height, pitch, motion_threshold (ransac_iters and inlier_threshold are not read)
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists;
+  int64_t cap;              // >= the longest list: the grids of the per-record kernels are sized by it
+  int64_t slot_stride;
+  const vh_mono_model *model;  // [n_lists]; not read where ok_in = 0
+  const int32_t *ok_in;        // [n_lists]
+  double *hdr;              // [n_lists][VH_MONO_POSE_HDR]
+  double *dist, *d;         // per record slot: the L1 distance (later the vote's sum) and the ground-plane coordinate of the points in front
+  double *tr;               // [n_lists][6]
+  int32_t *ok;              // [n_lists]
+  vh_mono_pose *pose;       // [n_lists]
+};
+// launch k of the six, in this order on one stream: 0 head, 1 tri, 2 front, 3 rank, 4 vote, 5 finish (a launch each, so
+// that a handle can time every kernel under a scope of its own: vh_mono_pose_scope(k))
+#define VH_MONO_POSE_STAGES 6
+void vh_launch_mono_pose_stage(const VhMonoPoseArgs &a, int32_t k, hipStream_t st);
+const char *vh_mono_pose_scope(int32_t k);
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

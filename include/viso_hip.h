@@ -923,6 +923,67 @@ int32_t vh_group_refit_model_mono(vh_group *g, const vh_mono_params *e, int32_t 
                                   int32_t *ok_out, double *w_out, int32_t *counts);
 int32_t vh_match_refit_model_mono(vh_matcher *m, const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out,
                                   int32_t *ok_out, double *w_out, int32_t *count);
+
+/* ---- the mono pose on whole lists: R|t, chirality and scale (csrc/kernels_mono_pose.hip) -----------------
+ * The rest of VisualOdometryMono::estimateMotion after the refit (src/viso_mono.cpp:83-158) for any flow or quad list
+ * (pass an inlier list) under a vh_mono_model: the six motion parameters, and what they were formed from.  The scale
+ * comes from where the reference takes it, the ground-plane vote of :116-143, over the triangulated points of the list
+ * the pose is computed on.  Per list:
+ *   1. F out of the model's frame: Tp = {sp,0,-sp*cpu, 0,sp,-sp*cpv, 0,0,1}, Tc likewise from c[2], c[3], s[1]
+ *      (:226-227); F = ~Tc*F*Tp, E = ~K*F*K, the rank-2 step on E (:83-94);
+ *   2. EtoRt (:317-348): Matrix::svd of E, the four candidates (Ra,t), (Ra,-t), (Rb,t), (Rb,-t), the projection
+ *      matrices of :370-375;
+ *   3. triangulateChieral (:380-397) per record and candidate on the raw u1p, v1p, u1c, v1c; the winner is the first
+ *      candidate with the strictly largest count;
+ *   4. under the winner X / X(3,:) (a zero w gives the zero point), the points with z > 0 in list order, their
+ *      dist = |x|+|y|+|z| and d = cos(-pitch)*y + sin(-pitch)*z;
+ *   5. median: the element of rank np/2 of dist, by counting, ties broken by position (smallerThanMedian);
+ *   6. the ground-plane vote (:124-142): for every i with d[i] > median/motion_threshold the sum over all j, ascending
+ *      from 0, of exp(-(d[j]-d[i])^2 * weight); the first i with the largest sum wins, plane = d[i];
+ *   7. tr as :143-158: the angles of R, t * height / plane.
+ * Double precision, every product and sum rounded on its own, every sum in an order fixed by the list's length alone:
+ * the same bytes from run to run, alone or among other lists, and from the stateless and the handle forms.  exp, asin,
+ * cos and sin are the device library's.  On a bucketed list with the model vh_estimate_motion_mono_model returned for
+ * it, tr, ok and the winner are that call's.
+ * f, cu, cv, height, pitch and motion_threshold of vh_mono_params are read; ransac_iters and inlier_threshold are not. */
+typedef struct vh_mono_pose {   /* 152 bytes */
+  double R[9];        /* the winning rotation, row-major */
+  double t[3];        /* the winning translation, unit length as EtoRt leaves it (sign applied) */
+  double scale;       /* height / plane: tr[3..5] = t * height / plane, formed as the estimator forms it */
+  double median;      /* smallerThanMedian's median of the L1 distances of the points in front */
+  double plane;       /* d[best_idx] of the ground-plane vote */
+  int32_t chirality[4];  /* triangulateChieral's count per candidate (Ra,t), (Ra,-t), (Rb,t), (Rb,-t) */
+  int32_t candidate;  /* the winner 0..3, -1 if none */
+  int32_t n_front;    /* points with z > 0 under the winner */
+  int32_t reason;     /* 0 ok; see below */
+  int32_t reserved_;  /* 0 */
+} vh_mono_pose;
+/* reason: the first of these that applies; each gives ok = 0, tr = 0 and zeros for the fields not yet determined, never
+ * an error of the call:
+ *   1  ok_in == 0 (the model is not read)            2  fewer than 10 records (:45)
+ *   3  no candidate has a positive chirality count   4  fewer than 10 points in front (:105)
+ *   5  median > motion_threshold (:113)              6  fabs(plane) < 1e-20
+ *   7  a non-finite value in R, t, median, plane or tr (the fields stay as computed; tr = 0)
+ * A record with a NaN coordinate is in front of no camera (every comparison with NaN is false): it counts for no
+ * candidate and is not among the points in front.
+ *
+ * Stateless: lists laid out and validated as for vh_refit_model_mono; model[n_sets], ok_in[n_sets] -> tr[n_sets][6],
+ * ok[n_sets], pose[n_sets] (pose may be NULL).  n_sets == 0 or no records at all: VH_OK (outputs zero, reason 1 or 2 per
+ * list), nothing is launched and no device is needed. */
+int32_t vh_pose_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                     const vh_mono_model *model, const int32_t *ok_in, double *tr, int32_t *ok, vh_mono_pose *pose);
+/* The same on the compacted inlier lists of the handle's current MONO classification, under the model / ok that
+ * classification was made under (after vh_group_refit_model_mono(reclassify = 1): the refined model with its inliers);
+ * nothing goes up, tr[S][6], ok[S], pose[S] (nullable) and counts[S] (nullable: the lists' lengths) come back; the call
+ * is synchronous.  VH_ERR_STATE before any classification of the current lists, after the next push or match, and when
+ * the current result is a stereo classification.  Plain groups, sequence handles and lone matchers.  The first call adds
+ * one block: 16 bytes per record slot (dist, d: 8 + 8, S * max_matches slots) and 972 bytes per stream (a header of 768,
+ * tr 48, ok 4, pose 152; each of the six arrays rounded up to 256 bytes), counted by vh_group_device_bytes; a handle that never calls
+ * it allocates and launches nothing.  A refused allocation is VH_ERR_HIP before any launch and leaves the handle as it
+ * was; the call may be repeated.  Profile scopes: "mono_pose_head", "mono_pose_tri", "mono_pose_front",
+ * "mono_pose_rank", "mono_pose_vote", "mono_pose_finish". */
+int32_t vh_group_pose_mono(vh_group *g, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts);
+int32_t vh_match_pose_mono(vh_matcher *m, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose);
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
@@ -1214,7 +1275,8 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  in its device mode those two record nothing and "sparse_vote" (the vote's kernels together), "prior_stats" take their place;
  *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
  *  "motion_refit" per vh_group_refit_motion, "motion_cov" per vh_group_motion_covariance, "mono_refit" per
- *  vh_group_refit_model_mono;
+ *  vh_group_refit_model_mono, "mono_pose_head", "mono_pose_tri", "mono_pose_front", "mono_pose_rank", "mono_pose_vote"
+ *  and "mono_pose_finish" per vh_group_pose_mono;
  *  with vh_group_set_gain "gain_copy" per sub-batch of a push, and "gain_ratio", "gain_sum" per vh_group_gain(_indices))
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
