@@ -91,6 +91,7 @@ ABI_SYMBOLS = (
     "vh_motion_covariance", "vh_group_motion_covariance", "vh_match_motion_covariance",
     "vh_refit_model_mono", "vh_group_refit_model_mono", "vh_match_refit_model_mono",
     "vh_pose_mono", "vh_group_pose_mono", "vh_match_pose_mono",
+    "vh_pose_mono_refined", "vh_group_pose_mono_refined", "vh_match_pose_mono_refined",
 )
 
 
@@ -176,6 +177,10 @@ MONO_MODEL_DTYPE = np.dtype([("c", "<f8", (4,)), ("s", "<f8", (2,)), ("F", "<f8"
 # vh_mono_pose (152 bytes): what pose_mono / poseMono formed tr from
 MONO_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "<f8"), ("median", "<f8"), ("plane", "<f8"),
                             ("chirality", "<i4", (4,)), ("candidate", "<i4"), ("n_front", "<i4"), ("reason", "<i4"), ("reserved_", "<i4")])
+# vh_mono_refine (288 bytes): what pose_mono / poseMono with refine=True made of the winner -- the tangent basis at the
+# refined t, the 5 x 5 covariance of (w0, w1, w2, tau0, tau1), the sums of squared Sampson distances before and after
+MONO_REFINE_DTYPE = np.dtype([("B", "<f8", (6,)), ("cov", "<f8", (25,)), ("ssr_start", "<f8"), ("ssr", "<f8"), ("moved_R", "<f8"),
+                              ("moved_t", "<f8"), ("status", "<i4"), ("n_updates", "<i4")])
 
 
 def _models(model, n):
@@ -347,6 +352,8 @@ def _lib():
             "vh_group_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_model_mono": [vp, vp, i32, vp, vp, vp, vp],
             "vh_pose_mono": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
             "vh_group_pose_mono": [vp, vp, vp, vp, vp, vp], "vh_match_pose_mono": [vp, vp, vp, vp, vp],
+            "vh_pose_mono_refined": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_pose_mono_refined": [vp, vp, vp, vp, vp, vp, vp], "vh_match_pose_mono_refined": [vp, vp, vp, vp, vp, vp],
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
@@ -582,12 +589,19 @@ class Matcher:
                "vh_match_refit_model_mono")
         return model, bool(ok.value), w, n.value
 
-    def poseMono(self, mono: "MonoParams", pose: bool = False):
+    def poseMono(self, mono: "MonoParams", pose: bool = False, refine: bool = False):
         """The mono pose (reference src/viso_mono.cpp:83-158: E, R|t, chirality, the ground-plane scale) over ALL inliers of
         the last motionInliersMono, under the model it classified under (vh_match_pose_mono) -> (tr [6], ok) and, with
-        pose=True, the MONO_POSE_DTYPE record [1] as a third value."""
+        pose=True, the MONO_POSE_DTYPE record [1] as a third value.  refine=True: the winning R|t is refined by Gauss-Newton
+        on the Sampson distance of every inlier before the scale tail (vh_match_pose_mono_refined), and the
+        MONO_REFINE_DTYPE record [1] is one more value at the end."""
         tr = np.zeros(6, np.float64); ok = C.c_int32(0)
         rec = np.zeros(1, MONO_POSE_DTYPE)
+        if refine:
+            ref = np.zeros(1, MONO_REFINE_DTYPE)
+            _check(_lib().vh_match_pose_mono_refined(self._h, C.byref(mono), _ptr(tr), C.byref(ok), _ptr(rec) if pose else None, _ptr(ref)),
+                   "vh_match_pose_mono_refined")
+            return (tr, bool(ok.value), rec, ref) if pose else (tr, bool(ok.value), ref)
         _check(_lib().vh_match_pose_mono(self._h, C.byref(mono), _ptr(tr), C.byref(ok), _ptr(rec) if pose else None), "vh_match_pose_mono")
         return (tr, bool(ok.value), rec) if pose else (tr, bool(ok.value))
 
@@ -889,13 +903,20 @@ class StreamGroup:
                "vh_group_refit_model_mono")
         return model, ok.astype(bool), w, counts
 
-    def poseMono(self, mono: "MonoParams", pose: bool = False):
+    def poseMono(self, mono: "MonoParams", pose: bool = False, refine: bool = False):
         """The mono pose (reference src/viso_mono.cpp:83-158: E, R|t, chirality, the ground-plane scale) over every stream's
         compacted inlier list of the last motionInliersMono, under the model / ok it classified under -- after
         refitModelMono(reclassify=True) the refined model with its inliers (vh_group_pose_mono) -> (tr [S, 6], ok [S],
-        counts [S]) and, with pose=True, the MONO_POSE_DTYPE records [S] as a fourth value."""
+        counts [S]) and, with pose=True, the MONO_POSE_DTYPE records [S] as a fourth value.  refine=True: every winning R|t
+        is refined by Gauss-Newton on the Sampson distance of every inlier before the scale tail
+        (vh_group_pose_mono_refined), and the MONO_REFINE_DTYPE records [S] are one more value at the end."""
         tr = np.zeros((self.S, 6), np.float64); ok = np.zeros(self.S, np.int32); counts = np.zeros(self.S, np.int32)
         rec = np.zeros(self.S, MONO_POSE_DTYPE)
+        if refine:
+            ref = np.zeros(self.S, MONO_REFINE_DTYPE)
+            _check(_lib().vh_group_pose_mono_refined(self._h, C.byref(mono), _ptr(tr), _ptr(ok), _ptr(rec) if pose else None, _ptr(ref),
+                                                     _ptr(counts)), "vh_group_pose_mono_refined")
+            return (tr, ok.astype(bool), counts, rec, ref) if pose else (tr, ok.astype(bool), counts, ref)
         _check(_lib().vh_group_pose_mono(self._h, C.byref(mono), _ptr(tr), _ptr(ok), _ptr(rec) if pose else None, _ptr(counts)), "vh_group_pose_mono")
         return (tr, ok.astype(bool), counts, rec) if pose else (tr, ok.astype(bool), counts)
 
@@ -1444,10 +1465,13 @@ def refit_model_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
     return model_out[:n], ok_out[:n].astype(bool), w[:n]
 
 
-def pose_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
+def pose_mono(mono: MonoParams, match_lists, model, ok, device: int = 0, refine: bool = False):
     """The rest of VisualOdometryMono::estimateMotion after the refit (reference src/viso_mono.cpp:83-158) over whole flow or
     quad lists under model [n] (MONO_MODEL_DTYPE) / ok [n] (vh_pose_mono): E, the four (R, t) candidates, the chirality count
-    of every record, the ground-plane vote over the points in front.  -> (tr [n, 6], ok [n] bool, pose [n] MONO_POSE_DTYPE)."""
+    of every record, the ground-plane vote over the points in front.  -> (tr [n, 6], ok [n] bool, pose [n] MONO_POSE_DTYPE).
+    refine=True: the winning R|t of every list is refined by Gauss-Newton on the Sampson distance of every record before
+    the scale tail (vh_pose_mono_refined); the MONO_REFINE_DTYPE records [n] (the 5 x 5 covariance of the refined pose among
+    them) are a fourth value."""
     lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
     n = len(lists)
     offsets = np.zeros(n + 1, np.int32)
@@ -1456,6 +1480,11 @@ def pose_mono(mono: MonoParams, match_lists, model, ok, device: int = 0):
     model = _models(model, n) if n else np.zeros(1, MONO_MODEL_DTYPE)
     ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
     tr = np.zeros((max(n, 1), 6), np.float64); ok_out = np.zeros(max(n, 1), np.int32); pose = np.zeros(max(n, 1), MONO_POSE_DTYPE)
+    if refine:
+        ref = np.zeros(max(n, 1), MONO_REFINE_DTYPE)
+        _check(_lib().vh_pose_mono_refined(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(tr), _ptr(ok_out),
+                                           _ptr(pose), _ptr(ref)), "vh_pose_mono_refined")
+        return tr[:n], ok_out[:n].astype(bool), pose[:n], ref[:n]
     _check(_lib().vh_pose_mono(C.byref(mono), device, n, _ptr(pm), _ptr(offsets), _ptr(model), _ptr(ok), _ptr(tr), _ptr(ok_out), _ptr(pose)),
            "vh_pose_mono")
     return tr[:n], ok_out[:n].astype(bool), pose[:n]

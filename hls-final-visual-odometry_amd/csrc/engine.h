@@ -321,6 +321,7 @@ struct MonoPoseState {
   double *d_tr = nullptr;                    // [S][6]
   vh_mono_pose *d_pose = nullptr;            // [S]
   int32_t *d_ok = nullptr;                   // [S]
+  vh_mono_refine *d_refine = nullptr;        // [S] a block of its own, allocated by the first vh_group_pose_mono_refined
 };
 
 // The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
@@ -648,7 +649,9 @@ struct Group {
   int32_t refit_model_mono(const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out, int32_t *ok_out, double *w_out, int32_t *counts);
 
   // ---- engine_mono_pose.hip ----
-  int32_t pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts);
+  // refined: the winner is refined between the chirality count and the tail (vh_group_pose_mono_refined); refine is nullable
+  int32_t pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts, bool refined = false,
+                    vh_mono_refine *refine = nullptr);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

@@ -33,16 +33,7 @@ namespace {
 
 #define MP_T 256
 #define MP_TILE VH_MONO_POSE_TILE
-// the header of a list (doubles)
-#define MP_H_RT 0     /* Ra[9], Rb[9], t0[3] */
-#define MP_H_P1 21    /* [K | 0], [12] */
-#define MP_H_P2 33    /* P2 of the four candidates, [4][12] */
-#define MP_H_MED 81   /* the median (mono_pose_rank) */
-#define MP_H_INT 82   /* int32 from here: counts[4], reason, winner, np */
-#define MP_I_REASON 4
-#define MP_I_BEST 5
-#define MP_I_NP 6
-static_assert(MP_H_INT * 8 + 7 * 4 <= VH_MONO_POSE_HDR * 8, "mono pose header");
+// (the header of a list, MP_H_* / MP_I_*: vh_dev.h)
 
 struct MpList {
   VhList l;
@@ -118,8 +109,7 @@ mono_pose_front_kernel(VhMonoPoseArgs a) {
   if (tid == 0) sBase = 0;
   __syncthreads();  // (every lane has read the header before lane 0 writes to it)
   if (before != 0) return;
-  int32_t cbest = -1, max_in = 0;
-  for (int32_t c = 0; c < 4; c++) if (cnt[c] > max_in) { max_in = cnt[c]; cbest = c; }  // strict `>`, src/viso_mono.cpp:353
+  const int32_t cbest = mono_pose_winner(cnt);
   if (cbest < 0) {  // (the reference dereferences an empty matrix here)
     if (tid == 0) L.ih[MP_I_REASON] = 3;
     return;

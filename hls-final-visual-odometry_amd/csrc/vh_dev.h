@@ -493,6 +493,16 @@ void vh_launch_mono_refit(const VhMonoRefitArgs &a, hipStream_t st);
 // (concatenated lists) or at s * slot_stride (fixed-stride slots).
 #define VH_MONO_POSE_TILE 512  // elements of a list staged in LDS per trip of the rank and vote kernels
 #define VH_MONO_POSE_HDR 96    // doubles per list: Ra[9] Rb[9] t0[3] | P1[12] | P2[4][12] | median | int32: counts[4], reason, winner, np
+// the header of a list (doubles): kernels_mono_pose.hip writes and reads it, kernels_mono_pose_refine.hip rewrites the winner's slot
+#define MP_H_RT 0     /* Ra[9], Rb[9], t0[3] */
+#define MP_H_P1 21    /* [K | 0], [12] */
+#define MP_H_P2 33    /* P2 of the four candidates, [4][12] */
+#define MP_H_MED 81   /* the median (mono_pose_rank) */
+#define MP_H_INT 82   /* int32 from here: counts[4], reason, winner, np */
+#define MP_I_REASON 4
+#define MP_I_BEST 5
+#define MP_I_NP 6
+static_assert(MP_H_INT * 8 + 7 * 4 <= VH_MONO_POSE_HDR * 8, "mono pose header");
 struct VhMonoPoseArgs {
   vh_mono_params e;         // f, cu, cv, height, pitch, motion_threshold (ransac_iters and inlier_threshold are not read)
   const vh_p_match *pm;
@@ -515,6 +525,11 @@ struct VhMonoPoseArgs {
 #define VH_MONO_POSE_STAGES 6
 void vh_launch_mono_pose_stage(const VhMonoPoseArgs &a, int32_t k, hipStream_t st);
 const char *vh_mono_pose_scope(int32_t k);
+// The pose refined between launches 1 and 2 (kernels_mono_pose_refine.hip): Gauss-Newton on the
+// Sampson distance of every record from the winner of the chirality counts, one workgroup of VH_REFIT_THREADS lanes per
+// list; where it converges, the refined R, t and projection matrix replace the winner's in the list's header, which the
+// launches 2..5 then read as they always do.  refine: [n_lists].  grid: a.n_lists workgroups.
+void vh_launch_mono_pose_refine(const VhMonoPoseArgs &a, vh_mono_refine *refine, hipStream_t st);
 
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride

@@ -126,6 +126,13 @@ VH_RANK2_DI bool mono_pose_in_front_of_both(const double *P1, const double *P2, 
   return a * x[3] > 0 && b * x[3] > 0;
 }
 
+// the winner of the four chirality counts: the first with the strictly largest (src/viso_mono.cpp:353), -1 where none is positive
+VH_RANK2_DI int32_t mono_pose_winner(const int32_t *cnt) {
+  int32_t cbest = -1, max_in = 0;
+  for (int32_t c = 0; c < 4; c++) if (cnt[c] > max_in) { max_in = cnt[c]; cbest = c; }
+  return cbest;
+}
+
 // X / X(3,:) of one point (src/viso_mono.cpp:100); a zero w gives the zero point
 VH_RANK2_DI void mono_pose_point(double X0, double X1, double X2, double wq, double &x, double &y, double &z) {
   x = 0; y = 0; z = 0;

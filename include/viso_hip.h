@@ -984,6 +984,66 @@ int32_t vh_pose_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, co
  * "mono_pose_rank", "mono_pose_vote", "mono_pose_finish". */
 int32_t vh_group_pose_mono(vh_group *g, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts);
 int32_t vh_match_pose_mono(vh_matcher *m, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose);
+
+/* ---- the mono pose refined on whole lists: Gauss-Newton on R|t, covariance (csrc/kernels_mono_pose_refine.hip) ----
+ * vh_pose_mono decomposes an algebraic F; here the winning (R, unit t) is refined by Gauss-Newton on the signed Sampson
+ * distance of EVERY record of the list, the scale tail then runs under the refined pose, and the 5 x 5 covariance of the
+ * refined pose is returned.  Neither the reference nor stock libviso2 has a counterpart: the contract is this text.
+ * Per list, every record active, double precision, every product and sum rounded on its own, K = {f, cu, cv}:
+ *   1. Start: steps 1-3 of vh_pose_mono unchanged; the start is the winner's R and signed unit t.  With pose reasons 1, 2
+ *      or 3 there is nothing to refine: status = 1, everything else is vh_pose_mono's result for the list.
+ *   2. Residual of a record: xp = (((double)u1p - cu) / f, ((double)v1p - cv) / f, 1), xc likewise from u1c, v1c;
+ *      E = [t]x R; n = xc^T E xp; a = E xp; b = E^T xc; s = a0^2 + a1^2 + b0^2 + b1^2; r = f * n / sqrt(s), the signed
+ *      Sampson distance in pixels.  Nothing is clamped: s = 0 or a NaN coordinate propagates and ends in status = 4.
+ *   3. Parameters delta = (w0, w1, w2, tau0, tau1): w a left rotation, R <- Exp([w]x) * R by Rodrigues (I + [w]x below
+ *      |w| = 1e-12); tau in the tangent plane of the unit sphere at t: m the first index of the smallest |t_m|,
+ *      b0 = normalise(e_m - (e_m . t) t), b1 = t x b0, t <- normalise(t + tau0 b0 + tau1 b1); the basis is rebuilt at
+ *      every update.
+ *   4. Jacobian, analytic and complete: E_k = [t]x [e_k]x R for w_k, E_k = [b_k]x R for tau_k; dn = xc^T E_k xp,
+ *      da = E_k xp, db = E_k^T xc, ds = 2 (a0 da0 + a1 da1 + b0 db0 + b1 db1),
+ *      J_k = f * (dn / sqrt(s) - n * ds / (2 s sqrt(s))).
+ *   5. Update: A = sum J^T J (15 sums, the upper triangle mirrored), g = sum J^T r, ssr = sum r^2; delta = -A^-1 g by
+ *      Matrix::solve (src/matrix.cpp:417-504); step size 1.  The update that reports max |delta_k| < 1e-8 is applied
+ *      and ends the loop as converged; at most 102 updates.
+ *   6. Covariance: one more accumulation at the converged pose gives A and ssr; cov = ssr / (N - 5) * A^-1 by
+ *      Matrix::solve on the five unit right-hand sides, the upper triangle computed and mirrored, in the order of delta.
+ *      B = (b0, b1) at the converged t maps the two translation coordinates to 3-D: dt = tau0 b0 + tau1 b1.
+ *   7. Tail: steps 4-7 of vh_pose_mono under the refined R, t with their own reasons 4-7.  The sign of t is the
+ *      winner's; the chirality vote is not repeated.
+ *   8. A refused refinement is not a refused pose: for status != 0 the tail runs under the unrefined winner; tr, ok and
+ *      the vh_mono_pose are byte for byte those of vh_pose_mono on that list; cov, B, ssr, moved_R, moved_t are zero,
+ *      ssr_start is kept where it was finite.  Never an error of the call.
+ *   9. Sums run in an order fixed by the list's length alone, no atomics: the same bytes from run to run, alone or
+ *      among other lists, and from the stateless and the handle forms.  sin and asin are the device library's. */
+typedef struct vh_mono_refine {   /* 288 bytes */
+  double B[6];        /* b0[3], b1[3]: the tangent basis at the refined t */
+  double cov[25];     /* row-major, exactly symmetric, in the order (w0, w1, w2, tau0, tau1): rad^2 */
+  double ssr_start;   /* sum r^2 at the winner (px^2) */
+  double ssr;         /* sum r^2 at the refined pose */
+  double moved_R;     /* angle between the start and the refined rotation: 2 asin(|R1 - R0|_F / (2 sqrt 2)), rad */
+  double moved_t;     /* angle between the start and the refined direction: 2 asin(|t1 - t0| / 2), rad */
+  int32_t status;     /* 0 refined; see below */
+  int32_t n_updates;  /* updates applied: 0 .. 102 */
+} vh_mono_refine;
+/* status: 0  converged, the pose is the refined one
+ *         1  nothing to refine (pose reason 1, 2 or 3)      2  Matrix::solve refused (a pivot below 1e-20)
+ *         3  not converged after 102 updates                4  a sum, R, t or a covariance entry is not finite
+ *
+ * Stateless: layout, validation and empty-input behaviour are vh_pose_mono's; refine[n_sets] (nullable; status 1 where
+ * nothing is launched). */
+int32_t vh_pose_mono_refined(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+                             const vh_mono_model *model, const int32_t *ok_in, double *tr, int32_t *ok, vh_mono_pose *pose,
+                             vh_mono_refine *refine);
+/* The same on the compacted inlier lists of the handle's current MONO classification: state rules, outputs and the
+ * arena block are vh_group_pose_mono's (the two share the block); refine[S] is nullable.  The first call adds one array
+ * of 288 bytes per stream, rounded up to 256 bytes, counted by vh_group_device_bytes; a handle that never calls these
+ * entries allocates and launches nothing for them.  A refused allocation is VH_ERR_HIP before any launch and leaves the
+ * handle as it was; the call may be repeated.  Profile scope: "mono_pose_refine", between "mono_pose_tri" and
+ * "mono_pose_front". */
+int32_t vh_group_pose_mono_refined(vh_group *g, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose,
+                                   vh_mono_refine *refine, int32_t *counts);
+int32_t vh_match_pose_mono_refined(vh_matcher *m, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose,
+                                   vh_mono_refine *refine);
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
@@ -1276,7 +1336,7 @@ int32_t vh_debug_vote_stack_slots(int32_t slots);
  *  "ego_kernel" per vh_group_estimate_motion, "inlier_flag" / "inlier_flag_mono" and "inlier_compact" per classification,
  *  "motion_refit" per vh_group_refit_motion, "motion_cov" per vh_group_motion_covariance, "mono_refit" per
  *  vh_group_refit_model_mono, "mono_pose_head", "mono_pose_tri", "mono_pose_front", "mono_pose_rank", "mono_pose_vote"
- *  and "mono_pose_finish" per vh_group_pose_mono;
+ *  and "mono_pose_finish" per vh_group_pose_mono, with "mono_pose_refine" per vh_group_pose_mono_refined;
  *  with vh_group_set_gain "gain_copy" per sub-batch of a push, and "gain_ratio", "gain_sum" per vh_group_gain(_indices))
  *  since the last reset. */
 int32_t vh_group_profile_enable(vh_group *g, int32_t on);
