@@ -92,6 +92,7 @@ ABI_SYMBOLS = (
     "vh_refit_model_mono", "vh_group_refit_model_mono", "vh_match_refit_model_mono",
     "vh_pose_mono", "vh_group_pose_mono", "vh_match_pose_mono",
     "vh_pose_mono_refined", "vh_group_pose_mono_refined", "vh_match_pose_mono_refined",
+    "vh_group_post_device_tail", "vh_group_post_device_shape", "vh_group_post_finish_device_tail",
 )
 
 
@@ -198,6 +199,16 @@ class PostDense(C.Structure):
     """vh_post_dense: the nullable output pointers of vh_group_post_finish_device_dense (include/viso_hip.h)."""
     _fields_ = [(n, C.c_void_p) for n in ("voted_counts", "inlier_counts", "tr_refit", "ok_refit", "n_updates", "model",
                                           "voted_pm", "flags", "inlier_pm", "src_pos")]
+
+
+#: stages of vh_group_post_device_tail (StreamGroup.postDeviceTail): a bit mask
+POST_TAIL_COV, POST_TAIL_MONO_REFIT, POST_TAIL_MONO_POSE, POST_TAIL_MONO_REFINE = 1, 2, 4, 8
+
+
+class PostTail(C.Structure):
+    """vh_post_tail: its size, then the nullable output pointers of vh_group_post_finish_device_tail (include/viso_hip.h)."""
+    _fields_ = [("size", C.c_uint32), ("reserved", C.c_uint32)] + [
+        (n, C.c_void_p) for n in ("cov", "ssr", "ok_cov", "model_refit", "ok_model", "w", "tr_pose", "ok_pose", "pose", "refine")]
 
 
 class ReconParams(C.Structure):
@@ -357,6 +368,8 @@ def _lib():
             "vh_group_refit_motion": [vp, vp, i32, vp, vp, vp, vp], "vh_match_refit_motion": [vp, vp, i32, vp, vp, vp, vp],
             "vh_group_post_device_dense": [vp, i32],
             "vh_group_post_finish_device_dense": [vp, i32, vp, vp, vp, vp, i32, vp, vp],
+            "vh_group_post_device_tail": [vp, C.c_uint32], "vh_group_post_device_shape": [vp, vp, vp],
+            "vh_group_post_finish_device_tail": [vp, i32, vp, vp, vp, vp, i32, vp, vp, vp],
             "vh_gain": [i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp],
             "vh_group_set_gain": [vp, i32], "vh_set_gain": [vp, i32],
             "vh_group_gain": [vp, vp, vp], "vh_match_gain": [vp, vp, vp],
@@ -1020,6 +1033,21 @@ class StreamGroup:
         _check(_lib().vh_group_post_device_dense(self._h, int(mode)), "vh_group_post_device_dense")
         self._dense_mode = int(mode)
 
+    def postDeviceTail(self, stages: int):
+        """The covariance, the mono refit and the mono pose as stages of the device post chain behind the dense ones
+        (vh_group_post_device_tail): a mask of POST_TAIL_COV (stereo estimator, dense mode >= 1), POST_TAIL_MONO_REFIT,
+        POST_TAIL_MONO_POSE and POST_TAIL_MONO_REFINE (mono estimator, dense mode 1; REFINE needs POSE); 0 off (the
+        default).  Not while steps are in flight."""
+        _check(_lib().vh_group_post_device_tail(self._h, int(stages)), "vh_group_post_device_tail")
+        self._tail_mask = int(stages)
+
+    def postDeviceShape(self):
+        """-> (steps per batch, batches) in effect (vh_group_post_device_shape): the first postBeginDevice of a ring may
+        have halved the steps per batch postDeviceConfig asked for; before it, the configured shape."""
+        steps, batches = C.c_int32(0), C.c_int32(0)
+        _check(_lib().vh_group_post_device_shape(self._h, C.byref(steps), C.byref(batches)), "vh_group_post_device_shape")
+        return steps.value, batches.value
+
     def postBeginDevice(self, cap_per_stream: int, max_features: int, bucket_width: float, bucket_height: float,
                         ego: "EgoParams" = None, rand3=None, mono: "MonoParams" = None, rand8=None, want_lists: bool = False):
         """This step's match lists enter the device post stage: removeOutliers -> bucketFeatures -> estimateMotion, all on
@@ -1039,40 +1067,69 @@ class StreamGroup:
         steps = self.__dict__.setdefault("_dense_steps", [])
         steps.append((getattr(self, "_dense_mode", 0), mono is not None))
         del steps[:-(256 * 64)]
+        tails = self.__dict__.setdefault("_tail_steps", [])   # and postFinishDevice(tail=...) likewise
+        tails.append(getattr(self, "_tail_mask", 0))
+        del tails[:-(256 * 64)]
 
     def postFinishDevice(self, age: int, want_lists: bool = False, list_cap: int = 4096, estimator: bool = True, strict: bool = True,
-                         dense=None):
+                         dense=None, tail=None):
         """Results of the step begun `age` begins ago (vh_group_post_finish_device) -> dict(tr, ok, n_inliers, lists, counts).
         strict=False: a refused list does not raise; its stream reports counts = -1 and the dict carries the code as "rc".
         dense (vh_group_post_finish_device_dense, after postDeviceDense(mode >= 1)): a tuple of "counts" -- adds voted_counts
         [S], inlier_counts [S], with modes 2 and 3 tr_refit [S, 6], ok_refit [S], n_updates [S], with the monocular estimator
         model [S] -- and "lists" -- adds voted, flags, inliers, src_pos: one array per stream (empty where the count is
-        -1; every list must fit list_cap).  "refit" / "model" ask for those outputs whatever the step was begun with."""
+        -1; every list must fit list_cap).  "refit" / "model" ask for those outputs whatever the step was begun with.
+        tail (vh_group_post_finish_device_tail, after postDeviceTail(mask)): names out of "cov" -- adds cov [S, 6, 6], ssr
+        [S], ok_cov [S] --, "mono_refit" -- model_refit [S], ok_model [S], w [S, 2] --, "pose" -- tr_pose [S, 6], ok_pose
+        [S], pose [S] (MONO_POSE_DTYPE) -- and "refine" -- refine [S] (MONO_REFINE_DTYPE); () adds what the step was begun
+        with, a name asks for its outputs whatever the step was begun with."""
         S = self.S
         tr = np.zeros((S, 6), np.float64); ok = np.zeros(S, np.int32); ninl = np.zeros(S, np.int32); counts = np.zeros(S, np.int32)
         out = np.zeros((S, int(list_cap)), P_MATCH_DTYPE) if want_lists else None
         args = (self._h, int(age), _ptr(tr) if estimator else None, _ptr(ok) if estimator else None,
                 _ptr(ninl) if estimator else None, _ptr(out), int(list_cap) if want_lists else 0, _ptr(counts))
-        if dense is None:
+        extra_t = {}
+        if tail is not None:
+            tail = (tail,) if isinstance(tail, str) else tuple(tail)
+            assert set(tail) <= {"cov", "mono_refit", "pose", "refine"}, tail
+            tails = getattr(self, "_tail_steps", [])
+            mask = tails[-1 - int(age)] if int(age) < len(tails) else 0
+            if mask & POST_TAIL_COV or "cov" in tail:
+                extra_t.update(cov=np.zeros((S, 6, 6), np.float64), ssr=np.zeros(S, np.float64), ok_cov=np.zeros(S, np.int32))
+            if mask & POST_TAIL_MONO_REFIT or "mono_refit" in tail:
+                extra_t.update(model_refit=np.zeros(S, MONO_MODEL_DTYPE), ok_model=np.zeros(S, np.int32), w=np.zeros((S, 2), np.float64))
+            if mask & POST_TAIL_MONO_POSE or "pose" in tail:
+                extra_t.update(tr_pose=np.zeros((S, 6), np.float64), ok_pose=np.zeros(S, np.int32), pose=np.zeros(S, MONO_POSE_DTYPE))
+            if mask & POST_TAIL_MONO_REFINE or "refine" in tail:
+                extra_t["refine"] = np.zeros(S, MONO_REFINE_DTYPE)
+        if dense is None and tail is None:
             name = "vh_group_post_finish_device"
             rc = _lib().vh_group_post_finish_device(*args)
         else:
             name = "vh_group_post_finish_device_dense"
-            dense = (dense,) if isinstance(dense, str) else tuple(dense)
-            assert dense and set(dense) <= {"counts", "lists", "refit", "model"}, dense
-            steps = getattr(self, "_dense_steps", [])
-            mode, mono = steps[-1 - int(age)] if int(age) < len(steps) else (0, False)
-            cap = int(list_cap)
-            extra = {"voted_counts": np.zeros(S, np.int32), "inlier_counts": np.zeros(S, np.int32)}
-            if mode >= 2 or "refit" in dense:
-                extra.update(tr_refit=np.zeros((S, 6), np.float64), ok_refit=np.zeros(S, np.int32), n_updates=np.zeros(S, np.int32))
-            if mono or "model" in dense:
-                extra["model"] = np.zeros(S, MONO_MODEL_DTYPE)
-            if "lists" in dense:
-                extra.update(voted_pm=np.zeros((S, cap), P_MATCH_DTYPE), flags=np.zeros((S, cap), np.uint8),
-                             inlier_pm=np.zeros((S, cap), P_MATCH_DTYPE), src_pos=np.zeros((S, cap), np.int32))
-            d = PostDense(**{k: v.ctypes.data for k, v in extra.items()})
-            rc = _lib().vh_group_post_finish_device_dense(*(args[:6] + (cap if (want_lists or "lists" in dense) else 0, args[7], C.byref(d))))
+            dargs = args + (None,)
+            if dense is not None:
+                dense = (dense,) if isinstance(dense, str) else tuple(dense)
+                assert dense and set(dense) <= {"counts", "lists", "refit", "model"}, dense
+                steps = getattr(self, "_dense_steps", [])
+                mode, mono = steps[-1 - int(age)] if int(age) < len(steps) else (0, False)
+                cap = int(list_cap)
+                extra = {"voted_counts": np.zeros(S, np.int32), "inlier_counts": np.zeros(S, np.int32)}
+                if mode >= 2 or "refit" in dense:
+                    extra.update(tr_refit=np.zeros((S, 6), np.float64), ok_refit=np.zeros(S, np.int32), n_updates=np.zeros(S, np.int32))
+                if mono or "model" in dense:
+                    extra["model"] = np.zeros(S, MONO_MODEL_DTYPE)
+                if "lists" in dense:
+                    extra.update(voted_pm=np.zeros((S, cap), P_MATCH_DTYPE), flags=np.zeros((S, cap), np.uint8),
+                                 inlier_pm=np.zeros((S, cap), P_MATCH_DTYPE), src_pos=np.zeros((S, cap), np.int32))
+                d = PostDense(**{k: v.ctypes.data for k, v in extra.items()})
+                dargs = args[:6] + (cap if (want_lists or "lists" in dense) else 0, args[7], C.byref(d))
+            if tail is None:
+                rc = _lib().vh_group_post_finish_device_dense(*dargs)
+            else:
+                name = "vh_group_post_finish_device_tail"
+                pt = PostTail(size=C.sizeof(PostTail), **{k: v.ctypes.data for k, v in extra_t.items()})
+                rc = _lib().vh_group_post_finish_device_tail(*(dargs + (C.byref(pt),)))
         if strict or rc in (VH_ERR_INVALID_ARG, VH_ERR_STATE, VH_ERR_HIP, VH_ERR_NO_DEVICE):
             _check(rc, name)
         lists = [out[s, :max(int(counts[s]), 0)].copy() for s in range(S)] if want_lists else None
@@ -1088,6 +1145,10 @@ class StreamGroup:
                 extra["src_pos"] = [extra["src_pos"][s, :ni[s]].copy() for s in range(S)]
                 del extra["voted_pm"], extra["inlier_pm"]
             res.update(extra)
+        for k in ("ok_cov", "ok_model", "ok_pose"):
+            if k in extra_t:
+                extra_t[k] = extra_t[k].astype(bool)
+        res.update(extra_t)
         return res
 
     def estimateMotionMono(self, mono: "MonoParams", rand8, model: bool = False):

@@ -276,6 +276,8 @@ struct InlierTest {
 
 // the launch grid is lists x tiles workgroups of 256 threads
 inline bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
+// vh_launch_mono_pose_stage needs lists * ceil(cap / 64) workgroups in one grid dimension
+inline bool mono_pose_grid_ok(int64_t lists, int64_t cap) { return lists * ((cap + 63) / 64) < ((int64_t)1 << 30); }
 
 // The lists as the getters return them once a list was replaced on the host (vh_remove_outliers, vh_bucket_features), staged
 // on the device by Group::stage_host_lists: one arena block, allocated by the first need.
@@ -383,6 +385,44 @@ struct VoteDense {
   static size_t bytes_for(size_t lists, size_t cap, bool model) { return VoteDense().carve(nullptr, lists, cap, model); }
 };
 
+// The per-list outputs of a batch's tail stages (vh_group_post_device_tail): the same arrays on the device and in the
+// page-locked mirror they come down into, each present only with its stage's bit.
+struct TailLists {
+  double *cov = nullptr, *ssr = nullptr; int32_t *ok_cov = nullptr;                    // [lists][36], [lists], [lists]  VH_POST_TAIL_COV
+  vh_mono_model *model = nullptr; double *w = nullptr; int32_t *ok_model = nullptr;    // [lists], [lists][2], [lists]   VH_POST_TAIL_MONO_REFIT
+  double *tr = nullptr; int32_t *ok_pose = nullptr; vh_mono_pose *pose = nullptr;      // [lists][6], [lists], [lists]   VH_POST_TAIL_MONO_POSE
+  vh_mono_refine *refine = nullptr;                                                    // [lists]                        VH_POST_TAIL_MONO_REFINE
+  void carve(Carver &c, size_t lists, uint32_t mask) {
+    *this = TailLists();
+    if (mask & VH_POST_TAIL_COV) { cov = c.ptr<double>(36 * lists); ssr = c.ptr<double>(lists); ok_cov = c.ptr<int32_t>(lists); }
+    if (mask & VH_POST_TAIL_MONO_REFIT) { model = c.ptr<vh_mono_model>(lists); w = c.ptr<double>(2 * lists); ok_model = c.ptr<int32_t>(lists); }
+    if (mask & VH_POST_TAIL_MONO_POSE) { tr = c.ptr<double>(6 * lists); ok_pose = c.ptr<int32_t>(lists); pose = c.ptr<vh_mono_pose>(lists); }
+    if (mask & VH_POST_TAIL_MONO_REFINE) refine = c.ptr<vh_mono_refine>(lists);
+  }
+};
+// The tail stages of a batch (vh_group_post_device_tail; engine_post.hip): one block beside the
+// dense stages', cut like it -- the per-list outputs and, with the pose, its headers and the two doubles per record slot --
+// and the page-locked mirror of the outputs.  Nothing here exists while the mask is 0.
+struct VoteTail {
+  DeviceBlock block;
+  size_t bytes = 0;
+  int32_t lists = 0, cap = 0;  // what the block was cut for
+  uint32_t mask = 0;
+  TailLists d;
+  double *d_hdr = nullptr, *d_dist = nullptr, *d_d = nullptr;  // [lists][VH_MONO_POSE_HDR], [lists][cap], [lists][cap]
+  HostBlock<uint8_t> h_block;
+  int32_t h_lists = 0; uint32_t h_mask = 0;
+  TailLists h;
+  size_t carve(void *base, size_t lists, size_t cap, uint32_t m) {
+    Carver c(base);
+    d.carve(c, lists, m);
+    d_hdr = d_dist = d_d = nullptr;
+    if (m & VH_POST_TAIL_MONO_POSE) { d_hdr = c.ptr<double>(lists * VH_MONO_POSE_HDR); d_dist = c.ptr<double>(lists * cap); d_d = c.ptr<double>(lists * cap); }
+    return c.bytes();
+  }
+  static size_t bytes_for(size_t lists, size_t cap, uint32_t m) { return VoteTail().carve(nullptr, lists, cap, m); }
+};
+
 // a batch of the device post pipeline (engine_post.hip); its blocks live outside the arena
 struct VoteBatch {
   VoteBuffers vb;
@@ -406,6 +446,8 @@ struct VoteBatch {
   bool want_lists = false;
   int32_t dense_mode = 0;  // vh_group_post_device_dense, as it was when the batch was started
   VoteDense dn;
+  uint32_t tail = 0;       // vh_group_post_device_tail, as it was when the batch was started
+  VoteTail tl;
   VoteBatch() = default;
   VoteBatch(VoteBatch &&) = default;
   ~VoteBatch() { if (launched && ev_done) (void)hipEventSynchronize(ev_done); }  // (before the members free what the kernels use)
@@ -519,6 +561,7 @@ struct Group {
   // flight over that latency, and a wave of 64 lists costs the chip 1/14 of what 64 single-list waves cost.
   int32_t vote_steps = 64, vote_batches = 3, vote_lanes = 16;
   int32_t vote_dense = 0;     // vh_group_post_device_dense: 0 off, 1 classify, 2 + refit, 3 + classify again
+  uint32_t vote_tail = 0;     // vh_group_post_device_tail: the VH_POST_TAIL_* stages behind the dense ones
   int64_t post_dev_seq = 0;   // steps begun
   int32_t vote_cur = 0;       // batch receiving steps
   // vh_group_set_vote_rule: VH_VOTE_REFERENCE (the reference's flow vote under its literal 5; stereo lists are not voted)
@@ -677,7 +720,11 @@ struct Group {
   void vote_release() { vbatch.clear(); vstep.clear(); post_dev_seq = 0; vote_cur = 0; }
   int32_t post_device_config(int32_t steps_per_batch, int32_t batches, int32_t lanes);
   int32_t post_device_dense(int32_t mode);
+  int32_t post_device_tail(uint32_t stages);
+  int32_t post_device_shape(int32_t *steps_per_batch, int32_t *batches) const;
   int32_t vote_dense_alloc(VoteBatch &b, int32_t lists, bool model);
+  int32_t vote_tail_alloc(VoteBatch &b, int32_t lists, uint32_t mask);
+  int32_t vote_tail_launch(VoteBatch &b, const VhVote &v, const InlierTest &t, VhInlierArgs &a, hipStream_t vs);
   int32_t vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs);
   int32_t bucket_need(int32_t max_features, float bw, float bh, int64_t *need, int64_t *grid = nullptr) const;
   int32_t vote_launch(VoteBatch &b, int32_t index);
@@ -687,7 +734,7 @@ struct Group {
   int32_t post_begin_device(int32_t cap_ps, int32_t max_features, float bw, float bh, const vh_ego_params *e, const int32_t *rand3,
                             const vh_mono_params *mono, const int32_t *rand8, int32_t want_lists);
   int32_t post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
-                             const vh_post_dense *d = nullptr);
+                             const vh_post_dense *d = nullptr, const vh_post_tail *t = nullptr);
 };
 
 // times the HIP work queued on `st` during its lifetime under `name` (only while the group profiles)

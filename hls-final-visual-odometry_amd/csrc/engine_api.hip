@@ -255,7 +255,7 @@ int64_t vh_group_device_bytes(const vh_group *g) {  // (the matcher's arrays and
   int64_t b = (int64_t)gq->device_bytes;
   if (gq->sparse) b += vh_group_device_bytes((const vh_group *)gq->sparse.get());  // the sparse sets of multi-stage matching
   b += (int64_t)gq->ms_vb.bytes;                                             // and the voted sparse lists of its device mode
-  for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes + (int64_t)vb.dn.bytes;  // (dn: the dense stages' block)
+  for (const auto &vb : gq->vbatch) b += (int64_t)vb.vb.bytes + (int64_t)vb.block_bytes + (int64_t)vb.dn.bytes + (int64_t)vb.tl.bytes;  // (dn, tl: the dense and the tail stages' blocks)
   b += gq->rh.bytes;                                                         // the ring and the gather buffers of reconstruction
   return b;
 }
@@ -740,6 +740,24 @@ int32_t vh_group_post_finish_device_dense(vh_group *g, int32_t age, double *tr, 
                                           int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d) {
   Group *gq = (Group *)g; ENTER(gq);
   return gq->post_finish_device(age, tr, ok, n_inliers, bucketed, cap_per_stream, counts, d);
+}
+int32_t vh_group_post_device_tail(vh_group *g, uint32_t stages) {
+  // the mask first, and with a message of its own: it can be judged without a device, and a caller (or a test) can tell it from the handle's refusal
+  if ((stages & ~(uint32_t)VH_POST_TAIL_ALL) || ((stages & VH_POST_TAIL_MONO_REFINE) && !(stages & VH_POST_TAIL_MONO_POSE))) {
+    t_last_error = "vh_group_post_device_tail: unknown VH_POST_TAIL bits, or VH_POST_TAIL_MONO_REFINE without VH_POST_TAIL_MONO_POSE";
+    return VH_ERR_INVALID_ARG;
+  }
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->post_device_tail(stages);
+}
+int32_t vh_group_post_device_shape(vh_group *g, int32_t *steps_per_batch, int32_t *batches) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->post_device_shape(steps_per_batch, batches);
+}
+int32_t vh_group_post_finish_device_tail(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
+                                         int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d, const vh_post_tail *t) {
+  Group *gq = (Group *)g; ENTER(gq);
+  return gq->post_finish_device(age, tr, ok, n_inliers, bucketed, cap_per_stream, counts, d, t);
 }
 
 // ---- monocular egomotion -----------------------------------------

@@ -6,9 +6,6 @@
 
 namespace vh_engine {
 
-// vh_launch_mono_pose_stage needs lists * ceil(cap / 64) workgroups in one grid dimension
-static bool mono_pose_grid_ok(int64_t lists, int64_t cap) { return lists * ((cap + 63) / 64) < ((int64_t)1 << 30); }
-
 // E, the candidates, chirality, the ground-plane vote and tr over the compacted inlier lists of the current mono
 // classification, under the model / ok it was made under (inl.d_model / inl.d_ok).
 int32_t Group::pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts, bool refined, vh_mono_refine *refine) {

@@ -405,6 +405,116 @@ int32_t Group::post_device_dense(int32_t mode) {
   return VH_OK;
 }
 
+// The tail stages of the batches (include/viso_hip.h: vh_group_post_device_tail), under the rules of the dense mode: a
+// change of the mask changes what a batch holds, so the ring is released and the next begin call sizes it again.
+int32_t Group::post_device_tail(uint32_t stages) {
+  for (auto &b : vbatch) if (b.busy) return VH_ERR_STATE;  // (the mask itself is judged by the ABI entry, before the handle)
+  if (stages == vote_tail) return VH_OK;
+  vote_release();
+  vote_tail = stages;
+  return VH_OK;
+}
+
+// The ring's shape in effect: the first begin call of a ring may have halved the configured steps per batch
+int32_t Group::post_device_shape(int32_t *steps_per_batch, int32_t *batches) const {
+  if (!steps_per_batch || !batches) return VH_ERR_INVALID_ARG;
+  *steps_per_batch = vote_steps; *batches = vote_batches;
+  return VH_OK;
+}
+
+// The tail block of batch b and its page-locked mirror, as vote_dense_alloc: before the batch's first launch; a refusal
+// leaves the batch without one.
+int32_t Group::vote_tail_alloc(VoteBatch &b, int32_t lists, uint32_t mask) {
+  VoteTail &q = b.tl;
+  const int32_t cap = b.vb.v.cap;
+  // (the mirror too: a page-locked allocation that failed after the device block's must not pass for a finished one)
+  if (q.block.p && q.lists >= lists && q.cap == cap && q.mask == mask && q.h_block.p && q.h_lists >= q.lists && q.h_mask == mask) return VH_OK;
+  q.block = DeviceBlock(); q.bytes = 0; q.lists = 0; q.h = TailLists();
+  if (alloc_refused()) return VH_ERR_HIP;
+  const size_t total = VoteTail::bytes_for((size_t)lists, (size_t)cap, mask);
+  VH_HIP(q.block.alloc(total));
+  q.carve(q.block.p, (size_t)lists, (size_t)cap, mask);
+  q.bytes = total; q.lists = lists; q.cap = cap; q.mask = mask;
+  if (q.h_lists < lists || q.h_mask != mask) {
+    q.h_lists = 0;
+    Carver measure;
+    TailLists().carve(measure, (size_t)lists, mask);
+    VH_HIP(q.h_block.alloc(measure.bytes(), hipHostMallocDefault));
+    q.h_lists = lists; q.h_mask = mask;
+  }
+  Carver c(q.h_block.p);
+  q.h.carve(c, (size_t)q.h_lists, mask);
+  return VH_OK;
+}
+
+// The tail stages of batch b, queued behind its dense stages (a: the classification's arguments as they stand, t: its test).
+// Stereo: the covariance over the final inlier lists under the motion they belong to.  Mono: the model refitted on the
+// inliers -> the classification again under it (a pointer switch, as mode 3) -> the pose over the final inlier lists
+// under the model they were classified under, refined between its launches 1 and 2 -> the small downloads.  The kernels
+// are the stateless entries' over the batch's fixed-stride slots; a list the gate closed has no records and ok = 0.
+int32_t Group::vote_tail_launch(VoteBatch &b, const VhVote &v, const InlierTest &t, VhInlierArgs &a, hipStream_t vs) {
+  VoteDense &q = b.dn;
+  VoteTail &tl = b.tl;
+  const size_t P = (size_t)v.P;
+  if (b.tail & VH_POST_TAIL_COV) {
+    VhCovArgs c{};
+    c.e = b.ego;
+    c.pm = q.d_out; c.pm_stride = v.cap; c.counts = q.d_ninl; c.count_cap = v.cap; c.n_lists = v.P;
+    c.tr = b.dense_mode >= 2 ? q.d_tr_refit : b.d_tr; c.ok = b.dense_mode >= 2 ? q.d_ok_refit : q.d_ok;
+    c.cov = tl.d.cov; c.ssr = tl.d.ssr; c.ok_out = tl.d.ok_cov;
+    {
+      Scope sc(this, "motion_cov", vs);
+      vh_launch_motion_cov(c, vs);
+    }
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipMemcpyAsync(tl.h.cov, tl.d.cov, sizeof(double) * 36 * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.ssr, tl.d.ssr, sizeof(double) * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.ok_cov, tl.d.ok_cov, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+  }
+  if (b.tail & VH_POST_TAIL_MONO_REFIT) {
+    VhMonoRefitArgs r{};
+    r.pm = q.d_out; r.pm_stride = v.cap; r.counts = q.d_ninl; r.count_cap = v.cap; r.n_lists = v.P;
+    r.model_in = q.d_model; r.ok_in = q.d_ok;
+    r.model_out = tl.d.model; r.ok_out = tl.d.ok_model; r.w_out = tl.d.w;
+    {
+      Scope sc(this, "mono_refit", vs);
+      vh_launch_mono_refit(r, vs);
+    }
+    VH_HIP(hipGetLastError());
+    a.model = tl.d.model; a.ok = tl.d.ok_model;  // (the estimator's model stays where it is: vh_post_dense::model)
+    launch_inliers(t, a, vs, this);
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipMemcpyAsync(tl.h.model, tl.d.model, sizeof(vh_mono_model) * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.w, tl.d.w, sizeof(double) * 2 * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.ok_model, tl.d.ok_model, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+  }
+  if (b.tail & VH_POST_TAIL_MONO_POSE) {
+    const bool refined = (b.tail & VH_POST_TAIL_MONO_REFINE) != 0;
+    VhMonoPoseArgs m{};
+    m.e = b.mono;
+    m.pm = q.d_out; m.pm_stride = v.cap; m.counts = q.d_ninl; m.count_cap = v.cap; m.n_lists = v.P;
+    m.cap = v.cap; m.slot_stride = v.cap;
+    m.model = a.model; m.ok_in = a.ok;
+    m.hdr = tl.d_hdr; m.dist = tl.d_dist; m.d = tl.d_d; m.tr = tl.d.tr; m.ok = tl.d.ok_pose; m.pose = tl.d.pose;
+    for (int32_t k = 0; k < VH_MONO_POSE_STAGES; k++) {
+      {
+        Scope sc(this, vh_mono_pose_scope(k), vs);
+        vh_launch_mono_pose_stage(m, k, vs);
+      }
+      if (refined && k == 1) {  // where Group::pose_mono puts it
+        Scope sr(this, "mono_pose_refine", vs);
+        vh_launch_mono_pose_refine(m, tl.d.refine, vs);
+      }
+    }
+    VH_HIP(hipGetLastError());
+    VH_HIP(hipMemcpyAsync(tl.h.tr, tl.d.tr, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.ok_pose, tl.d.ok_pose, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
+    VH_HIP(hipMemcpyAsync(tl.h.pose, tl.d.pose, sizeof(vh_mono_pose) * P, hipMemcpyDeviceToHost, vs));
+    if (refined) VH_HIP(hipMemcpyAsync(tl.h.refine, tl.d.refine, sizeof(vh_mono_refine) * P, hipMemcpyDeviceToHost, vs));
+  }
+  return VH_OK;
+}
+
 // The dense block of batch b for `lists` lists of the batch's record slots: allocated (or grown) before the batch's first
 // launch; a refusal leaves the batch without one.
 int32_t Group::vote_dense_alloc(VoteBatch &b, int32_t lists, bool model) {
@@ -466,6 +576,7 @@ int32_t Group::vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs) 
     VH_HIP(hipMemcpyAsync(q.h_int + 3 * L, q.d_nupd, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
     VH_HIP(hipMemcpyAsync(q.h_tr, q.d_tr_refit, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, vs));
   }
+  if (b.tail) { const int32_t rc = vote_tail_launch(b, v, t, a, vs); if (rc) return rc; }  // (before the counts come down: the mono refit classifies again)
   VH_HIP(hipMemcpyAsync(q.h_int, q.d_voted, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
   VH_HIP(hipMemcpyAsync(q.h_int + L, q.d_ninl, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
   if (b.has_mono) VH_HIP(hipMemcpyAsync(q.h_model, q.d_model, sizeof(vh_mono_model) * P, hipMemcpyDeviceToHost, vs));
@@ -528,6 +639,9 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   if (mono && (!rand8 || mono->ransac_iters < 1 || (int64_t)S * vote_steps * mono->ransac_iters > (int64_t)1 << 31)) return VH_ERR_INVALID_ARG;
   if (vote_dense >= 1 && !e && !mono) return VH_ERR_INVALID_ARG;  // the dense stages classify under the batch's motion
   if (vote_dense >= 2 && mono) return VH_ERR_INVALID_ARG;         // (the reference has no mono refit)
+  if (vote_tail && vote_dense < 1) return VH_ERR_INVALID_ARG;                         // the tail stages read the dense stages' inlier lists
+  if ((vote_tail & VH_POST_TAIL_COV) && !e) return VH_ERR_INVALID_ARG;                // the covariance is the stereo motion's
+  if ((vote_tail & ~(uint32_t)VH_POST_TAIL_COV) && !mono) return VH_ERR_INVALID_ARG;  // refit and pose the mono model's
   if ((int64_t)S * vote_steps > 65535) return VH_ERR_UNSUPPORTED;  // (the tally and the monocular kernels put the list on grid.y: fewer steps per batch)
   if (!allocated || last_method < 0) return VH_ERR_STATE;
   if (e && last_method != VH_METHOD_QUAD) return VH_ERR_STATE;        // the stereo estimator needs both cameras of both frames
@@ -548,7 +662,8 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
       const size_t post = (e ? sizeof(double) * 4 * (size_t)P * (size_t)need : 0) + (mono ? (size_t)vh_mono_scratch_bytes(P, (int32_t)need, mono->ransac_iters) : 0) +
                           sizeof(double) * 6 * (size_t)P + sizeof(int32_t) * 2 * (size_t)P +
                           sizeof(int32_t) * (size_t)steps * (e ? (size_t)S * e->ransac_iters * 3 : (mono ? (size_t)S * mono->ransac_iters * 8 : 0)) +
-                          (vote_dense ? VoteDense::bytes_for((size_t)P, (size_t)std::max(cap_ps, 4), mono != nullptr) : 0);
+                          (vote_dense ? VoteDense::bytes_for((size_t)P, (size_t)std::max(cap_ps, 4), mono != nullptr) : 0) +
+                          (vote_tail ? VoteTail::bytes_for((size_t)P, (size_t)std::max(cap_ps, 4), vote_tail) : 0);
       return (double)vote_batches * (double)(VhVoteBuffers::bytes_for(P, cap_ps, (int32_t)need, (int32_t)grid) + post);
     };
     int32_t steps = vote_steps;
@@ -573,7 +688,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   const auto same = [&](const VoteBatch &q) {
     return q.method == last_method && q.rule == vote_rule && q.max_features == max_features && q.bw == bw && q.bh == bh && q.has_ego == (e != nullptr) &&
            q.has_mono == (mono != nullptr) && (!e || memcmp(&q.ego, e, sizeof(*e)) == 0) && (!mono || memcmp(&q.mono, mono, sizeof(*mono)) == 0) &&
-           q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0) && q.dense_mode == vote_dense;
+           q.vb.v.cap >= cap_ps && q.want_lists == (want_lists != 0) && q.dense_mode == vote_dense && q.tail == vote_tail;
   };
   if (b->steps > 0 && (b->launched || b->steps >= vote_steps || !same(*b))) {  // the batch is closed (full, flushed, or configured differently): next one
     if ((rc = vote_launch(*b, vote_cur))) return rc;
@@ -593,6 +708,7 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
     const int32_t P = vote_steps * S;
     // (the classification's launch grid: lists x tiles of the slots the batch will have)
     if (vote_dense && !inlier_grid_ok(P, (std::max(b->vb.v.cap, cap_ps) + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
+    if ((vote_tail & VH_POST_TAIL_MONO_POSE) && !mono_pose_grid_ok(P, std::max(b->vb.v.cap, cap_ps))) return VH_ERR_UNSUPPORTED;  // (the pose's per-record launches.  Not reachable today: the tail needs a dense mode, and the line above refuses at 2^24 tiles of 1 024 records, long before lists * ceil(cap / 64) reaches 2^30; it stands for the day that limit moves)
     if (b->vb.v.cap < cap_ps || b->vb.out_cap < need || b->vb.v.P < P || b->vb.v.nb_max < grid) {
       if (b->vb.block) {  // a batch grows (longer lists than the ring was sized for): only if the difference fits
         size_t free_b = 0, total_b = 0;
@@ -641,6 +757,9 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
     b->dense_mode = 0;  // (until its block exists: a refused allocation leaves a batch that launches nothing of it)
     if (vote_dense && (rc = vote_dense_alloc(*b, P, mono != nullptr))) return rc;
     b->dense_mode = vote_dense;
+    b->tail = 0;
+    if (vote_tail && (rc = vote_tail_alloc(*b, P, vote_tail))) return rc;
+    b->tail = vote_tail;
   }
   // the step's lists leave the matcher's buffer behind the emission that wrote them; the next emission waits for that (ev_down)
   VH_HIP(hipStreamWaitEvent(down_stream, ev_post[last_buf], 0));
@@ -663,9 +782,20 @@ int32_t Group::post_begin_device(int32_t cap_ps, int32_t max_features, float bw,
   return VH_OK;
 }
 
-// (d, nullable: the dense stages' outputs, include/viso_hip.h: vh_post_dense)
+// The members of *t that the caller's t->size covers (include/viso_hip.h: vh_post_tail), the others null
+static int32_t tail_outputs(const vh_post_tail *t, vh_post_tail &o) {
+  memset(&o, 0, sizeof(o));
+  if (!t) return VH_OK;
+  if (t->size < 8 || (t->size - 8) % 8) return VH_ERR_INVALID_ARG;
+  memcpy(&o, t, std::min<size_t>(t->size, sizeof(o)));
+  return VH_OK;
+}
+
+// (d, t, nullable: the dense and the tail stages' outputs, include/viso_hip.h: vh_post_dense, vh_post_tail)
 int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t *ninl, vh_p_match *out, int32_t out_cap, int32_t *out_counts,
-                                  const vh_post_dense *d) {
+                                  const vh_post_dense *d, const vh_post_tail *t_in) {
+  vh_post_tail t;
+  { const int32_t rt = tail_outputs(t_in, t); if (rt) return rt; }
   const bool d_records = d && (d->voted_pm || d->flags || d->inlier_pm || d->src_pos);
   if (age < 0 || ((out || d_records) && out_cap < 1)) return VH_ERR_INVALID_ARG;
   if (vstep.empty() || post_dev_seq - 1 - age < 0 || age >= (int64_t)vstep.size()) return VH_ERR_STATE;
@@ -678,6 +808,10 @@ int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t 
     if ((d->tr_refit || d->ok_refit || d->n_updates) && b.dense_mode < 2) return VH_ERR_STATE;
     if (d->model && !b.has_mono) return VH_ERR_STATE;
   }
+  // (the same for the tail's outputs and the step's mask)
+  if (((t.cov || t.ssr || t.ok_cov) && !(b.tail & VH_POST_TAIL_COV)) || ((t.model_refit || t.ok_model || t.w) && !(b.tail & VH_POST_TAIL_MONO_REFIT)) ||
+      ((t.tr_pose || t.ok_pose || t.pose) && !(b.tail & VH_POST_TAIL_MONO_POSE)) || (t.refine && !(b.tail & VH_POST_TAIL_MONO_REFINE)))
+    return VH_ERR_STATE;
   int32_t rc = vote_launch(b, st.batch);  // (a batch that is not full yet is closed and launched now)
   if (rc) return rc;
   VH_HIP(hipEventSynchronize(b.ev_done));
@@ -711,6 +845,20 @@ int32_t Group::post_finish_device(int32_t age, double *tr, int32_t *ok, int32_t 
       if (k > out_cap) { ret = VH_ERR_CAPACITY; if (out_counts) out_counts[s] = -1; continue; }
       memcpy(out + (size_t)s * out_cap, b.h_out + (p0 + s) * (size_t)b.vb.out_cap, sizeof(vh_p_match) * (size_t)k);
     }
+  }
+  // The tail stages' outputs: everything came down with the batch.  A refused stream's are the zero records.
+  for (int32_t s = 0; s < S && b.tail; s++) {
+    const size_t p = p0 + (size_t)s;
+    const VhVoteMeta &m = b.h_meta[p];
+    const bool bad = m.status != VH_VOTE_OK && m.status != VH_VOTE_SKIP;
+    const TailLists &h = b.tl.h;
+    const auto give = [&](auto *dst, const auto *src, size_t n) {
+      if (!dst) return;
+      if (bad) memset(dst + n * (size_t)s, 0, sizeof(*dst) * n); else memcpy(dst + n * (size_t)s, src + n * p, sizeof(*dst) * n);
+    };
+    give(t.cov, h.cov, 36); give(t.ssr, h.ssr, 1); give(t.ok_cov, h.ok_cov, 1);
+    give(t.model_refit, h.model, 1); give(t.ok_model, h.ok_model, 1); give(t.w, h.w, 2);
+    give(t.tr_pose, h.tr, 6); give(t.ok_pose, h.ok_pose, 1); give(t.pose, h.pose, 1); give(t.refine, h.refine, 1);
   }
   if (!d || b.dense_mode < 1) return ret;
   // The dense stages' outputs.  The small ones came down with the batch; the records of this step's lists are copied out

@@ -1141,6 +1141,86 @@ int32_t vh_group_post_device_dense(vh_group *g, int32_t mode);
 int32_t vh_group_post_finish_device_dense(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
                                           int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d);
 
+/* ---- the covariance, the mono refit and the mono pose as stages of the device post chain ----
+ * vh_group_motion_covariance, vh_group_refit_model_mono, vh_group_pose_mono and vh_group_pose_mono_refined work on the
+ * lists of the handle's last match call, which the pipelined chain has overwritten long before a batch's motion arrives.
+ * With a tail mask set the batch runs the same kernels over its own inlier lists, on its vote stream behind the dense
+ * stages and before the small downloads: no new stream, no event, no host wait, no upload.
+ *   vh_group_post_device_tail    stages: a mask of the bits below; 0 is the default, and with it every call allocates,
+ *                         launches and returns what it did without this entry.
+ *                           VH_POST_TAIL_COV          stereo estimator, dense mode >= 1: the covariance of
+ *                               vh_motion_covariance over the batch's final inlier lists under the batch's final motion --
+ *                               mode 1: tr / ok of the estimator over the classification's inliers; mode 2: tr_refit /
+ *                               ok_refit over the FIRST classification's inliers (the reclassify = 0 pairing of
+ *                               vh_group_refit_motion + vh_group_motion_covariance); mode 3: tr_refit / ok_refit over
+ *                               the second classification's.
+ *                           VH_POST_TAIL_MONO_REFIT   mono estimator, dense mode 1: vh_refit_model_mono on the compacted
+ *                               inliers from the estimator's model / ok, then the classification again under the
+ *                               refitted model / its ok (reclassify = 1 of vh_group_refit_model_mono).  The counts,
+ *                               flags, records and positions vh_post_dense hands out are then the second
+ *                               classification's; vh_post_dense::model stays the estimator's.
+ *                           VH_POST_TAIL_MONO_POSE    mono estimator, dense mode 1: vh_pose_mono over the final inlier
+ *                               lists under the model they were classified under (the refitted one with
+ *                               VH_POST_TAIL_MONO_REFIT, else the estimator's).
+ *                           VH_POST_TAIL_MONO_REFINE  with VH_POST_TAIL_MONO_POSE: the pose is vh_pose_mono_refined's.
+ *                         VH_ERR_INVALID_ARG for an unknown bit or REFINE without POSE; VH_ERR_STATE while steps are in
+ *                         flight; a change of the mask releases the ring (as vh_group_post_device_dense), and the next
+ *                         begin call sizes it again.  The mask is part of a batch's configuration.
+ *                         With a mask set vh_group_post_begin_device returns VH_ERR_INVALID_ARG when the dense mode is
+ *                         0, when COV is set without the stereo estimator, and when any other bit is set without the
+ *                         mono estimator; VH_ERR_UNSUPPORTED when POSE is set and steps_per_batch * S lists of
+ *                         ceil(cap_per_stream / 64) workgroups reach 2^30 (the pose's per-record launches) -- a limit
+ *                         the dense mode's own (2^24 tiles of 1 024 records, above) is reached long before, so today
+ *                         the dense mode's refusal is the one a caller meets.
+ *                         Device memory, per batch, in a block beside the dense stages': per list 300 bytes (COV), 148
+ *                         (MONO_REFIT), 972 (MONO_POSE: tr, ok, vh_mono_pose and the 768-byte header) and 288
+ *                         (MONO_REFINE), each array rounded up to 256 bytes, and with MONO_POSE 16 bytes per record
+ *                         slot.  It is part of the ring the first begin call sizes against 80 % of the free memory,
+ *                         counted by vh_group_device_bytes, allocated before the batch's first launch (a refusal is
+ *                         VH_ERR_HIP, nothing has moved, the begin call can be repeated) and released with the ring.
+ *                         Profile scopes (on the batch's stream): "motion_cov", "mono_refit", "mono_pose_head" ..
+ *                         "mono_pose_finish", "mono_pose_refine", and the classification's once more with MONO_REFIT.
+ *   vh_group_post_device_shape   the ring's shape in effect: the steps per batch and the batches of
+ *                         vh_group_post_device_config, the steps per batch as the first begin call of a ring left
+ *                         them.  The configured value is an upper bound -- that call halves it until the ring fits
+ *                         80 % of the free device memory, and the tail's block makes that likelier; before it, this
+ *                         returns the configured shape.  A caller sizes its lead (steps_per_batch * (batches - 1)) by it.
+ *   vh_group_post_finish_device_tail   vh_group_post_finish_device_dense with one more argument; t = NULL, or a struct
+ *                         whose pointers are all NULL, is that call: tr, ok, n_inliers, bucketed, counts, every output
+ *                         of d and the return value are the same bits under any mask (with MONO_REFIT the
+ *                         classification d hands out is the second one, see above).
+ * vh_post_tail: nullable output pointers, each for this step's S streams, behind the size the caller compiled:
+ * 88 bytes, pointer k at offset 8 + 8 k.  Members beyond `size` are not read, so a later, longer struct stays compatible. */
+#define VH_POST_TAIL_COV 1u
+#define VH_POST_TAIL_MONO_REFIT 2u
+#define VH_POST_TAIL_MONO_POSE 4u
+#define VH_POST_TAIL_MONO_REFINE 8u
+#define VH_POST_TAIL_ALL 15u
+typedef struct vh_post_tail {
+  uint32_t size;            /* sizeof(vh_post_tail) as the caller compiled it; members beyond it are not read */
+  uint32_t reserved;        /* 0 */
+  double *cov;              /* [S][36]  VH_POST_TAIL_COV; row-major, zero where ok_cov = 0 */
+  double *ssr;              /* [S]      VH_POST_TAIL_COV */
+  int32_t *ok_cov;          /* [S]      VH_POST_TAIL_COV */
+  vh_mono_model *model_refit; /* [S]    VH_POST_TAIL_MONO_REFIT; the zero record where ok_model = 0 */
+  int32_t *ok_model;        /* [S]      VH_POST_TAIL_MONO_REFIT */
+  double *w;                /* [S][2]   VH_POST_TAIL_MONO_REFIT */
+  double *tr_pose;          /* [S][6]   VH_POST_TAIL_MONO_POSE */
+  int32_t *ok_pose;         /* [S]      VH_POST_TAIL_MONO_POSE */
+  vh_mono_pose *pose;       /* [S]      VH_POST_TAIL_MONO_POSE */
+  vh_mono_refine *refine;   /* [S]      VH_POST_TAIL_MONO_REFINE */
+} vh_post_tail;
+/* VH_ERR_INVALID_ARG for a size below 8 or not 8 + a multiple of 8.  VH_ERR_STATE when t asks for an output the step's
+ * mask did not produce (checked first, with d's: the step stays open and can be finished again).  Every output came
+ * down with the batch's results: nothing is copied per record.  A refused refinement is not a refused pose (as
+ * vh_pose_mono_refined: refine[s].status says why, and the pose is the plain one).  A stream whose list the vote
+ * refused takes part in nothing: its tail outputs are the zero records with ok = 0, and the call returns the
+ * refusal's code as vh_group_post_finish_device does.  Sequence handles as vh_group_post_begin_device. */
+int32_t vh_group_post_device_tail(vh_group *g, uint32_t stages);
+int32_t vh_group_post_device_shape(vh_group *g, int32_t *steps_per_batch, int32_t *batches);
+int32_t vh_group_post_finish_device_tail(vh_group *g, int32_t age, double *tr, int32_t *ok, int32_t *n_inliers, vh_p_match *bucketed,
+                                         int32_t cap_per_stream, int32_t *counts, const vh_post_dense *d, const vh_post_tail *t);
+
 /* vh_group_post_finish with the MONOCULAR estimator as its last stage: what VisualOdometryMono::process runs
  * after the matching (src/viso_mono.cpp:34-37: bucketFeatures, then estimateMotion on the bucketed list; the
  * Delaunay vote before them is the tail of matchFeatures) for every stream of a group, flow or quad lists,
