@@ -93,6 +93,9 @@ ABI_SYMBOLS = (
     "vh_pose_mono", "vh_group_pose_mono", "vh_match_pose_mono",
     "vh_pose_mono_refined", "vh_group_pose_mono_refined", "vh_match_pose_mono_refined",
     "vh_group_post_device_tail", "vh_group_post_device_shape", "vh_group_post_finish_device_tail",
+    "vh_default_scene_params", "vh_scene_points_stereo", "vh_scene_points_mono",
+    "vh_group_scene_points_stereo", "vh_match_scene_points_stereo", "vh_group_scene_points_mono", "vh_match_scene_points_mono",
+    "vh_group_get_scene_points", "vh_group_get_scene_points_all", "vh_get_scene_points", "vh_group_scene_points_device",
 )
 
 
@@ -182,6 +185,35 @@ MONO_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("scale", "<
 # refined t, the 5 x 5 covariance of (w0, w1, w2, tau0, tau1), the sums of squared Sampson distances before and after
 MONO_REFINE_DTYPE = np.dtype([("B", "<f8", (6,)), ("cov", "<f8", (25,)), ("ssr_start", "<f8"), ("ssr", "<f8"), ("moved_R", "<f8"),
                               ("moved_t", "<f8"), ("status", "<i4"), ("n_updates", "<i4")])
+
+
+# vh_scene_point (32 bytes): one 3-d point per surviving record of scene_points_stereo / _mono / scenePoints
+SCENE_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("sigma_z", "<f4"), ("err", "<f4"), ("src_pos", "<i4"),
+                              ("i1p", "<i4"), ("i1c", "<i4")])
+
+
+class SceneParams(C.Structure):
+    """vh_scene_params: the frame the points are given in (0 previous, 1 current left camera) and the three filters."""
+    _fields_ = [("frame", C.c_int32), ("min_disp", C.c_float), ("max_depth", C.c_double), ("max_err", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw):
+        e = cls(frame=1, min_disp=0.0, max_depth=0.0, max_err=0.0)
+        for k, v in kw.items():
+            if not hasattr(e, k):
+                raise AttributeError(k)
+            setattr(e, k, v)
+        return e
+
+
+def _scene_Tw(Tw, n):
+    """None, or [n, 4, 4] doubles (one 4x4 serves every list)."""
+    if Tw is None:
+        return None
+    Tw = np.asarray(Tw, np.float64)
+    if Tw.shape == (4, 4):
+        Tw = np.broadcast_to(Tw, (n, 4, 4))
+    return np.ascontiguousarray(Tw).reshape(n, 16)
 
 
 def _models(model, n):
@@ -375,6 +407,12 @@ def _lib():
             "vh_group_gain": [vp, vp, vp], "vh_match_gain": [vp, vp, vp],
             "vh_group_gain_indices": [vp, vp, vp, vp, vp], "vh_match_gain_indices": [vp, vp, i32, vp, vp],
             "vh_sequence_set_multi_stage": [vp, i32], "vh_set_multi_stage_prior": [vp, i32], "vh_group_set_multi_stage_prior": [vp, i32],
+            "vh_scene_points_stereo": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_scene_points_mono": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_scene_points_stereo": [vp, vp, vp, vp, vp], "vh_match_scene_points_stereo": [vp, vp, vp, vp, vp],
+            "vh_group_scene_points_mono": [vp, vp, vp, vp, vp], "vh_match_scene_points_mono": [vp, vp, vp, vp, vp],
+            "vh_group_get_scene_points": [vp, i32, vp, i32, vp], "vh_group_get_scene_points_all": [vp, vp, i32, vp],
+            "vh_get_scene_points": [vp, vp, i32, vp], "vh_group_scene_points_device": [vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -384,6 +422,8 @@ def _lib():
         lib.vh_track_carry_free.restype = None
         lib.vh_default_recon_params.argtypes = [vp]
         lib.vh_default_recon_params.restype = None
+        lib.vh_default_scene_params.argtypes = [vp]
+        lib.vh_default_scene_params.restype = None
         lib.vh_reconstruct_last_kernel_ms.argtypes = []
         lib.vh_reconstruct_last_kernel_ms.restype = f64
         lib.vh_group_device_bytes.argtypes = [vp]
@@ -617,6 +657,26 @@ class Matcher:
             return (tr, bool(ok.value), rec, ref) if pose else (tr, bool(ok.value), ref)
         _check(_lib().vh_match_pose_mono(self._h, C.byref(mono), _ptr(tr), C.byref(ok), _ptr(rec) if pose else None), "vh_match_pose_mono")
         return (tr, bool(ok.value), rec) if pose else (tr, bool(ok.value))
+
+    def scenePoints(self, e, sp: "SceneParams | None" = None, Tw=None) -> np.ndarray:
+        """The 3-d point of every inlier of the current classification (vh_match_scene_points_stereo for an EgoParams: under
+        the motion of the last motionInliers / refitMotion(reclassify=True); vh_match_scene_points_mono for a MonoParams:
+        under the pose of the last poseMono) -> SCENE_POINT_DTYPE [n], in list order.  Tw: None or a 4x4 applied last."""
+        sp = sp or SceneParams.default()
+        tw = _scene_Tw(Tw, 1)
+        n = C.c_int32(0)
+        fn = "vh_match_scene_points_mono" if isinstance(e, MonoParams) else "vh_match_scene_points_stereo"
+        _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), None if tw is None else _ptr(tw), C.byref(n)), fn)
+        return self.getScenePoints()
+
+    def getScenePoints(self) -> np.ndarray:
+        """The points of the last scenePoints, valid until the next matchFeatures (vh_get_scene_points)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_get_scene_points(self._h, None, 0, C.byref(n)), "vh_get_scene_points", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, SCENE_POINT_DTYPE)
+        if n.value:
+            _check(_lib().vh_get_scene_points(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_scene_points")
+        return out
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images on the device for getGain (vh_set_gain): before the first pushBack."""
@@ -932,6 +992,40 @@ class StreamGroup:
             return (tr, ok.astype(bool), counts, rec, ref) if pose else (tr, ok.astype(bool), counts, ref)
         _check(_lib().vh_group_pose_mono(self._h, C.byref(mono), _ptr(tr), _ptr(ok), _ptr(rec) if pose else None, _ptr(counts)), "vh_group_pose_mono")
         return (tr, ok.astype(bool), counts, rec) if pose else (tr, ok.astype(bool), counts)
+
+    def scenePoints(self, e, sp: "SceneParams | None" = None, Tw=None) -> np.ndarray:
+        """The 3-d point of every inlier of every stream's current classification, left on the device: with an EgoParams
+        the stereo form (vh_group_scene_points_stereo, under the motion the stereo classification was made under -- after
+        refitMotion(reclassify=True) the refined one), with a MonoParams the mono form (vh_group_scene_points_mono, under
+        the pose of the last poseMono); the other kind of classification is VH_ERR_STATE.  Tw: None, one 4x4 or [S, 4, 4],
+        applied last.  -> counts [S]; getScenePoints(stream) / getScenePointsAll / scenePointsDevice give the points."""
+        sp = sp or SceneParams.default()
+        tw = _scene_Tw(Tw, self.S)
+        counts = np.zeros(self.S, np.int32)
+        fn = "vh_group_scene_points_mono" if isinstance(e, MonoParams) else "vh_group_scene_points_stereo"
+        _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), None if tw is None else _ptr(tw), _ptr(counts)), fn)
+        return counts
+
+    def getScenePoints(self, stream: int) -> np.ndarray:
+        """The stream's points of the last scenePoints in list order, SCENE_POINT_DTYPE [n] (vh_group_get_scene_points)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_group_get_scene_points(self._h, stream, None, 0, C.byref(n)), "vh_group_get_scene_points", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, SCENE_POINT_DTYPE)
+        if n.value:
+            _check(_lib().vh_group_get_scene_points(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_scene_points")
+        return out
+
+    def getScenePointsAll(self, cap_per_stream: int):
+        """-> (points [S, cap_per_stream], counts [S]) (vh_group_get_scene_points_all)."""
+        out = np.zeros((self.S, max(cap_per_stream, 1)), SCENE_POINT_DTYPE); counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_get_scene_points_all(self._h, _ptr(out), out.shape[1], _ptr(counts)), "vh_group_get_scene_points_all")
+        return out, counts
+
+    def scenePointsDevice(self):
+        """-> (device address of stream 0's points, stride in records): valid until the next matchFeatures."""
+        d = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_scene_points_device(self._h, C.byref(d), C.byref(stride)), "vh_group_scene_points_device")
+        return d.value, stride.value
 
     def setGain(self, on: bool = True):
         """Keep the pushed left images of every stream (sequence handle: frame) on the device for gain()
@@ -1462,6 +1556,39 @@ def motion_covariance(ego: EgoParams, match_lists, tr, ok, device: int = 0):
     _check(_lib().vh_motion_covariance(C.byref(ego), device, n, _ptr(pm), _ptr(offsets), _ptr(tr), _ptr(ok), _ptr(cov), _ptr(ssr),
                                        _ptr(ok_out)), "vh_motion_covariance")
     return cov[:n], ssr[:n], ok_out[:n].astype(bool)
+
+
+def _scene_points(fn, e, match_lists, motion, ok, sp, Tw, device):
+    lists = [np.ascontiguousarray(m, dtype=P_MATCH_DTYPE) for m in match_lists]
+    n = len(lists)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum([len(m) for m in lists])
+    total = int(offsets[-1])
+    pm = np.concatenate(lists) if total else np.zeros(0, P_MATCH_DTYPE)
+    ok = np.ascontiguousarray(ok).astype(np.int32).reshape(n)
+    sp = sp or SceneParams.default()
+    tw = _scene_Tw(Tw, n)
+    out = np.zeros(max(total, 1), SCENE_POINT_DTYPE); counts = np.zeros(max(n, 1), np.int32)
+    _check(getattr(_lib(), fn)(C.byref(e), C.byref(sp), device, n, _ptr(pm), _ptr(offsets), _ptr(motion), _ptr(ok),
+                               None if tw is None else _ptr(tw), _ptr(out), _ptr(counts)), fn)
+    return [out[int(offsets[s]):int(offsets[s]) + int(counts[s])].copy() for s in range(n)], counts[:n]
+
+
+def scene_points_stereo(ego: EgoParams, match_lists, tr, ok, sp: "SceneParams | None" = None, Tw=None, device: int = 0):
+    """The 3-d point of every record of whole quad lists under the motions tr [n, 6] / ok [n] (vh_scene_points_stereo): the
+    previous pair's point as getInlier forms it, moved by tr for sp.frame = 1, with its reprojection error and sigma_z;
+    records behind the camera, non-finite ones and those the filters of `sp` cut are dropped, survivors keep list order.
+    Tw: None, one 4x4 or [n, 4, 4], applied last.  -> ([SCENE_POINT_DTYPE array per list], counts [n])."""
+    tr = np.ascontiguousarray(tr, np.float64).reshape(len(match_lists), 6)
+    return _scene_points("vh_scene_points_stereo", ego, match_lists, tr, ok, sp, Tw, device)
+
+
+def scene_points_mono(mono: MonoParams, match_lists, pose, ok, sp: "SceneParams | None" = None, Tw=None, device: int = 0):
+    """The triangulated point of every record of whole flow / quad lists under the poses `pose` (MONO_POSE_DTYPE [n], as
+    pose_mono returns them: R, t and scale are read) / ok [n] (vh_scene_points_mono), scaled to metres.
+    -> ([SCENE_POINT_DTYPE array per list], counts [n])."""
+    pose = np.ascontiguousarray(pose, MONO_POSE_DTYPE).reshape(len(match_lists))
+    return _scene_points("vh_scene_points_mono", mono, match_lists, pose, ok, sp, Tw, device)
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):

@@ -7,6 +7,7 @@
 //   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
 //   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
+//   engine_scene.hip  the 3-d points of whole lists (kernels_scene.hip) and their part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -297,6 +298,7 @@ struct InlierState : InlierArrays {      // [S][mcap], [S][tiles], [S], [S][6]
   bool from_host = false;                 // it read `host` (a list was replaced on the host), not the emission's lists
   bool valid = false, truncated = false;  // a classification exists (of the lists of match call `seq`) / of a truncated list
   int64_t seq = 0;
+  int64_t gen = 0;                        // classifications made so far: what was computed on one's lists is stale after the next
   std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
 };
 
@@ -324,6 +326,21 @@ struct MonoPoseState {
   vh_mono_pose *d_pose = nullptr;            // [S]
   int32_t *d_ok = nullptr;                   // [S]
   vh_mono_refine *d_refine = nullptr;        // [S] a block of its own, allocated by the first vh_group_pose_mono_refined
+  // d_pose / d_ok hold the pose of classification `pose_gen` of match call `pose_seq` (Group::scene_points reads them there)
+  int64_t pose_seq = -1, pose_gen = -1;
+};
+
+// The 3-d points of the compacted inlier lists (vh_group_scene_points_stereo / _mono; engine_scene.hip, DESIGN.md section
+// 4.20): one arena block, allocated by the first call.
+struct SceneState {
+  vh_scene_point *d_out = nullptr;  // [S][mcap]
+  int32_t *d_tiles = nullptr;       // [S][tiles]
+  double *d_Tw = nullptr;           // [S][16]
+  int32_t *d_n = nullptr;           // [S]
+  int32_t tiles = 0;
+  bool valid = false;               // points exist, of the lists of match call `seq`
+  int64_t seq = 0;
+  std::vector<int32_t> n;           // [S] points per stream
 };
 
 // The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
@@ -589,6 +606,7 @@ struct Group {
   CovState cv;
   MonoRefitState mrf;
   MonoPoseState mps;
+  SceneState scn;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -695,6 +713,13 @@ struct Group {
   // refined: the winner is refined between the chirality count and the tail (vh_group_pose_mono_refined); refine is nullable
   int32_t pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose, int32_t *counts, bool refined = false,
                     vh_mono_refine *refine = nullptr);
+
+  // ---- engine_scene.hip ----
+  // e (stereo) or m (mono): the one that is given names the kind
+  int32_t scene_points(const vh_ego_params *e, const vh_mono_params *m, const vh_scene_params *sp, const double *Tw, int32_t *counts);
+  bool scene_current() const { return allocated && scn.valid && scn.seq == match_seq; }
+  int32_t get_scene_points(int32_t s, vh_scene_point *out, int32_t capo, int32_t *n);
+  int32_t get_scene_points_all(vh_scene_point *out, int32_t cap_per_stream, int32_t *counts);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

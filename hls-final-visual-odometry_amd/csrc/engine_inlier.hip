@@ -79,7 +79,7 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
     inl.n_list[s] = std::min(inl.n_list[s], mcap);
     counts[s] = inl.n_inl[s];
   }
-  inl.valid = true; inl.seq = match_seq; inl.mono = t.is_mono; inl.from_host = replaced;
+  inl.valid = true; inl.seq = match_seq; inl.gen++; inl.mono = t.is_mono; inl.from_host = replaced;
   return inl.truncated ? VH_ERR_CAPACITY : VH_OK;
 }
 

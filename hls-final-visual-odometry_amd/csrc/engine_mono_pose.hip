@@ -63,7 +63,9 @@ int32_t Group::pose_mono(const vh_mono_params *e, double *tr, int32_t *ok, vh_mo
   if (pose) VH_HIP(hipMemcpyAsync(pose, mps.d_pose, sizeof(vh_mono_pose) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   if (refined && refine) VH_HIP(hipMemcpyAsync(refine, mps.d_refine, sizeof(vh_mono_refine) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   if (counts) for (int32_t s = 0; s < S; s++) counts[s] = inl.n_inl[s];
+  mps.pose_seq = -1;  // (should the wait fail, d_pose is nobody's)
   VH_HIP(hipStreamSynchronize(post_stream));
+  mps.pose_seq = match_seq; mps.pose_gen = inl.gen;
   return check_violation();
 }
 

@@ -531,6 +531,31 @@ const char *vh_mono_pose_scope(int32_t k);
 // launches 2..5 then read as they always do.  refine: [n_lists].  grid: a.n_lists workgroups.
 void vh_launch_mono_pose_refine(const VhMonoPoseArgs &a, vh_mono_refine *refine, hipStream_t st);
 
+// The 3-d points of whole lists, compacted in list order (kernels_scene.hip).  The lists are
+// addressed as vh_list does; out (and src, where given) of list s begin at offsets[s] (concatenated lists) or at
+// s * out_stride (fixed-stride slots).
+#define VH_SCENE_TILE 256  // records per workgroup, one per lane
+struct VhSceneArgs {
+  vh_ego_params e;          // stereo: f, cu, cv, base
+  vh_mono_params m;         // mono: f, cu, cv
+  vh_scene_params sp;
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap;
+  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_SCENE_TILE)
+  const double *tr;         // stereo: [n_lists][6]; not read where ok = 0
+  const vh_mono_pose *pose; // mono: [n_lists]; R, t, scale are read, and not where ok = 0
+  const int32_t *ok;        // [n_lists]; 0: the list has no points
+  const double *Tw;         // null, or [n_lists][16] row-major
+  const int32_t *src;       // null (a record's src_pos is its position in the list), or indexed like out: the value to store
+  int64_t out_stride;
+  int32_t *tile_cnt;        // [n_lists][tiles_per_list] survivors per tile, then (after the scan) survivors before the tile
+  int32_t *n_out;           // [n_lists]
+  vh_scene_point *out;      // the points in list order
+};
+void vh_launch_scene_points(const VhSceneArgs &a, bool mono, hipStream_t st);  // flag, scan, store
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

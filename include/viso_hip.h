@@ -1044,6 +1044,78 @@ int32_t vh_group_pose_mono_refined(vh_group *g, const vh_mono_params *e, double 
                                    vh_mono_refine *refine, int32_t *counts);
 int32_t vh_match_pose_mono_refined(vh_matcher *m, const vh_mono_params *e, double *tr, int32_t *ok, vh_mono_pose *pose,
                                    vh_mono_refine *refine);
+/* ---- scene points: the 3-d point of every record of whole lists, stereo and mono (csrc/kernels_scene.hip) ----
+ * One point per record of a list (pass an inlier list), compacted in list order: the per-step cloud beside the pose.
+ * Double precision, every product and sum rounded on its own, one rounding to float at the store.
+ * Stereo, a quad list under tr[6] (vh_ego_params: f, cu, cv, base are read):
+ *   the point of the previous pair as getInlier forms it (src/viso_stereo.cpp:80-86), float df = max(u1p - u2p, 0.0001f):
+ *   X = (u1p - cu) * base / df, Y = (v1p - cv) * base / df, Z = f * base / df;  frame 0: (X, Y, Z);  frame 1: the point
+ *   moved by tr, X1c = r00 X + r01 Y + r02 Z + tx and so on (:274-276);  err = sqrt of the sum of the four squared
+ *   differences between (u1c, v1c, u2c, v2c) and the prediction (:317-321) -- the sum vh_motion_inliers compares -- for
+ *   either frame;  sigma_z = z * z / (f * base) of the point in the frame asked for.
+ * Mono, a flow or quad list under a vh_mono_pose (vh_mono_params: f, cu, cv are read):
+ *   P1 = K [I | 0], P2 = K [R | t] from the pose's R and unit t; the record triangulated as triangulateChieral does
+ *   (src/viso_mono.cpp:378-387); X / X(3,:), a zero w giving the zero point (:100);  frame 0: that point times
+ *   pose.scale;  frame 1: (R X + t) times pose.scale;  err = sqrt of the sum of the four squared differences between
+ *   (u1p, v1p), (u1c, v1c) and the projections of X by P1, P2;  sigma_z = 0.
+ * A record is dropped, never an error: in a list with ok = 0 (count 0; tr / pose is not read); where x, y, z or err is
+ * not finite (also: not finite as a float); where z <= 0;  stereo: where min_disp > 0 and the float u1p - u2p <
+ * min_disp;  where max_depth > 0 and z > max_depth;  where max_err > 0 and err > max_err -- strict compares in double on
+ * the values in the frame asked for, before Tw.  Tw (nullable; [n][16], a row-major 4x4 per list of which the top three
+ * rows are read) is applied last: x' = Tw[0] x + Tw[1] y + Tw[2] z + Tw[3], added left to right.
+ * Survivors keep list order; the same bytes from run to run, alone or among other lists, and from the stateless and the
+ * handle forms.  The stereo rotation's sin / cos are the device library's. */
+typedef struct vh_scene_point {   /* 32 bytes */
+  float   x, y, z;      /* metres, in the frame asked for, after Tw if given */
+  float   sigma_z;      /* stereo: z * z / (f * base), depth std-dev per pixel of disparity error, of the camera-frame
+                         * point before Tw; mono: 0 */
+  float   err;          /* reprojection error in pixels */
+  int32_t src_pos;      /* position of the record in the list the classification ran on (stateless: in the list given) */
+  int32_t i1p, i1c;     /* copied from the record: joins vh_track / features */
+} vh_scene_point;
+typedef struct vh_scene_params {
+  int32_t frame;        /* 0: previous left camera, 1: current left camera */
+  float   min_disp;     /* stereo: drop records with u1p - u2p < min_disp (0: keep all) */
+  double  max_depth;    /* drop camera-frame z > max_depth (<= 0: no limit) */
+  double  max_err;      /* drop err > max_err (<= 0: no limit) */
+} vh_scene_params;
+void vh_default_scene_params(vh_scene_params *sp);   /* frame 1, 0, 0, 0 */
+/* Stateless: lists laid out and validated as for vh_motion_inliers (the same length limits); tr[n_sets][6] (mono:
+ * pose[n_sets]), ok[n_sets], Tw NULL or [n_sets][16] -> out (indexed like pm: list s compacted at [offsets[s],
+ * offsets[s] + counts[s]), the rest of each slice not written) and counts[n_sets].  sp->frame outside 0..1 is
+ * VH_ERR_INVALID_ARG.  n_sets == 0 or no records at all: VH_OK with zero counts, nothing is launched and no device is needed. */
+int32_t vh_scene_points_stereo(const vh_ego_params *e, const vh_scene_params *sp, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                               const int32_t *offsets, const double *tr, const int32_t *ok, const double *Tw, vh_scene_point *out,
+                               int32_t *counts);
+int32_t vh_scene_points_mono(const vh_mono_params *e, const vh_scene_params *sp, int32_t device, int32_t n_sets, const vh_p_match *pm,
+                             const int32_t *offsets, const vh_mono_pose *pose, const int32_t *ok, const double *Tw, vh_scene_point *out,
+                             int32_t *counts);
+/* The same on the compacted inlier lists of the handle's current classification, the motion / pose taken from the
+ * device: nothing goes up but Tw (nullable, [S][16]); counts[S] comes back; synchronous.  src_pos is the position in the
+ * list the classification ran on (vh_group_get_inlier_matches' src_pos_out of the record).
+ *   _stereo: under the tr / ok the STEREO classification was made under (after vh_group_refit_motion(reclassify = 1)
+ *     the refined motion); VH_ERR_STATE wherever vh_group_motion_covariance returns it.
+ *   _mono: under the pose the last vh_group_pose_mono / _refined left on the device for the current MONO classification
+ *     (R, t, scale, ok); VH_ERR_STATE without one, after the next push, match or classification, and on a stereo
+ *     classification.
+ * Plain groups, sequence handles (rows without a pair: count 0) and lone matchers.  The first call adds one block: 32
+ * bytes per record slot (S x max_matches slots), 4 bytes per tile of 256 slots (S x ceil(max_matches / 256)) and 128 + 4
+ * bytes per stream (Tw, counts), each of the four arrays rounded up to 256 bytes, counted by vh_group_device_bytes; a
+ * handle that never calls these allocates and launches nothing.  A refused allocation is VH_ERR_HIP before any launch
+ * and leaves the handle as it was; the call may be repeated.  Profile scope: "scene_points". */
+int32_t vh_group_scene_points_stereo(vh_group *g, const vh_ego_params *e, const vh_scene_params *sp, const double *Tw, int32_t *counts);
+int32_t vh_match_scene_points_stereo(vh_matcher *m, const vh_ego_params *e, const vh_scene_params *sp, const double *Tw, int32_t *count);
+int32_t vh_group_scene_points_mono(vh_group *g, const vh_mono_params *e, const vh_scene_params *sp, const double *Tw, int32_t *counts);
+int32_t vh_match_scene_points_mono(vh_matcher *m, const vh_mono_params *e, const vh_scene_params *sp, const double *Tw, int32_t *count);
+/* The points of the last such call, valid until the next match call (VH_ERR_STATE before one on the current lists),
+ * under the getters' capacity rule: *n is the full number, at most cap records are written, VH_ERR_CAPACITY when there
+ * are more.  The _all form writes stream s at [s * cap_per_stream ..] and counts[S].  _device: the array itself, stream
+ * s at [s * *stride ..] (records). */
+int32_t vh_group_get_scene_points(vh_group *g, int32_t stream, vh_scene_point *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_scene_points_all(vh_group *g, vh_scene_point *out, int32_t cap_per_stream, int32_t *counts);
+int32_t vh_get_scene_points(vh_matcher *m, vh_scene_point *out, int32_t cap, int32_t *n);
+int32_t vh_group_scene_points_device(vh_group *g, const vh_scene_point **d_points, int64_t *stride);
+
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
