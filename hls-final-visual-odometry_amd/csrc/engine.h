@@ -3,7 +3,7 @@
 //   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
-//   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays
+//   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays, the stages' arrays
 //   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
 //   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
@@ -118,6 +118,28 @@ struct DeviceBlock {
     return e;
   }
   template <class T> T *as() const { return (T *)p; }
+};
+// The one device block of a stateless entry.  The entry describes its arrays once, in a function over a Carver (DESIGN.md
+// section 4.0): alloc calls it without a base to measure, allocates, and calls it again to bind the pointers.  The copies
+// are blocking; every member answers with HIP's code, for VH_HIP.
+struct StagedBlock {
+  DeviceBlock blk;
+  template <class F> hipError_t alloc(F &&arrays) {
+    Carver measure;
+    arrays(measure);
+    const hipError_t e = blk.alloc(measure.bytes());
+    if (e != hipSuccess) return e;
+    Carver bind(blk.p);
+    arrays(bind);
+    return hipSuccess;
+  }
+  template <class T> static hipError_t up(T *dev, const T *host, size_t count) { return hipMemcpy(dev, host, sizeof(T) * count, hipMemcpyHostToDevice); }
+  template <class T> static hipError_t down(T *host, const T *dev, size_t count) { return hipMemcpy(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost); }
+  // the records [offsets[0], offsets[n]) to the slots of the same numbers, and the n + 1 offsets
+  static hipError_t up_lists(const PackedArrays &d, const vh_p_match *pm, const int32_t *offsets, const ListSpan &sp, size_t lists) {
+    const hipError_t e = sp.total > 0 ? up(d.d_pm + sp.first, pm + sp.first, (size_t)sp.total) : hipSuccess;
+    return e != hipSuccess ? e : up(d.d_off, offsets, lists + 1);
+  }
 };
 // VhVoteBuffers (vh_vote.h) is released by hand; this one releases itself
 struct VoteBuffers : VhVoteBuffers {
@@ -275,10 +297,7 @@ struct InlierTest {
   bool args_ok() const { return params_ok() && (is_mono ? model != nullptr : tr != nullptr); }
 };
 
-// the launch grid is lists x tiles workgroups of 256 threads
-inline bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
-// vh_launch_mono_pose_stage needs lists * ceil(cap / 64) workgroups in one grid dimension
-inline bool mono_pose_grid_ok(int64_t lists, int64_t cap) { return lists * ((cap + 63) / 64) < ((int64_t)1 << 30); }
+static_assert(kListMax == (int64_t)VH_TRACK_POS_MASK && kInlierTile == VH_INLIER_TILE, "engine_lists.h restates both");
 
 // The lists as the getters return them once a list was replaced on the host (vh_remove_outliers, vh_bucket_features), staged
 // on the device by Group::stage_host_lists: one arena block, allocated by the first need.
@@ -302,29 +321,9 @@ struct InlierState : InlierArrays {      // [S][mcap], [S][tiles], [S], [S][6]
   std::vector<int32_t> n_list, n_inl;     // [S] records classified, inliers
 };
 
-// The motion refined on the compacted inlier lists (vh_group_refit_motion; engine_inlier.hip):
-// one arena block, allocated by the first call -- the kernel joins its partial sums in LDS, so the outputs are all of it.
-struct RefitState {
-  double *d_tr = nullptr;                      // [S][6]
-  int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
-};
-
-// The epipolar model refitted on the compacted inlier lists of a mono classification (vh_group_refit_model_mono;
-// engine_mono_refit.hip): one arena block, allocated by the first call -- the outputs are all of it.
-struct MonoRefitState {
-  vh_mono_model *d_model = nullptr;  // [S]
-  double *d_w = nullptr;             // [S][2]
-  int32_t *d_ok = nullptr;           // [S]
-};
-
 // The mono pose over the compacted inlier lists of a mono classification (vh_group_pose_mono; engine_mono_pose.hip,
 // DESIGN.md section 4.17): one arena block, allocated by the first call.
-struct MonoPoseState {
-  double *d_dist = nullptr, *d_d = nullptr;  // [S][mcap] the points in front: L1 distance (later the vote's sum), ground-plane coordinate
-  double *d_hdr = nullptr;                   // [S][VH_MONO_POSE_HDR]
-  double *d_tr = nullptr;                    // [S][6]
-  vh_mono_pose *d_pose = nullptr;            // [S]
-  int32_t *d_ok = nullptr;                   // [S]
+struct MonoPoseState : MonoPoseArrays {
   vh_mono_refine *d_refine = nullptr;        // [S] a block of its own, allocated by the first vh_group_pose_mono_refined
   // d_pose / d_ok hold the pose of classification `pose_gen` of match call `pose_seq` (Group::scene_points reads them there)
   int64_t pose_seq = -1, pose_gen = -1;
@@ -332,39 +331,22 @@ struct MonoPoseState {
 
 // The 3-d points of the compacted inlier lists (vh_group_scene_points_stereo / _mono; engine_scene.hip, DESIGN.md section
 // 4.20): one arena block, allocated by the first call.
-struct SceneState {
-  vh_scene_point *d_out = nullptr;  // [S][mcap]
-  int32_t *d_tiles = nullptr;       // [S][tiles]
-  double *d_Tw = nullptr;           // [S][16]
-  int32_t *d_n = nullptr;           // [S]
+struct SceneState : SceneArrays {
   int32_t tiles = 0;
   bool valid = false;               // points exist, of the lists of match call `seq`
   int64_t seq = 0;
   std::vector<int32_t> n;           // [S] points per stream
 };
 
-// The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance; engine_cov.hip, DESIGN.md section
-// 4.15): one arena block, allocated by the first call -- the outputs, and the arrays a caller-given tr / ok go up into.
-struct CovState {
-  double *d_cov = nullptr;                     // [S][36]
-  double *d_ssr = nullptr;                     // [S]
-  int32_t *d_ok = nullptr;                     // [S] ok_out
-  double *d_tr = nullptr;                      // [S][6] the caller's motion (the classification's own stays in inl.d_tr)
-  int32_t *d_okin = nullptr;                   // [S]
-};
-
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
 // arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
 // first call that needs it.  Nothing here exists while the switch is off.
-struct GainState {
+struct GainState : GainIndexArrays {  // (the caller's index lists; the block grows)
   uint8_t *d_planes = nullptr;  // [VH_RING][S][H][pitch]: plane (ring slot, row) = left set id >> 1
   int64_t plane = 0;            // bytes per plane: pitch * H
   int32_t pitch = 0;            // W rounded up to 16
   float *d_gain = nullptr;      // [S], and behind it int32 num [S]
   float *d_ratio = nullptr;     // [S][mcap] the ratios over the classification's positions
-  int32_t *d_idx = nullptr;     // the caller's index lists: idx [idx_cap] | ratio [idx_cap] | offsets [S + 1]; grows
-  float *d_idx_ratio = nullptr;
-  int32_t *d_idx_off = nullptr;
   int64_t idx_cap = 0;
   size_t idx_bytes = 0;
   HostLists host;               // what the index lists are positions in, once a list was replaced on the host
@@ -645,6 +627,21 @@ struct Group {
     *out = (T *)q;
     return VH_OK;
   }
+  // One arena block for the arrays of `a` (a struct of engine_lists.h with a carve(Carver &, args...)): measured on a
+  // scratch copy, allocated, bound -- a refused allocation leaves `a` as it was.  tight: the last array as long as it is.
+  template <class A, class... Args> int32_t dmalloc_carved(A &a, size_t *bytes, bool tight, Args... args) {
+    A scratch;
+    Carver measure;
+    scratch.carve(measure, args...);
+    const size_t n = tight ? measure.tight() : measure.bytes();
+    uint8_t *d = nullptr;
+    const int32_t rc = dmalloc(&d, n, false);
+    if (rc) return rc;
+    Carver bind(d);
+    a.carve(bind, args...);
+    if (bytes) *bytes = n;
+    return VH_OK;
+  }
   void dfree(void *q);
   static int32_t block_count(int32_t extent, int32_t n);
   int32_t setup_geometry(const int32_t d[3]);
@@ -697,6 +694,18 @@ struct Group {
 
   // ---- engine_inlier.hip ----
   bool inliers_current() const { return allocated && inl.valid && inl.seq == match_seq; }
+  // the compacted inlier lists of the classification: what every stage behind it reads
+  VhLists inlier_lists() const { return VhLists::slots(inl.d_out, mcap, inl.d_ninl, mcap, S); }
+  // The first min(n, capo) elements of slot s of a device array [S][mcap] into out; queued: on the post stream (the
+  // caller waits for it), else blocking.  over: set where the slot holds more than capo.
+  template <class T> int32_t get_slot(T *out, const T *d, int32_t s, int32_t n, int32_t capo, bool queued, bool &over) {
+    over = over || n > capo;
+    const size_t k = (size_t)std::max(std::min(n, capo), 0);
+    if (!k) return VH_OK;
+    if (queued) VH_HIP(hipMemcpyAsync(out, d + (size_t)s * mcap, sizeof(T) * k, hipMemcpyDeviceToHost, post_stream));
+    else VH_HIP(hipMemcpy(out, d + (size_t)s * mcap, sizeof(T) * k, hipMemcpyDeviceToHost));
+    return VH_OK;
+  }
   int32_t motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts);
   int32_t refit_motion(const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out, int32_t *n_updates, int32_t *counts);
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
@@ -794,6 +803,10 @@ int32_t link_lists_device(int32_t n_lists, const vh_p_match *pm, int64_t stride,
 // engine_inlier.hip
 // The flag pass of either test, then the scan and the scatter, on `st`; g: the handle whose profile takes the scopes (nullable)
 void launch_inliers(const InlierTest &t, VhInlierArgs &a, hipStream_t st, Group *g);
+// engine_mono_pose.hip
+// The six launches of the mono pose on `st`, the refinement between launches 1 and 2 where refined; g: the handle whose
+// profile takes a scope per launch (nullable)
+void launch_mono_pose(const VhMonoPoseArgs &a, bool refined, vh_mono_refine *refine, hipStream_t st, Group *g);
 // engine_post.hip
 // Matcher::bucketFeatures (matcher.cpp:140-187) on the records pm[0, n): the selected records are written to
 // out (at most out_cap of them) in the reference's order; returns how many the reference would keep.

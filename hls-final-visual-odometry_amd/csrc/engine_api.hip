@@ -697,7 +697,7 @@ int32_t vh_estimate_motion_stereo(const vh_ego_params *e, int32_t device, int32_
   return estimate_stateless(device, n_sets, e->ransac_iters, 3, false, pm, offsets, rand3, tr, ok, n_inliers, inliers,
     [&](int64_t cap) { return sizeof(double) * 4 * (size_t)n_sets * (size_t)cap; },  // xyz + flags
     [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl, uint8_t *) {
-      vh_launch_ego(*e, n_sets, d_pm, 0, d_off, nullptr, 0, d_rand, (double *)d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, nullptr);
+      vh_launch_ego(*e, VhLists::packed(d_pm, d_off, n_sets), d_rand, (double *)d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, nullptr);
     });
 }
 
@@ -787,7 +787,7 @@ static int32_t estimate_mono_stateless(const vh_mono_params *e, int32_t device, 
   return estimate_stateless(device, n_sets, e->ransac_iters, 8, unsupported, pm, offsets, rand8, tr, ok, n_inliers, inliers,
     [&](int64_t cap) { return (size_t)vh_mono_scratch_bytes(n_sets, cap, e->ransac_iters); },  // per-list scratch
     [&](const vh_p_match *d_pm, const int32_t *d_off, const int32_t *d_rand, uint8_t *d_scr, int64_t cap, double *d_tr, int32_t *d_ok, int32_t *d_inl, uint8_t *d_model) {
-      vh_launch_mono(*e, n_sets, d_pm, 0, d_off, nullptr, 0, d_rand, d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, (vh_mono_model *)d_model, nullptr);
+      vh_launch_mono(*e, VhLists::packed(d_pm, d_off, n_sets), d_rand, d_scr, cap, d_tr, d_ok, d_ok + n_sets, d_inl, 0, (vh_mono_model *)d_model, nullptr);
     }, model, model ? sizeof(vh_mono_model) * (size_t)std::max(n_sets, 0) : 0);
 }
 int32_t vh_estimate_motion_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm,

@@ -39,26 +39,24 @@ int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float 
   if (by_inliers && !gn.d_ratio && (rc = dmalloc(&gn.d_ratio, (size_t)S * mcap, false))) return rc;
   if (!by_inliers && gn.idx_cap < total) {  // idx | ratio | offsets; grows (the work on the old block has completed: every call waits)
     const int64_t want = total + total / 4;
-    Carver c;
-    const size_t o_idx = c.take<int32_t>((size_t)want), o_ratio = c.take<float>((size_t)want), o_off = c.take<int32_t>((size_t)S + 1);
-    uint8_t *d = nullptr;
-    if ((rc = dmalloc(&d, c.tight(), false))) return rc;
-    if (gn.d_idx) { dfree(gn.d_idx); device_bytes -= (int64_t)gn.idx_bytes; }
-    gn.d_idx = (int32_t *)(d + o_idx); gn.d_idx_ratio = (float *)(d + o_ratio); gn.d_idx_off = (int32_t *)(d + o_off);
-    gn.idx_cap = want; gn.idx_bytes = c.tight();
+    int32_t *const old = gn.d_idx;
+    const size_t old_bytes = gn.idx_bytes;
+    if ((rc = dmalloc_carved(static_cast<GainIndexArrays &>(gn), &gn.idx_bytes, true, (size_t)want, (size_t)S))) return rc;
+    if (old) { dfree(old); device_bytes -= (int64_t)old_bytes; }
+    gn.idx_cap = want;
   }
   hipStream_t ps = post_stream;
   VhGainArgs a{};
-  a.pm = (const vh_p_match *)mt.d_matches; a.pm_stride = mcap; a.counts = mt.d_match_count; a.count_cap = mcap;
+  a.lists = VhLists::slots((const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, S);
   std::vector<int32_t> off;
   if (by_inliers) {
-    if (inl.from_host) { a.pm = inl.host.d_pm; a.counts = inl.host.d_cnt; }  // the lists the classification read
+    if (inl.from_host) { a.lists.pm = inl.host.d_pm; a.lists.counts = inl.host.d_cnt; }  // the lists the classification read
     a.idx = inl.d_src; a.idx_stride = mcap; a.idx_counts = inl.d_ninl; a.idx_cap = mcap;
     a.ok = inl.d_ok;
     a.ratio = gn.d_ratio;
   } else {
     bool replaced = false;  // the getters serve a host-side list for some stream: the positions are positions in that list
-    if ((rc = stage_host_lists(gn.host, ps, replaced, a.pm, a.counts))) return rc;
+    if ((rc = stage_host_lists(gn.host, ps, replaced, a.lists.pm, a.lists.counts))) return rc;
     off.resize((size_t)S + 1);
     for (int32_t s = 0; s <= S; s++) off[s] = idx_offsets[s] - idx_offsets[0];
     VH_HIP(hipMemcpyAsync(gn.d_idx, idx + sp.first, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, ps));
@@ -66,7 +64,7 @@ int32_t Group::gain_lists(const int32_t *idx, const int32_t *idx_offsets, float 
     a.idx = gn.d_idx; a.idx_offsets = gn.d_idx_off;
     a.ratio = gn.d_idx_ratio;
   }
-  a.n_lists = S; a.tiles_per_list = (int32_t)tiles;
+  a.tiles_per_list = (int32_t)tiles;
   a.planes_prev = a.planes_cur = gn.d_planes; a.plane = gn.plane; a.pitch = gn.pitch; a.W = dims[0]; a.H = dims[1];
   a.by_set = 1; a.m = role_args();
   a.gain = gn.d_gain; a.num = (int32_t *)(gn.d_gain + S);
@@ -87,7 +85,7 @@ using namespace vh_engine;
 
 // The stateless gain: validation, one device block (records | offsets | index entries | their offsets | ratios | gain,
 // num | check words | the image planes, repacked to the pitch of a handle's), two launches, one download.
-static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dims, const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride,
+extern "C" int32_t vh_gain(int32_t device, int32_t n_sets, const int32_t *dims, const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride,
                               const vh_p_match *pm, const int32_t *offsets, const int32_t *idx, const int32_t *idx_offsets, float *gain,
                               int32_t *num) {
   if (n_sets < 0) return VH_ERR_INVALID_ARG;
@@ -98,7 +96,7 @@ static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dim
   const int32_t rd = check_dims(dims, true);
   if (rd) return rd;
   if (check_offsets(offsets, n_sets, rec) || check_offsets(idx_offsets, n_sets, pos)) return VH_ERR_INVALID_ARG;
-  const int64_t nmax = rec.longest, kmax = pos.longest, end = rec.end, total = rec.total, k_end = pos.end, k_total = pos.total;
+  const int64_t nmax = rec.longest, kmax = pos.longest, total = rec.total, k_end = pos.end, k_total = pos.total;
   if ((total > 0 && !pm) || (k_total > 0 && (!idx || !I_prev || !I_cur))) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) { gain[s] = 1.0f; num[s] = 0; }
   if (k_total == 0) return VH_OK;  // nothing to do: nothing is launched
@@ -109,39 +107,41 @@ static int32_t gain_stateless(int32_t device, int32_t n_sets, const int32_t *dim
   const size_t lists = (size_t)n_sets;
   const int32_t pitch = round_up(dims[0], 16);
   const size_t plane = (size_t)pitch * dims[1];
-  Carver c;
-  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
-  const size_t o_idx = c.take<int32_t>((size_t)k_end), o_ioff = c.take<int32_t>(lists + 1), o_ratio = c.take<float>((size_t)k_end);
-  const size_t o_gain = c.take<float>(lists), o_num = c.take<int32_t>(lists), o_check = c.take<uint32_t>(64);
-  const size_t o_prev = c.take<uint8_t>(plane * lists), o_cur = c.take<uint8_t>(plane * lists);
-  DeviceBlock blk;
-  VH_HIP(blk.alloc(c.bytes()));
-  uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)rec.first, k_first = (size_t)pos.first;
-  if (total > 0) VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_idx + sizeof(int32_t) * k_first, idx + k_first, sizeof(int32_t) * (size_t)k_total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_ioff, idx_offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
-  VH_HIP(hipMemset(d + o_check, 0, 256));
-  VH_HIP(hipMemset(d + o_prev, 0, c.bytes() - o_prev));  // (the planes' padding columns: read, never summed)
+  PackedArrays in;
+  int32_t *d_idx = nullptr, *d_ioff = nullptr, *d_num = nullptr;
+  float *d_ratio = nullptr, *d_gain = nullptr;
+  uint32_t *d_check = nullptr;
+  uint8_t *d_prev = nullptr, *d_cur = nullptr;
+  StagedBlock blk;
+  VH_HIP(blk.alloc([&](Carver &c) {
+    in.carve(c, rec, lists);
+    d_idx = c.ptr<int32_t>((size_t)k_end); d_ioff = c.ptr<int32_t>(lists + 1); d_ratio = c.ptr<float>((size_t)k_end);
+    d_gain = c.ptr<float>(lists); d_num = c.ptr<int32_t>(lists); d_check = c.ptr<uint32_t>(64);
+    d_prev = c.ptr<uint8_t>(plane * lists); d_cur = c.ptr<uint8_t>(plane * lists);
+  }));
+  VH_HIP(blk.up_lists(in, pm, offsets, rec, lists));  // (the records only where there are some: pm may be null)
+  VH_HIP(blk.up(d_idx + pos.first, idx + pos.first, (size_t)k_total));
+  VH_HIP(blk.up(d_ioff, idx_offsets, lists + 1));
+  VH_HIP(hipMemset(d_check, 0, 256));
+  VH_HIP(hipMemset(d_prev, 0, 2 * up256(plane * lists)));  // (both to the end of the block; the planes' padding columns: read, never summed)
   for (size_t s = 0; s < lists; s++) {
-    VH_HIP(hipMemcpy2D(d + o_prev + s * plane, (size_t)pitch, I_prev + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
-    VH_HIP(hipMemcpy2D(d + o_cur + s * plane, (size_t)pitch, I_cur + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
+    VH_HIP(hipMemcpy2D(d_prev + s * plane, (size_t)pitch, I_prev + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
+    VH_HIP(hipMemcpy2D(d_cur + s * plane, (size_t)pitch, I_cur + s * (size_t)image_stride, (size_t)dims[2], (size_t)dims[0], (size_t)dims[1], hipMemcpyHostToDevice));
   }
   VhGainArgs a{};
-  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
-  a.idx = (const int32_t *)(d + o_idx); a.idx_offsets = (const int32_t *)(d + o_ioff);
-  a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
-  a.planes_prev = d + o_prev; a.planes_cur = d + o_cur; a.plane = (int64_t)plane; a.pitch = pitch; a.W = dims[0]; a.H = dims[1];
-  a.ratio = (float *)(d + o_ratio); a.gain = (float *)(d + o_gain); a.num = (int32_t *)(d + o_num);
-  a.check = (uint32_t *)(d + o_check);
+  a.lists = VhLists::packed(in.d_pm, in.d_off, n_sets);
+  a.idx = d_idx; a.idx_offsets = d_ioff;
+  a.tiles_per_list = (int32_t)tiles;
+  a.planes_prev = d_prev; a.planes_cur = d_cur; a.plane = (int64_t)plane; a.pitch = pitch; a.W = dims[0]; a.H = dims[1];
+  a.ratio = d_ratio; a.gain = d_gain; a.num = d_num;
+  a.check = d_check;
   vh_launch_gain_ratio(a, nullptr);
   vh_launch_gain_sum(a, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
   { const int32_t rv = report_violation(a.check); if (rv) return rv; }
-  VH_HIP(hipMemcpy(gain, a.gain, sizeof(float) * lists, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(num, a.num, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  VH_HIP(blk.down(gain, d_gain, lists));
+  VH_HIP(blk.down(num, d_num, lists));
   return VH_OK;
 }
 
@@ -155,10 +155,6 @@ int32_t vh_group_set_gain(vh_group *g, int32_t on) {
   return VH_OK;
 }
 int32_t vh_set_gain(vh_matcher *m, int32_t on) { return vh_group_set_gain((vh_group *)m, on); }
-int32_t vh_gain(int32_t device, int32_t n_sets, const int32_t dims[3], const uint8_t *I_prev, const uint8_t *I_cur, int64_t image_stride_bytes,
-                const vh_p_match *pm, const int32_t *offsets, const int32_t *idx, const int32_t *idx_offsets, float *gain, int32_t *num) {
-  return gain_stateless(device, n_sets, dims, I_prev, I_cur, image_stride_bytes, pm, offsets, idx, idx_offsets, gain, num);
-}
 int32_t vh_group_gain(vh_group *g, float *gain, int32_t *num) {
   Group *gq = (Group *)g; ENTER(gq);
   return gq->gain_lists(nullptr, nullptr, gain, num);

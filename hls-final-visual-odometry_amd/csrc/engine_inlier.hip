@@ -31,13 +31,11 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
   const int32_t tiles = (mcap + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
   if (!inlier_grid_ok(S, tiles)) return VH_ERR_UNSUPPORTED;
   inl.valid = false;
-  const size_t bytes = InlierArrays().carve(nullptr, (size_t)S, (size_t)S * mcap, (size_t)tiles).bytes();
+  size_t bytes = 0;
   const bool first = !inl.d_flags;
   if (first) {  // one block: a refused allocation leaves nothing behind
-    uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, bytes, false);
+    const int32_t rc = dmalloc_carved(static_cast<InlierArrays &>(inl), &bytes, false, (size_t)S, (size_t)S * mcap, (size_t)tiles);
     if (rc) return rc;
-    inl.carve(d, (size_t)S, (size_t)S * mcap, (size_t)tiles);
     inl.tiles = tiles;
   }
   if (t.is_mono && !inl.d_model) {  // the models of the mono test: a block of their own, so that the stereo path allocates what it always did
@@ -62,8 +60,8 @@ int32_t Group::motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *c
     VH_HIP(hipMemcpyAsync(inl.d_ok, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
   }
   VhInlierArgs a{};
-  a.pm = d_lists; a.pm_stride = mcap; a.counts = d_counts; a.count_cap = mcap;
-  a.n_lists = S; a.tiles_per_list = inl.tiles;
+  a.lists = VhLists::slots(d_lists, mcap, d_counts, mcap, S);
+  a.tiles_per_list = inl.tiles;
   a.tr = t.is_mono ? nullptr : inl.d_tr; a.model = t.is_mono ? inl.d_model : nullptr; a.ok = inl.d_ok; a.out_stride = mcap;
   a.flags = inl.d_flags; a.tile_cnt = inl.d_tiles; a.n_inl = inl.d_ninl; a.out = inl.d_out; a.src_pos = inl.d_src;
   launch_inliers(t, a, post_stream, this);
@@ -90,22 +88,15 @@ int32_t Group::refit_motion(const vh_ego_params *e, int32_t reclassify, double *
   // (a push ends the pair the lists belong to: last_method)
   if (!inliers_current() || inl.mono || last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
   if (!rft.d_tr) {  // one block: a refused allocation leaves nothing behind
-    Carver c;
-    const size_t o_tr = c.take<double>(6 * (size_t)S), o_ok = c.take<int32_t>((size_t)S), o_nupd = c.take<int32_t>((size_t)S);
-    uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, c.bytes(), false);
+    const int32_t rc = dmalloc_carved(rft, nullptr, false, (size_t)S);
     if (rc) return rc;
-    rft.d_tr = (double *)(d + o_tr); rft.d_ok = (int32_t *)(d + o_ok); rft.d_nupd = (int32_t *)(d + o_nupd);
   }
   VhRefitArgs a{};
   a.e = *e;
-  a.pm = inl.d_out; a.pm_stride = mcap; a.counts = inl.d_ninl; a.count_cap = mcap; a.n_lists = S;
+  a.lists = inlier_lists();
   a.tr_in = inl.d_tr; a.ok_in = inl.d_ok;
   a.tr_out = rft.d_tr; a.ok_out = rft.d_ok; a.n_updates = rft.d_nupd;
-  {
-    Scope sc(this, "motion_refit", post_stream);
-    vh_launch_refit(a, post_stream);
-  }
+  { Scope sc(this, "motion_refit", post_stream); vh_launch_refit(a, post_stream); }
   VH_HIP(hipGetLastError());
   // the results come down behind the refit whatever happens to the classification after it
   VH_HIP(hipMemcpyAsync(tr_out, rft.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, post_stream));
@@ -133,9 +124,9 @@ int32_t Group::get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *
   *n = 0;
   if (!inliers_current()) return VH_ERR_STATE;
   *n = inl.n_list[s];
-  const int32_t k = std::min(*n, capo);
-  if (k > 0) VH_HIP(hipMemcpy(out, inl.d_flags + (size_t)s * mcap, (size_t)k, hipMemcpyDeviceToHost));
-  return (*n > capo || inl.truncated) ? VH_ERR_CAPACITY : VH_OK;
+  bool over = inl.truncated;
+  const int32_t rc = get_slot(out, inl.d_flags, s, *n, capo, false, over);
+  return rc ? rc : over ? VH_ERR_CAPACITY : VH_OK;
 }
 
 int32_t Group::get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n) {
@@ -143,12 +134,10 @@ int32_t Group::get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, 
   *n = 0;
   if (!inliers_current()) return VH_ERR_STATE;
   *n = inl.n_inl[s];
-  const int32_t k = std::min(*n, capo);
-  if (k > 0) {
-    VH_HIP(hipMemcpy(out, inl.d_out + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost));
-    if (src_pos) VH_HIP(hipMemcpy(src_pos, inl.d_src + (size_t)s * mcap, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost));
-  }
-  return (*n > capo || inl.truncated) ? VH_ERR_CAPACITY : VH_OK;
+  bool over = inl.truncated;
+  int32_t rc = get_slot(out, inl.d_out, s, *n, capo, false, over);
+  if (!rc && src_pos) rc = get_slot(src_pos, inl.d_src, s, *n, capo, false, over);
+  return rc ? rc : over ? VH_ERR_CAPACITY : VH_OK;
 }
 
 int32_t Group::get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts) {
@@ -158,12 +147,9 @@ int32_t Group::get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t
   bool over = inl.truncated;
   for (int32_t s = 0; s < S; s++) {
     counts[s] = inl.n_inl[s];
-    over = over || counts[s] > cap_per_stream;
-    const int32_t k = std::min(counts[s], cap_per_stream);
-    if (k <= 0) continue;
-    VH_HIP(hipMemcpyAsync(out + (size_t)s * cap_per_stream, inl.d_out + (size_t)s * mcap, sizeof(vh_p_match) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
-    if (src_pos)
-      VH_HIP(hipMemcpyAsync(src_pos + (size_t)s * cap_per_stream, inl.d_src + (size_t)s * mcap, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, post_stream));
+    int32_t rc = get_slot(out + (size_t)s * cap_per_stream, inl.d_out, s, counts[s], cap_per_stream, true, over);
+    if (!rc && src_pos) rc = get_slot(src_pos + (size_t)s * cap_per_stream, inl.d_src, s, counts[s], cap_per_stream, true, over);
+    if (rc) return rc;
   }
   VH_HIP(hipStreamSynchronize(post_stream));
   return over ? VH_ERR_CAPACITY : VH_OK;
@@ -180,103 +166,91 @@ static int32_t inliers_stateless(const InlierTest &t, int32_t device, int32_t n_
   if (!t.params_ok() || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
   ListSpan sp;
-  if (!t.args_ok() || !ok || !n_inliers || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
-  const int64_t nmax = sp.longest, end = sp.end, total = sp.total;
-  if (total > 0 && (!pm || !flags)) return VH_ERR_INVALID_ARG;
+  if (!t.args_ok() || !ok || !n_inliers || packed_args(offsets, n_sets, pm, sp)) return VH_ERR_INVALID_ARG;
+  if (sp.total > 0 && !flags) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) n_inliers[s] = 0;
-  if (total == 0) return VH_OK;
-  const int64_t tiles = (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE;
-  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, tiles)) return VH_ERR_UNSUPPORTED;  // (a list longer than any handle holds)
+  if (sp.total == 0) return VH_OK;
+  if (packed_limit(sp, n_sets)) return VH_ERR_UNSUPPORTED;
   const int32_t rc = select_device(device);
   if (rc) return rc;
+  const size_t lists = (size_t)n_sets, tiles = (size_t)((sp.longest + VH_INLIER_TILE - 1) / VH_INLIER_TILE);
   // one block: the arrays of a classification | the records up to offsets[n_sets] | offsets | (mono) the models
   InlierArrays ia;
-  Carver c = ia.carve(nullptr, (size_t)n_sets, (size_t)end, (size_t)tiles);
-  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>((size_t)n_sets + 1);
-  const size_t o_model = c.take<vh_mono_model>(t.is_mono ? (size_t)n_sets : 0);
-  DeviceBlock blk;
-  VH_HIP(blk.alloc(c.bytes()));
-  uint8_t *d = blk.as<uint8_t>();
-  ia.carve(d, (size_t)n_sets, (size_t)end, (size_t)tiles);
-  const size_t first = (size_t)sp.first;
-  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * ((size_t)n_sets + 1), hipMemcpyHostToDevice));
-  if (t.is_mono) VH_HIP(hipMemcpy(d + o_model, t.model, sizeof(vh_mono_model) * (size_t)n_sets, hipMemcpyHostToDevice));
-  else VH_HIP(hipMemcpy(ia.d_tr, t.tr, sizeof(double) * 6 * (size_t)n_sets, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(ia.d_ok, ok, sizeof(int32_t) * (size_t)n_sets, hipMemcpyHostToDevice));
+  PackedArrays in;
+  vh_mono_model *d_model = nullptr;
+  StagedBlock blk;
+  VH_HIP(blk.alloc([&](Carver &c) {
+    ia.carve(c, lists, (size_t)sp.end, tiles);
+    in.carve(c, sp, lists);
+    d_model = c.ptr<vh_mono_model>(t.is_mono ? lists : 0);
+  }));
+  VH_HIP(blk.up_lists(in, pm, offsets, sp, lists));
+  if (t.is_mono) VH_HIP(blk.up(d_model, t.model, lists));
+  else VH_HIP(blk.up(ia.d_tr, t.tr, 6 * lists));
+  VH_HIP(blk.up(ia.d_ok, ok, lists));
   VhInlierArgs a{};
-  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
-  a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
+  a.lists = VhLists::packed(in.d_pm, in.d_off, n_sets);
+  a.tiles_per_list = (int32_t)tiles;
   a.tr = t.is_mono ? nullptr : ia.d_tr;  // (each flag kernel reads its own of the two)
-  a.model = t.is_mono ? (const vh_mono_model *)(d + o_model) : nullptr;
+  a.model = t.is_mono ? d_model : nullptr;
   a.ok = ia.d_ok;
   a.flags = ia.d_flags; a.out = ia.d_out; a.src_pos = ia.d_src; a.tile_cnt = ia.d_tiles; a.n_inl = ia.d_ninl;
   launch_inliers(t, a, nullptr, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-  VH_HIP(hipMemcpy(n_inliers, a.n_inl, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(flags + first, a.flags + first, (size_t)total, hipMemcpyDeviceToHost));
+  VH_HIP(blk.down(n_inliers, ia.d_ninl, lists));
+  VH_HIP(blk.down(flags + sp.first, ia.d_flags + sp.first, (size_t)sp.total));
   // (the compacted lists: list s's n_inliers[s] records at offsets[s]; what lies behind them in its slice is not written)
   for (int32_t s = 0; s < n_sets && (inlier_pm || src_pos); s++) {
     const size_t o = (size_t)offsets[s], k = (size_t)n_inliers[s];
     if (!k) continue;
-    if (inlier_pm) VH_HIP(hipMemcpy(inlier_pm + o, a.out + o, sizeof(vh_p_match) * k, hipMemcpyDeviceToHost));
-    if (src_pos) VH_HIP(hipMemcpy(src_pos + o, a.src_pos + o, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+    if (inlier_pm) VH_HIP(blk.down(inlier_pm + o, ia.d_out + o, k));
+    if (src_pos) VH_HIP(blk.down(src_pos + o, ia.d_src + o, k));
   }
   return VH_OK;
 }
 
 // The stateless refit: validation as inliers_stateless, one device block (records | offsets | tr, ok in | tr, ok, updates
 // out), one launch.
-static int32_t refit_stateless(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+extern "C" int32_t vh_refit_motion(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
                                const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates) {
   if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
   ListSpan sp;
-  if (!tr_in || !ok_in || !tr_out || !ok_out || !n_updates || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
-  const int64_t nmax = sp.longest, end = sp.end, total = sp.total;
-  if (total > 0 && !pm) return VH_ERR_INVALID_ARG;
+  if (!tr_in || !ok_in || !tr_out || !ok_out || !n_updates || packed_args(offsets, n_sets, pm, sp)) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) {
     ok_out[s] = 0; n_updates[s] = 0;
     for (int32_t m = 0; m < 6; m++) tr_out[6 * (size_t)s + m] = 0;
   }
-  if (total == 0) return VH_OK;
-  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
+  if (sp.total == 0) return VH_OK;
+  if (packed_limit(sp, n_sets)) return VH_ERR_UNSUPPORTED;
   const int32_t rc = select_device(device);
   if (rc) return rc;
   const size_t lists = (size_t)n_sets;
-  Carver c;
-  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
-  const size_t o_tr = c.take<double>(6 * lists), o_ok = c.take<int32_t>(lists);
-  const size_t o_tr2 = c.take<double>(6 * lists), o_ok2 = c.take<int32_t>(lists), o_nupd = c.take<int32_t>(lists);
-  DeviceBlock blk;
-  VH_HIP(blk.alloc(c.bytes()));
-  uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)sp.first;
-  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_tr, tr_in, sizeof(double) * 6 * lists, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_ok, ok_in, sizeof(int32_t) * lists, hipMemcpyHostToDevice));
+  PackedArrays in;
+  double *d_tr = nullptr; int32_t *d_ok = nullptr;
+  RefitState out;
+  StagedBlock blk;
+  VH_HIP(blk.alloc([&](Carver &c) { in.carve(c, sp, lists); d_tr = c.ptr<double>(6 * lists); d_ok = c.ptr<int32_t>(lists); out.carve(c, lists); }));
+  VH_HIP(blk.up_lists(in, pm, offsets, sp, lists));
+  VH_HIP(blk.up(d_tr, tr_in, 6 * lists));
+  VH_HIP(blk.up(d_ok, ok_in, lists));
   VhRefitArgs a{};
   a.e = *e;
-  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off); a.n_lists = n_sets;
-  a.tr_in = (const double *)(d + o_tr); a.ok_in = (const int32_t *)(d + o_ok);
-  a.tr_out = (double *)(d + o_tr2); a.ok_out = (int32_t *)(d + o_ok2); a.n_updates = (int32_t *)(d + o_nupd);
+  a.lists = VhLists::packed(in.d_pm, in.d_off, n_sets);
+  a.tr_in = d_tr; a.ok_in = d_ok;
+  a.tr_out = out.d_tr; a.ok_out = out.d_ok; a.n_updates = out.d_nupd;
   vh_launch_refit(a, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-  VH_HIP(hipMemcpy(tr_out, a.tr_out, sizeof(double) * 6 * lists, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(ok_out, a.ok_out, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(n_updates, a.n_updates, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  VH_HIP(blk.down(tr_out, out.d_tr, 6 * lists));
+  VH_HIP(blk.down(ok_out, out.d_ok, lists));
+  VH_HIP(blk.down(n_updates, out.d_nupd, lists));
   return VH_OK;
 }
 
 extern "C" {
 
-int32_t vh_refit_motion(const vh_ego_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
-                        const double *tr_in, const int32_t *ok_in, double *tr_out, int32_t *ok_out, int32_t *n_updates) {
-  return refit_stateless(e, device, n_sets, pm, offsets, tr_in, ok_in, tr_out, ok_out, n_updates);
-}
 int32_t vh_group_refit_motion(vh_group *g, const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out,
                               int32_t *n_updates, int32_t *counts) {
   Group *gq = (Group *)g; ENTER(gq);

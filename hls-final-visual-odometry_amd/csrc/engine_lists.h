@@ -1,6 +1,7 @@
 // engine_lists.h -- the host plumbing every entry point shares, free of HIP: the checks of caller-owned lists (packed
-// behind offsets, or strided with counts) and of dims, and the carving of one device block into arrays.  Only standard
-// headers and the ABI's codes and records: a plain host compiler builds tests/cpp/engine_lists_check.cpp from it.
+// behind offsets, or strided with counts) and of dims, the carving of one device block into arrays, and the arrays of
+// every whole-list stage's block.  Only standard headers and the ABI's codes and records: a plain
+// host compiler builds tests/cpp/engine_lists_check.cpp from it.
 #ifndef VH_ENGINE_LISTS_H
 #define VH_ENGINE_LISTS_H
 #include "../../include/viso_hip.h"
@@ -24,6 +25,28 @@ inline int32_t check_offsets(const int32_t *offsets, int32_t n, ListSpan &out) {
     out.longest = std::max<int64_t>(out.longest, (int64_t)offsets[s + 1] - offsets[s]);
   }
   out.first = offsets[0]; out.end = offsets[std::max(n, 0)]; out.total = out.end - out.first;
+  return VH_OK;
+}
+
+// What the whole-list kernels are launched under (engine.h asserts that they are vh_dev.h's VH_TRACK_POS_MASK and VH_INLIER_TILE)
+constexpr int64_t kListMax = (1 << 24) - 1;  // the longest list a handle holds
+constexpr int64_t kInlierTile = 1024;
+// the launch grid is lists x tiles workgroups of 256 threads
+inline bool inlier_grid_ok(int64_t lists, int64_t tiles) { return tiles <= 65535 && lists * tiles < ((int64_t)1 << 24); }
+// vh_launch_mono_pose_stage needs lists * ceil(cap / 64) workgroups in one grid dimension
+inline bool mono_pose_grid_ok(int64_t lists, int64_t cap) { return lists * ((cap + 63) / 64) < ((int64_t)1 << 30); }
+
+// The checks every packed-list stateless entry shares, in the two steps its refusals come in.  An entry judges its own
+// pointers beside packed_args, zeroes its outputs and returns VH_OK at total = 0 between the two, and adds its own limit
+// behind packed_limit.
+// 1. VH_ERR_INVALID_ARG: what check_offsets refuses, and lists that hold records without a records pointer
+inline int32_t packed_args(const int32_t *offsets, int32_t n, const void *pm, ListSpan &out) {
+  if (check_offsets(offsets, n, out) || (out.total > 0 && !pm)) return VH_ERR_INVALID_ARG;
+  return VH_OK;
+}
+// 2. VH_ERR_UNSUPPORTED: a list longer than any handle holds, or more classification tiles than one launch grid takes
+inline int32_t packed_limit(const ListSpan &sp, int32_t n) {
+  if (sp.longest > kListMax || !inlier_grid_ok(n, (sp.longest + kInlierTile - 1) / kInlierTile)) return VH_ERR_UNSUPPORTED;
   return VH_OK;
 }
 
@@ -72,14 +95,84 @@ struct InlierArrays {
   int32_t *d_tiles = nullptr;   // [lists][tiles]
   int32_t *d_ninl = nullptr, *d_ok = nullptr;  // [lists]
   double *d_tr = nullptr;       // [lists][6]
-  // -> the carver behind them: bytes() is the block's size, further takes lie behind the arrays
-  Carver carve(void *base, size_t lists, size_t slots, size_t tiles) {
-    Carver c(base);
+  void carve(Carver &c, size_t lists, size_t slots, size_t tiles) {
     d_flags = c.ptr<uint8_t>(slots); d_out = c.ptr<vh_p_match>(slots); d_src = c.ptr<int32_t>(slots);
     d_tiles = c.ptr<int32_t>(lists * tiles); d_ninl = c.ptr<int32_t>(lists); d_ok = c.ptr<int32_t>(lists);
     d_tr = c.ptr<double>(6 * lists);
+  }
+  // ... at the front of a block at `base` -> the carver behind them: bytes() is the block's size, further takes lie behind the arrays
+  Carver carve(void *base, size_t lists, size_t slots, size_t tiles) {
+    Carver c(base);
+    carve(c, lists, slots, tiles);
     return c;
   }
+};
+
+// The records and offsets of a packed-list entry's block: records [offsets[n]] (the slots in front of offsets[0] stay
+// unwritten) | offsets [n + 1]
+struct PackedArrays {
+  vh_p_match *d_pm = nullptr;
+  int32_t *d_off = nullptr;
+  void carve(Carver &c, const ListSpan &sp, size_t lists) { d_pm = c.ptr<vh_p_match>((size_t)sp.end); d_off = c.ptr<int32_t>(lists + 1); }
+};
+
+// ---- the arrays of a handle's first-use blocks, one struct per stage: carve(c, ...) takes them from c in the block's order ----
+// The motion refined on the compacted inlier lists (vh_group_refit_motion): the
+// kernel joins its partial sums in LDS, so the outputs are all of it.
+struct RefitState {
+  double *d_tr = nullptr;                      // [S][6]
+  int32_t *d_ok = nullptr, *d_nupd = nullptr;  // [S]
+  void carve(Carver &c, size_t lists) { d_tr = c.ptr<double>(6 * lists); d_ok = c.ptr<int32_t>(lists); d_nupd = c.ptr<int32_t>(lists); }
+};
+// The covariance of a motion over the compacted inlier lists (vh_group_motion_covariance): the outputs, and the arrays a caller-given tr / ok go up into.
+struct CovState {
+  double *d_cov = nullptr;    // [S][36]
+  double *d_ssr = nullptr;    // [S]
+  int32_t *d_ok = nullptr;    // [S] ok_out
+  double *d_tr = nullptr;     // [S][6] the caller's motion (the classification's own stays in inl.d_tr)
+  int32_t *d_okin = nullptr;  // [S]
+  void carve(Carver &c, size_t lists) {
+    d_cov = c.ptr<double>(36 * lists); d_ssr = c.ptr<double>(lists); d_ok = c.ptr<int32_t>(lists);
+    d_tr = c.ptr<double>(6 * lists); d_okin = c.ptr<int32_t>(lists);
+  }
+};
+// The epipolar model refitted on the compacted inlier lists of a mono classification (vh_group_refit_model_mono, DESIGN.md
+// section 4.16): the outputs are all of it.
+struct MonoRefitState {
+  vh_mono_model *d_model = nullptr;  // [S]
+  double *d_w = nullptr;             // [S][2]
+  int32_t *d_ok = nullptr;           // [S]
+  void carve(Carver &c, size_t lists) { d_model = c.ptr<vh_mono_model>(lists); d_w = c.ptr<double>(2 * lists); d_ok = c.ptr<int32_t>(lists); }
+};
+// The main block of the mono pose (MonoPoseState, engine.h); hdr: doubles per list header (VH_MONO_POSE_HDR)
+struct MonoPoseArrays {
+  double *d_dist = nullptr, *d_d = nullptr;  // [slots] ([S][mcap]) the points in front: L1 distance (later the vote's sum), ground-plane coordinate
+  double *d_hdr = nullptr;                   // [S][hdr]
+  double *d_tr = nullptr;                    // [S][6]
+  vh_mono_pose *d_pose = nullptr;            // [S]
+  int32_t *d_ok = nullptr;                   // [S]
+  void carve(Carver &c, size_t lists, size_t slots, size_t hdr) {
+    d_dist = c.ptr<double>(slots); d_d = c.ptr<double>(slots); d_hdr = c.ptr<double>(lists * hdr);
+    d_tr = c.ptr<double>(6 * lists); d_pose = c.ptr<vh_mono_pose>(lists); d_ok = c.ptr<int32_t>(lists);
+  }
+};
+// The block of the scene points (SceneState, engine.h)
+struct SceneArrays {
+  vh_scene_point *d_out = nullptr;  // [slots] ([S][mcap])
+  int32_t *d_tiles = nullptr;       // [S][tiles]
+  double *d_Tw = nullptr;           // [S][16]
+  int32_t *d_n = nullptr;           // [S]
+  void carve(Carver &c, size_t lists, size_t slots, size_t tiles) {
+    d_out = c.ptr<vh_scene_point>(slots); d_tiles = c.ptr<int32_t>(lists * tiles); d_Tw = c.ptr<double>(16 * lists); d_n = c.ptr<int32_t>(lists);
+  }
+};
+// The caller's index lists of the gain (GainState, engine.h): idx [entries] | ratio [entries] | offsets [S + 1]; the block
+// is as long as tight() says
+struct GainIndexArrays {
+  int32_t *d_idx = nullptr;
+  float *d_idx_ratio = nullptr;
+  int32_t *d_idx_off = nullptr;
+  void carve(Carver &c, size_t entries, size_t lists) { d_idx = c.ptr<int32_t>(entries); d_idx_ratio = c.ptr<float>(entries); d_idx_off = c.ptr<int32_t>(lists + 1); }
 };
 
 }  // namespace vh_engine

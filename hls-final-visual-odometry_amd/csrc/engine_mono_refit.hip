@@ -13,21 +13,14 @@ int32_t Group::refit_model_mono(const vh_mono_params *e, int32_t reclassify, vh_
   // (a push ends the pair the lists belong to: last_method)
   if (!inliers_current() || !inl.mono || !(last_method == VH_METHOD_QUAD || last_method == VH_METHOD_FLOW)) return VH_ERR_STATE;
   if (!mrf.d_model) {  // one block, before any launch: a refused allocation leaves nothing behind
-    Carver c;
-    const size_t o_model = c.take<vh_mono_model>((size_t)S), o_w = c.take<double>(2 * (size_t)S), o_ok = c.take<int32_t>((size_t)S);
-    uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, c.bytes(), false);
+    const int32_t rc = dmalloc_carved(mrf, nullptr, false, (size_t)S);
     if (rc) return rc;
-    mrf.d_model = (vh_mono_model *)(d + o_model); mrf.d_w = (double *)(d + o_w); mrf.d_ok = (int32_t *)(d + o_ok);
   }
   VhMonoRefitArgs a{};
-  a.pm = inl.d_out; a.pm_stride = mcap; a.counts = inl.d_ninl; a.count_cap = mcap; a.n_lists = S;
+  a.lists = inlier_lists();
   a.model_in = inl.d_model; a.ok_in = inl.d_ok;
   a.model_out = mrf.d_model; a.ok_out = mrf.d_ok; a.w_out = mrf.d_w;
-  {
-    Scope sc(this, "mono_refit", post_stream);
-    vh_launch_mono_refit(a, post_stream);
-  }
+  { Scope sc(this, "mono_refit", post_stream); vh_launch_mono_refit(a, post_stream); }
   VH_HIP(hipGetLastError());
   // the results come down behind the refit whatever happens to the classification after it
   VH_HIP(hipMemcpyAsync(model_out, mrf.d_model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
@@ -56,55 +49,48 @@ using namespace vh_engine;
 
 // The stateless form: validation as the stereo refit's, one device block (records | offsets | model, ok in | model, ok, w
 // out), one launch.
-static int32_t mono_refit_stateless(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
+extern "C" int32_t vh_refit_model_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
                                     const vh_mono_model *model_in, const int32_t *ok_in, vh_mono_model *model_out, int32_t *ok_out,
                                     double *w_out) {
   if (!e || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
   ListSpan sp;
-  if (!model_in || !ok_in || !model_out || !ok_out || !w_out || check_offsets(offsets, n_sets, sp)) return VH_ERR_INVALID_ARG;
-  const int64_t nmax = sp.longest, end = sp.end, total = sp.total;
-  if (total > 0 && !pm) return VH_ERR_INVALID_ARG;
+  if (!model_in || !ok_in || !model_out || !ok_out || !w_out || packed_args(offsets, n_sets, pm, sp)) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) {
     ok_out[s] = 0; w_out[2 * (size_t)s] = 0; w_out[2 * (size_t)s + 1] = 0;
     model_out[s] = vh_mono_model{};
   }
-  if (total == 0) return VH_OK;
-  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
+  if (sp.total == 0) return VH_OK;
+  if (packed_limit(sp, n_sets)) return VH_ERR_UNSUPPORTED;
   const int32_t rc = select_device(device);
   if (rc) return rc;
   const size_t lists = (size_t)n_sets;
-  Carver c;
-  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
-  const size_t o_model = c.take<vh_mono_model>(lists), o_ok = c.take<int32_t>(lists);
-  const size_t o_model2 = c.take<vh_mono_model>(lists), o_ok2 = c.take<int32_t>(lists), o_w = c.take<double>(2 * lists);
-  DeviceBlock blk;
-  VH_HIP(blk.alloc(c.bytes()));
-  uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)sp.first;
-  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_model, model_in, sizeof(vh_mono_model) * lists, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_ok, ok_in, sizeof(int32_t) * lists, hipMemcpyHostToDevice));
+  PackedArrays in;
+  vh_mono_model *d_model = nullptr, *d_model_out = nullptr; int32_t *d_ok = nullptr, *d_ok_out = nullptr; double *d_w = nullptr;
+  StagedBlock blk;
+  VH_HIP(blk.alloc([&](Carver &c) {
+    in.carve(c, sp, lists);
+    d_model = c.ptr<vh_mono_model>(lists); d_ok = c.ptr<int32_t>(lists);
+    d_model_out = c.ptr<vh_mono_model>(lists); d_ok_out = c.ptr<int32_t>(lists); d_w = c.ptr<double>(2 * lists);
+  }));
+  VH_HIP(blk.up_lists(in, pm, offsets, sp, lists));
+  VH_HIP(blk.up(d_model, model_in, lists));
+  VH_HIP(blk.up(d_ok, ok_in, lists));
   VhMonoRefitArgs a{};
-  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off); a.n_lists = n_sets;
-  a.model_in = (const vh_mono_model *)(d + o_model); a.ok_in = (const int32_t *)(d + o_ok);
-  a.model_out = (vh_mono_model *)(d + o_model2); a.ok_out = (int32_t *)(d + o_ok2); a.w_out = (double *)(d + o_w);
+  a.lists = VhLists::packed(in.d_pm, in.d_off, n_sets);
+  a.model_in = d_model; a.ok_in = d_ok;
+  a.model_out = d_model_out; a.ok_out = d_ok_out; a.w_out = d_w;
   vh_launch_mono_refit(a, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-  VH_HIP(hipMemcpy(model_out, a.model_out, sizeof(vh_mono_model) * lists, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(ok_out, a.ok_out, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
-  VH_HIP(hipMemcpy(w_out, a.w_out, sizeof(double) * 2 * lists, hipMemcpyDeviceToHost));
+  VH_HIP(blk.down(model_out, d_model_out, lists));
+  VH_HIP(blk.down(ok_out, d_ok_out, lists));
+  VH_HIP(blk.down(w_out, d_w, 2 * lists));
   return VH_OK;
 }
 
 extern "C" {
 
-int32_t vh_refit_model_mono(const vh_mono_params *e, int32_t device, int32_t n_sets, const vh_p_match *pm, const int32_t *offsets,
-                            const vh_mono_model *model_in, const int32_t *ok_in, vh_mono_model *model_out, int32_t *ok_out, double *w_out) {
-  return mono_refit_stateless(e, device, n_sets, pm, offsets, model_in, ok_in, model_out, ok_out, w_out);
-}
 int32_t vh_group_refit_model_mono(vh_group *g, const vh_mono_params *e, int32_t reclassify, vh_mono_model *model_out, int32_t *ok_out,
                                   double *w_out, int32_t *counts) {
   Group *gq = (Group *)g; ENTER(gq);

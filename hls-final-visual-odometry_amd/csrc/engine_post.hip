@@ -229,7 +229,7 @@ int32_t Group::estimate_motion(const vh_ego_params *e, const int32_t *rand3, dou
   VH_HIP(hipMemcpyAsync(ego.d_ego_rand, rand3, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
   {
     Scope sc(this, "ego_kernel", post_stream);
-    vh_launch_ego(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_ego_rand, ego.d_ego_xyz, mcap, ego.d_ego_tr, ego.d_ego_ok,
+    vh_launch_ego(*e, VhLists::slots((const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, S), ego.d_ego_rand, ego.d_ego_xyz, mcap, ego.d_ego_tr, ego.d_ego_ok,
                   ego.d_ego_ok + S, nullptr, 0, post_stream);
   }
   return estimate_results(tr, ok, ninl);
@@ -257,7 +257,7 @@ int32_t Group::estimate_motion_mono(const vh_mono_params *e, const int32_t *rand
   }
   if (model && !ego.d_mono_model && (rc = dmalloc(&ego.d_mono_model, (size_t)S, false))) return rc;
   VH_HIP(hipMemcpyAsync(ego.d_mono_rand, rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, post_stream));
-  vh_launch_mono(*e, S, (const vh_p_match *)mt.d_matches, mcap, nullptr, mt.d_match_count, mcap, ego.d_mono_rand, ego.d_mono_scratch, mcap, ego.d_ego_tr,
+  vh_launch_mono(*e, VhLists::slots((const vh_p_match *)mt.d_matches, mcap, mt.d_match_count, mcap, S), ego.d_mono_rand, ego.d_mono_scratch, mcap, ego.d_ego_tr,
                  ego.d_ego_ok, ego.d_ego_ok + S, nullptr, 0, model ? ego.d_mono_model : nullptr, post_stream);
   if (model) VH_HIP(hipMemcpyAsync(model, ego.d_mono_model, sizeof(vh_mono_model) * (size_t)S, hipMemcpyDeviceToHost, post_stream));  // (estimate_results waits for the stream)
   return estimate_results(tr, ok, ninl);
@@ -362,8 +362,9 @@ int32_t Group::post_finish(int32_t age, int32_t max_features, float bw, float bh
   VH_HIP(hipMemcpyAsync(post.d_bucket, post.h_bucket, sizeof(vh_p_match) * (size_t)S * post.bcap, hipMemcpyHostToDevice, down_stream));
   VH_HIP(hipMemcpyAsync(post.d_bcnt, post.h_bcnt, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, down_stream));
   VH_HIP(hipMemcpyAsync(post.d_post_rand, e ? rand3 : rand8, sizeof(int32_t) * nr, hipMemcpyHostToDevice, down_stream));
-  if (e) vh_launch_ego(*e, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_xyz, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
-  else vh_launch_mono(*mono, S, post.d_bucket, post.bcap, nullptr, post.d_bcnt, post.bcap, post.d_post_rand, post.d_post_mono, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, nullptr, down_stream);
+  const VhLists bucketed = VhLists::slots(post.d_bucket, post.bcap, post.d_bcnt, post.bcap, S);
+  if (e) vh_launch_ego(*e, bucketed, post.d_post_rand, post.d_post_xyz, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, down_stream);
+  else vh_launch_mono(*mono, bucketed, post.d_post_rand, post.d_post_mono, post.bcap, post.d_post_tr, post.d_post_ok, post.d_post_ok + S, nullptr, 0, nullptr, down_stream);
   VH_HIP(hipGetLastError());
   VH_HIP(hipMemcpyAsync(tr, post.d_post_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, down_stream));
   VH_HIP(hipMemcpyAsync(ok, post.d_post_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, down_stream));
@@ -447,6 +448,9 @@ int32_t Group::vote_tail_alloc(VoteBatch &b, int32_t lists, uint32_t mask) {
   return VH_OK;
 }
 
+// the compacted inlier lists of a batch's classification: what the refit and every tail stage read
+static VhLists dense_lists(const VoteDense &q, const VhVote &v) { return VhLists::slots(q.d_out, v.cap, q.d_ninl, v.cap, v.P); }
+
 // The tail stages of batch b, queued behind its dense stages (a: the classification's arguments as they stand, t: its test).
 // Stereo: the covariance over the final inlier lists under the motion they belong to.  Mono: the model refitted on the
 // inliers -> the classification again under it (a pointer switch, as mode 3) -> the pose over the final inlier lists
@@ -454,18 +458,16 @@ int32_t Group::vote_tail_alloc(VoteBatch &b, int32_t lists, uint32_t mask) {
 // are the stateless entries' over the batch's fixed-stride slots; a list the gate closed has no records and ok = 0.
 int32_t Group::vote_tail_launch(VoteBatch &b, const VhVote &v, const InlierTest &t, VhInlierArgs &a, hipStream_t vs) {
   VoteDense &q = b.dn;
+  const VhLists inliers = dense_lists(q, v);
   VoteTail &tl = b.tl;
   const size_t P = (size_t)v.P;
   if (b.tail & VH_POST_TAIL_COV) {
     VhCovArgs c{};
     c.e = b.ego;
-    c.pm = q.d_out; c.pm_stride = v.cap; c.counts = q.d_ninl; c.count_cap = v.cap; c.n_lists = v.P;
+    c.lists = inliers;
     c.tr = b.dense_mode >= 2 ? q.d_tr_refit : b.d_tr; c.ok = b.dense_mode >= 2 ? q.d_ok_refit : q.d_ok;
     c.cov = tl.d.cov; c.ssr = tl.d.ssr; c.ok_out = tl.d.ok_cov;
-    {
-      Scope sc(this, "motion_cov", vs);
-      vh_launch_motion_cov(c, vs);
-    }
+    { Scope sc(this, "motion_cov", vs); vh_launch_motion_cov(c, vs); }
     VH_HIP(hipGetLastError());
     VH_HIP(hipMemcpyAsync(tl.h.cov, tl.d.cov, sizeof(double) * 36 * P, hipMemcpyDeviceToHost, vs));
     VH_HIP(hipMemcpyAsync(tl.h.ssr, tl.d.ssr, sizeof(double) * P, hipMemcpyDeviceToHost, vs));
@@ -473,13 +475,10 @@ int32_t Group::vote_tail_launch(VoteBatch &b, const VhVote &v, const InlierTest 
   }
   if (b.tail & VH_POST_TAIL_MONO_REFIT) {
     VhMonoRefitArgs r{};
-    r.pm = q.d_out; r.pm_stride = v.cap; r.counts = q.d_ninl; r.count_cap = v.cap; r.n_lists = v.P;
+    r.lists = inliers;
     r.model_in = q.d_model; r.ok_in = q.d_ok;
     r.model_out = tl.d.model; r.ok_out = tl.d.ok_model; r.w_out = tl.d.w;
-    {
-      Scope sc(this, "mono_refit", vs);
-      vh_launch_mono_refit(r, vs);
-    }
+    { Scope sc(this, "mono_refit", vs); vh_launch_mono_refit(r, vs); }
     VH_HIP(hipGetLastError());
     a.model = tl.d.model; a.ok = tl.d.ok_model;  // (the estimator's model stays where it is: vh_post_dense::model)
     launch_inliers(t, a, vs, this);
@@ -492,20 +491,11 @@ int32_t Group::vote_tail_launch(VoteBatch &b, const VhVote &v, const InlierTest 
     const bool refined = (b.tail & VH_POST_TAIL_MONO_REFINE) != 0;
     VhMonoPoseArgs m{};
     m.e = b.mono;
-    m.pm = q.d_out; m.pm_stride = v.cap; m.counts = q.d_ninl; m.count_cap = v.cap; m.n_lists = v.P;
+    m.lists = inliers;
     m.cap = v.cap; m.slot_stride = v.cap;
     m.model = a.model; m.ok_in = a.ok;
     m.hdr = tl.d_hdr; m.dist = tl.d_dist; m.d = tl.d_d; m.tr = tl.d.tr; m.ok = tl.d.ok_pose; m.pose = tl.d.pose;
-    for (int32_t k = 0; k < VH_MONO_POSE_STAGES; k++) {
-      {
-        Scope sc(this, vh_mono_pose_scope(k), vs);
-        vh_launch_mono_pose_stage(m, k, vs);
-      }
-      if (refined && k == 1) {  // where Group::pose_mono puts it
-        Scope sr(this, "mono_pose_refine", vs);
-        vh_launch_mono_pose_refine(m, tl.d.refine, vs);
-      }
-    }
+    launch_mono_pose(m, refined, tl.d.refine, vs, this);
     VH_HIP(hipGetLastError());
     VH_HIP(hipMemcpyAsync(tl.h.tr, tl.d.tr, sizeof(double) * 6 * P, hipMemcpyDeviceToHost, vs));
     VH_HIP(hipMemcpyAsync(tl.h.ok_pose, tl.d.ok_pose, sizeof(int32_t) * P, hipMemcpyDeviceToHost, vs));
@@ -548,8 +538,8 @@ int32_t Group::vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs) 
     vh_launch_vote_gate(v, b.d_ok, q.d_cnt, q.d_ok, q.d_voted, vs);
   }
   VhInlierArgs a{};
-  a.pm = v.pm; a.pm_stride = v.cap; a.counts = q.d_cnt; a.count_cap = v.cap;
-  a.n_lists = v.P; a.tiles_per_list = q.tiles;
+  a.lists = VhLists::slots(v.pm, v.cap, q.d_cnt, v.cap, v.P);  // the voted lists, the gate's counts
+  a.tiles_per_list = q.tiles;
   a.tr = b.has_mono ? nullptr : b.d_tr; a.model = b.has_mono ? q.d_model : nullptr; a.ok = q.d_ok; a.out_stride = v.cap;
   a.flags = q.d_flags; a.tile_cnt = q.d_tiles; a.n_inl = q.d_ninl; a.out = q.d_out; a.src_pos = q.d_src;
   const InlierTest t = b.has_mono ? InlierTest::monocular(&b.mono, nullptr) : InlierTest::stereo(&b.ego, nullptr);
@@ -559,13 +549,10 @@ int32_t Group::vote_dense_launch(VoteBatch &b, const VhVote &v, hipStream_t vs) 
   if (b.dense_mode >= 2) {
     VhRefitArgs r{};
     r.e = b.ego;
-    r.pm = q.d_out; r.pm_stride = v.cap; r.counts = q.d_ninl; r.count_cap = v.cap; r.n_lists = v.P;
+    r.lists = dense_lists(q, v);
     r.tr_in = b.d_tr; r.ok_in = q.d_ok;
     r.tr_out = q.d_tr_refit; r.ok_out = q.d_ok_refit; r.n_updates = q.d_nupd;
-    {
-      Scope sc(this, "motion_refit", vs);
-      vh_launch_refit(r, vs);
-    }
+    { Scope sc(this, "motion_refit", vs); vh_launch_refit(r, vs); }
     VH_HIP(hipGetLastError());
     if (b.dense_mode == 3) {  // (a pointer switch: the refit's results stay where they are)
       a.tr = q.d_tr_refit; a.ok = q.d_ok_refit;
@@ -613,8 +600,9 @@ int32_t Group::vote_launch(VoteBatch &b, int32_t index) {
   VH_HIP(hipStreamWaitEvent(vs, b.ev_prep, 0));
   vote_run(v, b.method, vote_lanes, b.max_features, b.bw, b.bh, b.vb, vs);
   VH_HIP(hipGetLastError());
-  if (b.has_ego) vh_launch_ego(b.ego, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
-  else if (b.has_mono) vh_launch_mono(b.mono, v.P, b.vb.out, b.vb.out_cap, nullptr, b.vb.out_count, b.vb.out_cap, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0,
+  const VhLists voted = VhLists::slots(b.vb.out, b.vb.out_cap, b.vb.out_count, b.vb.out_cap, v.P);
+  if (b.has_ego) vh_launch_ego(b.ego, voted, b.d_rand, b.d_xyz, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0, vs);
+  else if (b.has_mono) vh_launch_mono(b.mono, voted, b.d_rand, b.d_mono, b.vb.out_cap, b.d_tr, b.d_ok, b.d_ok + v.P, nullptr, 0,
                                        b.dense_mode ? b.dn.d_model : nullptr, vs);
   VH_HIP(hipGetLastError());
   if (b.dense_mode) { const int32_t rc = vote_dense_launch(b, v, vs); if (rc) return rc; }

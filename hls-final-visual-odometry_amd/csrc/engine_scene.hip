@@ -18,14 +18,8 @@ int32_t Group::scene_points(const vh_ego_params *e, const vh_mono_params *m, con
   if (mono && !(mps.d_pose && mps.pose_seq == match_seq && mps.pose_gen == inl.gen)) return VH_ERR_STATE;
   const int32_t tiles = (mcap + VH_SCENE_TILE - 1) / VH_SCENE_TILE;
   if (!scn.d_out) {  // one block, before any launch: a refused allocation leaves nothing behind
-    Carver c;
-    const size_t o_out = c.take<vh_scene_point>((size_t)S * (size_t)mcap), o_tiles = c.take<int32_t>((size_t)S * (size_t)tiles);
-    const size_t o_Tw = c.take<double>(16 * (size_t)S), o_n = c.take<int32_t>((size_t)S);
-    uint8_t *d = nullptr;
-    const int32_t rc = dmalloc(&d, c.bytes(), false);
+    const int32_t rc = dmalloc_carved(static_cast<SceneArrays &>(scn), nullptr, false, (size_t)S, (size_t)S * mcap, (size_t)tiles);
     if (rc) return rc;
-    scn.d_out = (vh_scene_point *)(d + o_out); scn.d_tiles = (int32_t *)(d + o_tiles);
-    scn.d_Tw = (double *)(d + o_Tw); scn.d_n = (int32_t *)(d + o_n);
     scn.tiles = tiles;
   }
   scn.valid = false;
@@ -34,15 +28,12 @@ int32_t Group::scene_points(const vh_ego_params *e, const vh_mono_params *m, con
   VhSceneArgs a{};
   if (mono) a.m = *m; else a.e = *e;
   a.sp = *sp;
-  a.pm = inl.d_out; a.pm_stride = mcap; a.counts = inl.d_ninl; a.count_cap = mcap;
-  a.n_lists = S; a.tiles_per_list = scn.tiles;
+  a.lists = inlier_lists();
+  a.tiles_per_list = scn.tiles;
   a.tr = mono ? nullptr : inl.d_tr; a.pose = mono ? mps.d_pose : nullptr; a.ok = mono ? mps.d_ok : inl.d_ok;
   a.Tw = Tw ? scn.d_Tw : nullptr; a.src = inl.d_src; a.out_stride = mcap;
   a.tile_cnt = scn.d_tiles; a.n_out = scn.d_n; a.out = scn.d_out;
-  {
-    Scope sc(this, "scene_points", post_stream);
-    vh_launch_scene_points(a, mono, post_stream);
-  }
+  { Scope sc(this, "scene_points", post_stream); vh_launch_scene_points(a, mono, post_stream); }
   VH_HIP(hipGetLastError());
   VH_HIP(hipMemcpyAsync(scn.n.data(), scn.d_n, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   VH_HIP(hipStreamSynchronize(post_stream));
@@ -57,9 +48,9 @@ int32_t Group::get_scene_points(int32_t s, vh_scene_point *out, int32_t capo, in
   *n = 0;
   if (!scene_current()) return VH_ERR_STATE;
   *n = scn.n[s];
-  const int32_t k = std::min(*n, capo);
-  if (k > 0) VH_HIP(hipMemcpy(out, scn.d_out + (size_t)s * mcap, sizeof(vh_scene_point) * (size_t)k, hipMemcpyDeviceToHost));
-  return *n > capo ? VH_ERR_CAPACITY : VH_OK;
+  bool over = false;
+  const int32_t rc = get_slot(out, scn.d_out, s, *n, capo, false, over);
+  return rc ? rc : over ? VH_ERR_CAPACITY : VH_OK;
 }
 
 int32_t Group::get_scene_points_all(vh_scene_point *out, int32_t cap_per_stream, int32_t *counts) {
@@ -69,11 +60,8 @@ int32_t Group::get_scene_points_all(vh_scene_point *out, int32_t cap_per_stream,
   bool over = false;
   for (int32_t s = 0; s < S; s++) {
     counts[s] = scn.n[s];
-    over = over || counts[s] > cap_per_stream;
-    const int32_t k = std::min(counts[s], cap_per_stream);
-    if (k <= 0) continue;
-    VH_HIP(hipMemcpyAsync(out + (size_t)s * cap_per_stream, scn.d_out + (size_t)s * mcap, sizeof(vh_scene_point) * (size_t)k, hipMemcpyDeviceToHost,
-                          post_stream));
+    const int32_t rc = get_slot(out + (size_t)s * cap_per_stream, scn.d_out, s, counts[s], cap_per_stream, true, over);
+    if (rc) return rc;
   }
   VH_HIP(hipStreamSynchronize(post_stream));
   return over ? VH_ERR_CAPACITY : VH_OK;
@@ -92,47 +80,46 @@ static int32_t scene_stateless(const vh_ego_params *e, const vh_mono_params *m, 
   if ((!e && !m) || !scene_params_ok(sp) || n_sets < 0) return VH_ERR_INVALID_ARG;
   if (n_sets == 0) return VH_OK;
   ListSpan span;
-  if (!(mono ? (const void *)pose : (const void *)tr) || !ok || !counts || check_offsets(offsets, n_sets, span)) return VH_ERR_INVALID_ARG;
-  const int64_t nmax = span.longest, end = span.end, total = span.total;
-  if (total > 0 && (!pm || !out)) return VH_ERR_INVALID_ARG;
+  if (!(mono ? (const void *)pose : (const void *)tr) || !ok || !counts || packed_args(offsets, n_sets, pm, span)) return VH_ERR_INVALID_ARG;
+  if (span.total > 0 && !out) return VH_ERR_INVALID_ARG;
   for (int32_t s = 0; s < n_sets; s++) counts[s] = 0;
-  if (total == 0) return VH_OK;
-  if (nmax > (1 << VH_TRACK_POS_BITS) - 1 || !inlier_grid_ok(n_sets, (nmax + VH_INLIER_TILE - 1) / VH_INLIER_TILE)) return VH_ERR_UNSUPPORTED;
-  const int64_t tiles = (nmax + VH_SCENE_TILE - 1) / VH_SCENE_TILE;  // (lists * tiles < 2^26 under the limits above)
+  if (span.total == 0) return VH_OK;
+  if (packed_limit(span, n_sets)) return VH_ERR_UNSUPPORTED;
+  const size_t lists = (size_t)n_sets, tiles = (size_t)((span.longest + VH_SCENE_TILE - 1) / VH_SCENE_TILE);  // (lists * tiles < 2^26 under the limits above)
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  const size_t lists = (size_t)n_sets;
-  Carver c;
-  const size_t o_pm = c.take<vh_p_match>((size_t)end), o_off = c.take<int32_t>(lists + 1);
-  const size_t o_tr = mono ? c.take<vh_mono_pose>(lists) : c.take<double>(6 * lists), o_ok = c.take<int32_t>(lists);
-  const size_t o_Tw = c.take<double>(Tw ? 16 * lists : 0), o_tiles = c.take<int32_t>(lists * (size_t)tiles), o_n = c.take<int32_t>(lists);
-  const size_t o_out = c.take<vh_scene_point>((size_t)end);
-  DeviceBlock blk;
-  VH_HIP(blk.alloc(c.bytes()));
-  uint8_t *d = blk.as<uint8_t>();
-  const size_t first = (size_t)span.first;
-  VH_HIP(hipMemcpy(d + o_pm + sizeof(vh_p_match) * first, pm + first, sizeof(vh_p_match) * (size_t)total, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_off, offsets, sizeof(int32_t) * (lists + 1), hipMemcpyHostToDevice));
-  if (mono) VH_HIP(hipMemcpy(d + o_tr, pose, sizeof(vh_mono_pose) * lists, hipMemcpyHostToDevice));
-  else VH_HIP(hipMemcpy(d + o_tr, tr, sizeof(double) * 6 * lists, hipMemcpyHostToDevice));
-  VH_HIP(hipMemcpy(d + o_ok, ok, sizeof(int32_t) * lists, hipMemcpyHostToDevice));
-  if (Tw) VH_HIP(hipMemcpy(d + o_Tw, Tw, sizeof(double) * 16 * lists, hipMemcpyHostToDevice));
+  PackedArrays in;
+  double *d_tr = nullptr, *d_Tw = nullptr; vh_mono_pose *d_pose = nullptr;
+  int32_t *d_ok = nullptr, *d_tiles = nullptr, *d_n = nullptr;
+  vh_scene_point *d_out = nullptr;
+  StagedBlock blk;
+  VH_HIP(blk.alloc([&](Carver &c) {
+    in.carve(c, span, lists);
+    if (mono) d_pose = c.ptr<vh_mono_pose>(lists); else d_tr = c.ptr<double>(6 * lists);
+    d_ok = c.ptr<int32_t>(lists);
+    d_Tw = c.ptr<double>(Tw ? 16 * lists : 0); d_tiles = c.ptr<int32_t>(lists * tiles); d_n = c.ptr<int32_t>(lists);
+    d_out = c.ptr<vh_scene_point>((size_t)span.end);
+  }));
+  VH_HIP(blk.up_lists(in, pm, offsets, span, lists));
+  if (mono) VH_HIP(blk.up(d_pose, pose, lists));
+  else VH_HIP(blk.up(d_tr, tr, 6 * lists));
+  VH_HIP(blk.up(d_ok, ok, lists));
+  if (Tw) VH_HIP(blk.up(d_Tw, Tw, 16 * lists));
   VhSceneArgs a{};
   if (mono) a.m = *m; else a.e = *e;
   a.sp = *sp;
-  a.pm = (const vh_p_match *)(d + o_pm); a.offsets = (const int32_t *)(d + o_off);
-  a.n_lists = n_sets; a.tiles_per_list = (int32_t)tiles;
-  a.tr = mono ? nullptr : (const double *)(d + o_tr); a.pose = mono ? (const vh_mono_pose *)(d + o_tr) : nullptr;
-  a.ok = (const int32_t *)(d + o_ok); a.Tw = Tw ? (const double *)(d + o_Tw) : nullptr;
-  a.tile_cnt = (int32_t *)(d + o_tiles); a.n_out = (int32_t *)(d + o_n); a.out = (vh_scene_point *)(d + o_out);
+  a.lists = VhLists::packed(in.d_pm, in.d_off, n_sets);
+  a.tiles_per_list = (int32_t)tiles;
+  a.tr = d_tr; a.pose = d_pose; a.ok = d_ok; a.Tw = Tw ? d_Tw : nullptr;
+  a.tile_cnt = d_tiles; a.n_out = d_n; a.out = d_out;
   vh_launch_scene_points(a, mono, nullptr);
   VH_HIP(hipGetLastError());
   VH_HIP(hipDeviceSynchronize());
-  VH_HIP(hipMemcpy(counts, a.n_out, sizeof(int32_t) * lists, hipMemcpyDeviceToHost));
+  VH_HIP(blk.down(counts, d_n, lists));
   // (list s's counts[s] points at offsets[s]; what lies behind them in its slice is not written)
   for (int32_t s = 0; s < n_sets; s++) {
     const size_t o = (size_t)offsets[s], k = (size_t)counts[s];
-    if (k) VH_HIP(hipMemcpy(out + o, a.out + o, sizeof(vh_scene_point) * k, hipMemcpyDeviceToHost));
+    if (k) VH_HIP(blk.down(out + o, d_out + o, k));
   }
   return VH_OK;
 }

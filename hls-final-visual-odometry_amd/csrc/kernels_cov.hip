@@ -39,7 +39,7 @@ motion_cov_kernel(VhCovArgs a) {
   __shared__ double sRot[36];
   __shared__ double sA[36], sB[36];
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   const int32_t n = L.n;
   double *cov = a.cov + 36 * (int64_t)s;
   if (!a.ok[s] || n < 6) {  // (no motion) / the rule of the refit -- tr is not read
@@ -116,7 +116,7 @@ motion_cov_kernel(VhCovArgs a) {
 
 }  // namespace
 
-// grid: a.n_lists workgroups (the caller keeps it below 2^24)
+// grid: a.lists.n_lists workgroups (the caller keeps it below 2^24)
 void vh_launch_motion_cov(const VhCovArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(motion_cov_kernel, dim3(a.n_lists), dim3(COV_T), 0, st, a);
+  hipLaunchKernelGGL(motion_cov_kernel, dim3(a.lists.n_lists), dim3(COV_T), 0, st, a);
 }

@@ -59,7 +59,7 @@ ego_kernel(vh_ego_params e, const vh_p_match *__restrict__ pm_base, int64_t pm_s
   __shared__ int32_t sWave[EGO_T / 64], sFlag, sBase;
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   // matches of this stream: a slice of a concatenated list (offsets) or a fixed-stride slot with a device-side count
-  const VhList L = vh_list(s, pm_base, pm_stride, offsets, counts, count_cap);
+  const VhList L = vh_list(VhLists{pm_base, pm_stride, offsets, counts, count_cap, 0}, s);
   const vh_p_match *pm = L.pm;
   const int32_t n = L.n;
   double *X = xyz + (int64_t)s * xyz_stride * 4, *Y = X + xyz_stride, *Z = Y + xyz_stride, *F = Z + xyz_stride;  // F: inlier flags of the winner
@@ -210,9 +210,9 @@ extern "C" int32_t vh_debug_ego_timing(unsigned long long *out, int32_t reset) {
   return 0;
 }
 
-void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
-                   const int32_t *counts, int32_t count_cap, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr,
-                   int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st) {
-  hipLaunchKernelGGL(ego_kernel, dim3(n_sets), dim3(EGO_T), 0, st, e, pm, pm_stride, offsets, counts, count_cap, rand3, xyz,
+// (the kernel takes the view's fields as loose parameters: as __restrict__ kernel arguments they are what its code was tuned under)
+void vh_launch_ego(const vh_ego_params &e, VhLists l, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr, int32_t *ok,
+                   int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st) {
+  hipLaunchKernelGGL(ego_kernel, dim3(l.n_lists), dim3(EGO_T), 0, st, e, l.pm, l.pm_stride, l.offsets, l.counts, l.count_cap, rand3, xyz,
                      xyz_stride, tr, ok, ninl, inl, inl_stride);
 }

@@ -36,7 +36,7 @@ struct GainList {
   const uint8_t *Ip, *Ic;
 };
 __device__ __forceinline__ GainList gain_list(const VhGainArgs &a, int32_t l) {
-  const VhList L = vh_list(l, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, l);
   GainList r;
   r.pm = L.pm; r.n = L.n;
   const int64_t i0 = a.idx_offsets ? (int64_t)a.idx_offsets[l] : (int64_t)l * a.idx_stride;
@@ -162,11 +162,11 @@ void vh_launch_gain_copy(const uint8_t *src, int64_t stride, int32_t bpl, int32_
 }
 
 void vh_launch_gain_ratio(const VhGainArgs &a, hipStream_t st) {
-  if (a.n_lists <= 0 || a.tiles_per_list <= 0) return;
-  hipLaunchKernelGGL(gain_ratio_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(GAIN_T), 0, st, a);
+  if (a.lists.n_lists <= 0 || a.tiles_per_list <= 0) return;
+  hipLaunchKernelGGL(gain_ratio_kernel, dim3(a.lists.n_lists, a.tiles_per_list), dim3(GAIN_T), 0, st, a);
 }
 
 void vh_launch_gain_sum(const VhGainArgs &a, hipStream_t st) {
-  if (a.n_lists <= 0) return;
-  hipLaunchKernelGGL(gain_sum_kernel, dim3(a.n_lists), dim3(64), 0, st, a);
+  if (a.lists.n_lists <= 0) return;
+  hipLaunchKernelGGL(gain_sum_kernel, dim3(a.lists.n_lists), dim3(64), 0, st, a);
 }

@@ -36,10 +36,10 @@ struct InlList {
   int64_t out0;  // first element of this list in flags / out / src_pos
 };
 __device__ __forceinline__ InlList inl_list(const VhInlierArgs &a, int32_t s) {
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   InlList r;
   r.pm = L.pm; r.n = L.n;
-  r.out0 = a.offsets ? (int64_t)a.offsets[s] : (int64_t)s * a.out_stride;
+  r.out0 = a.lists.offsets ? (int64_t)a.lists.offsets[s] : (int64_t)s * a.out_stride;
   return r;
 }
 
@@ -196,14 +196,14 @@ inlier_compact_kernel(VhInlierArgs a) {
 
 }  // namespace
 
-// grid: a.n_lists x a.tiles_per_list workgroups (the caller keeps the product below 2^24 and tiles_per_list <= 65535)
+// grid: a.lists.n_lists x a.tiles_per_list workgroups (the caller keeps the product below 2^24 and tiles_per_list <= 65535)
 void vh_launch_inlier_flag(const VhInlierArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(inlier_flag_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
+  hipLaunchKernelGGL(inlier_flag_kernel, dim3(a.lists.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
 }
 void vh_launch_inlier_flag_mono(const VhInlierArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(inlier_flag_mono_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
+  hipLaunchKernelGGL(inlier_flag_mono_kernel, dim3(a.lists.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
 }
 void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(inlier_scan_kernel, dim3(a.n_lists), dim3(INL_T), 0, st, a);
-  hipLaunchKernelGGL(inlier_compact_kernel, dim3(a.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
+  hipLaunchKernelGGL(inlier_scan_kernel, dim3(a.lists.n_lists), dim3(INL_T), 0, st, a);
+  hipLaunchKernelGGL(inlier_compact_kernel, dim3(a.lists.n_lists, a.tiles_per_list), dim3(INL_T), 0, st, a);
 }

@@ -196,7 +196,7 @@ __host__ __device__ inline int64_t mono_per_list(int64_t cap) { return (236 * ca
 __device__ __forceinline__ MonoList mono_list(int32_t s, const vh_p_match *pm_base, int64_t pm_stride, const int32_t *offsets,
                                               const int32_t *counts, int32_t count_cap, uint8_t *scratch, int64_t cap) {
   MonoList L;
-  const VhList l = vh_list(s, pm_base, pm_stride, offsets, counts, count_cap);
+  const VhList l = vh_list(VhLists{pm_base, pm_stride, offsets, counts, count_cap, 0}, s);
   L.pm = l.pm;
   L.n = l.n;
   uint8_t *b = scratch + (int64_t)s * mono_per_list(cap);
@@ -972,9 +972,13 @@ int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters)
   return (int64_t)n_sets * mono_per_list(cap) + mono_queue_bytes(n_sets, ransac_iters) + (int64_t)n_sets * ransac_iters * 72;  // lists | queue | F of every hypothesis
 }
 
-void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
-                    const int32_t *counts, int32_t count_cap, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr,
-                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st) {
+// (the kernels take the view's fields as loose parameters: as __restrict__ kernel arguments they are what their code was tuned under)
+void vh_launch_mono(const vh_mono_params &e, VhLists l, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr, int32_t *ok,
+                    int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st) {
+  const int32_t n_sets = l.n_lists, count_cap = l.count_cap;
+  const vh_p_match *pm = l.pm;
+  const int64_t pm_stride = l.pm_stride;
+  const int32_t *offsets = l.offsets, *counts = l.counts;
   hipLaunchKernelGGL(mono_norm_kernel, dim3(n_sets), dim3(MONO_T), 0, st, pm, pm_stride, offsets, counts, count_cap, scratch, cap);
   static const int32_t force_signed = [] { const char *v = getenv("VH_MONO_SIGNED"); return v && atoi(v) ? 1 : 0; }();
   const dim3 hgrid((e.ransac_iters + 127) / 128, n_sets);

@@ -42,10 +42,10 @@ struct MpList {
 };
 __device__ __forceinline__ MpList mp_list(const VhMonoPoseArgs &a, int32_t s) {
   MpList L;
-  L.l = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  L.l = vh_list(a.lists, s);
   L.hdr = a.hdr + (int64_t)s * VH_MONO_POSE_HDR;
   L.ih = (int32_t *)(L.hdr + MP_H_INT);
-  const int64_t base = a.offsets ? (int64_t)a.offsets[s] : (int64_t)s * a.slot_stride;
+  const int64_t base = a.lists.offsets ? (int64_t)a.lists.offsets[s] : (int64_t)s * a.slot_stride;
   L.dist = a.dist + base; L.d = a.d + base;
   return L;
 }
@@ -284,7 +284,7 @@ const char *vh_mono_pose_scope(int32_t k) {
 // workgroups beyond a list's length (rank, vote: beyond its points in front) return at once.
 void vh_launch_mono_pose_stage(const VhMonoPoseArgs &a, int32_t k, hipStream_t st) {
   const int32_t t64 = (int32_t)((a.cap + 63) / 64), t256 = (int32_t)((a.cap + MP_T - 1) / MP_T);
-  const uint32_t lists = (uint32_t)a.n_lists;
+  const uint32_t lists = (uint32_t)a.lists.n_lists;
   switch (k) {
     case 0: hipLaunchKernelGGL(mono_pose_head_kernel, dim3(lists), dim3(64), 0, st, a); break;
     case 1: hipLaunchKernelGGL(mono_pose_tri_kernel, dim3(lists * (uint32_t)t64), dim3(256), 0, st, a, t64); break;

@@ -58,7 +58,7 @@ mono_pose_refine_kernel(VhMonoPoseArgs a, vh_mono_refine *out) {
   __shared__ double sA[25], sB[25];
   __shared__ int32_t sNext;
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   const int32_t n = L.n;
   double *hdr = a.hdr + (int64_t)s * VH_MONO_POSE_HDR;
   const int32_t *ih = (const int32_t *)(hdr + MP_H_INT);
@@ -199,7 +199,7 @@ mono_pose_refine_kernel(VhMonoPoseArgs a, vh_mono_refine *out) {
 
 }  // namespace
 
-// grid: a.n_lists workgroups (the caller keeps it below 2^24)
+// grid: a.lists.n_lists workgroups (the caller keeps it below 2^24)
 void vh_launch_mono_pose_refine(const VhMonoPoseArgs &a, vh_mono_refine *refine, hipStream_t st) {
-  hipLaunchKernelGGL(mono_pose_refine_kernel, dim3(a.n_lists), dim3(MR_T), 0, st, a, refine);
+  hipLaunchKernelGGL(mono_pose_refine_kernel, dim3(a.lists.n_lists), dim3(MR_T), 0, st, a, refine);
 }

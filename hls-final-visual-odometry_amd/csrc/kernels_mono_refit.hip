@@ -32,7 +32,7 @@ __global__ void __launch_bounds__(MRF_T)
 mono_refit_kernel(VhMonoRefitArgs a) {
   __shared__ double sAcc[MRF_W][45];
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   const int32_t n = L.n;
   double *mo = (double *)(a.model_out + s);  // 16 doubles: c[4], s[2], F[9], valid
   if (!a.ok_in[s] || n < 10) {  // (no model to refine) / inliers.size() >= 10, src/viso_mono.cpp:76 -- model_in is not read
@@ -102,7 +102,7 @@ mono_refit_kernel(VhMonoRefitArgs a) {
 
 }  // namespace
 
-// grid: a.n_lists workgroups (the caller keeps it below 2^24)
+// grid: a.lists.n_lists workgroups (the caller keeps it below 2^24)
 void vh_launch_mono_refit(const VhMonoRefitArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(mono_refit_kernel, dim3(a.n_lists), dim3(MRF_T), 0, st, a);
+  hipLaunchKernelGGL(mono_refit_kernel, dim3(a.lists.n_lists), dim3(MRF_T), 0, st, a);
 }

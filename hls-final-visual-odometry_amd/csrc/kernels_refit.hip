@@ -41,7 +41,7 @@ refit_kernel(VhRefitArgs a) {
   __shared__ double sRot[36], sTr[6];
   __shared__ int32_t sFlag;
   const int32_t s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   const int32_t n = L.n;
   if (!a.ok_in[s] || n < 6) {  // (no start to refine) / inliers.size() >= 6, src/viso_stereo.cpp:127 -- tr_in is not read
     if (tid == 0) { a.ok_out[s] = 0; a.n_updates[s] = 0; for (int32_t m = 0; m < 6; m++) a.tr_out[6 * (int64_t)s + m] = 0; }
@@ -117,7 +117,7 @@ refit_kernel(VhRefitArgs a) {
 
 }  // namespace
 
-// grid: a.n_lists workgroups (the caller keeps it below 2^24)
+// grid: a.lists.n_lists workgroups (the caller keeps it below 2^24)
 void vh_launch_refit(const VhRefitArgs &a, hipStream_t st) {
-  hipLaunchKernelGGL(refit_kernel, dim3(a.n_lists), dim3(REFIT_T), 0, st, a);
+  hipLaunchKernelGGL(refit_kernel, dim3(a.lists.n_lists), dim3(REFIT_T), 0, st, a);
 }

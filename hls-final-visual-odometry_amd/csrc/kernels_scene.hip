@@ -37,10 +37,10 @@ struct ScnList {
   int64_t out0;  // first element of this list in out / src
 };
 __device__ __forceinline__ ScnList scn_list(const VhSceneArgs &a, int32_t s) {
-  const VhList L = vh_list(s, a.pm, a.pm_stride, a.offsets, a.counts, a.count_cap);
+  const VhList L = vh_list(a.lists, s);
   ScnList r;
   r.pm = L.pm; r.n = L.n;
-  r.out0 = a.offsets ? (int64_t)a.offsets[s] : (int64_t)s * a.out_stride;
+  r.out0 = a.lists.offsets ? (int64_t)a.lists.offsets[s] : (int64_t)s * a.out_stride;
   return r;
 }
 
@@ -272,10 +272,10 @@ scene_scan_kernel(VhSceneArgs a) {
 // The three launches on one stream.  The caller keeps n_lists * tiles_per_list below 2^30 and tiles_per_list >=
 // ceil(longest list / VH_SCENE_TILE).
 void vh_launch_scene_points(const VhSceneArgs &a, bool mono, hipStream_t st) {
-  const dim3 grid((uint32_t)a.n_lists * (uint32_t)a.tiles_per_list), block(SCN_T);
+  const dim3 grid((uint32_t)a.lists.n_lists * (uint32_t)a.tiles_per_list), block(SCN_T);
   if (mono) hipLaunchKernelGGL(scene_flag_mono_kernel, grid, block, 0, st, a);
   else hipLaunchKernelGGL(scene_flag_stereo_kernel, grid, block, 0, st, a);
-  hipLaunchKernelGGL(scene_scan_kernel, dim3(a.n_lists), block, 0, st, a);
+  hipLaunchKernelGGL(scene_scan_kernel, dim3(a.lists.n_lists), block, 0, st, a);
   if (mono) hipLaunchKernelGGL(scene_store_mono_kernel, grid, block, 0, st, a);
   else hipLaunchKernelGGL(scene_store_stereo_kernel, grid, block, 0, st, a);
 }

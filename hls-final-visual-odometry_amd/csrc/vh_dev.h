@@ -387,35 +387,42 @@ void vh_launch_recon_store(const VhReconGatherArgs &a, hipStream_t st);         
 void vh_launch_recon_tails(const VhReconGatherArgs &a, int32_t append, hipStream_t st);
 void vh_launch_recon_gather(const VhReconGatherArgs &a, hipStream_t st);
 
-// The match list of problem s of an estimator launch (vh_launch_ego, vh_launch_mono): a slice of one concatenated list
-// (offsets, n_sets + 1 entries) or a fixed-stride slot whose count lives on the device (counts, clamped to count_cap).
+// n lists of match records, the one view every whole-list stage and both estimators address their input through
+// (DESIGN.md section 4.0): slices of one concatenated array (offsets, n_lists + 1 entries: `packed`) or fixed-stride slots
+// whose counts live on the device (counts, clamped to count_cap: `slots`).
+struct VhLists {
+  const vh_p_match *pm;
+  int64_t pm_stride;
+  const int32_t *offsets, *counts;
+  int32_t count_cap, n_lists;
+  static VhLists packed(const vh_p_match *pm, const int32_t *offsets, int32_t n) { return VhLists{pm, 0, offsets, nullptr, 0, n}; }
+  static VhLists slots(const vh_p_match *pm, int64_t stride, const int32_t *counts, int32_t cap, int32_t n) {
+    return VhLists{pm, stride, nullptr, counts, cap, n};
+  }
+};
+// list s of them
 struct VhList {
   const vh_p_match *pm;
   int32_t n;
 };
-__device__ __forceinline__ VhList vh_list(int32_t s, const vh_p_match *pm_base, int64_t pm_stride, const int32_t *offsets,
-                                          const int32_t *counts, int32_t count_cap) {
+__device__ __forceinline__ VhList vh_list(const VhLists &l, int32_t s) {
   VhList L;
-  L.pm = offsets ? pm_base + offsets[s] : pm_base + (int64_t)s * pm_stride;
-  L.n = offsets ? offsets[s + 1] - offsets[s] : min(counts[s], count_cap);
+  L.pm = l.offsets ? l.pm + l.offsets[s] : l.pm + (int64_t)s * l.pm_stride;
+  L.n = l.offsets ? l.offsets[s + 1] - l.offsets[s] : min(l.counts[s], l.count_cap);
   return L;
 }
 
 struct vh_ego_params;
-void vh_launch_ego(const vh_ego_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
-                   const int32_t *counts, int32_t count_cap, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr,
-                   int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st);
+void vh_launch_ego(const vh_ego_params &e, VhLists lists, const int32_t *rand3, double *xyz, int64_t xyz_stride, double *tr, int32_t *ok,
+                   int32_t *ninl, int32_t *inl, int64_t inl_stride, hipStream_t st);
 
 // Motion inliers of whole lists (kernels_inlier.hip).  The lists are addressed as vh_list does;
 // flags, out and src_pos of list s begin at offsets[s] (concatenated lists) or at s * out_stride (fixed-stride slots).
 #define VH_INLIER_TILE 1024  // records per workgroup
 struct VhInlierArgs {
   vh_ego_params e;          // f, cu, cv, base, inlier_threshold (ransac_iters and reweighting are not read)
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_INLIER_TILE)
+  VhLists lists;
+  int32_t tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_INLIER_TILE)
   const double *tr;         // [n_lists][6]
   const int32_t *ok;        // [n_lists]; 0: the list has no inliers (tr is not read)
   int64_t out_stride;
@@ -434,17 +441,13 @@ void vh_launch_inlier_compact(const VhInlierArgs &a, hipStream_t st);  // the sc
 
 // The stereo motion refined on whole lists (kernels_refit.hip): the Gauss-Newton loop of
 // src/viso_stereo.cpp:126-139 on every record of each list, one workgroup of VH_REFIT_THREADS lanes per list.  The lists
-// are addressed as vh_list does.
+// are a VhLists.
 #ifndef VH_REFIT_THREADS
 #define VH_REFIT_THREADS 256
 #endif
 struct VhRefitArgs {
   vh_ego_params e;          // f, cu, cv, base, reweighting (ransac_iters and inlier_threshold are not read)
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists;
+  VhLists lists;
   const double *tr_in;      // [n_lists][6] the start; not read where ok_in = 0 or the list has fewer than 6 records
   const int32_t *ok_in;     // [n_lists]
   double *tr_out;           // [n_lists][6]; zero where ok_out = 0
@@ -457,11 +460,7 @@ void vh_launch_refit(const VhRefitArgs &a, hipStream_t st);
 // a fixed tr, sigma^2 (J^T J)^-1, one workgroup of VH_REFIT_THREADS lanes per list.  The lists are addressed as vh_list does.
 struct VhCovArgs {
   vh_ego_params e;          // f, cu, cv, base, reweighting (ransac_iters and inlier_threshold are not read)
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists;
+  VhLists lists;
   const double *tr;         // [n_lists][6]; not read where ok = 0 or the list has fewer than 6 records
   const int32_t *ok;        // [n_lists]
   double *cov;              // [n_lists][36] row-major, exactly symmetric; zero where ok_out = 0
@@ -474,11 +473,7 @@ void vh_launch_motion_cov(const VhCovArgs &a, hipStream_t st);
 // record of a list in the frame of the incoming model, one workgroup of VH_REFIT_THREADS lanes per list.  The lists are
 // addressed as vh_list does.
 struct VhMonoRefitArgs {
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists;
+  VhLists lists;
   const vh_mono_model *model_in;  // [n_lists]; not read where ok_in = 0 or the list has fewer than 10 records
   const int32_t *ok_in;           // [n_lists]
   vh_mono_model *model_out;       // [n_lists]; c, s copied, F refitted, valid = 1; the zero record where ok_out = 0
@@ -505,11 +500,7 @@ void vh_launch_mono_refit(const VhMonoRefitArgs &a, hipStream_t st);
 static_assert(MP_H_INT * 8 + 7 * 4 <= VH_MONO_POSE_HDR * 8, "mono pose header");
 struct VhMonoPoseArgs {
   vh_mono_params e;         // f, cu, cv, height, pitch, motion_threshold (ransac_iters and inlier_threshold are not read)
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists;
+  VhLists lists;
   int64_t cap;              // >= the longest list: the grids of the per-record kernels are sized by it
   int64_t slot_stride;
   const vh_mono_model *model;  // [n_lists]; not read where ok_in = 0
@@ -539,11 +530,8 @@ struct VhSceneArgs {
   vh_ego_params e;          // stereo: f, cu, cv, base
   vh_mono_params m;         // mono: f, cu, cv
   vh_scene_params sp;
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
-  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_SCENE_TILE)
+  VhLists lists;
+  int32_t tiles_per_list;  // tiles_per_list >= ceil(longest list / VH_SCENE_TILE)
   const double *tr;         // stereo: [n_lists][6]; not read where ok = 0
   const vh_mono_pose *pose; // mono: [n_lists]; R, t, scale are read, and not where ok = 0
   const int32_t *ok;        // [n_lists]; 0: the list has no points
@@ -562,16 +550,13 @@ void vh_launch_scene_points(const VhSceneArgs &a, bool mono, hipStream_t st);  /
 // The images are u8 planes of `pitch` bytes per row (a multiple of 4, the base 4-byte aligned), `plane` bytes apart.
 #define VH_GAIN_TILE 256  // index entries per workgroup of gain_ratio
 struct VhGainArgs {
-  const vh_p_match *pm;
-  int64_t pm_stride;
-  const int32_t *offsets, *counts;
-  int32_t count_cap;
+  VhLists lists;
   const int32_t *idx;
   int64_t idx_stride;
   const int32_t *idx_offsets, *idx_counts;
   int32_t idx_cap;
   const int32_t *ok;        // null, or [n_lists]; 0: the list reads as one without index entries
-  int32_t n_lists, tiles_per_list;  // tiles_per_list >= ceil(longest index list / VH_GAIN_TILE)
+  int32_t tiles_per_list;   // tiles_per_list >= ceil(longest index list / VH_GAIN_TILE)
   const uint8_t *planes_prev, *planes_cur;
   int64_t plane;
   int32_t pitch, W, H;
@@ -593,8 +578,7 @@ void vh_launch_gain_sum(const VhGainArgs &a, hipStream_t st);  // behind gain_ra
 struct vh_mono_params;
 int64_t vh_mono_scratch_bytes(int32_t n_sets, int64_t cap, int32_t ransac_iters);
 // model (nullable): [n_sets] the normalisation and the refit F of every list (vh_mono_model), written by mono_final_a
-void vh_launch_mono(const vh_mono_params &e, int32_t n_sets, const vh_p_match *pm, int64_t pm_stride, const int32_t *offsets,
-                    const int32_t *counts, int32_t count_cap, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr,
-                    int32_t *ok, int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st);
+void vh_launch_mono(const vh_mono_params &e, VhLists lists, const int32_t *rand8, uint8_t *scratch, int64_t cap, double *tr, int32_t *ok,
+                    int32_t *ninl, int32_t *inl, int64_t inl_stride, vh_mono_model *model, hipStream_t st);
 
 #endif

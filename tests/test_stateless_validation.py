@@ -148,6 +148,214 @@ def test_refit_motion(env):
     assert call(off=i32(0, POS_MAX + 1, POS_MAX + 1, POS_MAX)) == INVALID
 
 
+# ---- refusal precedence, every packed-list entry ------------------------------------------------------------------------
+# One table over the entries that take n lists packed behind offsets.  Per entry: the arguments behind (device, n_sets, pm,
+# offsets) in the ABI's order, each "in" (a required input), "out" (a required output), "slice" (an output indexed like the
+# records: required only where the lists hold records) or "opt" (an optional output).  Every output starts as bytes of
+# SEVEN; after the call it is "S" (untouched), "Z" (all zero) or, where every record of it holds the same bytes, those as hex.
+PACKED_ENTRIES = {
+    "vh_motion_inliers": ("ego", [], [("tr", "in"), ("ok", "in"), ("flags", "slice"), ("n_inliers", "out"), ("inlier_pm", "opt"), ("src_pos", "opt")]),
+    "vh_motion_inliers_mono": ("mono", [], [("model", "in"), ("ok", "in"), ("flags", "slice"), ("n_inliers", "out"), ("inlier_pm", "opt"), ("src_pos", "opt")]),
+    "vh_refit_motion": ("ego", [], [("tr", "in"), ("ok", "in"), ("tr_out", "out"), ("ok_out", "out"), ("n_updates", "out")]),
+    "vh_motion_covariance": ("ego", [], [("tr", "in"), ("ok", "in"), ("cov", "out"), ("ssr", "out"), ("ok_out", "out")]),
+    "vh_refit_model_mono": ("mono", [], [("model", "in"), ("ok", "in"), ("model_out", "out"), ("ok_out", "out"), ("w_out", "out")]),
+    "vh_pose_mono": ("mono", [], [("model", "in"), ("ok", "in"), ("tr_out", "out"), ("ok_out", "out"), ("pose_out", "opt")]),
+    "vh_pose_mono_refined": ("mono", [], [("model", "in"), ("ok", "in"), ("tr_out", "out"), ("ok_out", "out"), ("pose_out", "opt"), ("refine_out", "opt")]),
+    "vh_scene_points_stereo": ("ego", ["scene"], [("tr", "in"), ("ok", "in"), ("Tw", "opt"), ("points", "slice"), ("counts", "out")]),
+    "vh_scene_points_mono": ("mono", ["scene"], [("pose", "in"), ("ok", "in"), ("Tw", "opt"), ("points", "slice"), ("counts", "out")]),
+}
+PACKED_LISTS = 3
+PACKED_OFFSETS = {"good": (0, 2, 2, 5), "negative": (-1, 2, 2, 5), "decreasing": (0, 3, 2, 5), "empty_behind_3": (3, 3, 3, 3),
+                  "past_limit": (0, POS_MAX + 1, POS_MAX + 1, POS_MAX + 1)}
+# per list / per record of the good offsets' 5 records: bytes of one element, elements
+PACKED_ARRAYS = {"tr": (48, 3), "ok": (4, 3), "model": (128, 3), "pose": (152, 3), "Tw": (128, 3), "flags": (1, 5), "n_inliers": (4, 3),
+                 "inlier_pm": (48, 5), "src_pos": (4, 5), "tr_out": (48, 3), "ok_out": (4, 3), "n_updates": (4, 3), "cov": (288, 3), "ssr": (8, 3),
+                 "model_out": (128, 3), "w_out": (16, 3), "pose_out": (152, 3), "refine_out": (288, 3), "points": (32, 5), "counts": (4, 3)}
+ZERO_POSE = "00" * 120 + "00" * 16 + "ffffffff" + "00000000" + "02000000" + "00000000"   # candidate -1, reason 2: ok_in was set
+ZERO_REFINE = "00" * 280 + "01000000" + "00000000"                                      # status 1
+INV, UNS, OK_ = -1, -5, 0   # VH_ERR_INVALID_ARG, VH_ERR_UNSUPPORTED, VH_OK as the table below spells them: asserted against the package's in the test
+
+
+def packed_rows(name):
+    """(row, n_sets, offsets key or None, arguments passed as null) for every row of the entry"""
+    args = PACKED_ENTRIES[name][2]
+    rows = [("n_negative", -1, "good", ()), ("n_zero_all_null", 0, None, ("pm",) + tuple(a for a, _ in args)), ("offsets_null", 3, None, ()),
+            ("offsets_negative", 3, "negative", ()), ("offsets_decreasing", 3, "decreasing", ()), ("records_null", 3, "good", ("pm",))]
+    rows += [("null_" + a, 3, "good", (a,)) for a, kind in args if kind in ("in", "out", "slice")]
+    rows += [("all_empty", 3, "empty_behind_3", ("pm",) + tuple(a for a, kind in args if kind == "slice")), ("past_limit", 3, "past_limit", ())]
+    return rows
+
+
+def packed_call(env, name, n, off_key, nulls):
+    """-> (code, {output: form}) of one call"""
+    params, extra, args = PACKED_ENTRIES[name]
+    scene = C.create_string_buffer(bytes(24))                       # vh_scene_params: frame 0, no filter
+    bufs = {}
+    for a, kind in args:
+        size, count = PACKED_ARRAYS[a]
+        bufs[a] = np.full(size * count, 0 if kind == "in" or a == "Tw" else SEVEN, np.uint8)
+    bufs["ok"][:] = 1
+    off = None if off_key is None else i32(*PACKED_OFFSETS[off_key])
+    head = [C.byref(getattr(env, params))] + [scene for _ in extra]
+    tail = [None if a in nulls else ptr(bufs[a]) for a, _ in args]
+    code = getattr(env.lib, name)(*head, 0, n, None if "pm" in nulls else ptr(env.pm), ptr(off), *tail)
+    forms = {}
+    for a, kind in args:
+        if kind == "in" or a == "Tw":
+            continue
+        b = bufs[a]
+        rec = b.reshape(PACKED_ARRAYS[a][1], -1)
+        forms[a] = "S" if (b == SEVEN).all() else "Z" if (b == 0).all() else rec[0].tobytes().hex() if (rec == rec[0]).all() else "mixed:" + b.tobytes().hex()
+    return code, forms
+
+
+# entry -> row -> (code, the outputs that are not "S" afterwards): what the entries answered on the commit before they shared
+# their checks, recorded by running this table against that build
+PACKED_OBSERVED = {
+    "vh_motion_inliers": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_tr": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_flags": (-1, {}),
+        "null_n_inliers": (-1, {}),
+        "all_empty": (0, {"n_inliers": "Z"}),
+        "past_limit": (-5, {"n_inliers": "Z"}),
+    },
+    "vh_motion_inliers_mono": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_model": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_flags": (-1, {}),
+        "null_n_inliers": (-1, {}),
+        "all_empty": (0, {"n_inliers": "Z"}),
+        "past_limit": (-5, {"n_inliers": "Z"}),
+    },
+    "vh_refit_motion": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_tr": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_tr_out": (-1, {}),
+        "null_ok_out": (-1, {}),
+        "null_n_updates": (-1, {}),
+        "all_empty": (0, {"tr_out": "Z", "ok_out": "Z", "n_updates": "Z"}),
+        "past_limit": (-5, {"tr_out": "Z", "ok_out": "Z", "n_updates": "Z"}),
+    },
+    "vh_motion_covariance": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_tr": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_cov": (-1, {}),
+        "null_ssr": (-1, {}),
+        "null_ok_out": (-1, {}),
+        "all_empty": (0, {"cov": "Z", "ssr": "Z", "ok_out": "Z"}),
+        "past_limit": (-5, {"cov": "Z", "ssr": "Z", "ok_out": "Z"}),
+    },
+    "vh_refit_model_mono": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_model": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_model_out": (-1, {}),
+        "null_ok_out": (-1, {}),
+        "null_w_out": (-1, {}),
+        "all_empty": (0, {"model_out": "Z", "ok_out": "Z", "w_out": "Z"}),
+        "past_limit": (-5, {"model_out": "Z", "ok_out": "Z", "w_out": "Z"}),
+    },
+    "vh_pose_mono": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_model": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_tr_out": (-1, {}),
+        "null_ok_out": (-1, {}),
+        "all_empty": (0, {"tr_out": "Z", "ok_out": "Z", "pose_out": ZERO_POSE}),
+        "past_limit": (-5, {"tr_out": "Z", "ok_out": "Z", "pose_out": ZERO_POSE}),
+    },
+    "vh_pose_mono_refined": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_model": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_tr_out": (-1, {}),
+        "null_ok_out": (-1, {}),
+        "all_empty": (0, {"tr_out": "Z", "ok_out": "Z", "pose_out": ZERO_POSE, "refine_out": ZERO_REFINE}),
+        "past_limit": (-5, {"tr_out": "Z", "ok_out": "Z", "pose_out": ZERO_POSE, "refine_out": ZERO_REFINE}),
+    },
+    "vh_scene_points_stereo": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_tr": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_points": (-1, {}),
+        "null_counts": (-1, {}),
+        "all_empty": (0, {"counts": "Z"}),
+        "past_limit": (-5, {"counts": "Z"}),
+    },
+    "vh_scene_points_mono": {
+        "n_negative": (-1, {}),
+        "n_zero_all_null": (0, {}),
+        "offsets_null": (-1, {}),
+        "offsets_negative": (-1, {}),
+        "offsets_decreasing": (-1, {}),
+        "records_null": (-1, {}),
+        "null_pose": (-1, {}),
+        "null_ok": (-1, {}),
+        "null_points": (-1, {}),
+        "null_counts": (-1, {}),
+        "all_empty": (0, {"counts": "Z"}),
+        "past_limit": (-5, {"counts": "Z"}),
+    },
+}
+
+
+@pytest.mark.parametrize("name", sorted(PACKED_ENTRIES))
+def test_packed_entries_precedence(name, env):
+    assert (env.INVALID, env.UNSUPPORTED, env.OK) == (INV, UNS, OK_)
+    assert [r[0] for r in packed_rows(name)] == list(PACKED_OBSERVED[name])
+    for row, n, off_key, nulls in packed_rows(name):
+        code, forms = packed_call(env, name, n, off_key, nulls)
+        want_code, want_forms = PACKED_OBSERVED[name][row]
+        print(name, row, code, {a: f[:16] for a, f in forms.items() if f != "S"})
+        assert code == want_code, (name, row)
+        assert {a: f for a, f in forms.items() if f != "S"} == want_forms, (name, row)
+
+
 # ---- the camera gain ---------------------------------------------------------------------------------------------------
 def test_gain(env):
     lib = env.lib
