@@ -96,6 +96,8 @@ ABI_SYMBOLS = (
     "vh_default_scene_params", "vh_scene_points_stereo", "vh_scene_points_mono",
     "vh_group_scene_points_stereo", "vh_match_scene_points_stereo", "vh_group_scene_points_mono", "vh_match_scene_points_mono",
     "vh_group_get_scene_points", "vh_group_get_scene_points_all", "vh_get_scene_points", "vh_group_scene_points_device",
+    "vh_default_landmark_params", "vh_landmarks_update", "vh_group_landmarks", "vh_match_landmarks",
+    "vh_group_get_landmarks", "vh_group_get_landmarks_all", "vh_get_landmarks", "vh_group_landmarks_device",
 )
 
 
@@ -199,6 +201,29 @@ class SceneParams(C.Structure):
     @classmethod
     def default(cls, **kw):
         e = cls(frame=1, min_disp=0.0, max_depth=0.0, max_err=0.0)
+        for k, v in kw.items():
+            if not hasattr(e, k):
+                raise AttributeError(k)
+            setattr(e, k, v)
+        return e
+
+
+# vh_landmark_state (48 bytes): the sums of one track's accepted observations, one per record of a tracked list
+LANDMARK_STATE_DTYPE = np.dtype([("sw", "<f8"), ("swx", "<f8"), ("swy", "<f8"), ("swz", "<f8"), ("n_obs", "<i4"), ("n_missed", "<i4"),
+                                 ("reserved", "<i4", (2,))])
+# vh_landmark (48 bytes): one fused point per track observed in the step (landmarks_update / landmarks)
+LANDMARK_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("sigma", "<f4"), ("n_obs", "<i4"), ("age", "<i4"),
+                           ("birth_frame", "<i8"), ("birth_pos", "<i4"), ("src_pos", "<i4"), ("i1c", "<i4"), ("point_pos", "<i4")])
+
+
+class LandmarkParams(C.Structure):
+    """vh_landmark_params: the fewest observations of an emitted landmark, the longest gap a track's state survives (< 0: any)
+    and the gate T = max_dist + gate_sigma * sigma_z (T <= 0: none)."""
+    _fields_ = [("min_obs", C.c_int32), ("max_missed", C.c_int32), ("max_dist", C.c_double), ("gate_sigma", C.c_double)]
+
+    @classmethod
+    def default(cls, **kw):
+        e = cls(min_obs=2, max_missed=3, max_dist=0.0, gate_sigma=0.0)
         for k, v in kw.items():
             if not hasattr(e, k):
                 raise AttributeError(k)
@@ -413,6 +438,10 @@ def _lib():
             "vh_group_scene_points_mono": [vp, vp, vp, vp, vp], "vh_match_scene_points_mono": [vp, vp, vp, vp, vp],
             "vh_group_get_scene_points": [vp, i32, vp, i32, vp], "vh_group_get_scene_points_all": [vp, vp, i32, vp],
             "vh_get_scene_points": [vp, vp, i32, vp], "vh_group_scene_points_device": [vp, vp, vp],
+            "vh_landmarks_update": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_landmarks": [vp, vp, vp], "vh_match_landmarks": [vp, vp, vp],
+            "vh_group_get_landmarks": [vp, i32, vp, i32, vp], "vh_group_get_landmarks_all": [vp, vp, i32, vp],
+            "vh_get_landmarks": [vp, vp, i32, vp], "vh_group_landmarks_device": [vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -424,6 +453,8 @@ def _lib():
         lib.vh_default_recon_params.restype = None
         lib.vh_default_scene_params.argtypes = [vp]
         lib.vh_default_scene_params.restype = None
+        lib.vh_default_landmark_params.argtypes = [vp]
+        lib.vh_default_landmark_params.restype = None
         lib.vh_reconstruct_last_kernel_ms.argtypes = []
         lib.vh_reconstruct_last_kernel_ms.restype = f64
         lib.vh_group_device_bytes.argtypes = [vp]
@@ -676,6 +707,23 @@ class Matcher:
         out = np.zeros(n.value, SCENE_POINT_DTYPE)
         if n.value:
             _check(_lib().vh_get_scene_points(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_scene_points")
+        return out
+
+    def landmarks(self, params: "LandmarkParams | None" = None) -> np.ndarray:
+        """The scene points of the last scenePoints fused along the feature tracks (vh_match_landmarks; setTrackLinking, and
+        a scenePoints Tw that takes every step's points into one common frame) -> LANDMARK_DTYPE [n], in list order."""
+        lp = params or LandmarkParams.default()
+        n = C.c_int32(0)
+        _check(_lib().vh_match_landmarks(self._h, C.byref(lp), C.byref(n)), "vh_match_landmarks")
+        return self.getLandmarks()
+
+    def getLandmarks(self) -> np.ndarray:
+        """The landmarks of the last landmarks(), valid until the next matchFeatures (vh_get_landmarks)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_get_landmarks(self._h, None, 0, C.byref(n)), "vh_get_landmarks", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, LANDMARK_DTYPE)
+        if n.value:
+            _check(_lib().vh_get_landmarks(self._h, _ptr(out), n.value, C.byref(n)), "vh_get_landmarks")
         return out
 
     def setGain(self, on: bool = True):
@@ -1025,6 +1073,36 @@ class StreamGroup:
         """-> (device address of stream 0's points, stride in records): valid until the next matchFeatures."""
         d = C.c_void_p(); stride = C.c_int64(0)
         _check(_lib().vh_group_scene_points_device(self._h, C.byref(d), C.byref(stride)), "vh_group_scene_points_device")
+        return d.value, stride.value
+
+    def landmarks(self, params: "LandmarkParams | None" = None) -> np.ndarray:
+        """The scene points of the last scenePoints fused along every stream's feature tracks (vh_group_landmarks;
+        setTrackLinking, and a scenePoints Tw that takes every step's points into one common frame) -> counts [S];
+        getLandmarks(stream) / getLandmarksAll / landmarksDevice give the landmarks.  A SequenceGroup: VH_ERR_UNSUPPORTED."""
+        lp = params or LandmarkParams.default()
+        counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_landmarks(self._h, C.byref(lp), _ptr(counts)), "vh_group_landmarks")
+        return counts
+
+    def getLandmarks(self, stream: int) -> np.ndarray:
+        """The stream's landmarks of the last landmarks() in list order, LANDMARK_DTYPE [n] (vh_group_get_landmarks)."""
+        n = C.c_int32(0)
+        _check(_lib().vh_group_get_landmarks(self._h, stream, None, 0, C.byref(n)), "vh_group_get_landmarks", allow=(VH_ERR_CAPACITY,))
+        out = np.zeros(n.value, LANDMARK_DTYPE)
+        if n.value:
+            _check(_lib().vh_group_get_landmarks(self._h, stream, _ptr(out), n.value, C.byref(n)), "vh_group_get_landmarks")
+        return out
+
+    def getLandmarksAll(self, cap_per_stream: int):
+        """-> (landmarks [S, cap_per_stream], counts [S]) (vh_group_get_landmarks_all)."""
+        out = np.zeros((self.S, max(cap_per_stream, 1)), LANDMARK_DTYPE); counts = np.zeros(self.S, np.int32)
+        _check(_lib().vh_group_get_landmarks_all(self._h, _ptr(out), out.shape[1], _ptr(counts)), "vh_group_get_landmarks_all")
+        return out, counts
+
+    def landmarksDevice(self):
+        """-> (device address of stream 0's landmarks, stride in records): valid until the next matchFeatures."""
+        d = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_landmarks_device(self._h, C.byref(d), C.byref(stride)), "vh_group_landmarks_device")
         return d.value, stride.value
 
     def setGain(self, on: bool = True):
@@ -1589,6 +1667,35 @@ def scene_points_mono(mono: MonoParams, match_lists, pose, ok, sp: "SceneParams 
     -> ([SCENE_POINT_DTYPE array per list], counts [n])."""
     pose = np.ascontiguousarray(pose, MONO_POSE_DTYPE).reshape(len(match_lists))
     return _scene_points("vh_scene_points_mono", mono, match_lists, pose, ok, sp, Tw, device)
+
+
+def _packed(arrays, dtype):
+    """a list of arrays -> (their concatenation, offsets [n + 1])"""
+    arrays = [np.ascontiguousarray(a, dtype=dtype).reshape(-1) for a in arrays]
+    offsets = np.zeros(len(arrays) + 1, np.int32)
+    offsets[1:] = np.cumsum([len(a) for a in arrays])
+    return (np.concatenate(arrays) if offsets[-1] else np.zeros(0, dtype)), offsets
+
+
+def landmarks_update(tracks, points, prev_state=None, params: "LandmarkParams | None" = None, device: int = 0):
+    """One step of the landmarks for n independent lists (vh_landmarks_update): `tracks` (TRACK arrays, one per list), `points`
+    (SCENE_POINT_DTYPE arrays whose src_pos number the records of the same list, strictly increasing, all in one common
+    frame), prev_state (None, or LANDMARK_STATE_DTYPE arrays, one per predecessor list -- what the step before returned).
+    -> ([LANDMARK_DTYPE array per list], [LANDMARK_STATE_DTYPE array per list])."""
+    n = len(tracks)
+    assert len(points) == n and (prev_state is None or len(prev_state) == n)
+    lp = params or LandmarkParams.default()
+    trk, roff = _packed(tracks, TRACK)
+    pts, poff = _packed(points, SCENE_POINT_DTYPE)
+    prev, voff = _packed(prev_state, LANDMARK_STATE_DTYPE) if prev_state is not None else (None, None)
+    total = int(roff[-1])
+    state = np.zeros(max(total, 1), LANDMARK_STATE_DTYPE); out = np.zeros(max(total, 1), LANDMARK_DTYPE)
+    counts = np.zeros(max(n, 1), np.int32)
+    _check(_lib().vh_landmarks_update(C.byref(lp), device, n, _ptr(trk), _ptr(roff), _ptr(pts), _ptr(poff),
+                                      None if prev is None else _ptr(prev), None if voff is None else _ptr(voff),
+                                      _ptr(state), _ptr(out), _ptr(counts)), "vh_landmarks_update")
+    return ([out[int(roff[s]):int(roff[s]) + int(counts[s])].copy() for s in range(n)],
+            [state[int(roff[s]):int(roff[s + 1])].copy() for s in range(n)])
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):

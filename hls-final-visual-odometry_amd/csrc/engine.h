@@ -8,6 +8,7 @@
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
 //   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
 //   engine_scene.hip  the 3-d points of whole lists (kernels_scene.hip) and their part of the ABI
+//   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip) and their part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -338,6 +339,16 @@ struct SceneState : SceneArrays {
   std::vector<int32_t> n;           // [S] points per stream
 };
 
+// The landmarks of the current tracked lists (vh_group_landmarks; engine_landmark.hip): one arena
+// block, allocated by the first call.  State buffer b belongs to track buffer b (Group::trk_cur).
+struct LandmarkState : LandmarkArrays {
+  int32_t tiles = 0;
+  bool valid = false;               // landmarks exist, of the lists of match call `seq`
+  int64_t seq = 0;
+  int64_t state_seq[2] = {-1, -1};  // the match call whose tracked list each state buffer was computed for (-1: none)
+  std::vector<int32_t> n;           // [S] landmarks per stream
+};
+
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
 // arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
 // first call that needs it.  Nothing here exists while the switch is off.
@@ -544,6 +555,7 @@ struct Group {
   bool trk_pred_valid = false;  // group: the other buffer holds the predecessors; sequence: the carry slot is valid
   int32_t trk_carry_src = -1;   // sequence: row to copy into the carry before the next bids (-1: none)
   int64_t trk_serial = 0;       // group: serial of the current frame
+  int64_t trk_fill_seq[2] = {-1, -1};  // group: the match call (match_seq) that filled each track buffer; Group::landmarks compares it with LandmarkState::state_seq
 
   // streams whose current matches were post-processed on the host
   // (vh_remove_outliers / vh_bucket_features): served from here until the next step
@@ -589,6 +601,7 @@ struct Group {
   MonoRefitState mrf;
   MonoPoseState mps;
   SceneState scn;
+  LandmarkState lmk;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -675,7 +688,7 @@ struct Group {
   int32_t trk_slots() const { return seq ? S + 1 : 2 * S; }
   // no list is tracked any more (the tables were cleared, or are about to be)
   void trk_reset_lists() { trk_epoch = trk_cur_epoch = trk_pred_epoch = 0; trk_cur_valid = trk_pred_valid = false; trk_carry_src = -1; }
-  void trk_reset() { trk_reset_lists(); trk_cur = 0; trk_serial = 0; }  // ... and the sequence starts again (new dims)
+  void trk_reset() { trk_reset_lists(); trk_cur = 0; trk_serial = 0; trk_fill_seq[0] = trk_fill_seq[1] = -1; }  // ... and the sequence starts again (new dims)
   void trk_pushed(bool shifted, bool first, int32_t prev_chunk_rows);
   int32_t trk_ensure();
   VhTrackArgs trk_args(int32_t rows) const;
@@ -729,6 +742,12 @@ struct Group {
   bool scene_current() const { return allocated && scn.valid && scn.seq == match_seq; }
   int32_t get_scene_points(int32_t s, vh_scene_point *out, int32_t capo, int32_t *n);
   int32_t get_scene_points_all(vh_scene_point *out, int32_t cap_per_stream, int32_t *counts);
+
+  // ---- engine_landmark.hip ----
+  int32_t landmarks(const vh_landmark_params *lp, int32_t *counts);
+  bool landmarks_current() const { return allocated && lmk.valid && lmk.seq == match_seq; }
+  int32_t get_landmarks(int32_t s, vh_landmark *out, int32_t capo, int32_t *n);
+  int32_t get_landmarks_all(vh_landmark *out, int32_t cap_per_stream, int32_t *counts);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

@@ -166,6 +166,18 @@ struct SceneArrays {
     d_out = c.ptr<vh_scene_point>(slots); d_tiles = c.ptr<int32_t>(lists * tiles); d_Tw = c.ptr<double>(16 * lists); d_n = c.ptr<int32_t>(lists);
   }
 };
+// The block of the landmarks (LandmarkState, engine.h): two state buffers, as the track records have two
+struct LandmarkArrays {
+  vh_landmark_state *d_state[2] = {nullptr, nullptr};  // [slots] ([S][mcap]) each, indexed by the track buffer
+  vh_landmark *d_out = nullptr;     // [slots]
+  int32_t *d_obs = nullptr;         // [slots]
+  int32_t *d_tiles = nullptr;       // [S][tiles]
+  int32_t *d_n = nullptr;           // [S]
+  void carve(Carver &c, size_t lists, size_t slots, size_t tiles) {
+    d_state[0] = c.ptr<vh_landmark_state>(2 * slots); d_state[1] = d_state[0] ? d_state[0] + slots : nullptr;  // (one array of the five)
+    d_out = c.ptr<vh_landmark>(slots); d_obs = c.ptr<int32_t>(slots); d_tiles = c.ptr<int32_t>(lists * tiles); d_n = c.ptr<int32_t>(lists);
+  }
+};
 // The caller's index lists of the gain (GainState, engine.h): idx [entries] | ratio [entries] | offsets [S + 1]; the block
 // is as long as tight() says
 struct GainIndexArrays {

@@ -381,6 +381,7 @@ int32_t Group::trk_queue(const VhMatchArgs &a, hipStream_t ps) {
   { Scope sc(this, "track_rank", ps); vh_launch_track_rank(t, ps); }
   VH_HIP(hipGetLastError());
   trk_cur_valid = true; trk_cur_epoch = trk_epoch;
+  if (!seq) trk_fill_seq[trk_cur] = match_seq;  // (a state computed for the buffer's earlier list is stale now)
   return VH_OK;
 }
 

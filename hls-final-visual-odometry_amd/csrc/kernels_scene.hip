@@ -275,7 +275,13 @@ void vh_launch_scene_points(const VhSceneArgs &a, bool mono, hipStream_t st) {
   const dim3 grid((uint32_t)a.lists.n_lists * (uint32_t)a.tiles_per_list), block(SCN_T);
   if (mono) hipLaunchKernelGGL(scene_flag_mono_kernel, grid, block, 0, st, a);
   else hipLaunchKernelGGL(scene_flag_stereo_kernel, grid, block, 0, st, a);
-  hipLaunchKernelGGL(scene_scan_kernel, dim3(a.lists.n_lists), block, 0, st, a);
+  vh_launch_scene_scan(a, st);
   if (mono) hipLaunchKernelGGL(scene_store_mono_kernel, grid, block, 0, st, a);
   else hipLaunchKernelGGL(scene_store_stereo_kernel, grid, block, 0, st, a);
+}
+
+// The scan alone, for every stage that compacts tiles of VH_SCENE_TILE records in list order (kernels_landmark.hip): it
+// reads the lists' lengths (never a record), ok, tile_cnt and tiles_per_list, and writes tile_cnt and n_out.
+void vh_launch_scene_scan(const VhSceneArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(scene_scan_kernel, dim3(a.lists.n_lists), dim3(SCN_T), 0, st, a);
 }

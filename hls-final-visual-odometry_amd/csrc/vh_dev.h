@@ -543,6 +543,35 @@ struct VhSceneArgs {
   vh_scene_point *out;      // the points in list order
 };
 void vh_launch_scene_points(const VhSceneArgs &a, bool mono, hipStream_t st);  // flag, scan, store
+void vh_launch_scene_scan(const VhSceneArgs &a, hipStream_t st);                // the scan alone: lists (lengths only), ok, tile_cnt, n_out
+
+// Landmarks: the scene points of a step fused along the feature tracks (kernels_landmark.hip).
+// Three families of lists, each either slices of one concatenated array (offsets, n_lists + 1 entries) or fixed-stride
+// slots whose counts live on the device (counts, clamped to the stride): the records (trk, and state_out / out / obs
+// indexed like it), their scene points, and the predecessor lists' states (prev null: no list has a predecessor).
+struct VhLandmarkArgs {
+  vh_landmark_params lp;
+  int32_t n_lists;
+  int32_t tiles_per_list;          // >= ceil(longest record list / VH_SCENE_TILE)
+  const vh_track *trk;
+  const int32_t *rec_offsets, *rec_counts;
+  int64_t rec_stride;
+  const vh_scene_point *pts;
+  const int32_t *pt_offsets, *pt_counts;
+  int64_t pt_stride;
+  const int32_t *ok;               // [n_lists] the scan's ok: non-zero where the list has points (0: count 0, its tile counts are not read)
+  const vh_landmark_state *prev;
+  const int32_t *prev_offsets, *prev_counts;
+  int64_t prev_stride;
+  vh_landmark_state *state_out;
+  vh_landmark *out;                // list s compacted at its first record's position
+  int32_t *obs;                    // per record: the position of its scene point, -1: none; after landmark_fuse: of the emitted ones only
+  int32_t *tile_cnt;               // [n_lists][tiles_per_list] emitted per tile, then (after the scan) emitted before the tile
+  int32_t *n_out;                  // [n_lists]
+};
+// the memset of obs, then index, fuse, scan, store on one stream; obs_elems: the elements of obs the lists span.
+// The caller keeps n_lists * tiles_per_list below 2^30.  -> the memset's code
+hipError_t vh_launch_landmarks(const VhLandmarkArgs &a, int64_t obs_elems, hipStream_t st);
 
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride

@@ -1116,6 +1116,92 @@ int32_t vh_group_get_scene_points_all(vh_group *g, vh_scene_point *out, int32_t 
 int32_t vh_get_scene_points(vh_matcher *m, vh_scene_point *out, int32_t cap, int32_t *n);
 int32_t vh_group_scene_points_device(vh_group *g, const vh_scene_point **d_points, int64_t *stride);
 
+/* ---- landmarks: the scene points of a step fused along the feature tracks (csrc/kernels_landmark.hip) ----
+ * One landmark per live track that was observed in this step: its position averaged, weighted by 1 / sigma_z^2, over
+ * every step that saw it, with the uncertainty of that mean and the number of observations.  The join of vh_track
+ * (prev: the record continued in the predecessor list) and vh_scene_point (src_pos: the record a point belongs to) is a
+ * gather, one lane per record; the per-track state travels from list to list in vh_landmark_state.
+ * THE CALLER'S DUTY: the points of every step must lie in ONE COMMON FRAME -- call vh_group_scene_points_* (or the
+ * stateless forms) with a Tw that takes the camera of sp.frame to the world.  The entries cannot check it: points given
+ * in the moving camera's frame are averaged all the same (or restart at the gate).
+ * Record j of a list, in this order; all arithmetic in double, every product and sum rounded on its own, sums added
+ * left to right:
+ *   1. carry: st = prev_state[trk[j].prev] where a predecessor state exists and 0 <= trk[j].prev < n_prev, else all
+ *      zeros (a prev outside the predecessor list is never dereferenced).
+ *   2. the observation is the scene point k with pts[k].src_pos == j (at most one).  Without one: if st.n_obs > 0 then
+ *      st.n_missed += 1, and if max_missed >= 0 && st.n_missed > max_missed st becomes zeros; nothing is emitted.
+ *   3. with one, (x, y, z, s = sigma_z) widened to double: w = s > 0 ? 1.0 / (s * s) : 1.0 (mono: sigma_z = 0).  The
+ *      gate, only if st.n_obs > 0 and T = max_dist + gate_sigma * s is > 0: dx = x - st.swx / st.sw, likewise dy, dz; if
+ *      dx*dx + dy*dy + dz*dz > T*T, st becomes zeros (the landmark restarts from this observation).  Then st.sw += w;
+ *      st.swx += w*x; st.swy += w*y; st.swz += w*z; st.n_obs += 1; st.n_missed = 0.  If the new sw, swx, swy or swz is
+ *      not finite, st becomes zeros and nothing is emitted.
+ *   4. state_out[j] = st.
+ *   5. the record emits a vh_landmark iff it had an observation and st.n_obs >= min_obs.
+ * Survivors are compacted in list order; the same bytes from run to run, alone or among other lists, and from the
+ * stateless and the handle forms. */
+typedef struct vh_landmark_state {   /* 48 bytes, one per record of a tracked list */
+  double  sw, swx, swy, swz;         /* sum of w, w*x, w*y, w*z over the accepted observations */
+  int32_t n_obs;                     /* accepted observations; 0: no state, every field 0 */
+  int32_t n_missed;                  /* consecutive records of the track without an observation since the last one */
+  int32_t reserved[2];               /* 0 */
+} vh_landmark_state;
+typedef struct vh_landmark {         /* 48 bytes */
+  float   x, y, z;                   /* swx / sw, swy / sw, swz / sw: double quotients, one rounding to float */
+  float   sigma;                     /* sqrt(1.0 / sw) in double, rounded once */
+  int32_t n_obs;
+  int32_t age;                       /* vh_track.age of the record */
+  int64_t birth_frame;               /* the track id, */
+  int32_t birth_pos;                 /*   copied from vh_track */
+  int32_t src_pos;                   /* position of the record in the tracked list */
+  int32_t i1c;                       /* copied from the scene point */
+  int32_t point_pos;                 /* position of this step's scene point in its list */
+} vh_landmark;
+typedef struct vh_landmark_params {
+  int32_t min_obs;                   /* emit only landmarks with n_obs >= min_obs; >= 1 */
+  int32_t max_missed;                /* < 0: a track keeps its state through any gap; else the state is dropped once n_missed > max_missed */
+  double  max_dist;                  /* the gate: T = max_dist + gate_sigma * sigma_z, applied where T > 0; both <= 0: no gate */
+  double  gate_sigma;
+} vh_landmark_params;
+void vh_default_landmark_params(vh_landmark_params *lp);   /* 2, 3, 0, 0 */
+/* Stateless: one step for n_sets independent lists, host pointers.  The three families of lists are laid out and
+ * validated as for vh_motion_inliers / vh_scene_points_* (the same offsets convention and length limits): trk behind
+ * rec_offsets, pts behind pt_offsets (src_pos numbering the records of the same list), prev behind prev_offsets (both
+ * NULL: no list has a predecessor).  state_out and out are indexed like trk: list s's landmarks compacted at
+ * [rec_offsets[s], rec_offsets[s] + counts[s]), the rest of each slice of out not written.
+ * VH_ERR_INVALID_ARG: min_obs < 1; a list whose src_pos values are not strictly increasing and inside [0, n_rec) -- checked
+ * on the host before anything is launched -- or that holds more points than records; only one of prev / prev_offsets given;
+ * null pointers.  n_sets == 0 or no records at all: VH_OK with zero counts, nothing is launched and no device is needed. */
+int32_t vh_landmarks_update(const vh_landmark_params *lp, int32_t device, int32_t n_sets,
+                            const vh_track *trk, const int32_t *rec_offsets,
+                            const vh_scene_point *pts, const int32_t *pt_offsets,
+                            const vh_landmark_state *prev, const int32_t *prev_offsets,
+                            vh_landmark_state *state_out, vh_landmark *out, int32_t *counts);
+/* The same on a handle: the current tracked lists (vh_group_set_track_linking) and the scene points of the last
+ * vh_group_scene_points_* call, both on the device; nothing goes up but the params; counts[S] comes back; synchronous.
+ * The predecessor state is what the last vh_group_landmarks call wrote for the predecessor list as it stands (the list
+ * vh_track.prev indexes): no call for that list, a list matched again after the call, or no predecessor at all, and every
+ * record starts without state (prev = NULL of the stateless form).  A repeated call in one step reads the same
+ * predecessor state and gives the same bytes; after matching the same pair again the next call recomputes the current
+ * state from the predecessor's, which is kept.
+ * VH_ERR_STATE with track linking off, without a tracked list for the current pair (before a match call, after the next
+ * push), without scene points of the current lists, and where the classification read lists replaced on the host
+ * (vh_remove_outliers / vh_bucket_features: their positions are not the tracked list's).  VH_ERR_UNSUPPORTED on a
+ * sequence handle (the predecessor of row r is row r - 1 of the same call: a chain, not a gather).
+ * Plain groups and lone matchers.  The first call adds one block: 2 x 48 bytes of state, 48 bytes of output and 4 bytes
+ * of observation index per record slot (S x max_matches slots), 4 bytes per tile of 256 slots and 4 bytes per stream,
+ * each of the five arrays rounded up to 256 bytes, counted by vh_group_device_bytes; a handle that never calls these
+ * allocates and launches nothing.  A refused allocation is VH_ERR_HIP before any launch and leaves the handle as it was;
+ * the call may be repeated.  Profile scope: "landmarks". */
+int32_t vh_group_landmarks(vh_group *g, const vh_landmark_params *lp, int32_t *counts);
+int32_t vh_match_landmarks(vh_matcher *m, const vh_landmark_params *lp, int32_t *count);
+/* The landmarks of the last such call, valid until the next match call (VH_ERR_STATE before one on the current lists),
+ * under the getters' capacity rule, as vh_group_get_scene_points.  _device: the array itself, stream s at
+ * [s * *stride ..] (records). */
+int32_t vh_group_get_landmarks(vh_group *g, int32_t stream, vh_landmark *out, int32_t cap, int32_t *n);
+int32_t vh_group_get_landmarks_all(vh_group *g, vh_landmark *out, int32_t cap_per_stream, int32_t *counts);
+int32_t vh_get_landmarks(vh_matcher *m, vh_landmark *out, int32_t cap, int32_t *n);
+int32_t vh_group_landmarks_device(vh_group *g, const vh_landmark **d_out, int64_t *stride);
+
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
