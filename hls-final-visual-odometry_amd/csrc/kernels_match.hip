@@ -253,6 +253,8 @@ __device__ __forceinline__ uint64_t tested_key_uniform_query(const uint32_t (&qd
 //             (SAD <= 8160 < 2^13); classes of <= VH_CLASS_POS_MAX features
 //   KEY_64    SAD << 32 | position in 64 bits (compare + two selects per candidate):
 //             any class size -- only images of more than 524 224 NMS blocks can need it
+// rows_tile builds these per candidate; flow_tile builds a chunk-local KEY_HI16 key per candidate in every mode and
+// one key of the class's encoding per query and chunk (see there).
 enum { KEY_HI16 = 0, KEY_W19 = 1, KEY_64 = 2 };
 template <int KM> struct KeyT { typedef uint32_t type; };
 template <> struct KeyT<KEY_64> { typedef uint64_t type; };
@@ -262,6 +264,13 @@ __device__ __forceinline__ typename KeyT<KM>::type sad_key(const uint4 &a0, cons
   const uint32_t sad = sad32(a0, a1, b0, b1, 0);
   if (KM == KEY_W19) return (typename KeyT<KM>::type)((sad << 19) | seed);
   return (typename KeyT<KM>::type)(((uint64_t)sad << 32) | seed);
+}
+// The smallest key that stands for "no candidate": a SAD field of 0xFFFF (0x1FFF in 19-bit keys; no SAD exceeds 8160)
+// over a zero position field.  ~0 is one such key; flow_tile's rejected candidates end as this one plus a position.
+template <int KM>
+__device__ __forceinline__ typename KeyT<KM>::type key_none_floor() {
+  typedef typename KeyT<KM>::type key_t;
+  return KM == KEY_HI16 ? (key_t)0xFFFF0000u : KM == KEY_W19 ? (key_t)0xFFF80000u : (key_t)0x0000FFFF00000000ull;
 }
 __device__ __forceinline__ int32_t key_mode_of(int32_t class_count, int32_t wide_keys) {
   // (+64: the copies past the end of a run carry positions up to 63 past it)
@@ -291,13 +300,13 @@ __device__ __forceinline__ int32_t join_phases(const typename KeyT<KM>::type (&b
       for (int32_t d = 16; d < 64; d <<= 1) k[qi] = min(k[qi], vh_shfl_xor_u64(k[qi], d));
     }
     const uint64_t kk = (threadIdx.x & 32) ? k[1] : k[0];
-    return kk == ~0ull ? -1 : (int32_t)(uint32_t)kk;
+    return kk >= key_none_floor<KEY_64>() ? -1 : (int32_t)(uint32_t)kk;
   }
   const auto h = __builtin_amdgcn_permlane32_swap((uint32_t)best_key[0], (uint32_t)best_key[1], false, false);
   const uint32_t kh = min(h[0], h[1]);
   const auto r = __builtin_amdgcn_permlane16_swap(kh, kh, false, false);
   const uint32_t k = min(r[0], r[1]);
-  return k == 0xFFFFFFFFu ? -1 : (int32_t)(k & (KM == KEY_HI16 ? 0xFFFFu : 0x7FFFFu));
+  return k >= key_none_floor<KM>() ? -1 : (int32_t)(k & (KM == KEY_HI16 ? 0xFFFFu : 0x7FFFFu));
 }
 
 // Second half of the speculative searches.  A query whose winner over the walked region lies
@@ -558,6 +567,8 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
                                           int32_t pbase, uint4 *wD, uint32_t *wU, TileOut<Q> &out) {
   constexpr int L = 64 / P;
   constexpr int TRIP = 2 * P;  // candidates per trip: two steps, joined by one v_min3_u32 per query
+  constexpr int CH = 64 / TRIP;  // trips of a full chunk
+  static_assert(P * (2 * CH - 1) <= 64, "the chunk-local seeds P * k must be inline constants (integers up to 64)");
   const int32_t ph = (threadIdx.x & 63) / L;
   const uint32_t *__restrict__ cuv = s.s_uv + (int64_t)cset * s.cap;
   const uint4 *__restrict__ cdesc = (const uint4 *)(s.s_desc + (int64_t)cset * s.cap * 8);
@@ -577,9 +588,31 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
   }
   const us2 span2 = window_span2(a.radius, rv);
 
-  // best = min over candidates of the key (sad_key): SAD, then bin-order position.
+  // best = min over candidates of the key (SAD, then bin-order position), the encoding KM of sad_key.
+  //
+  // Chunk-local keys.  Inside a chunk [pc, pc + 64) the lanes of phase ph see the slots ph + P * k, k = 0 .. 2 * CH - 1.
+  // The loop does not build the key of a slot with its class-relative position (pc - pbase) + ph + P * k, which cost a
+  // register and an add per step: it builds the LOCAL key SAD << 16 | P * k -- one v_sad_hi_u8 chain seeded with P * k,
+  // a compile-time constant of the unrolled trip and at most 60, so an inline operand -- whatever the encoding KM (a SAD
+  // is below 2^13, so the local key always fits 32 bits).  The lane keeps the minimum of the local keys over the chunk
+  // and turns it into the key of encoding KM ONCE per query and chunk (global_key): SAD field moved to its place, position
+  // field P * k + vbase, vbase = (pc - pbase) + ph.  This is still findMatch's first strict minimum:
+  //  * global_key of a slot's local key IS the key the loop built for that slot before: same SAD, same position (below
+  //    2^16 / 2^19 by key_mode_of, so nothing carries into the SAD field);
+  //  * vbase is the same for every slot a lane sees in a chunk and P * k ascends with the position, so global_key is
+  //    strictly monotone over them: global_key of the minimum local key is the minimum of those slots' global keys;
+  //  * the minimum is associative: the minimum over chunks, phases and lanes of these per-chunk minima is the minimum
+  //    over the very set of keys the loop folded one by one before -- bit for bit, copies included.
+  // The trailing slots of a short chunk hold copies of the column's last candidate, and a copy in slot j gets the
+  // position (pc - pbase) + j, beyond the true one, exactly as before.  Its key never wins: the original sits in slot
+  // mcnt - 1 < j with the same SAD; in the same lane that is a smaller P * k, in another phase it is that lane's global
+  // key at the true, smaller position, and both reach the same final minimum.
+  // A candidate the accept test rejects gets LNONE, an all-ones SAD field over a zero position field: it is above every
+  // real local key, and global_key takes it to key_none_floor or above without wrapping, which join_phases reads as
+  // "none" like the ~0 the minima start from.
   // TEST: 2 = full (u,v) window test, 1 = v only, 0 = none
-  auto make_key = [&](auto test, int32_t qi, uint32_t uv2, const uint4 &b0, const uint4 &b1, uint32_t seed) -> key_t {
+  constexpr uint32_t LNONE = 0xFFFF0000u;
+  auto make_key = [&](auto test, int32_t qi, uint32_t uv2, const uint4 &b0, const uint4 &b1, uint32_t seed) -> uint32_t {
     constexpr int TEST = decltype(test)::value;
     bool out = false;
     if (TEST == 2) {
@@ -587,55 +620,73 @@ __device__ __forceinline__ void flow_tile(const VhSets &s, const VhMatchArgs &a,
     } else if (TEST == 1) {
       out = (uint32_t)((int32_t)(uv2 >> 16) - v_lo[qi]) > (uint32_t)(2 * rv);
     }
-    const key_t key = sad_key<KM>(a0[qi], a1[qi], b0, b1, seed);
-    return (TEST != 0 && out) ? KNONE : key;
+    const uint32_t key = sad_key<KEY_HI16>(a0[qi], a1[qi], b0, b1, seed);
+    return (TEST != 0 && out) ? LNONE : key;
+  };
+  // the key of encoding KM of a local key `k` of a chunk whose slot 0 this lane sees at class-relative position vbase
+  auto global_key = [](uint32_t k, uint32_t vbase) -> key_t {
+    if (KM == KEY_HI16) return (key_t)(k + vbase);
+    const uint32_t pos = (k & 0xFFFFu) + vbase;
+    if (KM == KEY_W19) return (key_t)(((k & 0xFFFF0000u) << 3) | pos);
+    return (key_t)(((uint64_t)(k >> 16) << 32) | pos);
   };
   walk_region_lds<!SPEC>(s, cbs, cuv, cdesc, c, r.UB0, r.UB1, r.VB0, r.VB1, r.ULO_MAX, r.UHI_MIN, r.VA0, r.VA1, wD, wU,
     [&](int32_t pc, int32_t p1, int32_t pa0, int32_t pa1, const uint4 *cD, const uint32_t *cU) {
       VH_STAT(1, 1);
       const int32_t mcnt = min(64, p1 - pc);
-      const int32_t jend = (mcnt + TRIP - 1) & ~(TRIP - 1);  // <= 64: trailing slots hold copies of the last candidate
-      const uint4 *rd = cD + ph;                              // this phase's slot of step 0 (second half: +64)
+      const int32_t nt = (mcnt + TRIP - 1) / TRIP;  // 1..CH trips: trailing slots hold copies of the last candidate
+      const uint4 *rd = cD + ph;                     // this phase's slot of step 0 (second half: +64)
       const uint32_t *ru = cU + ph;
-      uint32_t seedA = (uint32_t)(pc - pbase + ph), seedB = seedA + P;
-      int32_t j = 0;
-      // one trip: candidates (j + ph) and (j + P + ph) at slot offset `o` of this phase's read pointers
-      auto trip = [&](auto test, int32_t o) {
+      uint32_t cm[Q];  // the chunk's minima of the local keys
+      // trip t of the chunk: candidates (TRIP * t + ph) and (TRIP * t + P + ph), steps k = 2t and 2t + 1 of this lane.
+      // Called with t constant (unrolled), so the slots are immediate offsets of the LDS reads and the seeds P * k are
+      // inline constants: no pointer and no seed lives in a register or is advanced inside a chunk.
+      auto trip = [&](auto test, int32_t t) __attribute__((always_inline)) {
+        VH_STAT(2 + decltype(test)::value, 1);
+        const int32_t o = TRIP * t;
         const uint4 dA0 = rd[o], dA1 = rd[o + 64], dB0 = rd[o + P], dB1 = rd[o + 64 + P];
         uint32_t uA = 0, uB = 0;
         if (decltype(test)::value != 0) { uA = ru[o]; uB = ru[o + P]; }
 #pragma unroll
         for (int32_t qi = 0; qi < Q; qi++) {
-          const key_t kA = make_key(test, qi, uA, dA0, dA1, seedA + (uint32_t)o), kB = make_key(test, qi, uB, dB0, dB1, seedB + (uint32_t)o);
-          best_key[qi] = min(min(kA, kB), best_key[qi]);
+          // (slot o + ph is step k = o / P of this lane: the seed P * k is o)
+          const uint32_t kA = make_key(test, qi, uA, dA0, dA1, (uint32_t)o), kB = make_key(test, qi, uB, dB0, dB1, (uint32_t)(o + P));
+          cm[qi] = t == 0 ? min(kA, kB) : min(min(kA, kB), cm[qi]);  // (trip 0 runs in every chunk)
         }
       };
-      auto run = [&](auto test, int32_t jstop) {
-        if (jstop > j) VH_STAT(2 + decltype(test)::value, (jstop - j) / TRIP);
-        // two trips per loop iteration: the pointer and seed updates (and the loop control) once per 16 candidates
-        for (; j + 2 * TRIP <= jstop; j += 2 * TRIP) {
-          trip(test, 0); trip(test, TRIP);
-          rd += 2 * TRIP; ru += 2 * TRIP; seedA += 2 * TRIP; seedB += 2 * TRIP;
+      if (SPEC && nt == CH) {
+        // full chunk: one straight run of CH trips
+#pragma unroll
+        for (int32_t t = 0; t < CH; t++) {
+          trip(std::integral_constant<int, 0>{}, t);
+          // reads are scheduled at most two trips ahead, as in a loop of two trips: further ahead they cost registers
+          if (t & 1) __builtin_amdgcn_sched_barrier(0);
         }
-        if (j < jstop) {
-          trip(test, 0);
-          j += TRIP; rd += TRIP; ru += TRIP; seedA += TRIP; seedB += TRIP;
+      } else if (SPEC || pa0 > pa1) {
+        // partial chunk (tested loop: any chunk of a column that is not interior): the same trips, left after nt of them
+        constexpr int TEST = SPEC ? 0 : 2;
+#pragma unroll
+        for (int32_t t = 0; t < CH; t++) {
+          if (t >= nt) break;
+          trip(std::integral_constant<int, TEST>{}, t);
         }
-      };
-      if (SPEC) {
-        run(std::integral_constant<int, 0>{}, jend);
-      } else if (pa0 <= pa1) {
-        // interior column.  [0, ja): v test, [ja, jb): no test, [jb, jend): v test -- the
+      } else {
+        // interior column.  Trips [0, ta): v test, [ta, tb): no test, [tb, nt): v test -- the
         // untested range shrunk inward to whole trips (testing a candidate that would
         // not need it is always valid)
-        const int32_t ja = min((min(max(pa0 - pc, 0), mcnt) + TRIP - 1) & ~(TRIP - 1), jend);
-        const int32_t jb = max(min(max(pa1 - pc, 0), mcnt) & ~(TRIP - 1), ja);
-        run(std::integral_constant<int, 1>{}, ja);
-        run(std::integral_constant<int, 0>{}, jb);
-        run(std::integral_constant<int, 1>{}, jend);
-      } else {
-        run(std::integral_constant<int, 2>{}, jend);
+        const int32_t ta = min((min(max(pa0 - pc, 0), mcnt) + TRIP - 1) / TRIP, nt);
+        const int32_t tb = max(min(max(pa1 - pc, 0), mcnt) / TRIP, ta);
+#pragma unroll
+        for (int32_t t = 0; t < CH; t++) {
+          if (t >= nt) break;
+          if (t >= ta && t < tb) trip(std::integral_constant<int, 0>{}, t);
+          else trip(std::integral_constant<int, 1>{}, t);
+        }
       }
+      // the chunk's winners as global keys, once per query
+      const uint32_t vbase = (uint32_t)(pc - pbase + ph);
+#pragma unroll
+      for (int32_t qi = 0; qi < Q; qi++) best_key[qi] = min(best_key[qi], global_key(cm[qi], vbase));
     });
   // join the phases: lanes l, l+L, l+2L, .. hold partial minima of the same query
   out.wp = join_phases<Q, P, KM>(best_key);
