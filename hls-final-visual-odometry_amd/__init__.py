@@ -98,6 +98,7 @@ ABI_SYMBOLS = (
     "vh_group_get_scene_points", "vh_group_get_scene_points_all", "vh_get_scene_points", "vh_group_scene_points_device",
     "vh_default_landmark_params", "vh_landmarks_update", "vh_group_landmarks", "vh_match_landmarks",
     "vh_group_get_landmarks", "vh_group_get_landmarks_all", "vh_get_landmarks", "vh_group_landmarks_device",
+    "vh_landmarks_chain", "vh_sequence_set_landmarks",
 )
 
 
@@ -442,6 +443,7 @@ def _lib():
             "vh_group_landmarks": [vp, vp, vp], "vh_match_landmarks": [vp, vp, vp],
             "vh_group_get_landmarks": [vp, i32, vp, i32, vp], "vh_group_get_landmarks_all": [vp, vp, i32, vp],
             "vh_get_landmarks": [vp, vp, i32, vp], "vh_group_landmarks_device": [vp, vp, vp],
+            "vh_landmarks_chain": [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], "vh_sequence_set_landmarks": [vp, i32],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -1078,7 +1080,8 @@ class StreamGroup:
     def landmarks(self, params: "LandmarkParams | None" = None) -> np.ndarray:
         """The scene points of the last scenePoints fused along every stream's feature tracks (vh_group_landmarks;
         setTrackLinking, and a scenePoints Tw that takes every step's points into one common frame) -> counts [S];
-        getLandmarks(stream) / getLandmarksAll / landmarksDevice give the landmarks.  A SequenceGroup: VH_ERR_UNSUPPORTED."""
+        getLandmarks(stream) / getLandmarksAll / landmarksDevice give the landmarks.  A SequenceGroup: after setLandmarks(True),
+        else VH_ERR_UNSUPPORTED."""
         lp = params or LandmarkParams.default()
         counts = np.zeros(self.S, np.int32)
         _check(_lib().vh_group_landmarks(self._h, C.byref(lp), _ptr(counts)), "vh_group_landmarks")
@@ -1459,6 +1462,12 @@ class SequenceGroup(StreamGroup):
             raise VisoHipError(VH_ERR_STATE, "vh_sequence_set_multi_stage")
         self.setMultiStage(2 if on else 1)
 
+    def setLandmarks(self, on: bool = True):
+        """Landmarks along the rows of a chunk (vh_sequence_set_landmarks): before the first pushBack, with setTrackLinking.
+        landmarks() then fuses the scene points of the last scenePoints along the tracks of the chunk's rows, row 0
+        continuing the previous chunk's last row; getLandmarks(row) / getLandmarksAll / landmarksDevice serve rows."""
+        _check(_lib().vh_sequence_set_landmarks(self._h, 1 if on else 0), "vh_sequence_set_landmarks")
+
     def setReconstruction(self, recon: "ReconParams | None", history_frames: int = 0):
         """3-d points from the tracks that end, gathered on the device (vh_sequence_set_reconstruction): before the first
         push only; switches track linking on.  history_frames >= 1: lost tracks older than that come back RECON_HISTORY.
@@ -1694,6 +1703,27 @@ def landmarks_update(tracks, points, prev_state=None, params: "LandmarkParams | 
     _check(_lib().vh_landmarks_update(C.byref(lp), device, n, _ptr(trk), _ptr(roff), _ptr(pts), _ptr(poff),
                                       None if prev is None else _ptr(prev), None if voff is None else _ptr(voff),
                                       _ptr(state), _ptr(out), _ptr(counts)), "vh_landmarks_update")
+    return ([out[int(roff[s]):int(roff[s]) + int(counts[s])].copy() for s in range(n)],
+            [state[int(roff[s]):int(roff[s + 1])].copy() for s in range(n)])
+
+
+def landmarks_chain(tracks, points, carry=None, params: "LandmarkParams | None" = None, device: int = 0):
+    """The landmarks of n lists that are the rows of one chain (vh_landmarks_chain): list s's prev indexes list s - 1 of the
+    same call (what link_tracks returns), list 0's indexes `carry` (None, or a LANDMARK_STATE_DTYPE array: the last list's
+    states of the call before).  tracks / points as landmarks_update's.
+    -> ([LANDMARK_DTYPE array per list], [LANDMARK_STATE_DTYPE array per list])."""
+    n = len(tracks)
+    assert len(points) == n
+    lp = params or LandmarkParams.default()
+    trk, roff = _packed(tracks, TRACK)
+    pts, poff = _packed(points, SCENE_POINT_DTYPE)
+    cs = None if carry is None else np.ascontiguousarray(carry, LANDMARK_STATE_DTYPE).reshape(-1)
+    total = int(roff[-1])
+    state = np.zeros(max(total, 1), LANDMARK_STATE_DTYPE); out = np.zeros(max(total, 1), LANDMARK_DTYPE)
+    counts = np.zeros(max(n, 1), np.int32)
+    _check(_lib().vh_landmarks_chain(C.byref(lp), device, n, _ptr(trk), _ptr(roff), _ptr(pts), _ptr(poff),
+                                     None if cs is None or not len(cs) else _ptr(cs), 0 if cs is None else len(cs),
+                                     _ptr(state), _ptr(out), _ptr(counts)), "vh_landmarks_chain")
     return ([out[int(roff[s]):int(roff[s]) + int(counts[s])].copy() for s in range(n)],
             [state[int(roff[s]):int(roff[s + 1])].copy() for s in range(n)])
 

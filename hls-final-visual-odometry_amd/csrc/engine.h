@@ -8,7 +8,7 @@
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
 //   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
 //   engine_scene.hip  the 3-d points of whole lists (kernels_scene.hip) and their part of the ABI
-//   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip) and their part of the ABI
+//   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip, kernels_landmark_chain.hip) and their part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -347,6 +347,11 @@ struct LandmarkState : LandmarkArrays {
   int64_t seq = 0;
   int64_t state_seq[2] = {-1, -1};  // the match call whose tracked list each state buffer was computed for (-1: none)
   std::vector<int32_t> n;           // [S] landmarks per stream
+  // A sequence handle with vh_sequence_set_landmarks on: d_state[0] holds the states of the
+  // chunk's rows, d_state[1] the carry -- the last row's states of the last call on the previous chunk, copied when the
+  // first call of the next chunk is queued (the rule of the track carry, whose slot its positions number).
+  int32_t carry_src = -1;           // row to copy into the carry before the next launches (-1: none)
+  bool carry_valid = false;         // the carry holds the states of the list in the track carry slot
 };
 
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
@@ -602,6 +607,7 @@ struct Group {
   MonoPoseState mps;
   SceneState scn;
   LandmarkState lmk;
+  bool lmk_chain = false;  // vh_sequence_set_landmarks: vh_group_landmarks runs the chain form over the chunk's rows
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -745,6 +751,8 @@ struct Group {
 
   // ---- engine_landmark.hip ----
   int32_t landmarks(const vh_landmark_params *lp, int32_t *counts);
+  int32_t landmarks_chain(const vh_landmark_params *lp, int32_t *counts);  // a sequence handle's
+  void lmk_pushed(bool first, int32_t prev_chunk_rows);
   bool landmarks_current() const { return allocated && lmk.valid && lmk.seq == match_seq; }
   int32_t get_landmarks(int32_t s, vh_landmark *out, int32_t capo, int32_t *n);
   int32_t get_landmarks_all(vh_landmark *out, int32_t cap_per_stream, int32_t *counts);

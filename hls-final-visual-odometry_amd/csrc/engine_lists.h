@@ -177,6 +177,15 @@ struct LandmarkArrays {
     d_state[0] = c.ptr<vh_landmark_state>(2 * slots); d_state[1] = d_state[0] ? d_state[0] + slots : nullptr;  // (one array of the five)
     d_out = c.ptr<vh_landmark>(slots); d_obs = c.ptr<int32_t>(slots); d_tiles = c.ptr<int32_t>(lists * tiles); d_n = c.ptr<int32_t>(lists);
   }
+  // A sequence handle's block: the rows' states in d_state[0], the carry's (carry_slots records)
+  // in d_state[1]; the observation index and the forward links are the halves of one array of 8 bytes per slot.
+  int32_t *d_next = nullptr;        // [slots]
+  void carve(Carver &c, size_t lists, size_t slots, size_t tiles, size_t carry_slots) {
+    d_state[0] = c.ptr<vh_landmark_state>(slots); d_state[1] = c.ptr<vh_landmark_state>(carry_slots);
+    d_out = c.ptr<vh_landmark>(slots);
+    d_obs = c.ptr<int32_t>(2 * slots); d_next = d_obs ? d_obs + slots : nullptr;
+    d_tiles = c.ptr<int32_t>(lists * tiles); d_n = c.ptr<int32_t>(lists);
+  }
 };
 // The caller's index lists of the gain (GainState, engine.h): idx [entries] | ratio [entries] | offsets [S + 1]; the block
 // is as long as tight() says

@@ -57,7 +57,7 @@ int32_t Group::match_recover() {
   last_method = -1;
   // tracks: the failed call's lists are void (match()); a carry copy it may have left half done is void as well, so the
   // next lists of a sequence start new tracks instead of following a table in an unknown state
-  if (trk_on && seq) { trk_pred_valid = false; trk_carry_src = -1; }
+  if (trk_on && seq) { trk_pred_valid = false; trk_carry_src = -1; lmk.carry_valid = false; lmk.carry_src = -1; }  // (the landmark states go with the lists they belong to)
   match_dirty = false;
   return VH_OK;
 }
@@ -309,6 +309,7 @@ int32_t Group::match_post(int32_t method, const VhMatchArgs &a, int32_t buf, boo
 void Group::trk_pushed(bool shifted, bool first, int32_t prev_chunk_rows) {
   if (!trk_on) return;
   if (seq) {
+    lmk_pushed(first, prev_chunk_rows);  // (before the flags of the chunk that ends are reset)
     if (first) { trk_pred_valid = false; trk_carry_src = -1; }
     else if (trk_cur_valid) trk_carry_src = prev_chunk_rows - 1;        // (supersedes a carry that was never needed)
     else { trk_pred_valid = false; trk_carry_src = -1; }                  // the previous chunk was never matched

@@ -17,49 +17,14 @@
 //                   as three 16-byte stores, at the tile's position + vh_compact4's rank: thread order is list order.
 // Every output position is a function of the keep decisions alone: no atomics, the same bytes from run to run, whatever
 // else the launch holds.
-#include "vh_dev.h"
+#include "vh_landmark.h"
 #include "vh_wave.h"
 
 namespace {
 
 #define LMK_T VH_SCENE_TILE
 static_assert(LMK_T == 256, "vh_compact4 joins four waves; the tiles are scene_scan's");
-static_assert(sizeof(vh_landmark_state) == 48 && sizeof(vh_landmark) == 48 && sizeof(vh_scene_point) == 32 && sizeof(vh_track) == 24,
-              "the vector loads and stores below");
-
-struct LmkList {
-  int64_t rec0, pt0, prev0;    // first element of the list in trk / state_out / out / obs, in pts, in prev
-  int32_t n, n_pt, n_prev;
-};
-__device__ __forceinline__ int32_t lmk_count(const int32_t *counts, int32_t s, int64_t stride) {
-  return (int32_t)min((int64_t)max(counts[s], 0), stride);
-}
-__device__ __forceinline__ LmkList lmk_list(const VhLandmarkArgs &a, int32_t s) {
-  LmkList L;
-  if (a.rec_offsets) { L.rec0 = a.rec_offsets[s]; L.n = a.rec_offsets[s + 1] - a.rec_offsets[s]; }
-  else { L.rec0 = (int64_t)s * a.rec_stride; L.n = lmk_count(a.rec_counts, s, a.rec_stride); }
-  if (a.pt_offsets) { L.pt0 = a.pt_offsets[s]; L.n_pt = a.pt_offsets[s + 1] - a.pt_offsets[s]; }
-  else { L.pt0 = (int64_t)s * a.pt_stride; L.n_pt = lmk_count(a.pt_counts, s, a.pt_stride); }
-  L.prev0 = 0; L.n_prev = 0;
-  if (a.prev) {
-    if (a.prev_offsets) { L.prev0 = a.prev_offsets[s]; L.n_prev = a.prev_offsets[s + 1] - a.prev_offsets[s]; }
-    else { L.prev0 = (int64_t)s * a.prev_stride; L.n_prev = lmk_count(a.prev_counts, s, a.prev_stride); }
-  }
-  return L;
-}
-
-struct LmkState {
-  double sw, swx, swy, swz;
-  int32_t n_obs, n_missed;
-};
-__device__ __forceinline__ LmkState lmk_zero() { LmkState st; st.sw = st.swx = st.swy = st.swz = 0.0; st.n_obs = st.n_missed = 0; return st; }
-__device__ __forceinline__ LmkState lmk_load(const vh_landmark_state *p) {
-  const double2 a = ((const double2 *)p)[0], b = ((const double2 *)p)[1];
-  const int2 c = ((const int2 *)p)[4];
-  LmkState st;
-  st.sw = a.x; st.swx = a.y; st.swy = b.x; st.swz = b.y; st.n_obs = c.x; st.n_missed = c.y;
-  return st;
-}
+static_assert(sizeof(vh_landmark) == 48 && sizeof(vh_track) == 24, "the vector loads and stores below");
 
 // grid: n_lists * tiles_per_list workgroups, list-major (a list holds no more points than records)
 __global__ void __launch_bounds__(LMK_T)
@@ -86,32 +51,10 @@ landmark_fuse_kernel(VhLandmarkArgs a) {
     const int32_t q = a.trk[r].prev, k = a.obs[r];
     LmkState st = lmk_zero();
     if (q >= 0 && q < L.n_prev) st = lmk_load(a.prev + L.prev0 + q);  // 1. carry
-    if (k < 0 || k >= L.n_pt) {                                        // 2. no observation
-      if (st.n_obs > 0) {
-        st.n_missed += 1;
-        if (a.lp.max_missed >= 0 && st.n_missed > a.lp.max_missed) st = lmk_zero();
-      }
-    } else {                                                           // 3. the observation
-      const float4 p = *(const float4 *)(a.pts + L.pt0 + k);
-      const double x = p.x, y = p.y, z = p.z, sg = p.w;
-      const double wt = sg > 0.0 ? 1.0 / (sg * sg) : 1.0;
-      if (st.n_obs > 0) {
-        const double T = a.lp.max_dist + a.lp.gate_sigma * sg;
-        if (T > 0.0) {
-          const double dx = x - st.swx / st.sw, dy = y - st.swy / st.sw, dz = z - st.swz / st.sw;
-          if (dx * dx + dy * dy + dz * dz > T * T) st = lmk_zero();
-        }
-      }
-      st.sw += wt; st.swx += wt * x; st.swy += wt * y; st.swz += wt * z;
-      st.n_obs += 1; st.n_missed = 0;
-      if (!(isfinite(st.sw) && isfinite(st.swx) && isfinite(st.swy) && isfinite(st.swz))) st = lmk_zero();
-      else keep = st.n_obs >= a.lp.min_obs;                            // 5.
-      if (!keep) a.obs[r] = -1;
-    }
-    double2 *o = (double2 *)(a.state_out + r);                         // 4.
-    o[0] = make_double2(st.sw, st.swx);
-    o[1] = make_double2(st.swy, st.swz);
-    ((int4 *)o)[2] = make_int4(st.n_obs, st.n_missed, 0, 0);
+    const bool seen = k >= 0 && k < L.n_pt;
+    keep = lmk_step(st, a.lp, seen ? a.pts + L.pt0 + k : nullptr);     // 2., 3., 5. (vh_landmark.h)
+    if (seen && !keep) a.obs[r] = -1;
+    lmk_store(a.state_out + r, st);                                    // 4.
   }
   const VhCompact c = vh_compact4(keep, sWave, w, lane);
   if (tid == 0) a.tile_cnt[(int64_t)s * a.tiles_per_list + tile] = c.total;
@@ -146,17 +89,29 @@ landmark_store_kernel(VhLandmarkArgs a) {
 
 }  // namespace
 
-hipError_t vh_launch_landmarks(const VhLandmarkArgs &a, int64_t obs_elems, hipStream_t st) {
-  const hipError_t e = hipMemsetAsync(a.obs, 0xFF, sizeof(int32_t) * (size_t)obs_elems, st);
-  if (e != hipSuccess) return e;
-  const dim3 grid((uint32_t)a.n_lists * (uint32_t)a.tiles_per_list), block(LMK_T);
-  hipLaunchKernelGGL(landmark_index_kernel, grid, block, 0, st, a);
-  hipLaunchKernelGGL(landmark_fuse_kernel, grid, block, 0, st, a);
+static dim3 landmark_grid(const VhLandmarkArgs &a) { return dim3((uint32_t)a.n_lists * (uint32_t)a.tiles_per_list); }
+
+// the pieces the chain form shares (kernels_landmark_chain.hip)
+void vh_launch_landmark_index(const VhLandmarkArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(landmark_index_kernel, landmark_grid(a), dim3(LMK_T), 0, st, a);
+}
+void vh_launch_landmark_scan(const VhLandmarkArgs &a, hipStream_t st) {
   VhSceneArgs sc{};  // what scene_scan reads: the record lists' lengths, ok, the tile counts
   sc.lists = a.rec_offsets ? VhLists::packed(nullptr, a.rec_offsets, a.n_lists)
                            : VhLists::slots(nullptr, a.rec_stride, a.rec_counts, (int32_t)a.rec_stride, a.n_lists);
   sc.tiles_per_list = a.tiles_per_list; sc.ok = a.ok; sc.out_stride = a.rec_stride; sc.tile_cnt = a.tile_cnt; sc.n_out = a.n_out;
   vh_launch_scene_scan(sc, st);
-  hipLaunchKernelGGL(landmark_store_kernel, grid, block, 0, st, a);
+}
+void vh_launch_landmark_store(const VhLandmarkArgs &a, hipStream_t st) {
+  hipLaunchKernelGGL(landmark_store_kernel, landmark_grid(a), dim3(LMK_T), 0, st, a);
+}
+
+hipError_t vh_launch_landmarks(const VhLandmarkArgs &a, int64_t obs_elems, hipStream_t st) {
+  const hipError_t e = hipMemsetAsync(a.obs, 0xFF, sizeof(int32_t) * (size_t)obs_elems, st);
+  if (e != hipSuccess) return e;
+  vh_launch_landmark_index(a, st);
+  hipLaunchKernelGGL(landmark_fuse_kernel, landmark_grid(a), dim3(LMK_T), 0, st, a);
+  vh_launch_landmark_scan(a, st);
+  vh_launch_landmark_store(a, st);
   return hipSuccess;
 }

@@ -124,7 +124,8 @@ struct VhSets {
 //          7 winner position of a search, 8 track_link predecessor position, 9 track_rank successor position,
 //          10 recon_store predecessor position of a continued mark, 11 recon_gather position followed through the ring,
 //          12 gain_ratio byte offset of a dword inside its image plane, 13 gain_ratio list position of an index entry,
-//          14 flow_queries query position gathered through snake_pos
+//          14 flow_queries query position gathered through snake_pos,
+//          15 landmark_chain successor position followed to the next row
 #ifdef VH_CHECK
 #define VH_CHECK_RANGE(s_, code_, x_, lo_, hi_)                                          \
   do {                                                                                   \
@@ -572,6 +573,28 @@ struct VhLandmarkArgs {
 // the memset of obs, then index, fuse, scan, store on one stream; obs_elems: the elements of obs the lists span.
 // The caller keeps n_lists * tiles_per_list below 2^30.  -> the memset's code
 hipError_t vh_launch_landmarks(const VhLandmarkArgs &a, int64_t obs_elems, hipStream_t st);
+// its index, scan and store launches alone (what the chain form shares)
+void vh_launch_landmark_index(const VhLandmarkArgs &a, hipStream_t st);
+void vh_launch_landmark_scan(const VhLandmarkArgs &a, hipStream_t st);
+void vh_launch_landmark_store(const VhLandmarkArgs &a, hipStream_t st);
+
+// Landmarks of lists that are the rows of one chain (kernels_landmark_chain.hip): list s's
+// predecessor is list s - 1 of the same call, list 0's the carry.  a.prev* are not read.
+struct VhLandmarkChainArgs {
+  VhLandmarkArgs a;
+  int32_t *next;                   // indexed like a.obs, and the array right behind it: the record of the next list that continues this one, -1: none
+  const vh_landmark_state *carry;  // null: list 0 has no predecessor
+  const int32_t *carry_count;      // the carry's length on the device (clamped to [0, carry_cap]); null: n_carry
+  int32_t n_carry, carry_cap;
+  uint32_t *check;                 // VH_CHECK builds: {violations, code, value, bound}
+};
+// the memset of obs and next (obs_elems each), then launch k of the six, in this order on one stream: 0 index, 1 link,
+// 2 chain, 3 count, 4 scan, 5 store (a launch each, so that a handle can time every kernel under a scope of its own).
+// The caller keeps n_lists * tiles_per_list below 2^30.
+#define VH_LANDMARK_CHAIN_STAGES 6
+hipError_t vh_launch_landmarks_chain_clear(const VhLandmarkChainArgs &c, int64_t obs_elems, hipStream_t st);
+void vh_launch_landmarks_chain_stage(const VhLandmarkChainArgs &c, int32_t k, hipStream_t st);
+const char *vh_landmark_chain_scope(int32_t k);
 
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride

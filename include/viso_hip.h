@@ -1186,7 +1186,8 @@ int32_t vh_landmarks_update(const vh_landmark_params *lp, int32_t device, int32_
  * VH_ERR_STATE with track linking off, without a tracked list for the current pair (before a match call, after the next
  * push), without scene points of the current lists, and where the classification read lists replaced on the host
  * (vh_remove_outliers / vh_bucket_features: their positions are not the tracked list's).  VH_ERR_UNSUPPORTED on a
- * sequence handle (the predecessor of row r is row r - 1 of the same call: a chain, not a gather).
+ * sequence handle without vh_sequence_set_landmarks (below; checked before the state), where the predecessor of row r is
+ * row r - 1 of the same call: a chain, not a gather.
  * Plain groups and lone matchers.  The first call adds one block: 2 x 48 bytes of state, 48 bytes of output and 4 bytes
  * of observation index per record slot (S x max_matches slots), 4 bytes per tile of 256 slots and 4 bytes per stream,
  * each of the five arrays rounded up to 256 bytes, counted by vh_group_device_bytes; a handle that never calls these
@@ -1201,6 +1202,44 @@ int32_t vh_group_get_landmarks(vh_group *g, int32_t stream, vh_landmark *out, in
 int32_t vh_group_get_landmarks_all(vh_group *g, vh_landmark *out, int32_t cap_per_stream, int32_t *counts);
 int32_t vh_get_landmarks(vh_matcher *m, vh_landmark *out, int32_t cap, int32_t *n);
 int32_t vh_group_landmarks_device(vh_group *g, const vh_landmark **d_out, int64_t *stride);
+
+/* ---- landmarks along the rows of one chain (csrc/kernels_landmark_chain.hip) ----
+ * The lists of a call are the rows 0 .. n_sets - 1 of one chain, as vh_link_tracks links them: list s's predecessor is
+ * list s - 1 OF THE SAME CALL, so vh_track.prev of list s indexes list s - 1 and the predecessor state of a record is the
+ * state_out this very call computes for it.  List 0's predecessor is the carry: n_carry states (carry NULL, n_carry 0:
+ * none), for instance the last list's slice of state_out of the call before.  Every record follows the rule above, steps
+ * 1 - 5, with "predecessor state" read so: step 1 for record j of list s > 0 is st = state_out[list s - 1][trk[j].prev]
+ * where 0 <= trk[j].prev < n_rec[s - 1], for list 0 st = carry[trk[j].prev] where 0 <= trk[j].prev < n_carry, else zeros
+ * (a prev outside is never dereferenced; an empty list ends every chain).  The result is the bytes of n_sets
+ * vh_landmarks_update calls, one list at a time, each fed the state_out of the one before -- in one call: the device walks
+ * every track from its first record in the call to its last, the 48-byte state in registers, the same arithmetic in the
+ * same order.  Lists, points, outputs, refusals and the n_sets == 0 / no-records shortcuts are vh_landmarks_update's.
+ * One refusal more, made on the host before any device work: two records of one list with the same prev inside their
+ * predecessor list (list 0: inside the carry) are VH_ERR_INVALID_ARG -- a record is continued at most once (the link
+ * rule of vh_link_tracks), and the walk relies on it.  n_carry < 0, or n_carry > 0 without carry: VH_ERR_INVALID_ARG. */
+int32_t vh_landmarks_chain(const vh_landmark_params *lp, int32_t device, int32_t n_sets,
+                           const vh_track *trk, const int32_t *rec_offsets,
+                           const vh_scene_point *pts, const int32_t *pt_offsets,
+                           const vh_landmark_state *carry, int32_t n_carry,
+                           vh_landmark_state *state_out, vh_landmark *out, int32_t *counts);
+/* Sequence handles.  on = 1, before the first push only (VH_ERR_STATE afterwards; VH_ERR_UNSUPPORTED on a plain group or
+ * a lone matcher; as vh_sequence_set_multi_stage): vh_group_landmarks(g, lp, counts[S]) then runs the chain form over the
+ * rows of the current chunk's tracked lists and the points of the last vh_group_scene_points_* call, both on the device;
+ * only the params go up.  Its VH_ERR_STATE conditions are the group's; rows without a pair (row 0 of the first chunk, the
+ * rows behind a short chunk) give count 0; vh_group_get_landmarks(_all) and vh_group_landmarks_device serve rows as they
+ * serve streams.  Off (the default): everything as before, VH_ERR_UNSUPPORTED from vh_group_landmarks included.
+ * The carry: row 0 continues the last row of the previous chunk.  The rows' states stay on the device; the last row's
+ * are copied aside when the first landmarks call of the next chunk is queued (the rule of the track carry), and used iff
+ * the track carry is valid, the last landmarks call on the previous chunk came after that chunk's last match call, and no
+ * chunk went without a call in between; otherwise every record of row 0 starts without state.  A repeated call gives the
+ * same bytes; matching the chunk again and repeating scene points and landmarks recomputes the rows from the same carry;
+ * a match call that failed half way voids the carry with the track carry.
+ * The first call adds one block, counted by vh_group_device_bytes: 48 bytes of state, 48 of output and 8 of observation
+ * index and forward link per record slot (S x max_matches slots), 48 bytes per carry slot (max_matches), 4 bytes per tile
+ * of 256 slots and 4 per row, each of the six arrays rounded up to 256 bytes.  A refused allocation is VH_ERR_HIP before
+ * any launch and leaves the handle as it was.  Profile scope: "landmarks" (and one per launch inside it: "landmark_index",
+ * "landmark_link", "landmark_chain", "landmark_count", "landmark_scan", "landmark_store"). */
+int32_t vh_sequence_set_landmarks(vh_group *g, int32_t on);
 
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
