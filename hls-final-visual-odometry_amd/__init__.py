@@ -99,6 +99,10 @@ ABI_SYMBOLS = (
     "vh_default_landmark_params", "vh_landmarks_update", "vh_group_landmarks", "vh_match_landmarks",
     "vh_group_get_landmarks", "vh_group_get_landmarks_all", "vh_get_landmarks", "vh_group_landmarks_device",
     "vh_landmarks_chain", "vh_sequence_set_landmarks",
+    "vh_default_traj_params", "vh_trajectory", "vh_group_set_trajectory", "vh_sequence_set_trajectory", "vh_set_trajectory",
+    "vh_group_trajectory", "vh_match_trajectory", "vh_group_get_poses", "vh_get_pose", "vh_group_poses_device", "vh_group_set_pose",
+    "vh_group_scene_points_stereo_world", "vh_group_scene_points_mono_world",
+    "vh_match_scene_points_stereo_world", "vh_match_scene_points_mono_world",
 )
 
 
@@ -230,6 +234,37 @@ class LandmarkParams(C.Structure):
                 raise AttributeError(k)
             setattr(e, k, v)
         return e
+
+
+#: policy of the trajectory for a row that is not accepted (vh_traj_params.on_fail) / the motion a handle steps under
+TRAJ_HOLD, TRAJ_REPEAT = 0, 1
+TRAJ_STEREO, TRAJ_MONO = 0, 1
+#: rows of a chain one round of the trajectory kernel takes (csrc/vh_trajectory.h: VH_TRAJ_ROUND)
+TRAJ_ROUND = 256
+# vh_traj_pose (272 bytes): one per row of trajectory / trajectory(source)
+TRAJ_POSE_DTYPE = np.dtype([("Tw_prev", "<f8", (4, 4)), ("Tw_cur", "<f8", (4, 4)), ("status", "<i4"), ("step", "<i4"), ("reserved", "<i4", (2,))])
+# vh_traj_carry (272 bytes): what a chain carries from call to call
+TRAJ_CARRY_DTYPE = np.dtype([("Tw", "<f8", (4, 4)), ("Tinv", "<f8", (4, 4)), ("step", "<i4"), ("has_tinv", "<i4"), ("reserved", "<i4", (2,))])
+
+
+class TrajParams(C.Structure):
+    """vh_traj_params: what a row that is not accepted does to the pose (TRAJ_HOLD: nothing; TRAJ_REPEAT: the last accepted
+    step again)."""
+    _fields_ = [("on_fail", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def default(cls, **kw):
+        e = cls(on_fail=TRAJ_HOLD, reserved=0)
+        for k, v in kw.items():
+            if not hasattr(e, k):
+                raise AttributeError(k)
+            setattr(e, k, v)
+        return e
+
+
+def _traj_T0(T0, n):
+    """None, or [n, 4, 4] doubles (one 4x4 serves every chain) -> [n, 16]"""
+    return _scene_Tw(T0, n)
 
 
 def _scene_Tw(Tw, n):
@@ -444,6 +479,13 @@ def _lib():
             "vh_group_get_landmarks": [vp, i32, vp, i32, vp], "vh_group_get_landmarks_all": [vp, vp, i32, vp],
             "vh_get_landmarks": [vp, vp, i32, vp], "vh_group_landmarks_device": [vp, vp, vp],
             "vh_landmarks_chain": [vp, i32, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp], "vh_sequence_set_landmarks": [vp, i32],
+            "vh_trajectory": [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_set_trajectory": [vp, vp, vp], "vh_sequence_set_trajectory": [vp, vp, vp], "vh_set_trajectory": [vp, vp, vp],
+            "vh_group_trajectory": [vp, i32, vp], "vh_match_trajectory": [vp, i32, vp],
+            "vh_group_get_poses": [vp, vp], "vh_get_pose": [vp, vp], "vh_group_poses_device": [vp, vp, vp],
+            "vh_group_set_pose": [vp, i32, vp],
+            "vh_group_scene_points_stereo_world": [vp, vp, vp, vp], "vh_group_scene_points_mono_world": [vp, vp, vp, vp],
+            "vh_match_scene_points_stereo_world": [vp, vp, vp, vp], "vh_match_scene_points_mono_world": [vp, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -457,6 +499,8 @@ def _lib():
         lib.vh_default_scene_params.restype = None
         lib.vh_default_landmark_params.argtypes = [vp]
         lib.vh_default_landmark_params.restype = None
+        lib.vh_default_traj_params.argtypes = [vp]
+        lib.vh_default_traj_params.restype = None
         lib.vh_reconstruct_last_kernel_ms.argtypes = []
         lib.vh_reconstruct_last_kernel_ms.restype = f64
         lib.vh_group_device_bytes.argtypes = [vp]
@@ -700,6 +744,41 @@ class Matcher:
         n = C.c_int32(0)
         fn = "vh_match_scene_points_mono" if isinstance(e, MonoParams) else "vh_match_scene_points_stereo"
         _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), None if tw is None else _ptr(tw), C.byref(n)), fn)
+        return self.getScenePoints()
+
+    def setTrajectory(self, params: "TrajParams | None" = None, T0=None, on: bool = True):
+        """Accumulate the camera's pose on the device (vh_set_trajectory): before the first pushBack.  T0: the start pose
+        (None: the unit matrix); on=False switches the feature off."""
+        tp = params or TrajParams.default()
+        t0 = _traj_T0(T0, 1)
+        _check(_lib().vh_set_trajectory(self._h, C.byref(tp) if on else None, _ptr(t0)), "vh_set_trajectory")
+
+    def trajectory(self, source: int = TRAJ_STEREO) -> np.ndarray:
+        """One step of the pose under the motion of the current classification (vh_match_trajectory; TRAJ_STEREO: the
+        motion of motionInliers / refitMotion(reclassify=True), TRAJ_MONO: poseMono's) -> TRAJ_POSE_DTYPE [1].  A
+        repeated call for the same pair recomputes the step."""
+        out = np.zeros(1, TRAJ_POSE_DTYPE)
+        _check(_lib().vh_match_trajectory(self._h, source, _ptr(out)), "vh_match_trajectory")
+        return out
+
+    def getPoses(self) -> np.ndarray:
+        """The record of the last trajectory(), valid until the next pushBack (vh_get_pose) -> TRAJ_POSE_DTYPE [1]."""
+        out = np.zeros(1, TRAJ_POSE_DTYPE)
+        _check(_lib().vh_get_pose(self._h, _ptr(out)), "vh_get_pose")
+        return out
+
+    def setPose(self, T):
+        """The chain continues from the 4x4 T (vh_group_set_pose)."""
+        t = np.ascontiguousarray(T, np.float64).reshape(16)
+        _check(_lib().vh_group_set_pose(self._h, 0, _ptr(t)), "vh_group_set_pose")
+
+    def scenePointsWorld(self, e, sp: "SceneParams | None" = None) -> np.ndarray:
+        """scenePoints with Tw taken from the trajectory's pose on the device: Tw_prev for sp.frame 0, Tw_cur for 1
+        (vh_match_scene_points_stereo_world / _mono_world); after trajectory() of the current match."""
+        sp = sp or SceneParams.default()
+        n = C.c_int32(0)
+        fn = "vh_match_scene_points_mono_world" if isinstance(e, MonoParams) else "vh_match_scene_points_stereo_world"
+        _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), C.byref(n)), fn)
         return self.getScenePoints()
 
     def getScenePoints(self) -> np.ndarray:
@@ -1054,6 +1133,51 @@ class StreamGroup:
         counts = np.zeros(self.S, np.int32)
         fn = "vh_group_scene_points_mono" if isinstance(e, MonoParams) else "vh_group_scene_points_stereo"
         _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), None if tw is None else _ptr(tw), _ptr(counts)), fn)
+        return counts
+
+    def setTrajectory(self, params: "TrajParams | None" = None, T0=None, on: bool = True):
+        """Accumulate every stream's pose on the device (vh_group_set_trajectory; a SequenceGroup: one pose along the rows
+        of its chunks, vh_sequence_set_trajectory): before the first pushBack.  T0: None, one 4x4 or [S, 4, 4] (a
+        SequenceGroup: one 4x4); on=False switches the feature off."""
+        tp = params or TrajParams.default()
+        seq = isinstance(self, SequenceGroup)
+        t0 = _traj_T0(T0, 1 if seq else self.S)
+        fn = "vh_sequence_set_trajectory" if seq else "vh_group_set_trajectory"
+        _check(getattr(_lib(), fn)(self._h, C.byref(tp) if on else None, _ptr(t0)), fn)
+
+    def trajectory(self, source: int = TRAJ_STEREO) -> np.ndarray:
+        """One step of every pose under the motions of the current classification (vh_group_trajectory; TRAJ_STEREO: the
+        motion of motionInliers / refitMotion(reclassify=True), TRAJ_MONO: poseMono's) -> TRAJ_POSE_DTYPE [S] (a
+        SequenceGroup: one record per row of the chunk, walked as one chain).  A repeated call for the same pair
+        recomputes the step."""
+        out = np.zeros(self.S, TRAJ_POSE_DTYPE)
+        _check(_lib().vh_group_trajectory(self._h, source, _ptr(out)), "vh_group_trajectory")
+        return out
+
+    def getPoses(self) -> np.ndarray:
+        """The records of the last trajectory(), valid until the next pushBack (vh_group_get_poses) -> TRAJ_POSE_DTYPE [S]."""
+        out = np.zeros(self.S, TRAJ_POSE_DTYPE)
+        _check(_lib().vh_group_get_poses(self._h, _ptr(out)), "vh_group_get_poses")
+        return out
+
+    def posesDevice(self):
+        """-> (device address of the records of the last trajectory(), stride in records)"""
+        d = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_poses_device(self._h, C.byref(d), C.byref(stride)), "vh_group_poses_device")
+        return d.value, stride.value
+
+    def setPose(self, stream: int, T):
+        """The chain of `stream` (a SequenceGroup: 0) continues from the 4x4 T (vh_group_set_pose)."""
+        t = np.ascontiguousarray(T, np.float64).reshape(16)
+        _check(_lib().vh_group_set_pose(self._h, stream, _ptr(t)), "vh_group_set_pose")
+
+    def scenePointsWorld(self, e, sp: "SceneParams | None" = None) -> np.ndarray:
+        """scenePoints with Tw taken from the trajectory's poses on the device: Tw_prev for sp.frame 0, Tw_cur for 1
+        (vh_group_scene_points_stereo_world / _mono_world); after trajectory() of the current match.  -> counts [S]"""
+        sp = sp or SceneParams.default()
+        counts = np.zeros(self.S, np.int32)
+        fn = "vh_group_scene_points_mono_world" if isinstance(e, MonoParams) else "vh_group_scene_points_stereo_world"
+        _check(getattr(_lib(), fn)(self._h, C.byref(e), C.byref(sp), _ptr(counts)), fn)
         return counts
 
     def getScenePoints(self, stream: int) -> np.ndarray:
@@ -1726,6 +1850,30 @@ def landmarks_chain(tracks, points, carry=None, params: "LandmarkParams | None" 
                                      _ptr(state), _ptr(out), _ptr(counts)), "vh_landmarks_chain")
     return ([out[int(roff[s]):int(roff[s]) + int(counts[s])].copy() for s in range(n)],
             [state[int(roff[s]):int(roff[s + 1])].copy() for s in range(n)])
+
+
+def trajectory(tr_chains, ok_chains, T0=None, carry=None, params: "TrajParams | None" = None, device: int = 0):
+    """Poses accumulated along n chains of rows (vh_trajectory): tr_chains a list of [rows, 6] arrays, ok_chains of [rows]
+    int arrays (0: not ok, < 0: the row holds no pair).  T0: None, one 4x4 or [n, 4, 4]; carry: None or a TRAJ_CARRY_DTYPE
+    array [n] (what an earlier call returned: T0 is then not read).
+    -> ([TRAJ_POSE_DTYPE array per chain], TRAJ_CARRY_DTYPE [n])."""
+    n = len(tr_chains)
+    assert len(ok_chains) == n
+    tp = params or TrajParams.default()
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in tr_chains])
+    total = int(off[-1])
+    tr = np.zeros((max(total, 1), 6), np.float64); ok = np.zeros(max(total, 1), np.int32)
+    for c in range(n):
+        tr[off[c]:off[c + 1]] = np.asarray(tr_chains[c], np.float64).reshape(-1, 6)
+        ok[off[c]:off[c + 1]] = np.asarray(ok_chains[c]).astype(np.int32)
+    t0 = _traj_T0(T0, n)
+    cin = None if carry is None else np.ascontiguousarray(carry, TRAJ_CARRY_DTYPE).reshape(-1)
+    assert cin is None or len(cin) == n
+    out = np.zeros(max(total, 1), TRAJ_POSE_DTYPE); cout = np.zeros(max(n, 1), TRAJ_CARRY_DTYPE)
+    _check(_lib().vh_trajectory(C.byref(tp), device, n, _ptr(off), _ptr(tr), _ptr(ok), _ptr(t0), _ptr(cin), _ptr(out), _ptr(cout)),
+           "vh_trajectory")
+    return [out[int(off[c]):int(off[c + 1])].copy() for c in range(n)], cout[:n]
 
 
 def estimate_motion_mono(mono: MonoParams, match_lists, rand8, device: int = 0, model: bool = False):

@@ -9,6 +9,7 @@
 //   engine_mono_pose.hip   the mono pose tail on whole lists (kernels_mono_pose.hip) and its part of the ABI
 //   engine_scene.hip  the 3-d points of whole lists (kernels_scene.hip) and their part of the ABI
 //   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip, kernels_landmark_chain.hip) and their part of the ABI
+//   engine_trajectory.hip  the camera's pose accumulated from the motions (kernels_trajectory.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -354,6 +355,18 @@ struct LandmarkState : LandmarkArrays {
   bool carry_valid = false;         // the carry holds the states of the list in the track carry slot
 };
 
+// The trajectory (vh_group_set_trajectory, vh_group_trajectory; engine_trajectory.hip): one arena
+// block, allocated by the first call.  d_base: every chain's carry before the current pair; d_cur: behind it.
+struct TrajState : TrajArrays {
+  bool latched = false;   // d_base holds the carry the current pair's step starts from
+  bool stepped = false;   // d_cur = step(d_base) was computed for the current pair
+  bool valid = false;     // d_out holds the records of a call behind the last push (vh_group_get_poses)
+  // what the last call stepped under: the match call, the classification (inl.gen) and the source -- the _world entries
+  // refuse poses of a motion the current lists were not classified under
+  int64_t seq = -1, gen = -1;
+  int32_t source = -1;
+};
+
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
 // arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
 // first call that needs it.  Nothing here exists while the switch is off.
@@ -608,6 +621,12 @@ struct Group {
   SceneState scn;
   LandmarkState lmk;
   bool lmk_chain = false;  // vh_sequence_set_landmarks: vh_group_landmarks runs the chain form over the chunk's rows
+  // vh_group_set_trajectory: the switch, the policy and the start poses [chains][16] (empty: unit matrices) are settings
+  // and survive release(); trj is device state and does not -- after new dims every chain starts from its T0 again
+  bool traj_on = false;
+  vh_traj_params traj_params{};
+  std::vector<double> traj_T0;
+  TrajState trj;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -744,7 +763,9 @@ struct Group {
 
   // ---- engine_scene.hip ----
   // e (stereo) or m (mono): the one that is given names the kind
-  int32_t scene_points(const vh_ego_params *e, const vh_mono_params *m, const vh_scene_params *sp, const double *Tw, int32_t *counts);
+  // world: Tw is the trajectory's poses on the device (Tw_prev for sp->frame 0, Tw_cur for 1), the argument is not read
+  int32_t scene_points(const vh_ego_params *e, const vh_mono_params *m, const vh_scene_params *sp, const double *Tw, int32_t *counts,
+                       bool world = false);
   bool scene_current() const { return allocated && scn.valid && scn.seq == match_seq; }
   int32_t get_scene_points(int32_t s, vh_scene_point *out, int32_t capo, int32_t *n);
   int32_t get_scene_points_all(vh_scene_point *out, int32_t cap_per_stream, int32_t *counts);
@@ -756,6 +777,20 @@ struct Group {
   bool landmarks_current() const { return allocated && lmk.valid && lmk.seq == match_seq; }
   int32_t get_landmarks(int32_t s, vh_landmark *out, int32_t capo, int32_t *n);
   int32_t get_landmarks_all(vh_landmark *out, int32_t cap_per_stream, int32_t *counts);
+
+  // ---- engine_trajectory.hip ----
+  int32_t traj_chains() const { return seq ? 1 : S; }
+  int32_t set_trajectory(const vh_traj_params *tp, const double *T0);
+  void traj_pushed(bool shifted);
+  // the motion of `source` is the one the scene points of the same kind would be computed under -> VH_OK / VH_ERR_STATE
+  int32_t traj_source(int32_t source, const double *&d_tr, const int32_t *&d_ok) const;
+  int32_t trajectory(int32_t source, vh_traj_pose *out);
+  bool traj_current(bool mono) const {
+    return allocated && traj_on && trj.d_out && trj.valid && trj.seq == match_seq && trj.gen == inl.gen &&
+           trj.source == (mono ? VH_TRAJ_MONO : VH_TRAJ_STEREO);
+  }
+  int32_t get_poses(vh_traj_pose *out);
+  int32_t set_pose(int32_t s, const double *T);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

@@ -103,7 +103,7 @@ void Group::release() {
   vote_release();
   rh.release_device();
   allocs.clear(); device_bytes = 0;
-  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {}; cv = {}; mrf = {}; mps = {}; scn = {}; lmk = {}; gn = {};
+  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {}; cv = {}; mrf = {}; mps = {}; scn = {}; lmk = {}; trj = {}; gn = {};
   allocated = false;
 }
 
@@ -327,6 +327,7 @@ int32_t Group::push_device(const void *dI1, const void *dI2, int64_t stride, con
     failed = false;
     trk_pushed(pair_cur != old_cur, old_frames == 0, seq_n);
     recon_pushed(old_frames == 0, pair_cur != old_cur);
+    traj_pushed(pair_cur != old_cur || old_frames == 0);
     if (seq) { seq_n_prev = seq_n; seq_n = rows; seq_first = seq_total; seq_total += rows; }
   }
   return rc;

@@ -187,6 +187,15 @@ struct LandmarkArrays {
     d_tiles = c.ptr<int32_t>(lists * tiles); d_n = c.ptr<int32_t>(lists);
   }
 };
+// The block of the trajectory (TrajState, engine.h): the rows' records, and per chain the pose before the current pair and
+// the current one
+struct TrajArrays {
+  vh_traj_pose *d_out = nullptr;                       // [S]
+  vh_traj_carry *d_base = nullptr, *d_cur = nullptr;   // [chains]
+  void carve(Carver &c, size_t rows, size_t chains) {
+    d_out = c.ptr<vh_traj_pose>(rows); d_base = c.ptr<vh_traj_carry>(chains); d_cur = c.ptr<vh_traj_carry>(chains);
+  }
+};
 // The caller's index lists of the gain (GainState, engine.h): idx [entries] | ratio [entries] | offsets [S + 1]; the block
 // is as long as tight() says
 struct GainIndexArrays {

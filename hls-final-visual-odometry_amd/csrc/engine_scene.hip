@@ -9,9 +9,11 @@ static bool scene_params_ok(const vh_scene_params *sp) { return sp && (sp->frame
 
 // Stereo (e): under the tr / ok the classification was made under (inl.d_tr / inl.d_ok).  Mono (m): under the pose the
 // last pose_mono left in mps.d_pose / mps.d_ok for this very classification.  Nothing goes up but Tw.
-int32_t Group::scene_points(const vh_ego_params *e, const vh_mono_params *m, const vh_scene_params *sp, const double *Tw, int32_t *counts) {
+int32_t Group::scene_points(const vh_ego_params *e, const vh_mono_params *m, const vh_scene_params *sp, const double *Tw, int32_t *counts,
+                            bool world) {
   const bool mono = m != nullptr;
   if ((!e && !m) || !scene_params_ok(sp) || !counts) return VH_ERR_INVALID_ARG;
+  if (world && !traj_current(mono)) return VH_ERR_STATE;
   if (!inliers_current() || inl.mono != mono) return VH_ERR_STATE;
   // (a push ends the pair the lists belong to: last_method)
   if (mono ? !(last_method == VH_METHOD_QUAD || last_method == VH_METHOD_FLOW) : last_method != VH_METHOD_QUAD) return VH_ERR_STATE;
@@ -24,14 +26,19 @@ int32_t Group::scene_points(const vh_ego_params *e, const vh_mono_params *m, con
   }
   scn.valid = false;
   scn.n.assign((size_t)S, 0);
-  if (Tw) VH_HIP(hipMemcpyAsync(scn.d_Tw, Tw, sizeof(double) * 16 * (size_t)S, hipMemcpyHostToDevice, post_stream));
+  if (world) {
+    // the kernel reads the top rows of a 16-double record per list: the chosen matrix of every pose record, device to device
+    const double *src = sp->frame == 0 ? trj.d_out->Tw_prev : trj.d_out->Tw_cur;
+    VH_HIP(hipMemcpy2DAsync(scn.d_Tw, sizeof(double) * 16, src, sizeof(vh_traj_pose), sizeof(double) * 16, (size_t)S, hipMemcpyDeviceToDevice,
+                            post_stream));
+  } else if (Tw) VH_HIP(hipMemcpyAsync(scn.d_Tw, Tw, sizeof(double) * 16 * (size_t)S, hipMemcpyHostToDevice, post_stream));
   VhSceneArgs a{};
   if (mono) a.m = *m; else a.e = *e;
   a.sp = *sp;
   a.lists = inlier_lists();
   a.tiles_per_list = scn.tiles;
   a.tr = mono ? nullptr : inl.d_tr; a.pose = mono ? mps.d_pose : nullptr; a.ok = mono ? mps.d_ok : inl.d_ok;
-  a.Tw = Tw ? scn.d_Tw : nullptr; a.src = inl.d_src; a.out_stride = mcap;
+  a.Tw = Tw || world ? scn.d_Tw : nullptr; a.src = inl.d_src; a.out_stride = mcap;
   a.tile_cnt = scn.d_tiles; a.n_out = scn.d_n; a.out = scn.d_out;
   { Scope sc(this, "scene_points", post_stream); vh_launch_scene_points(a, mono, post_stream); }
   VH_HIP(hipGetLastError());

@@ -596,6 +596,23 @@ hipError_t vh_launch_landmarks_chain_clear(const VhLandmarkChainArgs &c, int64_t
 void vh_launch_landmarks_chain_stage(const VhLandmarkChainArgs &c, int32_t k, hipStream_t st);
 const char *vh_landmark_chain_scope(int32_t k);
 
+// The trajectory (kernels_trajectory.hip): n_chains chains of rows, a workgroup each.  Chain c is
+// the rows [offsets[c], offsets[c + 1]), or without offsets the rows [c * rows_per_chain, (c + 1) * rows_per_chain).
+struct VhTrajArgs {
+  vh_traj_params p;
+  int32_t n_chains;
+  const int32_t *offsets;          // null: rows_per_chain rows each
+  int32_t rows_per_chain;
+  int32_t pair_lo, pair_hi;        // row k of a chain (counted from its first row) holds a pair iff pair_lo <= k < pair_hi
+  const double *tr;                // [rows][6]
+  const int32_t *ok;               // [rows]; < 0: the row holds no pair
+  const double *T0;                // [n_chains][16], null: the unit matrix; not read where carry_in is given
+  const vh_traj_carry *carry_in;   // [n_chains], nullable
+  vh_traj_pose *out;               // [rows]
+  vh_traj_carry *carry_out;        // [n_chains], nullable (may be carry_in: a chain reads its carry before it writes it)
+};
+void vh_launch_trajectory(const VhTrajArgs &a, hipStream_t st);
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

@@ -79,6 +79,73 @@ template <int N> SVD_HD bool vh_gauss_jordan(double (&A)[N][N], double (&b)[N]) 
   return true;
 }
 
+// The register form with NB right-hand sides: B [N][NB], column q being a right-hand side of its own; on success B holds
+// the solutions (the inverse, for the unit matrix).  The pivot search, the exchange and the elimination of A run once;
+// what is applied to a column of B is what the form above applies to b, so a column equals that right-hand side solved
+// alone, bit for bit.  A function of its own: the form above is untouched by it.  (vh_trajectory.h: the 4x4 inverse.)
+template <int N, int NB> SVD_HD bool vh_gauss_jordan_nb(double (&A)[N][N], double (&B)[N][NB]) {
+  int32_t ipiv[N];
+#pragma unroll
+  for (int32_t q = 0; q < N; q++) ipiv[q] = 0;
+  int32_t irow = 0, icol = 0;
+#pragma unroll
+  for (int32_t i = 0; i < N; i++) {
+    double big = 0.0;
+#pragma unroll
+    for (int32_t j = 0; j < N; j++)
+#pragma unroll
+      for (int32_t k = 0; k < N; k++) {
+        const double v = fabs(A[j][k]);
+        if (ipiv[j] != 1 && ipiv[k] == 0 && v >= big) { big = v; irow = j; icol = k; }
+      }
+#pragma unroll
+    for (int32_t q = 0; q < N; q++) ipiv[q] += q == icol ? 1 : 0;
+    double ri[N], rc[N], bi[NB], bc[NB];
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) { ri[l] = 0.0; rc[l] = 0.0; }
+#pragma unroll
+    for (int32_t q = 0; q < NB; q++) { bi[q] = 0.0; bc[q] = 0.0; }
+#pragma unroll
+    for (int32_t r = 0; r < N; r++) {
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) { ri[l] = r == irow ? A[r][l] : ri[l]; rc[l] = r == icol ? A[r][l] : rc[l]; }
+#pragma unroll
+      for (int32_t q = 0; q < NB; q++) { bi[q] = r == irow ? B[r][q] : bi[q]; bc[q] = r == icol ? B[r][q] : bc[q]; }
+    }
+#pragma unroll
+    for (int32_t r = 0; r < N; r++) {
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) A[r][l] = r == icol ? ri[l] : (r == irow ? rc[l] : A[r][l]);
+#pragma unroll
+      for (int32_t q = 0; q < NB; q++) B[r][q] = r == icol ? bi[q] : (r == irow ? bc[q] : B[r][q]);
+    }
+    double piv = 0.0;
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) piv = l == icol ? ri[l] : piv;
+    if (fabs(piv) < 1e-20) return false;
+    const double pivinv = 1.0 / piv;
+#pragma unroll
+    for (int32_t l = 0; l < N; l++) ri[l] = (l == icol ? 1.0 : ri[l]) * pivinv;
+#pragma unroll
+    for (int32_t q = 0; q < NB; q++) bi[q] *= pivinv;
+#pragma unroll
+    for (int32_t ll = 0; ll < N; ll++) {
+      double dum = 0.0;
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) dum = l == icol ? A[ll][l] : dum;
+      const bool prow = ll == icol;
+#pragma unroll
+      for (int32_t l = 0; l < N; l++) {
+        const double cur = l == icol ? 0.0 : A[ll][l];
+        A[ll][l] = prow ? ri[l] : cur - ri[l] * dum;
+      }
+#pragma unroll
+      for (int32_t q = 0; q < NB; q++) B[ll][q] = prow ? bi[q] : B[ll][q] - bi[q] * dum;
+    }
+  }
+  return true;
+}
+
 // The same elimination with NB right-hand sides, on arrays in addressable memory: A [N][N] and B [N][NB], row-major,
 // both changed in place; on success B holds the solutions (the inverse, for the unit matrix).  The pivot's row and
 // column index the arrays as they do in the original, so this is for memory where a data-dependent index is free -- the

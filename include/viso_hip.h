@@ -1241,6 +1241,101 @@ int32_t vh_landmarks_chain(const vh_landmark_params *lp, int32_t device, int32_t
  * "landmark_link", "landmark_chain", "landmark_count", "landmark_scan", "landmark_store"). */
 int32_t vh_sequence_set_landmarks(vh_group *g, int32_t on);
 
+/* ---- trajectory: the camera's pose in the world, accumulated from the motions (csrc/kernels_trajectory.hip) ----
+ * The reference's demo loop, pose = pose * Matrix::inv(viso.getMotion()) (src/demo.cpp), one row at a time along a chain
+ * of rows, strictly left to right.  The rule has one copy, csrc/vh_trajectory.h; all arithmetic in double, every product
+ * and sum rounded on its own.  One row with motion tr[6] and ok, the running pose P (row-major 4x4):
+ *   1. T = transformationVectorToMatrix(tr) (src/viso.cpp:59-84): the rotation of the estimators, the translation column
+ *      tr[3..5], the last row 0 0 0 1.
+ *   2. Tinv = Matrix::inv(T): the general Gauss-Jordan elimination of Matrix::solve on the unit matrix, not the rigid
+ *      shortcut.
+ *   3. status: 4 where the row holds no pair (ok < 0 in the stateless form; on a sequence handle row 0 of the first chunk
+ *      and the rows behind a short chunk), else 1 where ok == 0, else 2 where a value of tr is not finite, else 3 where
+ *      the elimination refuses (a pivot below 1e-20), else 2 where a value of Tinv is not finite, else 0: accepted.
+ *   4. accepted: P' = P * Tinv in Matrix::operator*'s order (c = 0; c += P[i][k] * Tinv[k][j], k ascending), step += 1,
+ *      and Tinv becomes the chain's last accepted one.  Not accepted is never an error of the call: under VH_TRAJ_HOLD the
+ *      pose stays (demo.cpp when process() fails); under VH_TRAJ_REPEAT a row of status 1..3 multiplies by the last
+ *      accepted Tinv of the chain once more (constant velocity; before any accepted row it holds).  Status 4 always holds.
+ *   5. the row's record: Tw_prev = P (the world pose of the previous camera), Tw_cur = P', status, step.
+ * What a chain carries from call to call is vh_traj_carry: the last Tw_cur, the last accepted Tinv and step.  The same
+ * bytes from run to run, for a chain alone or among others, and from the stateless and the handle forms. */
+#define VH_TRAJ_HOLD   0
+#define VH_TRAJ_REPEAT 1
+#define VH_TRAJ_STEREO 0
+#define VH_TRAJ_MONO   1
+typedef struct vh_traj_params {
+  int32_t on_fail;                   /* VH_TRAJ_HOLD / VH_TRAJ_REPEAT */
+  int32_t reserved;                  /* 0 */
+} vh_traj_params;
+typedef struct vh_traj_pose {        /* 272 bytes, one per row */
+  double  Tw_prev[16];               /* the pose before the row, row-major */
+  double  Tw_cur[16];                /* the pose after it */
+  int32_t status;                    /* 0 accepted, 1 ok == 0, 2 not finite, 3 elimination refused, 4 row without a pair */
+  int32_t step;                      /* accepted rows of the chain so far, this one included */
+  int32_t reserved[2];               /* 0 */
+} vh_traj_pose;
+typedef struct vh_traj_carry {       /* 272 bytes, one per chain */
+  double  Tw[16];                    /* the last Tw_cur */
+  double  Tinv[16];                  /* the last accepted Tinv (zeros while has_tinv == 0) */
+  int32_t step;
+  int32_t has_tinv;                  /* 0: no row of the chain was accepted yet */
+  int32_t reserved[2];               /* 0 */
+} vh_traj_carry;
+void vh_default_traj_params(vh_traj_params *tp);   /* VH_TRAJ_HOLD */
+/* Stateless, host pointers: n_chains chains, chain c the rows [offsets[c], offsets[c + 1]) of tr[.][6], ok[.] and out[.]
+ * (offsets as vh_motion_inliers': offsets[0] >= 0, not decreasing; an empty chain is allowed and only copies its start to
+ * carry_out).  A chain starts from carry_in[c] where carry_in is given (T0 is then not read), else from T0[c] (NULL: the
+ * unit matrix) with step 0 and no accepted Tinv.  carry_out (nullable) [n_chains].  One workgroup walks a chain in rounds
+ * of VH_TRAJ_ROUND rows (csrc/vh_trajectory.h).  VH_ERR_INVALID_ARG: null tp / offsets / (with rows) tr, ok, out;
+ * on_fail outside the two policies; n_chains < 0.  VH_ERR_UNSUPPORTED: more than 2^24 chains.  n_chains == 0: VH_OK;
+ * no rows at all: VH_OK, carry_out filled on the host; neither launches anything nor needs a device. */
+int32_t vh_trajectory(const vh_traj_params *tp, int32_t device, int32_t n_chains, const int32_t *offsets, const double *tr,
+                      const int32_t *ok, const double *T0, const vh_traj_carry *carry_in, vh_traj_pose *out,
+                      vh_traj_carry *carry_out);
+/* Handles, opt-in, before the first push only (VH_ERR_STATE afterwards); tp == NULL switches the feature off.  T0: the
+ * start pose of every stream [S][16] (a sequence handle and a lone matcher: one, [16]; NULL: the unit matrix).  A plain
+ * group is S chains that advance one row per pair; a sequence handle is ONE chain over the rows of its chunks
+ * (vh_sequence_set_trajectory; VH_ERR_UNSUPPORTED from vh_group_set_trajectory on it and the reverse).  Off (the default):
+ * nothing is allocated or launched and vh_group_device_bytes is unchanged.  On: the first vh_group_trajectory adds one
+ * block, counted by vh_group_device_bytes: 272 bytes per stream / row of poses and 2 x 272 bytes per chain of carries
+ * (base and current), each of the three arrays rounded up to 256 bytes. */
+int32_t vh_group_set_trajectory(vh_group *g, const vh_traj_params *tp, const double *T0);
+int32_t vh_sequence_set_trajectory(vh_group *g, const vh_traj_params *tp, const double *T0);
+int32_t vh_set_trajectory(vh_matcher *m, const vh_traj_params *tp, const double *T0);
+/* One step of every chain under the motion the device holds for the current classification; nothing goes up; out
+ * (nullable) [S] comes back; synchronous.
+ *   VH_TRAJ_STEREO: the tr / ok the current STEREO classification was made under (after
+ *     vh_group_refit_motion(reclassify = 1) the refined motion); VH_ERR_STATE wherever vh_group_scene_points_stereo
+ *     returns it.
+ *   VH_TRAJ_MONO: the tr / ok the last vh_group_pose_mono / _refined left on the device for the current MONO
+ *     classification; VH_ERR_STATE wherever vh_group_scene_points_mono returns it.
+ * The step belongs to the pushed pair and is idempotent: the first call behind a push latches base = current, and every
+ * call computes current = step(base) -- a repeated call, e.g. after a refit or after matching the pair again, recomputes
+ * the step instead of stepping twice.  A replace push undoes the step of the pair it replaces (current = base).  On a
+ * sequence handle one call walks the rows of the chunk as one chain: row 0 continues the previous chunk's last row, rows
+ * without a pair get status 4.  VH_ERR_STATE with the switch off; source outside the two: VH_ERR_INVALID_ARG.  A refused
+ * allocation is VH_ERR_HIP before any launch and leaves the handle as it was.  Profile scope: "trajectory". */
+int32_t vh_group_trajectory(vh_group *g, int32_t source, vh_traj_pose *out);
+int32_t vh_match_trajectory(vh_matcher *m, int32_t source, vh_traj_pose *out);
+/* The records of the last vh_group_trajectory call (a sequence handle: one per row), valid until the next push or
+ * vh_group_set_pose (VH_ERR_STATE otherwise, and with the switch off).  _device: the array itself, *stride in records. */
+int32_t vh_group_get_poses(vh_group *g, vh_traj_pose *out);
+int32_t vh_get_pose(vh_matcher *m, vh_traj_pose *out);
+int32_t vh_group_poses_device(vh_group *g, const vh_traj_pose **d_poses, int64_t *stride);
+/* Re-anchoring: the chain of `stream` (a sequence handle: 0) continues from T[16] with step 0 and no accepted Tinv; base
+ * and current are both set, the records of the last call become stale.  VH_ERR_STATE with the switch off. */
+int32_t vh_group_set_pose(vh_group *g, int32_t stream, const double *T);
+/* vh_group_scene_points_stereo / _mono with Tw taken from the trajectory's poses on the device: Tw_prev where
+ * sp->frame == 0, Tw_cur where it is 1 (a device-to-device copy of the chosen matrices; nothing goes up).
+ * VH_ERR_STATE unless vh_group_trajectory ran behind the current match call, under the current classification and from
+ * the source of the same kind (a classification made after the step -- another vh_group_motion_inliers, a refit with
+ * reclassify -- makes the poses stale: step again); otherwise everything as the plain entries, and vh_group_landmarks
+ * works unchanged behind them. */
+int32_t vh_group_scene_points_stereo_world(vh_group *g, const vh_ego_params *e, const vh_scene_params *sp, int32_t *counts);
+int32_t vh_group_scene_points_mono_world(vh_group *g, const vh_mono_params *e, const vh_scene_params *sp, int32_t *counts);
+int32_t vh_match_scene_points_stereo_world(vh_matcher *m, const vh_ego_params *e, const vh_scene_params *sp, int32_t *count);
+int32_t vh_match_scene_points_mono_world(vh_matcher *m, const vh_mono_params *e, const vh_scene_params *sp, int32_t *count);
+
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
