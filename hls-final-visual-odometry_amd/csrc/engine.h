@@ -3,6 +3,7 @@
 //   engine_match.hip  loop policy, matching (tables and ranged), prior, multi-stage ranges, tracks, load_features
 //   engine_post.hip   downloads and getters, outlier removal, estimators, the post pipelines, bucketing, statistics
 //   engine_api.hip    the extern "C" ABI of include/viso_hip.h and the stateless primitives
+//   vh_poison.h       VH_POISON=1 (test aid): what every allocation below, and vh_vote.h's, fills its fresh buffer with
 //   engine_lists.h    free of HIP: the checks of caller-owned lists and of dims, the carving of one block into arrays, the stages' arrays
 //   engine_cov.hip    the covariance of a motion over whole lists (kernels_cov.hip) and its part of the ABI
 //   engine_mono_refit.hip  the epipolar model refitted on whole lists (kernels_mono_refit.hip) and its part of the ABI
@@ -17,6 +18,7 @@
 #define VH_ENGINE_H
 #include "vh_dev.h"
 #include "../../include/viso_hip.h"
+#include "vh_poison.h"
 #include "vh_vote.h"
 #include "vh_recon.h"
 #include "engine_lists.h"
@@ -78,7 +80,10 @@ template <class T> struct HostBlock {
     reset();
     hipError_t e = hipHostMalloc((void **)&p, sizeof(T) * count, flags);
     if (e != hipSuccess) p = nullptr;
-    else if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer(&dev, p, 0);
+    else {
+      vh_poison_host(p, sizeof(T) * count);
+      if (flags & hipHostMallocMapped) e = hipHostGetDevicePointer(&dev, p, 0);
+    }
     return e;
   }
   operator T *() const { return p; }
@@ -116,8 +121,8 @@ struct DeviceBlock {
   hipError_t alloc(size_t bytes) {
     *this = DeviceBlock();
     const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 1));
-    if (e != hipSuccess) p = nullptr;
-    return e;
+    if (e != hipSuccess) { p = nullptr; return e; }
+    return vh_poison_device(p, bytes);  // (a block its owner zeroes is poisoned first and zeroed second)
   }
   template <class T> T *as() const { return (T *)p; }
 };
@@ -656,12 +661,7 @@ struct Group {
     allocs.emplace_back(q);
     device_bytes += (int64_t)bytes;
     if (zero) VH_HIP(hipMemsetAsync(q, 0, bytes, stream));
-    else {
-      // VH_POISON=1 (test aid): fill every buffer that is not zero-initialised with 0xA5, so that a
-      // kernel consuming memory nobody wrote misbehaves the same way on every box
-      static const bool poison = [] { const char *e = getenv("VH_POISON"); return e && e[0] == '1'; }();
-      if (poison) { VH_HIP(hipMemset(q, 0xA5, bytes)); VH_HIP(hipDeviceSynchronize()); }  // (blocking: the buffer's first user may be any stream)
-    }
+    else VH_HIP(vh_poison_device(q, bytes));  // (vh_poison.h)
     *out = (T *)q;
     return VH_OK;
   }

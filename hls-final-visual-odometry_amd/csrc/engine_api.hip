@@ -40,7 +40,8 @@ static int32_t default_threads(int32_t host_threads) {
 
 // Device work buffer of the stateless estimators: one per device, grow-only, kept between calls (an allocation and its
 // release cost more than the kernels of a bucketed batch).  Requests above 1 GiB are not kept.  The lock is held for the
-// whole call: stateless estimates on one device run one at a time.
+// whole call: stateless estimates on one device run one at a time.  To a call its `need` bytes are a fresh buffer: with
+// VH_POISON=1 (vh_poison.h) every take fills them, kept or not, so that nothing of the call before it can come back.
 struct EgoWork {
   std::mutex mu;
   uint8_t *buf[16] = {};
@@ -64,9 +65,11 @@ struct EgoWorkLease {
         g_ego_work.bytes[device] = want;
       }
       d = g_ego_work.buf[device];
-      return hipSuccess;
+      return vh_poison_device(d, need);
     }
-    return hipMalloc((void **)&d, need);
+    const hipError_t er = hipMalloc((void **)&d, need);
+    if (er != hipSuccess) { d = nullptr; return er; }
+    return vh_poison_device(d, need);
   }
   ~EgoWorkLease() { if (d && !kept) (void)hipFree(d); }
 };
@@ -651,7 +654,7 @@ int32_t vh_host_alloc(int32_t device, size_t bytes, void **out) {
   *out = nullptr;
   const int32_t rc = select_device(device);
   if (rc) return rc;
-  VH_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));
+  VH_HIP(hipHostMalloc(out, bytes, hipHostMallocDefault));  // (the caller's own buffer: exempt from vh_poison.h's rule, the library reads nothing from it that the caller did not put there)
   return VH_OK;
 }
 int32_t vh_host_free(void *ptr) {

@@ -96,11 +96,6 @@ void recon_road(double road[4]) {
 // ---- reconstruction from tracked lists ------------------------------------------------------------------------------
 // gq: the handle (profile scopes, the allocation test hook), or null for vh_reconstruct_lists
 bool recon_refused(Group *gq) { return gq && gq->alloc_refused(); }
-// VH_POISON=1 (test aid, as Group::dmalloc): a fresh buffer holds 0xA5 bytes
-hipError_t recon_poison(void *q, size_t bytes) {
-  static const bool poison = [] { const char *e = getenv("VH_POISON"); return e && e[0] == '1'; }();
-  return poison ? hipMemset(q, 0xA5, bytes) : hipSuccess;
-}
 
 int32_t recon_grow(ReconHistory &h, Group *gq, ReconHistory::Grown &g, size_t need) {
   if (g.bytes >= need && g.b.p) return VH_OK;
@@ -108,7 +103,6 @@ int32_t recon_grow(ReconHistory &h, Group *gq, ReconHistory::Grown &g, size_t ne
   DeviceBlock nb;
   const size_t want = need + need / 4 + 256;
   VH_HIP(nb.alloc(want));
-  VH_HIP(recon_poison(nb.p, want));
   h.bytes += (int64_t)want - (int64_t)g.bytes;
   g.b = std::move(nb);  // (the old block goes with nb: its readers finished with the last call, which was synchronous)
   g.bytes = want;
@@ -126,7 +120,6 @@ int32_t recon_ensure_ring(ReconHistory &h, Group *gq, int32_t slots, int32_t lis
   VH_HIP(count.alloc(b_count));
   if (recon_refused(gq)) return VH_ERR_HIP;
   VH_HIP(totals.alloc(b_tot));
-  VH_HIP(recon_poison(ring.p, b_ring));
   VH_HIP(hipMemset(count.p, 0, b_count));
   h.b_ring = std::move(ring); h.b_count = std::move(count); h.b_totals = std::move(totals);
   h.ring_slots = slots; h.ring_lists = lists; h.ring_cap = cap;

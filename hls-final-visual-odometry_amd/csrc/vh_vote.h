@@ -4,6 +4,7 @@
 #define VH_VOTE_H
 
 #include "vh_dev.h"
+#include "vh_poison.h"
 #define VH_SH_LINK16 1  // hull links in 16 bits: device lists hold at most 65 535 records (VH_VOTE_LIST_MAX)
 #include "sweep_hull.h"
 
@@ -131,6 +132,8 @@ struct VhVoteBuffers {
     layout(P, cap, out_cap_, nb_max, off, &total);
     const hipError_t e = hipMalloc((void **)&block, total);
     if (e != hipSuccess) { block = nullptr; return e; }
+    const hipError_t ep = vh_poison_device(block, total);
+    if (ep != hipSuccess) { release(); return ep; }
     bytes = total;
     v.P = P; v.cap = cap; v.hsize = vh_sh::hash_size(cap);
     v.pm = (vh_p_match *)(block + off[0]); v.spts = (float2 *)(block + off[1]);
