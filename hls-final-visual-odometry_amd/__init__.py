@@ -103,6 +103,9 @@ ABI_SYMBOLS = (
     "vh_group_trajectory", "vh_match_trajectory", "vh_group_get_poses", "vh_get_pose", "vh_group_poses_device", "vh_group_set_pose",
     "vh_group_scene_points_stereo_world", "vh_group_scene_points_mono_world",
     "vh_match_scene_points_stereo_world", "vh_match_scene_points_mono_world",
+    "vh_default_traj_cov_params", "vh_trajectory_cov", "vh_group_set_trajectory_covariance", "vh_sequence_set_trajectory_covariance",
+    "vh_set_trajectory_covariance", "vh_group_get_pose_covariances", "vh_get_pose_covariance", "vh_group_pose_covariances_device",
+    "vh_group_set_pose_covariance",
 )
 
 
@@ -260,6 +263,39 @@ class TrajParams(C.Structure):
                 raise AttributeError(k)
             setattr(e, k, v)
         return e
+
+
+#: rows of a chain one round of the pose covariance kernel takes (csrc/vh_trajectory_cov.h: VH_TRAJ_COV_ROUND)
+TRAJ_COV_ROUND = 128
+# vh_traj_cov (304 bytes): one per row of trajectory_cov / getPoseCovariances
+TRAJ_COV_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("status", "<i4"), ("step", "<i4"), ("n_filled", "<i4"), ("reserved", "<i4")])
+# vh_traj_cov_carry (880 bytes): what a chain's covariance carries from call to call
+TRAJ_COV_CARRY_DTYPE = np.dtype([("cov", "<f8", (6, 6)), ("Ad_last", "<f8", (6, 6)), ("Q_last", "<f8", (6, 6)), ("n_filled", "<i4"),
+                                 ("has_ad", "<i4"), ("has_q", "<i4"), ("step", "<i4")])
+
+
+class TrajCovParams(C.Structure):
+    """vh_traj_cov_params: fill_scale, the share of the last own Q a step without a covariance of its own adds."""
+    _fields_ = [("fill_scale", C.c_double), ("reserved", C.c_int32 * 2)]
+
+    @classmethod
+    def default(cls, **kw) -> "TrajCovParams":
+        e = cls()
+        _lib().vh_default_traj_cov_params(C.byref(e))
+        for k, v in kw.items():
+            setattr(e, k, v)
+        return e
+
+
+def _traj_S0(Sigma0, n):
+    """None, or [n, 6, 6] doubles (one 6x6 serves every chain) -> [n, 36]"""
+    if Sigma0 is None:
+        return None
+    s = np.asarray(Sigma0, np.float64)
+    if s.shape == (6, 6):
+        s = np.broadcast_to(s, (n, 6, 6))
+    assert s.shape == (n, 6, 6), s.shape
+    return np.ascontiguousarray(s).reshape(n, 36)
 
 
 def _traj_T0(T0, n):
@@ -486,6 +522,11 @@ def _lib():
             "vh_group_set_pose": [vp, i32, vp],
             "vh_group_scene_points_stereo_world": [vp, vp, vp, vp], "vh_group_scene_points_mono_world": [vp, vp, vp, vp],
             "vh_match_scene_points_stereo_world": [vp, vp, vp, vp], "vh_match_scene_points_mono_world": [vp, vp, vp, vp],
+            "vh_trajectory_cov": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+            "vh_group_set_trajectory_covariance": [vp, vp, vp], "vh_sequence_set_trajectory_covariance": [vp, vp, vp],
+            "vh_set_trajectory_covariance": [vp, vp, vp],
+            "vh_group_get_pose_covariances": [vp, vp], "vh_get_pose_covariance": [vp, vp], "vh_group_pose_covariances_device": [vp, vp, vp],
+            "vh_group_set_pose_covariance": [vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
@@ -501,6 +542,8 @@ def _lib():
         lib.vh_default_landmark_params.restype = None
         lib.vh_default_traj_params.argtypes = [vp]
         lib.vh_default_traj_params.restype = None
+        lib.vh_default_traj_cov_params.argtypes = [vp]
+        lib.vh_default_traj_cov_params.restype = None
         lib.vh_reconstruct_last_kernel_ms.argtypes = []
         lib.vh_reconstruct_last_kernel_ms.restype = f64
         lib.vh_group_device_bytes.argtypes = [vp]
@@ -771,6 +814,25 @@ class Matcher:
         """The chain continues from the 4x4 T (vh_group_set_pose)."""
         t = np.ascontiguousarray(T, np.float64).reshape(16)
         _check(_lib().vh_group_set_pose(self._h, 0, _ptr(t)), "vh_group_set_pose")
+
+    def setTrajectoryCovariance(self, params: "TrajCovParams | None" = None, Sigma0=None, on: bool = True):
+        """Propagate the pose's covariance with the pose (vh_set_trajectory_covariance): behind setTrajectory, before the
+        first pushBack.  Sigma0: the start covariance 6x6 (None: zero); on=False switches it off.  trajectory() then needs
+        motionCovariance(ego) (tr None) of the current classification in front of it."""
+        tcp = params or TrajCovParams.default()
+        _check(_lib().vh_set_trajectory_covariance(self._h, C.byref(tcp) if on else None, _ptr(_traj_S0(Sigma0, 1))),
+               "vh_set_trajectory_covariance")
+
+    def getPoseCovariances(self) -> np.ndarray:
+        """The covariance record of the last trajectory() (vh_get_pose_covariance) -> TRAJ_COV_DTYPE [1]."""
+        out = np.zeros(1, TRAJ_COV_DTYPE)
+        _check(_lib().vh_get_pose_covariance(self._h, _ptr(out)), "vh_get_pose_covariance")
+        return out
+
+    def setPoseCovariance(self, Sigma):
+        """The chain's covariance continues from the 6x6 Sigma (vh_group_set_pose_covariance)."""
+        s = np.ascontiguousarray(Sigma, np.float64).reshape(36)
+        _check(_lib().vh_group_set_pose_covariance(self._h, 0, _ptr(s)), "vh_group_set_pose_covariance")
 
     def scenePointsWorld(self, e, sp: "SceneParams | None" = None) -> np.ndarray:
         """scenePoints with Tw taken from the trajectory's pose on the device: Tw_prev for sp.frame 0, Tw_cur for 1
@@ -1170,6 +1232,34 @@ class StreamGroup:
         """The chain of `stream` (a SequenceGroup: 0) continues from the 4x4 T (vh_group_set_pose)."""
         t = np.ascontiguousarray(T, np.float64).reshape(16)
         _check(_lib().vh_group_set_pose(self._h, stream, _ptr(t)), "vh_group_set_pose")
+
+    def setTrajectoryCovariance(self, params: "TrajCovParams | None" = None, Sigma0=None, on: bool = True):
+        """Propagate every pose's covariance with the pose (vh_group_set_trajectory_covariance; a SequenceGroup:
+        vh_sequence_set_trajectory_covariance): behind setTrajectory, before the first pushBack.  Sigma0: None, one 6x6 or
+        [S, 6, 6] (a SequenceGroup: one 6x6); on=False switches it off.  trajectory() then needs motionCovariance(ego)
+        (tr None) of the current classification in front of it."""
+        tcp = params or TrajCovParams.default()
+        seq = isinstance(self, SequenceGroup)
+        fn = "vh_sequence_set_trajectory_covariance" if seq else "vh_group_set_trajectory_covariance"
+        _check(getattr(_lib(), fn)(self._h, C.byref(tcp) if on else None, _ptr(_traj_S0(Sigma0, 1 if seq else self.S))), fn)
+
+    def getPoseCovariances(self) -> np.ndarray:
+        """The covariance records of the last trajectory() (vh_group_get_pose_covariances) -> TRAJ_COV_DTYPE [S]."""
+        out = np.zeros(self.S, TRAJ_COV_DTYPE)
+        _check(_lib().vh_group_get_pose_covariances(self._h, _ptr(out)), "vh_group_get_pose_covariances")
+        return out
+
+    def poseCovariancesDevice(self):
+        """-> (device address of the covariance records of the last trajectory(), stride in records)"""
+        d = C.c_void_p(); stride = C.c_int64(0)
+        _check(_lib().vh_group_pose_covariances_device(self._h, C.byref(d), C.byref(stride)), "vh_group_pose_covariances_device")
+        return d.value, stride.value
+
+    def setPoseCovariance(self, stream: int, Sigma):
+        """The covariance of the chain of `stream` (a SequenceGroup: 0) continues from the 6x6 Sigma
+        (vh_group_set_pose_covariance)."""
+        s = np.ascontiguousarray(Sigma, np.float64).reshape(36)
+        _check(_lib().vh_group_set_pose_covariance(self._h, stream, _ptr(s)), "vh_group_set_pose_covariance")
 
     def scenePointsWorld(self, e, sp: "SceneParams | None" = None) -> np.ndarray:
         """scenePoints with Tw taken from the trajectory's poses on the device: Tw_prev for sp.frame 0, Tw_cur for 1
@@ -1873,6 +1963,35 @@ def trajectory(tr_chains, ok_chains, T0=None, carry=None, params: "TrajParams | 
     out = np.zeros(max(total, 1), TRAJ_POSE_DTYPE); cout = np.zeros(max(n, 1), TRAJ_CARRY_DTYPE)
     _check(_lib().vh_trajectory(C.byref(tp), device, n, _ptr(off), _ptr(tr), _ptr(ok), _ptr(t0), _ptr(cin), _ptr(out), _ptr(cout)),
            "vh_trajectory")
+    return [out[int(off[c]):int(off[c + 1])].copy() for c in range(n)], cout[:n]
+
+
+def trajectory_cov(tr_chains, ok_chains, cov_chains, ok_cov_chains, Sigma0=None, carry=None, params: "TrajParams | None" = None,
+                   cov_params: "TrajCovParams | None" = None, device: int = 0):
+    """The pose's covariance propagated along n chains of rows (vh_trajectory_cov): tr_chains / ok_chains as trajectory()'s,
+    cov_chains a list of [rows, 6, 6] motion covariances, ok_cov_chains of [rows] int arrays.  Sigma0: None, one 6x6 or
+    [n, 6, 6]; carry: None or a TRAJ_COV_CARRY_DTYPE array [n] (Sigma0 is then not read).
+    -> ([TRAJ_COV_DTYPE array per chain], TRAJ_COV_CARRY_DTYPE [n])."""
+    n = len(tr_chains)
+    assert len(ok_chains) == n and len(cov_chains) == n and len(ok_cov_chains) == n
+    tp = params or TrajParams.default()
+    tcp = cov_params or TrajCovParams.default()
+    off = np.zeros(n + 1, np.int32)
+    off[1:] = np.cumsum([len(t) for t in tr_chains])
+    total = int(off[-1])
+    tr = np.zeros((max(total, 1), 6), np.float64); ok = np.zeros(max(total, 1), np.int32)
+    cov = np.zeros((max(total, 1), 36), np.float64); okc = np.zeros(max(total, 1), np.int32)
+    for c in range(n):
+        tr[off[c]:off[c + 1]] = np.asarray(tr_chains[c], np.float64).reshape(-1, 6)
+        ok[off[c]:off[c + 1]] = np.asarray(ok_chains[c]).astype(np.int32)
+        cov[off[c]:off[c + 1]] = np.asarray(cov_chains[c], np.float64).reshape(-1, 36)
+        okc[off[c]:off[c + 1]] = np.asarray(ok_cov_chains[c]).astype(np.int32)
+    s0 = _traj_S0(Sigma0, n)
+    cin = None if carry is None else np.ascontiguousarray(carry, TRAJ_COV_CARRY_DTYPE).reshape(-1)
+    assert cin is None or len(cin) == n
+    out = np.zeros(max(total, 1), TRAJ_COV_DTYPE); cout = np.zeros(max(n, 1), TRAJ_COV_CARRY_DTYPE)
+    _check(_lib().vh_trajectory_cov(C.byref(tp), C.byref(tcp), device, n, _ptr(off), _ptr(tr), _ptr(ok), _ptr(cov), _ptr(okc), _ptr(s0),
+                                    _ptr(cin), _ptr(out), _ptr(cout)), "vh_trajectory_cov")
     return [out[int(off[c]):int(off[c + 1])].copy() for c in range(n)], cout[:n]
 
 

@@ -11,6 +11,7 @@
 //   engine_scene.hip  the 3-d points of whole lists (kernels_scene.hip) and their part of the ABI
 //   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip, kernels_landmark_chain.hip) and their part of the ABI
 //   engine_trajectory.hip  the camera's pose accumulated from the motions (kernels_trajectory.hip) and its part of the ABI
+//   engine_trajectory_cov.hip  the pose's covariance along the same chains (kernels_trajectory_cov.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -372,6 +373,10 @@ struct TrajState : TrajArrays {
   int32_t source = -1;
 };
 
+// The pose covariance (vh_group_set_trajectory_covariance; engine_trajectory_cov.hip): one arena
+// block, allocated by the first vh_group_trajectory call with the switch on.  latched / stepped / valid are TrajState's.
+struct TrajCovState : TrajCovArrays {};
+
 // The camera gain (vh_group_set_gain, vh_group_gain; engine_gain.hip): the ring's left images, one
 // arena block allocated with the ring while the switch is on, and the blocks of the gain entries, each allocated by the
 // first call that needs it.  Nothing here exists while the switch is off.
@@ -632,6 +637,11 @@ struct Group {
   vh_traj_params traj_params{};
   std::vector<double> traj_T0;
   TrajState trj;
+  // vh_group_set_trajectory_covariance: settings as the trajectory's (the start covariances [chains][36], empty: zero)
+  bool tcov_on = false;
+  vh_traj_cov_params tcov_params{};
+  std::vector<double> tcov_S0;
+  TrajCovState tcv;
   bool gain_on = false;  // vh_group_set_gain: every push keeps the left images (gn.d_planes)
   GainState gn;
   // Multi-stage matching (vh_group_set_multi_stage_matching): `sparse` is a group of its own over the same S streams
@@ -791,6 +801,15 @@ struct Group {
   }
   int32_t get_poses(vh_traj_pose *out);
   int32_t set_pose(int32_t s, const double *T);
+
+  // ---- engine_trajectory_cov.hip ----
+  int32_t set_trajectory_covariance(const vh_traj_cov_params *tcp, const double *Sigma0);
+  // the motion covariance on the device is the current classification's own
+  bool tcov_input_current() const { return cv.d_cov && cv.seq == match_seq && cv.gen == inl.gen && cv.own_tr; }
+  int32_t tcov_alloc();                     // the block and the chains' starts, once
+  void tcov_launch(const double *d_tr, const int32_t *d_ok, int32_t pair_lo, int32_t pair_hi);
+  int32_t tcov_set(int32_t s, const double *Sigma, bool restart);   // set_pose (restart) / set_pose_covariance
+  int32_t get_pose_covariances(vh_traj_cov *out);
 
   // ---- engine_gain.hip ----
   int32_t gain_copy(const VhImages &im);

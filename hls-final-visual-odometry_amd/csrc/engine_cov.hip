@@ -19,6 +19,7 @@ int32_t Group::motion_covariance(const vh_ego_params *e, const double *tr, const
     VH_HIP(hipMemcpyAsync(cv.d_tr, tr, sizeof(double) * 6 * (size_t)S, hipMemcpyHostToDevice, post_stream));
     VH_HIP(hipMemcpyAsync(cv.d_okin, ok, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, post_stream));
   }
+  cv.seq = -1;  // (until this call has ended well)
   VhCovArgs a{};
   a.e = *e;
   a.lists = inlier_lists();
@@ -31,7 +32,9 @@ int32_t Group::motion_covariance(const vh_ego_params *e, const double *tr, const
   VH_HIP(hipMemcpyAsync(ok_out, cv.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   for (int32_t s = 0; s < S; s++) counts[s] = inl.n_inl[s];
   VH_HIP(hipStreamSynchronize(post_stream));
-  return check_violation();
+  { const int32_t rv_ = check_violation(); if (rv_) return rv_; }
+  cv.seq = match_seq; cv.gen = inl.gen; cv.own_tr = tr == nullptr;
+  return VH_OK;
 }
 
 }  // namespace vh_engine

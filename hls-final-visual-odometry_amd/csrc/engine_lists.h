@@ -131,6 +131,10 @@ struct CovState {
   int32_t *d_ok = nullptr;    // [S] ok_out
   double *d_tr = nullptr;     // [S][6] the caller's motion (the classification's own stays in inl.d_tr)
   int32_t *d_okin = nullptr;  // [S]
+  // what d_cov was last computed under: the match call, the classification (inl.gen), and whether under the
+  // classification's own motion (tr = NULL) -- the pose covariance steps under no other
+  int64_t seq = -1, gen = -1;
+  bool own_tr = false;
   void carve(Carver &c, size_t lists) {
     d_cov = c.ptr<double>(36 * lists); d_ssr = c.ptr<double>(lists); d_ok = c.ptr<int32_t>(lists);
     d_tr = c.ptr<double>(6 * lists); d_okin = c.ptr<int32_t>(lists);
@@ -194,6 +198,15 @@ struct TrajArrays {
   vh_traj_carry *d_base = nullptr, *d_cur = nullptr;   // [chains]
   void carve(Carver &c, size_t rows, size_t chains) {
     d_out = c.ptr<vh_traj_pose>(rows); d_base = c.ptr<vh_traj_carry>(chains); d_cur = c.ptr<vh_traj_carry>(chains);
+  }
+};
+// The block of the pose covariance (TrajCovState, engine.h): the rows' records, and per chain the carry before the current
+// pair and the current one -- TrajArrays' layout
+struct TrajCovArrays {
+  vh_traj_cov *d_out = nullptr;                            // [S]
+  vh_traj_cov_carry *d_base = nullptr, *d_cur = nullptr;   // [chains]
+  void carve(Carver &c, size_t rows, size_t chains) {
+    d_out = c.ptr<vh_traj_cov>(rows); d_base = c.ptr<vh_traj_cov_carry>(chains); d_cur = c.ptr<vh_traj_cov_carry>(chains);
   }
 };
 // The caller's index lists of the gain (GainState, engine.h): idx [entries] | ratio [entries] | offsets [S + 1]; the block

@@ -15,7 +15,7 @@ static vh_traj_carry traj_start(const double *T0) {
 
 int32_t Group::set_trajectory(const vh_traj_params *tp, const double *T0) {
   if (allocated) return VH_ERR_STATE;  // before the first push only
-  if (!tp) { traj_on = false; traj_T0.clear(); return VH_OK; }
+  if (!tp) { traj_on = false; traj_T0.clear(); tcov_on = false; tcov_S0.clear(); return VH_OK; }  // (the covariance needs the poses)
   if (!traj_params_ok(tp)) return VH_ERR_INVALID_ARG;
   traj_on = true; traj_params = *tp; traj_params.reserved = 0;
   traj_T0.clear();
@@ -45,8 +45,14 @@ int32_t Group::traj_source(int32_t source, const double *&d_tr, const int32_t *&
 int32_t Group::trajectory(int32_t source, vh_traj_pose *out) {
   if (source != VH_TRAJ_STEREO && source != VH_TRAJ_MONO) return VH_ERR_INVALID_ARG;
   if (!traj_on) return VH_ERR_STATE;
+  if (tcov_on && source == VH_TRAJ_MONO) return VH_ERR_UNSUPPORTED;  // (a 5x5 covariance and a scale without one)
   const double *d_tr = nullptr; const int32_t *d_ok = nullptr;
   { const int32_t rc = traj_source(source, d_tr, d_ok); if (rc) return rc; }
+  if (tcov_on) {  // before any launch or latch; its block before the poses': refused, the poses' state is as it was
+    if (!tcov_input_current()) return VH_ERR_STATE;
+    const int32_t rc = tcov_alloc();
+    if (rc) return rc;
+  }
   const size_t chains = (size_t)traj_chains();
   if (!trj.d_out) {  // one block, before any launch: a refused allocation leaves nothing behind
     const int32_t rc = dmalloc_carved(static_cast<TrajArrays &>(trj), nullptr, false, (size_t)S, chains);
@@ -60,6 +66,7 @@ int32_t Group::trajectory(int32_t source, vh_traj_pose *out) {
   trj.valid = false;
   if (!trj.latched) {
     VH_HIP(hipMemcpyAsync(trj.d_base, trj.d_cur, sizeof(vh_traj_carry) * chains, hipMemcpyDeviceToDevice, post_stream));
+    if (tcov_on) VH_HIP(hipMemcpyAsync(tcv.d_base, tcv.d_cur, sizeof(vh_traj_cov_carry) * chains, hipMemcpyDeviceToDevice, post_stream));
     trj.latched = true;
   }
   VhTrajArgs a{};
@@ -72,6 +79,10 @@ int32_t Group::trajectory(int32_t source, vh_traj_pose *out) {
   // (the motion was written on the post stream: the same stream orders this behind it)
   { Scope sc(this, "trajectory", post_stream); vh_launch_trajectory(a, post_stream); }
   VH_HIP(hipGetLastError());
+  if (tcov_on) {
+    tcov_launch(d_tr, d_ok, a.pair_lo, a.pair_hi);
+    VH_HIP(hipGetLastError());
+  }
   trj.stepped = true;
   if (out) VH_HIP(hipMemcpyAsync(out, trj.d_out, sizeof(vh_traj_pose) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   VH_HIP(hipStreamSynchronize(post_stream));
@@ -95,14 +106,14 @@ int32_t Group::set_pose(int32_t s, const double *T) {
   if (!trj.d_out) {  // nothing on the device yet: the chain's start
     if (traj_T0.empty()) for (int32_t c = 0; c < traj_chains(); c++) for (int32_t q = 0; q < 16; q++) traj_T0.push_back(q % 5 == 0 ? 1.0 : 0.0);
     std::copy(T, T + 16, traj_T0.begin() + 16 * (size_t)s);
-    return VH_OK;
+    return tcov_on ? tcov_set(s, nullptr, true) : VH_OK;
   }
   const vh_traj_carry c = traj_start(T);
   VH_HIP(hipStreamSynchronize(post_stream));
   VH_HIP(hipMemcpy(trj.d_base + s, &c, sizeof c, hipMemcpyHostToDevice));
   VH_HIP(hipMemcpy(trj.d_cur + s, &c, sizeof c, hipMemcpyHostToDevice));
   trj.valid = false;
-  return VH_OK;
+  return tcov_on ? tcov_set(s, nullptr, true) : VH_OK;
 }
 
 }  // namespace vh_engine

@@ -613,6 +613,26 @@ struct VhTrajArgs {
 };
 void vh_launch_trajectory(const VhTrajArgs &a, hipStream_t st);
 
+// The pose covariance along the same chains (kernels_trajectory_cov.hip): chains, rows and pairs
+// as VhTrajArgs'.
+struct VhTrajCovArgs {
+  vh_traj_params p;
+  double fill_scale;
+  int32_t n_chains;
+  const int32_t *offsets;               // null: rows_per_chain rows each
+  int32_t rows_per_chain;
+  int32_t pair_lo, pair_hi;
+  const double *tr;                     // [rows][6]
+  const int32_t *ok;                    // [rows]; < 0: the row holds no pair
+  const double *cov;                    // [rows][36] the motions' covariances
+  const int32_t *ok_cov;                // [rows]
+  const double *Sigma0;                 // [n_chains][36], null: zero; not read where carry_in is given
+  const vh_traj_cov_carry *carry_in;    // [n_chains], nullable
+  vh_traj_cov *out;                     // [rows]
+  vh_traj_cov_carry *carry_out;         // [n_chains], nullable (may be carry_in)
+};
+void vh_launch_trajectory_cov(const VhTrajCovArgs &a, hipStream_t st);
+
 // The camera gain over index lists into match lists (kernels_gain.hip).  The lists are addressed
 // as vh_list does, and so are the index lists: slices of one concatenated array (idx_offsets) or slots of idx_stride
 // entries whose counts live on the device (idx_counts, clamped to idx_cap); the ratio of an entry lies where the entry does.

@@ -1336,6 +1336,77 @@ int32_t vh_group_scene_points_mono_world(vh_group *g, const vh_mono_params *e, c
 int32_t vh_match_scene_points_stereo_world(vh_matcher *m, const vh_ego_params *e, const vh_scene_params *sp, int32_t *count);
 int32_t vh_match_scene_points_mono_world(vh_matcher *m, const vh_mono_params *e, const vh_scene_params *sp, int32_t *count);
 
+/* ---- pose covariance: the uncertainty of the trajectory's pose, propagated along the chains (csrc/kernels_trajectory_cov.hip) ----
+ * Stereo source only.  The uncertainty of a pose P is a right (camera-frame) perturbation, P_true = P * Exp(xi),
+ * xi = (phi_x, phi_y, phi_z, rho_x, rho_y, rho_z), Sigma = E[xi xi^T], 6x6 row-major.  The rule has one copy,
+ * csrc/vh_trajectory_cov.h; all arithmetic in double, every product and sum rounded on its own.  One accepted row with tr,
+ * R = the estimators' rotation of tr, t = tr[3..5] and the motion's covariance C (vh_motion_covariance's, in the order of tr):
+ *   1. G (6x6) maps a change of tr to the right perturbation of T(tr): column k of the upper-left 3x3 block is
+ *      vee(R^T dR_k) with dR_k the derivative of R by tr[k] and vee(W) = (W[2][1], W[0][2], W[1][0]); the lower-right block
+ *      is R^T; the rest is zero.
+ *   2. Q = G C G^T: W = G C in full (c = 0; c += G[i][k] * C[k][j], k = 0..5), Q[i][j] = sum_k W[i][k] * G[j][k] for i <= j,
+ *      mirrored.
+ *   3. Ad = [[R, 0], [[t]x R, R]], [t]x the cross-product matrix.
+ *   4. S = Sigma + Q; U = Ad S (k = 0..5, all six terms); Sigma'[i][j] = sum_k U[i][k] * Ad[j][k] for i <= j, mirrored:
+ *      Sigma' = Ad (Sigma + Q) Ad^T, which is what P' = P * inv(T) does to a right perturbation.
+ * Which rows step is the pose chain's: status and step of a record equal the pose record's.  A row that holds keeps Sigma.
+ * A step without a covariance of its own -- a row repeated under VH_TRAJ_REPEAT, or an accepted row whose ok_cov is 0 or
+ * whose C or Q holds a value that is not finite -- steps with the Ad it steps with (its own; repeated: the last accepted
+ * one), adds fill_scale * Q_last, Q_last being the Q of the chain's last step that had its own (zero before any), and
+ * counts in n_filled: n_filled > 0 reads "this covariance is a lower bound". */
+typedef struct vh_traj_cov_params {
+  double  fill_scale;                /* finite, >= 0 */
+  int32_t reserved[2];               /* 0 */
+} vh_traj_cov_params;
+typedef struct vh_traj_cov {         /* 304 bytes, one per row */
+  double  cov[36];                   /* Sigma behind the row, row-major, exactly symmetric */
+  int32_t status;                    /* the pose record's */
+  int32_t step;                      /* the pose record's */
+  int32_t n_filled;                  /* steps of the chain so far without a covariance of their own */
+  int32_t reserved;                  /* 0 */
+} vh_traj_cov;
+typedef struct vh_traj_cov_carry {   /* 880 bytes, one per chain */
+  double  cov[36];                   /* the last Sigma */
+  double  Ad_last[36];               /* Ad of the last accepted row (zeros while has_ad == 0) */
+  double  Q_last[36];                /* Q of the last step that had its own (zeros while has_q == 0) */
+  int32_t n_filled;
+  int32_t has_ad;                    /* the pose carry's has_tinv */
+  int32_t has_q;
+  int32_t step;                      /* the pose carry's step: what the records' step goes on from */
+} vh_traj_cov_carry;
+void vh_default_traj_cov_params(vh_traj_cov_params *tcp);   /* fill_scale 1.0 */
+/* Stateless, host pointers: chains as vh_trajectory's; cov[rows][36] and ok_cov[rows] are the rows' motion covariances
+ * (vh_motion_covariance's cov and ok_out).  A chain starts from carry_in[c] where given, else from Sigma0[c] (NULL: zero)
+ * with n_filled 0, step 0 and neither Ad_last nor Q_last.  carry_out (nullable) [n_chains].  One workgroup walks a chain in rounds
+ * of VH_TRAJ_COV_ROUND rows (csrc/vh_trajectory_cov.h).  VH_ERR_INVALID_ARG: null tp / tcp / offsets / (with rows) tr, ok,
+ * cov, ok_cov, out; on_fail outside the two policies; fill_scale negative or not finite; n_chains < 0.
+ * VH_ERR_UNSUPPORTED: more than 2^24 chains.  n_chains == 0: VH_OK; no rows at all: VH_OK, carry_out filled on the host;
+ * neither launches anything nor needs a device. */
+int32_t vh_trajectory_cov(const vh_traj_params *tp, const vh_traj_cov_params *tcp, int32_t device, int32_t n_chains,
+                          const int32_t *offsets, const double *tr, const int32_t *ok, const double *cov, const int32_t *ok_cov,
+                          const double *Sigma0, const vh_traj_cov_carry *carry_in, vh_traj_cov *out, vh_traj_cov_carry *carry_out);
+/* Handles, opt-in, before the first push only and only with the trajectory on (VH_ERR_STATE otherwise); tcp == NULL
+ * switches it off.  Sigma0: the start covariance of every chain [chains][36] (NULL: zero), finite.  Off (the default):
+ * nothing is allocated or launched.  On: vh_group_trajectory / vh_match_trajectory run both kernels in the one call.
+ * VH_TRAJ_MONO is then VH_ERR_UNSUPPORTED, and VH_TRAJ_STEREO needs the motion covariance of the current classification
+ * on the device -- vh_group_motion_covariance(tr = NULL) behind the current match call and the current classification
+ * -- else VH_ERR_STATE before any launch or latch, the handle as it was.  The covariance carries latch, step and go
+ * stale with the pose carries.  The first call adds one block, counted by vh_group_device_bytes: 304 bytes per stream /
+ * row of records and 2 x 880 bytes per chain of carries, each of the three arrays rounded up to 256 bytes; a refused
+ * allocation is VH_ERR_HIP before any launch and leaves the poses' state as it was.  Profile scope: "trajectory_cov". */
+int32_t vh_group_set_trajectory_covariance(vh_group *g, const vh_traj_cov_params *tcp, const double *Sigma0);
+int32_t vh_sequence_set_trajectory_covariance(vh_group *g, const vh_traj_cov_params *tcp, const double *Sigma0);
+int32_t vh_set_trajectory_covariance(vh_matcher *m, const vh_traj_cov_params *tcp, const double *Sigma0);
+/* The records of the last vh_group_trajectory call: VH_ERR_STATE where vh_group_get_poses returns it, or with the
+ * covariance off.  _device: the array itself, *stride in records. */
+int32_t vh_group_get_pose_covariances(vh_group *g, vh_traj_cov *out);
+int32_t vh_get_pose_covariance(vh_matcher *m, vh_traj_cov *out);
+int32_t vh_group_pose_covariances_device(vh_group *g, const vh_traj_cov **d_cov, int64_t *stride);
+/* The chain of `stream` continues from Sigma[36] (finite) with n_filled 0; Ad_last and Q_last stay.  Base and current are
+ * both set, the records of the last call become stale.  (vh_group_set_pose also resets the chain's covariance: zero, and
+ * neither Ad_last nor Q_last.)  VH_ERR_STATE with the covariance off. */
+int32_t vh_group_set_pose_covariance(vh_group *g, int32_t stream, const double *Sigma);
+
 /* ---- the same chain ON THE DEVICE: no host work between matching and the pose (csrc/kernels_vote.hip) ----
  * removeOutliers' Delaunay triangulation is a sequential chain per match list (csrc/sweep_hull.h); on the GPU a list
  * takes tens of milliseconds as one lane, and the throughput comes from the lists in flight:
