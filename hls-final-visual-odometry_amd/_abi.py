@@ -152,7 +152,21 @@ def _abi_table():
     }
 
 
+def _abi_ext_table():
+    """The rows of the extension headers beside include/viso_hip.h (viso_hip_lmk_refit.h): the same library exports them,
+    _lib() sets them in the same pass; they are kept out of ABI_SYMBOLS, which mirrors viso_hip.h alone."""
+    vp, i32 = C.c_void_p, C.c_int32
+    return {
+        "vh_default_lmk_refit_params": (None, [vp]),
+        "vh_refit_motion_landmarks": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "vh_group_refit_motion_landmarks": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "vh_match_refit_motion_landmarks": (i32, [vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]),
+        "vh_group_get_refit_priors": (i32, [vp, i32, vp, i32, vp]),
+    }
+
+
 _ABI = _abi_table()
+_ABI_EXT = _abi_ext_table()
 #: every symbol include/viso_hip.h declares (checked by the CPU test-suite)
 ABI_SYMBOLS = tuple(_ABI)
 
@@ -457,7 +471,7 @@ def _lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback for the HIP path)")
         lib = C.CDLL(LIB_PATH)
-        for name, proto in _ABI.items():
+        for name, proto in {**_ABI, **_ABI_EXT}.items():
             fn = getattr(lib, name)   # every declared symbol resolves, or the library is not the header's
             if proto is not None:
                 fn.restype = proto[0]

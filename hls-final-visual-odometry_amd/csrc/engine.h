@@ -12,6 +12,7 @@
 //   engine_landmark.hip  the scene points fused along the tracks (kernels_landmark.hip, kernels_landmark_chain.hip) and their part of the ABI
 //   engine_trajectory.hip  the camera's pose accumulated from the motions (kernels_trajectory.hip) and its part of the ABI
 //   engine_trajectory_cov.hip  the pose's covariance along the same chains (kernels_trajectory_cov.hip) and its part of the ABI
+//   engine_lmk_refit.hip  the motion refined with the landmarks as the 3-d prior (kernels_lmk_refit.hip) and its part of the ABI
 //   engine_inlier.hip motion inliers of the lists (kernels_inlier.hip), the motion refined on them (kernels_refit.hip) and
 //                     their part of the ABI
 //   engine_gain.hip   the camera gain over the lists (kernels_gain.hip) and its part of the ABI
@@ -361,6 +362,27 @@ struct LandmarkState : LandmarkArrays {
   bool carry_valid = false;         // the carry holds the states of the list in the track carry slot
 };
 
+// The motion refit on the landmarks (vh_group_refit_motion_landmarks): the arrays of its block
+// (here and not in engine_lists.h: the record is the extension header's): the priors, the poses of
+// the previous cameras, the counts of landmark points, and the refit's outputs
+struct LmkRefitArrays {
+  vh_refit_prior *d_prior = nullptr;  // [slots] ([S][mcap]), indexed like the compacted inlier records
+  double *d_Tw = nullptr;             // [S][16]
+  int32_t *d_nused = nullptr;         // [S]
+  RefitState out;
+  void carve(Carver &c, size_t lists, size_t slots) {
+    d_prior = c.ptr<vh_refit_prior>(slots); d_Tw = c.ptr<double>(16 * lists); d_nused = c.ptr<int32_t>(lists); out.carve(c, lists);
+  }
+};
+// The motion refit on the landmarks (vh_group_refit_motion_landmarks; engine_lmk_refit.hip): one
+// arena block, allocated by the first call.
+struct LmkRefitState : LmkRefitArrays {
+  bool valid = false;               // priors exist, of the inlier lists of match call `seq` as they were when the fit read them
+  int64_t seq = 0;
+  std::vector<int32_t> n;           // [S] priors per stream
+  std::vector<double> h_Tw;         // the chains' start poses, where they go up (the trajectory on, its block not there yet)
+};
+
 // The trajectory (vh_group_set_trajectory, vh_group_trajectory; engine_trajectory.hip): one arena
 // block, allocated by the first call.  d_base: every chain's carry before the current pair; d_cur: behind it.
 struct TrajState : TrajArrays {
@@ -630,6 +652,7 @@ struct Group {
   MonoPoseState mps;
   SceneState scn;
   LandmarkState lmk;
+  LmkRefitState lrf;
   bool lmk_chain = false;  // vh_sequence_set_landmarks: vh_group_landmarks runs the chain form over the chunk's rows
   // vh_group_set_trajectory: the switch, the policy and the start poses [chains][16] (empty: unit matrices) are settings
   // and survive release(); trj is device state and does not -- after new dims every chain starts from its T0 again
@@ -756,6 +779,10 @@ struct Group {
   }
   int32_t motion_inliers(const InlierTest &t, const int32_t *ok, int32_t *counts);
   int32_t refit_motion(const vh_ego_params *e, int32_t reclassify, double *tr_out, int32_t *ok_out, int32_t *n_updates, int32_t *counts);
+  // behind a refit's launches on the post stream: the downloads of r's arrays, then counts -- the classification's, or with
+  // reclassify the classification again under r's tr / ok
+  int32_t refit_finish(const vh_ego_params *e, int32_t reclassify, const RefitState &r, double *tr_out, int32_t *ok_out, int32_t *n_updates,
+                       int32_t *counts);
   int32_t get_inlier_flags(int32_t s, uint8_t *out, int32_t capo, int32_t *n);
   int32_t get_inlier_matches(int32_t s, vh_p_match *out, int32_t *src_pos, int32_t capo, int32_t *n);
   int32_t get_inlier_matches_all(vh_p_match *out, int32_t *src_pos, int32_t cap_per_stream, int32_t *counts);
@@ -787,6 +814,11 @@ struct Group {
   bool landmarks_current() const { return allocated && lmk.valid && lmk.seq == match_seq; }
   int32_t get_landmarks(int32_t s, vh_landmark *out, int32_t capo, int32_t *n);
   int32_t get_landmarks_all(vh_landmark *out, int32_t cap_per_stream, int32_t *counts);
+
+  // ---- engine_lmk_refit.hip ----
+  int32_t refit_motion_landmarks(const vh_ego_params *e, const vh_lmk_refit_params *rp, const double *Tw_prev, int32_t reclassify, double *tr_out,
+                                 int32_t *ok_out, int32_t *n_updates, int32_t *n_used, int32_t *counts);
+  int32_t get_refit_priors(int32_t s, vh_refit_prior *out, int32_t capo, int32_t *n);
 
   // ---- engine_trajectory.hip ----
   int32_t traj_chains() const { return seq ? 1 : S; }

@@ -103,7 +103,7 @@ void Group::release() {
   vote_release();
   rh.release_device();
   allocs.clear(); device_bytes = 0;
-  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {}; cv = {}; mrf = {}; mps = {}; scn = {}; lmk = {}; trj = {}; tcv = {}; gn = {};
+  sets = {}; rf = {}; det = {}; mt = {}; stg = {}; pri = {}; tk = {}; ego = {}; post = {}; rg = {}; ms_vb = {}; inl = {}; rft = {}; cv = {}; mrf = {}; mps = {}; scn = {}; lmk = {}; lrf = {}; trj = {}; tcv = {}; gn = {};
   allocated = false;
 }
 

@@ -98,10 +98,15 @@ int32_t Group::refit_motion(const vh_ego_params *e, int32_t reclassify, double *
   a.tr_out = rft.d_tr; a.ok_out = rft.d_ok; a.n_updates = rft.d_nupd;
   { Scope sc(this, "motion_refit", post_stream); vh_launch_refit(a, post_stream); }
   VH_HIP(hipGetLastError());
+  return refit_finish(e, reclassify, rft, tr_out, ok_out, n_updates, counts);
+}
+
+int32_t Group::refit_finish(const vh_ego_params *e, int32_t reclassify, const RefitState &r, double *tr_out, int32_t *ok_out, int32_t *n_updates,
+                            int32_t *counts) {
   // the results come down behind the refit whatever happens to the classification after it
-  VH_HIP(hipMemcpyAsync(tr_out, rft.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, post_stream));
-  VH_HIP(hipMemcpyAsync(ok_out, rft.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
-  VH_HIP(hipMemcpyAsync(n_updates, rft.d_nupd, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(tr_out, r.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(ok_out, r.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
+  VH_HIP(hipMemcpyAsync(n_updates, r.d_nupd, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, post_stream));
   if (!reclassify) {
     for (int32_t s = 0; s < S; s++) counts[s] = inl.n_inl[s];
     VH_HIP(hipStreamSynchronize(post_stream));
@@ -109,8 +114,8 @@ int32_t Group::refit_motion(const vh_ego_params *e, int32_t reclassify, double *
   }
   // the refined motion becomes the one the flag kernel reads: the host does not wait in between, and the one wait of the
   // classification covers the downloads above
-  VH_HIP(hipMemcpyAsync(inl.d_tr, rft.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
-  VH_HIP(hipMemcpyAsync(inl.d_ok, rft.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
+  VH_HIP(hipMemcpyAsync(inl.d_tr, r.d_tr, sizeof(double) * 6 * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
+  VH_HIP(hipMemcpyAsync(inl.d_ok, r.d_ok, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToDevice, post_stream));
   InlierTest t = InlierTest::stereo(e, nullptr);
   t.on_device = true;
   const int32_t rc = motion_inliers(t, nullptr, counts);

@@ -34,6 +34,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/viso_hip.h"
+#include "../../include/viso_hip_lmk_refit.h"
 
 #define VH_MARGIN 7          // src/matcher.cpp:38
 #ifndef VH_CHUNK
@@ -595,6 +596,41 @@ struct VhLandmarkChainArgs {
 hipError_t vh_launch_landmarks_chain_clear(const VhLandmarkChainArgs &c, int64_t obs_elems, hipStream_t st);
 void vh_launch_landmarks_chain_stage(const VhLandmarkChainArgs &c, int32_t k, hipStream_t st);
 const char *vh_landmark_chain_scope(int32_t k);
+
+// The motion refit on the landmarks (kernels_lmk_refit.hip): refit_prior writes every record's
+// point (vh_refit_prior.h), refit_prior_fit is the loop of VhRefitArgs over those points.  The lists are a VhLists; prior
+// of list s begins where its records do (offsets[s], or s * pm_stride).  A record's position in the predecessor list:
+// prev_pos (indexed like the records), or -- where it is null -- trk[src_pos[i]].prev with src_pos indexed like the
+// records and list s's tracked records the first min(trk_counts[s], slot_stride) of trk + s * slot_stride.  The
+// predecessor lists' states: slices of one array (prev_offsets) or slots of prev_stride whose counts live on the device
+// (prev_counts, clamped to the stride); prev null: no list has a predecessor.
+struct VhLmkRefitArgs {
+  vh_ego_params e;                 // f, cu, cv, base, reweighting
+  vh_lmk_refit_params rp;
+  VhLists lists;
+  int32_t tiles_per_list;          // >= ceil(longest list / VH_SCENE_TILE)
+  const int32_t *prev_pos;
+  const int32_t *src_pos;
+  const vh_track *trk;
+  const int32_t *trk_counts;
+  int64_t slot_stride;
+  const vh_landmark_state *prev;
+  const int32_t *prev_offsets, *prev_counts;
+  int64_t prev_stride;
+  const double *Tw;                // [n_lists][16] row-major, the previous camera to the world
+  vh_refit_prior *prior;
+  int32_t *n_used;                 // [n_lists], zeroed by the launch function: records with source == 1
+  const double *tr_in;             // the fit's arguments: VhRefitArgs'
+  const int32_t *ok_in;
+  double *tr_out;
+  int32_t *ok_out;
+  int32_t *n_updates;
+};
+// the memset of n_used and the refit_prior launch on one stream -> the memset's code.  The caller keeps
+// n_lists * tiles_per_list below 2^30.
+hipError_t vh_launch_refit_prior(const VhLmkRefitArgs &a, hipStream_t st);
+// behind it on the same stream; grid: a.lists.n_lists workgroups (the caller keeps it below 2^24)
+void vh_launch_refit_prior_fit(const VhLmkRefitArgs &a, hipStream_t st);
 
 // The trajectory (kernels_trajectory.hip): n_chains chains of rows, a workgroup each.  Chain c is
 // the rows [offsets[c], offsets[c + 1]), or without offsets the rows [c * rows_per_chain, (c + 1) * rows_per_chain).
